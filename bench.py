@@ -35,6 +35,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BYTES_PER_POINT = 568.0         # 35 complex + 1 real per grid point per apply
 PARITY_TOL = 1e-10              # BASELINE.json north_star
+DUMP_POINTS = 1 << 21           # --dump-outputs: at most 2^21 complex points of y, 32 MiB as float64 (re, im) pairs
+DUMP_SEED = 7
 
 
 def synthetic_nu(n, lo, hi):
@@ -63,6 +65,31 @@ def bench_vector(n, lo, hi):
         return v[lo * n * n:hi * n * n].copy()
     rng = np.random.default_rng(20250224 + lo)
     return rng.standard_normal(2 * (hi - lo) * n * n).view(np.complex128)
+
+
+def dump_indices(N):
+    """global points of y written by --dump-outputs: all of them when they fit, else a fixed seeded sample (sorted)"""
+    if N <= DUMP_POINTS:
+        return np.arange(N)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(N, DUMP_POINTS, replace=False))
+
+
+def gather_points(idx, slabs):
+    """y at the global points idx, from the slabs [(global offset, device tensor)] this process holds; zero elsewhere"""
+    import torch
+    out = torch.zeros(idx.size, dtype=torch.complex128, device=slabs[0][1].device)
+    for off, y in slabs:
+        sel = np.nonzero((idx >= off) & (idx < off + y.numel()))[0]
+        if sel.size:
+            vals = y[torch.from_numpy(idx[sel] - off).to(y.device)]
+            out[torch.from_numpy(sel).to(out.device)] = vals.to(out.device)
+    return out
+
+
+def write_outputs(path, y):
+    """y (complex128, numpy) -> path/y.npy as float64 [re, im] pairs"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "y.npy"), np.ascontiguousarray(y).view(np.float64).reshape(-1, 2))
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -207,7 +234,13 @@ def main():
     ap.add_argument("--single-process", action="store_true", help="drive all --gpus devices from this one process (multi-device plan)")
     ap.add_argument("--devices", type=str, default="", help="with --single-process: comma-separated device ids, one per rank; a device may repeat "
                     "(logical ranks on one GPU, peer-copy transport): a rehearsal of the path where fewer GPUs are visible, not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"after the timed steps write y of the last one to DIR/y.npy as float64 (re, im) rows: every point in flat order "
+                         f"when n^3 <= {DUMP_POINTS}, else the {DUMP_POINTS} points np.random.default_rng({DUMP_SEED}).choice(n^3, "
+                         f"{DUMP_POINTS}, replace=False), sorted")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -280,6 +313,8 @@ def main():
         elapsed, stages = out["elapsed_s"], out["stages"]
         pipeline, padded = "pruned-hip", list(multi.padded_dims)
         nloc = N // args.gpus
+        if args.dump_outputs:
+            ydump = gather_points(dump_indices(N), [(r * multi.local_n, y) for r, y in enumerate(out["ys"])]).cpu().numpy()
     else:
         lo = rank * n // world_eff
         xb = torch.from_numpy(bench_vector(n, lo, lo + nloc // (n * n))).to(dev)
@@ -305,6 +340,11 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if args.dump_outputs:
+            yd = gather_points(dump_indices(N), [(lo * n * n, yb)])
+            if dist is not None:
+                dist.all_reduce(torch.view_as_real(yd))     # each point is held by one rank, the others add zeros
+            ydump = yd.cpu().numpy()
         # per-kernel roofline: HIP events on the plan's stream around every stage of one apply.  With more than one
         # rank the stages contain collectives, so a failure must take the whole job down (no per-rank try/except:
         # a rank that skipped them would leave the others blocked in ncclRecv).
@@ -383,6 +423,9 @@ def main():
         if cb is not None:
             out["cpu_baseline"] = cb
             out["gpu_over_cpu"] = value / cb["value"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, ydump)
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "y.npy": f"{ydump.size} of {N} points, float64 (re, im)"}
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:

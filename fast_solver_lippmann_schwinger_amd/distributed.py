@@ -105,7 +105,7 @@ class MultiDeviceFastM3D(FastM3D):
 
     def bench(self, steps, warmup):
         """`steps` timed applies on device-resident slabs (host clock around the enqueue + a synchronisation of every
-        device), and the per-stage profile: what bench.py --single-process reports"""
+        device), the per-stage profile and the output slabs of the last timed apply: what bench.py --single-process reports"""
         import time
         import torch
         from .operators import profile_apply
@@ -125,7 +125,7 @@ class MultiDeviceFastM3D(FastM3D):
             self.apply_dev(xs, ys)
         self.synchronize()
         elapsed = time.perf_counter() - t0
-        return {"elapsed_s": elapsed, "stages": profile_apply(self, None, None, reps=3)}
+        return {"elapsed_s": elapsed, "stages": profile_apply(self, None, None, reps=3), "ys": ys}
 
 
 class SimulatedRanks:
