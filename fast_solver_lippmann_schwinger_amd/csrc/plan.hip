@@ -671,6 +671,18 @@ static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs,
     }
 }
 
+// kernel samples: the response to a unit source at grid index 0 (one FFT convolution, no nu), built once per plan
+void plan_kernel0(lsfc_plan* p) {
+    const int64_t N = p->N;
+    if (p->kernel0.n == (size_t)N) return;
+    p->kernel0.alloc((size_t)N);
+    DevBuf<cplx> e; e.alloc((size_t)N);
+    LSFC_HIP(hipMemsetAsync(e.p, 0, (size_t)N * sizeof(cplx), p->stream));
+    const cplx one = make_double2(1.0, 0.0);
+    LSFC_HIP(hipMemcpyAsync(e.p, &one, sizeof one, hipMemcpyHostToDevice, p->stream));
+    plan_convolve_dev(p, e.p, p->kernel0.p, false, 0.0, 1.0);
+    LSFC_HIP(hipStreamSynchronize(p->stream));
+}
 } // namespace lsfc
 
 using namespace lsfc;
@@ -869,16 +881,7 @@ int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, d
         lsfc_plan* p = plan;
         const int64_t N = p->N;
         for (int64_t s = 0; s < nsrc; ++s) LSFC_REQUIRE(sources[s] >= 0 && sources[s] < N, "source index %lld out of range", (long long)sources[s]);
-        // kernel samples: the response to a unit source at grid index 0 (one FFT convolution, no nu)
-        if (p->kernel0.n != (size_t)N) {
-            p->kernel0.alloc((size_t)N);
-            DevBuf<cplx> e; e.alloc((size_t)N);
-            LSFC_HIP(hipMemsetAsync(e.p, 0, (size_t)N * sizeof(cplx), p->stream));
-            const cplx one = make_double2(1.0, 0.0);
-            LSFC_HIP(hipMemcpyAsync(e.p, &one, sizeof one, hipMemcpyHostToDevice, p->stream));
-            plan_convolve_dev(p, e.p, p->kernel0.p, false, 0.0, 1.0);
-            LSFC_HIP(hipStreamSynchronize(p->stream));
-        }
+        plan_kernel0(p);
         DevBuf<int64_t> dsrc; dsrc.alloc((size_t)nsrc);
         LSFC_HIP(hipMemcpyAsync(dsrc.p, sources, (size_t)nsrc * sizeof(int64_t), hipMemcpyHostToDevice, p->stream));
         if (memspace == LSFC_MEM_DEVICE) {

@@ -198,6 +198,9 @@ void multi_allreduce_sum(lsfc_plan* root, cplx* const* dev, int count);   // dev
 void multi_synchronize(lsfc_plan* root);
 void multi_profile(lsfc_plan* root, int reps, int max_stages, const char** names, double* ms, double* bytes, int* nstages);
 
+// the spatial kernel: p->kernel0 = convolution of a unit source at grid index 0 (no nu), built on first use (plan.hip)
+void plan_kernel0(lsfc_plan* p);
+
 // GMRES (gmres.hip)
 void gmres_run(lsfc_plan* p, cplx* x_dev, const cplx* b_dev, const lsfc_gmres_opts* opts, double* resnorm, int64_t cap,
                lsfc_gmres_result* res);

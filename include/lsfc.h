@@ -226,6 +226,36 @@ int lsfc_precond_callback(void* user, double* v, int64_t n);
 /* dependency levels of the two triangular solves and kernel launches captured in the graph */
 int lsfc_precond_stats(const lsfc_precond* pc, int64_t* levels_L, int64_t* levels_U, int64_t* launches);
 
+/* ---- assembly of the sparsifying matrices (As, As*G, Msp) ------------------- */
+
+/* The reference builds the two matrices of SparsifyingPreconditioner(Msp, As) with buildSparseA / buildSparseAG
+ * (src/SparsifyingMatrix2D.jl:351-438, :806-884, Conv variants :441-532, :888-966) and buildSparseA3DConv /
+ * buildSparseAG3DConv (src/SparsifyingMatrix3D.jl:1410-1918), and the caller forms Msp = As + k^2 AG diag(nu)
+ * (examples/example.jl:67, examples/example3D.jl:61).  Every grid point belongs to one stencil class (2D: 9, 3D: 27;
+ * class numbers in the reference's order, DESIGN.md "Sparsifying matrices"); class c has a_c = U[:, end]' of
+ * svd(G[S_c, complement of S_c]) for its sample sources S_c, stamped on the rows of its class (As) together with
+ * a_c G[S_c, S_c] (AG, with the reference's entriesSparseG* source order).
+ * Matrices: CSR, 0-based, columns ascending in every row, every stencil entry stored (also an exact 0), values
+ * interleaved complex.  The three matrices share one pattern.
+ * Phase: U[:, end] is defined up to a unit complex factor; a_c is scaled so that its entry of largest modulus (the
+ * first one in the reference's stencil order on ties) is real and positive.  As and AG rows carry the same factor,
+ * so Msp^{-1} As does not depend on it. */
+
+/* Pattern of As / AG / Msp (identical) for a 2D (l == 1) or 3D grid: pure host arithmetic, no device.  nnz (out);
+ * rowptr[N+1], col[nnz], row_class[N] may each be NULL (query nnz first).  LSFC_EINVAL: an axis < 3, 2D with n or m even. */
+int lsfc_sparsify_pattern(int64_t n, int64_t m, int64_t l, int64_t* nnz, int64_t* rowptr, int64_t* col, int64_t* row_class);
+
+/* buildSparseA*Conv / buildSparseAG*Conv from the plan's own discrete kernel, and Msp = As + omega^2 AG diag(nu).
+ * Any value array may be NULL.  sigma (NULL or nclass*3): sigma_max, sigma_second_smallest, sigma_min per class.
+ * memspace: LSFC_MEM_HOST or LSFC_MEM_DEVICE for all array arguments.
+ * The rows are those of the plan's kernel (lsfc_sample_sources, no nu): a 2D trapezoidal plan gives the directly
+ * sampled sampleG rows of buildSparseA / buildSparseAG, Greengard-Vico plans the Conv variants.  nu and omega are the
+ * plan's.  LSFC_EINVAL: NULL, distributed or multi-device plan, unsupported grid (as lsfc_sparsify_pattern, or fewer
+ * than twice as many points as a stencil has sources), an array that is detectably not in `memspace`.
+ * Device memory: about 0.3 MB of tables plus, for LSFC_MEM_HOST, staging for the requested arrays. */
+int lsfc_sparsify_build(lsfc_plan* plan, int64_t* rowptr, int64_t* col, double* As_val, double* AG_val,
+                        double* Msp_val, double* sigma, int memspace);
+
 /* ---- streams, timing, profiling ------------------------------------------ */
 
 /* Run the plan on a caller-owned hipStream_t (NULL = the legacy default stream). */

@@ -134,6 +134,41 @@ function sampleG3D(k, X, Y, Z, indS, M::FastMHIP)
 end
 sampleGConv(k, X, Y, indS, M::FastMHIP) = sampleG3D(k, X, Y, nothing, indS, M)
 
+# buildSparseA*/buildSparseAG* assembled on the device -- src/SparsifyingMatrix2D.jl:351-532, :806-966,
+# src/SparsifyingMatrix3D.jl:1410-1918 -- and Msp = As + k^2 AG diag(nu) (examples/example.jl:67, example3D.jl:61).
+# CSR from the library is the CSC of the transpose: build the transpose's CSC, then transpose back.
+using SparseArrays
+function _sparsify(M::FastMHIP, which::Symbol)
+    N = length(M.nu); nnz = Ref{Int64}(0)
+    check(ccall((:lsfc_sparsify_pattern, liblsfc), Cint, (Int64, Int64, Int64, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                M.n, M.m, M.l, nnz, C_NULL, C_NULL, C_NULL))
+    rowptr = Vector{Int64}(undef, N + 1); col = Vector{Int64}(undef, nnz[]); val = Vector{Complex{Float64}}(undef, nnz[])
+    ptrs = [which == w ? pointer(val) : Ptr{Complex{Float64}}(C_NULL) for w in (:As, :AG, :Msp)]
+    check(ccall((:lsfc_sparsify_build, liblsfc), Cint,
+                (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Ptr{Float64}, Cint),
+                M.plan, rowptr, col, ptrs[1], ptrs[2], ptrs[3], C_NULL, 0))
+    return copy(transpose(SparseMatrixCSC(N, N, rowptr .+ 1, col .+ 1, val)))
+end
+function _check_k(k, M::FastMHIP)
+    k == M.omega || throw(ArgumentError("k = $k differs from the k of the fast convolution ($(M.omega))"))
+end
+buildSparseAConv(k, X, Y, M::FastMHIP, n, m) = (_check_k(k, M); _sparsify(M, :As))
+buildSparseAGConv(k, X, Y, M::FastMHIP, n, m) = (_check_k(k, M); _sparsify(M, :AG))
+buildSparseA3DConv(k, X, Y, Z, M::FastMHIP, n, m, l) = (_check_k(k, M); _sparsify(M, :As))
+buildSparseAG3DConv(k, X, Y, Z, M::FastMHIP, n, m, l) = (_check_k(k, M); _sparsify(M, :AG))
+# Msp and As of one device call, for SparsifyingPreconditioner(Msp, As) / SparsifyingPreconditionerHIP(Msp, As)
+sparsifying_pair(M::FastMHIP) = (_sparsify(M, :Msp), _sparsify(M, :As))
+# the direct-sampling builders (sampleG rows with the caller's D0): a trapezoidal plan with nu = 0 on the grid
+function _direct_plan(k, X, Y, D0, n, m)
+    plan = Ref{Ptr{Cvoid}}(C_NULL); nuv = zeros(n * m)
+    check(ccall((:lsfc_plan_create_trap2d, liblsfc), Cint,
+                (Ref{Ptr{Cvoid}}, Int64, Int64, Float64, Float64, Float64, Float64, Float64, Float64, Ptr{Float64}, Cuint, Cint),
+                plan, n, m, X[1], Y[1], abs(X[2] - X[1]), k, real(D0), imag(D0), nuv, 0, 0))
+    FastMHIP(plan[], nuv, n, m, 1, k, "trapezoidal")
+end
+buildSparseA(k, X, Y, D0, n, m) = _sparsify(_direct_plan(k, X, Y, D0, n, m), :As)
+buildSparseAG(k, X, Y, D0, n, m) = _sparsify(_direct_plan(k, X, Y, D0, n, m), :AG)
+
 # SparsifyingPreconditioner(Msp, As) with the apply on the device -- src/preconditioner.jl:27-58, 132-170.
 # lu(Msp) stays on the host (UMFPACK, as in the reference); its factors go to the device once:
 # (F.Rs .* Msp)[F.p, F.q] == F.L * F.U.  CSR arrays of a SparseMatrixCSC X are the CSC arrays of transpose(X).

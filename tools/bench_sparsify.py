@@ -1,0 +1,168 @@
+"""Timing of the device assembly of the sparsifying matrices (lsfc_sparsify_build) and of the routes around it.
+
+For every case: the device build into device memory (kernels only, median of --reps after one warm build that also
+creates the plan's spatial kernel), the build into host memory (kernels + download of the CSR arrays), the singular
+value spread of the classes; where it fits, the route a Python user had before (rows through lsfc_sample_sources,
+one numpy SVD per class); at 3D 48^3 the host LU of Msp (scipy splu, in a child process under a time limit).
+One JSON line per measurement on stdout and appended to --out.
+
+    python tools/bench_sparsify.py --out profiles/sparsify_timing.jsonl"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def emit(out, rec):
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out:
+        with open(out, "a") as f:
+            f.write(line + "\n")
+
+
+def operator(ndim, n):
+    import fast_solver_lippmann_schwinger_amd as pkg
+    if ndim == 2:                                          # examples/example.jl: h = 1/(n-1), k = 1/h, trapezoidal
+        h = 1.0 / (n - 1)
+        x = -0.5 + h * np.arange(n)
+        nu = lambda X, Y: 0.3 * np.exp(-40 * (X ** 2 + Y ** 2)) * (np.abs(X) < 0.48) * (np.abs(Y) < 0.48)   # noqa: E731
+        return pkg.buildFastConvolution(x, x, h, 1.0 / h, nu, quadRule="trapezoidal")
+    h = 1.0 / n                                            # examples/example3D.jl: h = 1/n, k = 1/h, Greengard-Vico
+    x = -0.5 + h * np.arange(n)
+    X, Y, Z = (a.reshape(-1, order="F") for a in np.meshgrid(x, x, x, indexing="ij"))
+    nu = 0.3 * np.exp(-40 * (X ** 2 + Y ** 2 + Z ** 2)) * (np.abs(X) < 0.48) * (np.abs(Y) < 0.48) * (np.abs(Z) < 0.48)
+    return pkg.buildFastConvolution3D(x, x, x, None, None, None, h, 1.0 / h, nu)
+
+
+def device_build(M, nnz, N, nclass, reps):
+    import ctypes as C
+    import torch
+    import fast_solver_lippmann_schwinger_amd._lib as L
+    t = [torch.empty(N + 1, dtype=torch.int64, device="cuda"), torch.empty(nnz, dtype=torch.int64, device="cuda"),
+         torch.empty(nnz, dtype=torch.complex128, device="cuda"), torch.empty(nnz, dtype=torch.complex128, device="cuda"),
+         torch.empty(nnz, dtype=torch.complex128, device="cuda"), torch.empty(nclass * 3, dtype=torch.float64, device="cuda")]
+    p = [C.c_void_p(v.data_ptr()) for v in t]
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        L.check(L.load().lsfc_sparsify_build(M._plan, *p, L.LSFC_MEM_DEVICE))
+        torch.cuda.synchronize()
+        ms.append(1e3 * (time.perf_counter() - t0))
+    del t
+    torch.cuda.empty_cache()
+    return ms
+
+
+def host_build(M, reps, values):
+    import fast_solver_lippmann_schwinger_amd as pkg
+    ms, a = [], None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        a = pkg.sparsify_arrays(M, values)
+        ms.append(1e3 * (time.perf_counter() - t0))
+    return ms, a
+
+
+def user_route(M, ndim, n):
+    """rows via lsfc_sample_sources, then one numpy SVD per class (the assembly a user could write before)"""
+    import fast_solver_lippmann_schwinger_amd as pkg
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sparsify_ref as ref
+    dims = (n, n, 1) if ndim == 2 else (n, n, n)
+    N = int(np.prod(dims))
+    t0 = time.perf_counter()
+    for sA, _, _, _ in ref.classes(*dims):
+        S = np.asarray(sA) - 1
+        R = pkg.sampleG3D(0, None, None, None, S, M) if ndim == 3 else _rows2d(M, S)
+        comp = np.ones(N, bool)
+        comp[S] = False
+        np.linalg.svd(R[:, comp], full_matrices=False)
+    return 1e3 * (time.perf_counter() - t0)
+
+
+def _rows2d(M, S):
+    import ctypes as C
+    import fast_solver_lippmann_schwinger_amd._lib as L
+    out = np.empty((len(S), M.N), dtype=np.complex128)
+    src = np.ascontiguousarray(S, dtype=np.int64)
+    L.check(L.load().lsfc_sample_sources(M._plan, src.ctypes.data_as(C.c_void_p), len(S), out.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST))
+    return out
+
+
+SPLU_CHILD = r"""
+import sys, time, numpy as np, scipy.sparse as sp, scipy.sparse.linalg as spla
+d = np.load(sys.argv[1])
+N = d["rowptr"].size - 1
+A = sp.csr_matrix((d["val"], d["col"], d["rowptr"]), shape=(N, N)).tocsc()
+t0 = time.perf_counter()
+lu = spla.splu(A)
+print((time.perf_counter() - t0) * 1e3, lu.L.nnz + lu.U.nnz)
+"""
+
+
+def splu_time(a, limit, tmpdir):
+    path = os.path.join(tmpdir, "msp_csr.npz")
+    np.savez(path, rowptr=a["rowptr"], col=a["col"], val=a["Msp"])
+    try:
+        r = subprocess.run([sys.executable, "-c", SPLU_CHILD, path], capture_output=True, text=True, timeout=limit)
+        ms, fill = r.stdout.split()
+        return {"splu_ms": float(ms), "lu_nnz": int(fill)}
+    except subprocess.TimeoutExpired:
+        return {"splu_ms": None, "note": f"splu did not finish within {limit} s"}
+    finally:
+        os.remove(path)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cases", default="2:201,3:48,3:128,3:256")
+    ap.add_argument("--splu-limit", type=float, default=240.0)
+    ap.add_argument("--device-only", action="store_true", help="only the device builds (for a kernel trace)")
+    args = ap.parse_args()
+    import torch
+    import fast_solver_lippmann_schwinger_amd as pkg
+    for spec in args.cases.split(","):
+        ndim, n = (int(v) for v in spec.split(":"))
+        dims = (n, n, 1) if ndim == 2 else (n, n, n)
+        N = int(np.prod(dims))
+        nclass = 9 if ndim == 2 else 27
+        M = operator(ndim, n)
+        nnz = int(pkg.sparsify_pattern(*dims)[1].size) if N <= 200 ** 3 else (3 * n - 2) ** ndim
+        first = device_build(M, nnz, N, nclass, 1)[0]               # includes the spatial kernel (one convolution)
+        ms = device_build(M, nnz, N, nclass, args.reps)
+        rec = {"case": f"{ndim}D n={n}", "N": N, "nnz": nnz, "first_build_ms": round(first, 3),
+               "device_build_ms_median": round(float(np.median(ms)), 3), "device_build_ms_min": round(min(ms), 3)}
+        csr_bytes = (N + 1) * 8 + nnz * 8 + 2 * nnz * 16
+        if args.device_only:
+            emit(args.out, rec)
+            continue
+        if csr_bytes < 40e9:
+            hms, a = host_build(M, args.reps if N <= 128 ** 3 else 2, ("As", "Msp"))
+            sig = a["sigma"]
+            rec.update({"host_build_ms_median": round(float(np.median(hms)), 3), "host_csr_MB": round(csr_bytes / 1e6, 1),
+                        "sigma_min_over_max": [float((sig[:, 2] / sig[:, 0]).min()), float((sig[:, 2] / sig[:, 0]).max())],
+                        "sigma_gap_min": float((sig[:, 1] / sig[:, 2]).min())})
+        else:
+            a = None
+        emit(args.out, rec)
+        if N * 27 * 16 <= 4e9:
+            emit(args.out, {"case": rec["case"], "user_route_sample_sources_numpy_svd_ms": round(user_route(M, ndim, n), 1)})
+        if ndim == 3 and n == 48 and a is not None:
+            emit(args.out, {"case": rec["case"], **splu_time(a, args.splu_limit, os.path.dirname(os.path.abspath(args.out or ".")))})
+        del a, M
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
