@@ -282,6 +282,7 @@ struct TriFactor {                 // one triangular factor, rows in level order
     std::vector<Run> runs;
     DevBuf<cplx> rdense, racc, rx;
     int ngroups = 0;
+    int64_t sched[10] = {};        // what the schedule reached (lsfc_precond_schedule, include/lsfc.h)
 };
 
 static int narrow_rows() {               // levels with at most this many rows (default 32: 42 -> 37 ms at N = 263 169 against
@@ -425,6 +426,18 @@ static void build_factor(TriFactor& F, int64_t N, const int64_t* rowptr, const i
     F.gacc.alloc(GROUP_ROWS);
     up(F.rdense, rdense); F.racc.alloc(RUN_MAX); F.rx.alloc(RUN_MAX);
     F.h_lvlptr = lvlptr; F.nlevels = nlev; F.ngroups = (int)grpdense.size();
+    // schedule counts: kind-0 levels by lanes per row, chain segments and their multi-level groups, heavy groups, run pieces
+    for (const auto& sg : F.segs) {
+        if (sg.kind == 0) ++F.sched[sg.lpr == 64 ? 3 : (sg.lpr == 32 ? 2 : (sg.lpr == 16 ? 1 : 0))];
+        else if (sg.kind == 1) { ++F.sched[4]; for (int gi = sg.l0; gi < sg.l1; ++gi) F.sched[5] += grpdense[(size_t)gi] >= 0; }
+        else if (sg.kind == 2) ++F.sched[6];
+        else {
+            const int R = F.runs[(size_t)sg.l0].R;
+            F.sched[8] = F.sched[7] ? std::max<int64_t>(F.sched[8], R) : R;
+            F.sched[9] = F.sched[7] ? std::min<int64_t>(F.sched[9], R) : R;
+            ++F.sched[7];
+        }
+    }
 }
 
 static void launch_factor(const TriFactor& F, const cplx* b, cplx* x, hipStream_t st) {
@@ -613,6 +626,15 @@ int lsfc_precond_stats(const lsfc_precond* pc, int64_t* levels_L, int64_t* level
         if (levels_L) *levels_L = pc->L.nlevels;
         if (levels_U) *levels_U = pc->U.nlevels;
         if (launches) *launches = pc->launches;
+    });
+}
+
+int lsfc_precond_schedule(const lsfc_precond* pc, int factor, int64_t out[10]) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && out, "NULL argument");
+        LSFC_REQUIRE(factor == 0 || factor == 1, "bad factor %d (0 = L, 1 = U)", factor);
+        const lsfc::TriFactor& F = factor == 0 ? pc->L : pc->U;
+        for (int i = 0; i < 10; ++i) out[i] = F.sched[i];
     });
 }
 

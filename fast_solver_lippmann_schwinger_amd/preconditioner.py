@@ -16,6 +16,11 @@ import numpy as np
 from . import _lib as L
 
 
+# lsfc_precond_schedule's ten counts (include/lsfc.h), in order
+SCHEDULE_FIELDS = ("level8", "level16", "level32", "level64", "chains", "chain_groups", "heavy_groups", "run_pieces",
+                   "run_max", "run_min")
+
+
 def _csr_arrays(A):
     A = A.tocsr()
     A.sort_indices()
@@ -83,10 +88,17 @@ class SparsifyingPreconditioner:
         L.check(L.load().lsfc_precond_set_stream(self._pc, C.c_void_p(int(stream))))
 
     def stats(self):
-        """dependency levels of the L and U solves, kernel launches captured in the graph"""
+        """dependency levels of the L and U solves, kernel launches captured in the graph, and what the launch schedule
+        of each solve reached (schedule_L / schedule_U, SCHEDULE_FIELDS of lsfc_precond_schedule)"""
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        L.check(L.load().lsfc_precond_stats(self._pc, C.byref(a), C.byref(b), C.byref(c)))
-        return {"levels_L": a.value, "levels_U": b.value, "launches": c.value, "nnz_L": self.nnz_L, "nnz_U": self.nnz_U}
+        lib = L.load()
+        L.check(lib.lsfc_precond_stats(self._pc, C.byref(a), C.byref(b), C.byref(c)))
+        st = {"levels_L": a.value, "levels_U": b.value, "launches": c.value, "nnz_L": self.nnz_L, "nnz_U": self.nnz_U}
+        for factor, name in ((0, "schedule_L"), (1, "schedule_U")):
+            out = (C.c_int64 * len(SCHEDULE_FIELDS))()
+            L.check(lib.lsfc_precond_schedule(self._pc, factor, out))
+            st[name] = dict(zip(SCHEDULE_FIELDS, out))
+        return st
 
     def close(self):
         if getattr(self, "_pc", None):

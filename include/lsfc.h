@@ -225,6 +225,18 @@ int lsfc_precond_apply(lsfc_precond* pc, double* v, int memspace);
 int lsfc_precond_callback(void* user, double* v, int64_t n);
 /* dependency levels of the two triangular solves and kernel launches captured in the graph */
 int lsfc_precond_stats(const lsfc_precond* pc, int64_t* levels_L, int64_t* levels_U, int64_t* launches);
+/* What the launch schedule of one triangular solve reached (factor 0 = L, 1 = U), fixed at lsfc_precond_create.
+ * The rows of a factor are sorted by dependency level and the levels cut into four kinds of segments:
+ *     out[0..3]  levels launched on their own (more than 32 rows -- LSFC_PRECOND_NARROW -- or more than 8192 entries) at
+ *                8, 16, 32, 64 lanes per row
+ *     out[4]     chain segments: runs of narrow, light levels walked by one workgroup
+ *     out[5]     groups of several levels (<= 16 rows, coupled through a dense block) inside the chain segments
+ *     out[6]     heavy groups: such a group with more than 8192 entries, launched on its own between chain segments
+ *     out[7]     dense-run pieces: >= 96 rows in consecutive levels of <= 4 rows, cut into pieces of <= 1024 rows
+ *     out[8]     rows of the largest dense-run piece (0 if none)
+ *     out[9]     rows of the smallest dense-run piece (0 if none)
+ * LSFC_EINVAL: NULL pc or out, factor not 0 or 1. */
+int lsfc_precond_schedule(const lsfc_precond* pc, int factor, int64_t out[10]);
 
 /* ---- assembly of the sparsifying matrices (As, As*G, Msp) ------------------- */
 
