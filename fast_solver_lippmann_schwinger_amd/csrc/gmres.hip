@@ -359,8 +359,14 @@ void solve(Team& T, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap
         zc acc(0);
         for (int i = 0; i < k; ++i) acc += std::conj(nullvec[i]) * H[i + (size_t)ldh * (k - 1)];
         nullvec[k] = -std::conj(acc / nrm);
-        accumulator += std::norm(nullvec[k]);
-        current = beta / std::sqrt(accumulator);
+        // an exhausted Krylov space (H[k+1,k] == 0, or an entry that overflows) holds the exact solution: converged, as
+        // numpy's abs(inf + nan im)^2 == inf has it, where std::norm gives NaN (GMRES); the least squares
+        // below uses columns 1..k only, so the unnormalisable v_{k+1} is never read
+        if (nrm == 0.0 || !std::isfinite(nullvec[k].real()) || !std::isfinite(nullvec[k].imag())) current = 0.0;
+        else {
+            accumulator += std::norm(nullvec[k]);
+            current = beta / std::sqrt(accumulator);
+        }
         ++k;
 
         if (k == restart + 1 || current <= tol) {
