@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fastconv applies/s on the 3D n=512^3 fp64 operator (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" is one pass of the hot path, y = x + omega^2 * G * (nu .* x) (FastM3D `*`,
 src/FastConvolution3D.jl:31-37 of the reference), on a synthetic contrast with the vectors
@@ -13,11 +13,13 @@ before anything in this process touches the GPU) and relays rank 0's line.  `--s
 the N-GPU job from ONE host process instead (lsfc_plan_create_gv3d_multi: the form a single Julia
 host uses).  Rank 0 prints ONE JSON line.
 
-Before any throughput is reported the same build is checked against the CPU oracle on the bench's own
-(nu, omega) recipe at n = 64 and n = 128 (n = 64 only when N > 1): relative l2 > 1e-10 aborts the run.
-The CPU baseline (the numpy/scipy oracle, a port of the reference arithmetic -- the reference itself
-is Julia and cannot run here) is timed on rank 0 at N = 1 only, on a bounded sample, and is never
-the thing measured as `value`.
+A plain run does only what its headline figure needs: it builds the plan and the inputs, runs the W warm-up and the K timed
+steps, writes --dump-outputs and prints the line.  `--full` adds the rest:
+before any throughput is reported the same build is checked against the CPU oracle on the bench's own (nu, omega) recipe at
+n = 64 and n = 128 (n = 64 only when N > 1): relative l2 > 1e-10 aborts the run.  After the timed steps the per-stage HIP-event
+profile of one apply gives the roofline (and, at N > 1, the un-overlapped exchange times), and the CPU baseline (the numpy/scipy
+oracle, a port of the reference arithmetic -- the reference itself is Julia and cannot run here) is timed on rank 0 at N = 1 only,
+on a bounded sample; it is never the thing measured as `value`.
 """
 import argparse
 import json
@@ -26,6 +28,7 @@ import socket
 import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -40,7 +43,10 @@ DUMP_SEED = 7
 
 
 def synthetic_nu(n, lo, hi):
-    """Sum of 8 Gaussians on z-planes [lo, hi) of the half-open unit box grid."""
+    """Sum of 8 Gaussians on z-planes [lo, hi) of the half-open unit box grid.
+
+    The sum is formed a plane or a few at a time, on a few threads: every point still adds the same eight products,
+    ((a * gz) * gy) * gx, in the same order to 0.0, so the array is bitwise what the whole-volume expression gives."""
     rng = np.random.default_rng(1234)
     cen = rng.uniform(-0.3, 0.3, size=(8, 3))
     amp = rng.uniform(-0.3, 0.3, size=8)
@@ -49,11 +55,20 @@ def synthetic_nu(n, lo, hi):
     x = -0.5 + h * np.arange(n)
     z = x[lo:hi]
     out = np.zeros((hi - lo, n, n))          # [z][y][x]  == column-major (x fastest) flat order
-    for c, a, b in zip(cen, amp, beta):
-        gx = np.exp(-b * (x - c[0]) ** 2)
-        gy = np.exp(-b * (x - c[1]) ** 2)
-        gz = np.exp(-b * (z - c[2]) ** 2)
-        out += a * gz[:, None, None] * gy[None, :, None] * gx[None, None, :]
+    terms = [(a, np.exp(-b * (z - c[2]) ** 2), np.exp(-b * (x - c[1]) ** 2), np.exp(-b * (x - c[0]) ** 2))
+             for c, a, b in zip(cen, amp, beta)]
+
+    def planes(k0, k1):
+        o = out[k0:k1]
+        t = np.empty_like(o)
+        for a, gz, gy, gx in terms:
+            np.multiply(a * gz[k0:k1, None, None] * gy[None, :, None], gx[None, None, :], out=t)
+            o += t
+
+    step = max(1, (1 << 17) // (n * n))      # about 1 MiB of out per piece (one plane at n >= 363)
+    cuts = list(range(0, hi - lo, step)) + [hi - lo]
+    with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1, len(cuts) - 1))) as ex:
+        list(ex.map(planes, cuts[:-1], cuts[1:]))
     return out.reshape(-1)
 
 
@@ -222,14 +237,70 @@ def parity_gate(lsfc, sizes, rank, world, local_rank, dist, multi_devices=None):
     return worst
 
 
-def main():
+def roofline_of(stages, traffic_applies):
+    """the roofline object of the --full line from the per-stage profile [(name, ms, algorithmic bytes)]; the PMC traffic
+    of profiles/traffic_latest.json is quoted where it was measured (one GPU, n = 512)"""
+    # dominant COMPUTE kernel (the un-overlapped all-to-all stages of the multi-GPU profile are listed, not ranked:
+    # they are bounded by the xGMI links, not by HBM)
+    dom = max((s for s in stages if not s[0].startswith("alltoall")), key=lambda s: s[1])
+    traffic, traffic_src = None, None
+    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+    if os.path.exists(tpath) and traffic_applies:
+        try:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            from csrc_hash import csrc_hash
+            rec = json.load(open(tpath))
+            if rec.get("_csrc_sha256") == csrc_hash(ROOT):
+                traffic = rec.get(dom[0])
+                traffic_src = ("profiles/traffic_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/one_apply.py 512 "
+                               "(tools/pmc_traffic.sh) on the kernel sources of THIS build (sha256 of csrc/ matches; per launch; not collected "
+                               "in this run -- counters need the profiler)")
+            else:
+                traffic_src = ("null: profiles/traffic_latest.json was measured on other kernel sources (sha256 of csrc/ differs) -- re-run "
+                               "tools/pmc_traffic.sh on this build")
+        except Exception as e:
+            traffic, traffic_src = None, f"null: {e}"
+    return {"bound": "hbm", "kernel": dom[0], "achieved": dom[2] / (dom[1] * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": dom[2] / (dom[1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
+            "traffic_over_algorithmic": (traffic / dom[2]) if traffic else None,
+            "algorithmic_bytes_per_launch": dom[2], "avg_launch_ms": dom[1],
+            "stages": [{"kernel": s[0], "ms": s[1], "GBps": s[2] / (s[1] * 1e-3) / 1e9} for s in stages]}
+
+
+def multi_timed(multi, steps, warmup):
+    """the timed applies of a multi-device plan (MultiDeviceFastM3D.bench without its per-stage profile): `steps` applies
+    on device-resident slabs, a host clock around the enqueue + a synchronisation of every device; -> (seconds, slabs
+    of y of the last timed apply)"""
+    import torch
+    ln = multi.local_n
+    xs, ys = [], []
+    for r, d in enumerate(multi.devices):
+        g = torch.Generator(device=f"cuda:{d}"); g.manual_seed(20250224 + r)
+        xs.append(torch.randn(ln, dtype=torch.complex128, device=f"cuda:{d}", generator=g))
+        ys.append(torch.empty(ln, dtype=torch.complex128, device=f"cuda:{d}"))
+    for d in set(multi.devices):
+        torch.cuda.synchronize(d)
+    for _ in range(warmup):
+        multi.apply_dev(xs, ys)
+    multi.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        multi.apply_dev(xs, ys)
+    multi.synchronize()
+    return time.perf_counter() - t0, ys
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--n", type=int, default=int(os.environ.get("LSFC_BENCH_N", 512)))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-gate", action="store_true", help="skip the oracle check (profiling runs only; the line then says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity gate against the CPU oracle before the timed "
+                         "steps, the per-stage profile (roofline, exchange times) and the CPU baseline after them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity-gate", action="store_true", help="with --full: skip the oracle check (profiling runs only; the line then says so)")
     ap.add_argument("--force-dist", action="store_true", help="use the distributed plan even with one rank (rehearsal of the multi-GPU path)")
     ap.add_argument("--single-process", action="store_true", help="drive all --gpus devices from this one process (multi-device plan)")
     ap.add_argument("--devices", type=str, default="", help="with --single-process: comma-separated device ids, one per rank; a device may repeat "
@@ -238,9 +309,14 @@ def main():
                     help=f"after the timed steps write y of the last one to DIR/y.npy as float64 (re, im) rows: every point in flat order "
                          f"when n^3 <= {DUMP_POINTS}, else the {DUMP_POINTS} points np.random.default_rng({DUMP_SEED}).choice(n^3, "
                          f"{DUMP_POINTS}, replace=False), sorted")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -263,13 +339,29 @@ def main():
             os._exit(3)
         threading.Thread(target=_watchdog, daemon=True).start()
 
-    import torch
-    import fast_solver_lippmann_schwinger_amd as lsfc
-
     n = args.n
     N = n ** 3
     h = 1.0 / n
     omega = 1.0 / h                      # omega = 1/h = 512, min|s-k| = 9.3e-5
+    multi_devs = None
+    if args.single_process and args.gpus > 1:
+        multi_devs = [int(d) for d in args.devices.split(",")] if args.devices else list(range(args.gpus))
+        if len(multi_devs) != args.gpus:
+            raise SystemExit(f"--devices lists {len(multi_devs)} ids for --gpus {args.gpus}")
+        world_eff = args.gpus
+    else:
+        single = world == 1 and not args.force_dist          # the single-GPU plan; else the distributed one, even with one rank
+        world_eff = 1 if single else world
+        # this rank's slab of x is drawn on a thread of its own from here on (one seeded stream, several seconds at n = 512;
+        # numpy's generator releases the GIL), beside the imports, the contrast and the plan build
+        lo, hi = rank * n // world_eff, (rank + 1) * n // world_eff
+        pool = ThreadPoolExecutor(max_workers=1)
+        xvec = pool.submit(bench_vector, n, lo, hi)
+        pool.shutdown(wait=False)
+
+    import torch
+    import fast_solver_lippmann_schwinger_amd as lsfc
+
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
 
@@ -279,45 +371,36 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
 
     parity = None
-    multi_devs = None
-    if args.single_process and args.gpus > 1:
-        multi_devs = [int(d) for d in args.devices.split(",")] if args.devices else list(range(args.gpus))
-        if len(multi_devs) != args.gpus:
-            raise SystemExit(f"--devices lists {len(multi_devs)} ids for --gpus {args.gpus}")
-    if not args.no_parity_gate:
+    if args.full and not args.no_parity_gate:
         parity = parity_gate(lsfc, [64, 128] if (world == 1 and multi_devs is None) else [64], rank, world, local_rank,
                              dist if world > 1 else None, multi_devs)
 
     nu_host = None
     multi = None
-    if args.single_process and args.gpus > 1:
+    if multi_devs is not None:
         from fast_solver_lippmann_schwinger_amd.distributed import MultiDeviceFastM3D
         nu_host = synthetic_nu(n, 0, n)
         multi = MultiDeviceFastM3D(n, h, omega, nu_host, devices=multi_devs)
-        world_eff = args.gpus
-    elif world == 1 and not args.force_dist:
+    elif single:
         nu_host = synthetic_nu(n, 0, n)
         x = -0.5 + h * np.arange(n)
         M = lsfc.buildFastConvolution3D(x, x, x, None, None, None, h, omega, nu_host, device=local_rank)
-        nloc = N
-        world_eff = 1
     else:
         from fast_solver_lippmann_schwinger_amd.distributed import build_distributed_3d
-        lo, hi = rank * n // world, (rank + 1) * n // world
         M = build_distributed_3d(n, h, omega, synthetic_nu(n, lo, hi), rank, world, local_rank)
-        nloc = (hi - lo) * n * n
-        world_eff = world
 
+    stages = None
     if multi is not None:
-        out = multi.bench(args.steps, args.warmup)
-        elapsed, stages = out["elapsed_s"], out["stages"]
+        elapsed, ys = multi_timed(multi, args.steps, args.warmup)
         pipeline, padded = "pruned-hip", list(multi.padded_dims)
         nloc = N // args.gpus
         if args.dump_outputs:
-            ydump = gather_points(dump_indices(N), [(r * multi.local_n, y) for r, y in enumerate(out["ys"])]).cpu().numpy()
+            ydump = gather_points(dump_indices(N), [(r * multi.local_n, y) for r, y in enumerate(ys)]).cpu().numpy()
+        if args.full:
+            stages = lsfc.profile_apply(multi, None, None, reps=3)
     else:
-        lo = rank * n // world_eff
-        xb = torch.from_numpy(bench_vector(n, lo, lo + nloc // (n * n))).to(dev)
+        nloc = (hi - lo) * n * n
+        xb = torch.from_numpy(xvec.result()).to(dev)
         yb = torch.empty_like(xb)
 
         def sync():
@@ -345,12 +428,12 @@ def main():
             if dist is not None:
                 dist.all_reduce(torch.view_as_real(yd))     # each point is held by one rank, the others add zeros
             ydump = yd.cpu().numpy()
-        # per-kernel roofline: HIP events on the plan's stream around every stage of one apply.  With more than one
-        # rank the stages contain collectives, so a failure must take the whole job down (no per-rank try/except:
+        # per-kernel roofline (--full): HIP events on the plan's stream around every stage of one apply.  With more than
+        # one rank the stages contain collectives, so a failure must take the whole job down (no per-rank try/except:
         # a rank that skipped them would leave the others blocked in ncclRecv).
-        if world_eff > 1:
+        if args.full and world_eff > 1:
             stages = lsfc.profile_apply(M, xb, yb, reps=5)
-        else:
+        elif args.full:
             try:
                 stages = lsfc.profile_apply(M, xb, yb, reps=5)
             except Exception as e:                   # never lose the headline line to the optional per-stage profile
@@ -360,32 +443,6 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     value = args.steps / elapsed
-
-    # dominant COMPUTE kernel (the un-overlapped all-to-all stages of the multi-GPU profile are listed, not ranked:
-    # they are bounded by the xGMI links, not by HBM)
-    dom = max((s for s in stages if not s[0].startswith("alltoall")), key=lambda s: s[1])
-    traffic, traffic_src = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tpath) and world_eff == 1 and n == 512:
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from csrc_hash import csrc_hash
-            rec = json.load(open(tpath))
-            if rec.get("_csrc_sha256") == csrc_hash(ROOT):
-                traffic = rec.get(dom[0])
-                traffic_src = ("profiles/traffic_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/one_apply.py 512 "
-                               "(tools/pmc_traffic.sh) on the kernel sources of THIS build (sha256 of csrc/ matches; per launch; not collected "
-                               "in this run -- counters need the profiler)")
-            else:
-                traffic_src = ("null: profiles/traffic_latest.json was measured on other kernel sources (sha256 of csrc/ differs) -- re-run "
-                               "tools/pmc_traffic.sh on this build")
-        except Exception as e:
-            traffic, traffic_src = None, f"null: {e}"
-    roofline = {"bound": "hbm", "kernel": dom[0], "achieved": dom[2] / (dom[1] * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": dom[2] / (dom[1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
-                "traffic_over_algorithmic": (traffic / dom[2]) if traffic else None,
-                "algorithmic_bytes_per_launch": dom[2], "avg_launch_ms": dom[1],
-                "stages": [{"kernel": s[0], "ms": s[1], "GBps": s[2] / (s[1] * 1e-3) / 1e9} for s in stages]}
     whole = BYTES_PER_POINT * N / (ms_per_step * 1e-3) / 1e9
 
     out = {"metric": "fastconv applies/sec, 3D n=512^3 fp64 (FastM3D apply)" if n == 512 else f"fastconv applies/sec, 3D n={n}^3 fp64",
@@ -400,9 +457,10 @@ def main():
                                       + ((f"ONE host process driving devices {multi.devices}" + (" -- REHEARSAL: ranks share a GPU, not a multi-GPU measurement" if len(set(multi.devices)) < len(multi.devices) else ""))
                                          if multi is not None else "one process per GPU, RCCL send/recv"))},
            "achieved_algorithmic_GBps_per_gpu": whole / world_eff, "hbm_roofline_frac_whole_apply": whole / world_eff / HBM_PEAK_GBPS,
-           "parity_rel_l2": parity if parity is not None else "gate skipped (--no-parity-gate)",
-           "parity_tol": PARITY_TOL,
-           "roofline": roofline}
+           "parity_rel_l2": parity if parity is not None else ("gate skipped (--no-parity-gate)" if args.full else "gate not run (run with --full)"),
+           "parity_tol": PARITY_TOL}
+    if stages is not None:
+        out["roofline"] = roofline_of(stages, world_eff == 1 and n == 512)
     if world_eff > 1:
         # the two slab transposes of an apply move 2 * 2N complex in total; rank p sends 2N*16 B*(P-1)/P^2 per transpose
         # over its P-1 direct xGMI links (one link per GPU pair).  A model, not a measurement: see DESIGN.md section 5.
@@ -411,6 +469,7 @@ def main():
                              "ms_at_76.8_GBps_per_direction": per_link / 76.8e9 * 1e3,
                              "note": "xGMI time floor of the two all-to-all transposes at the nominal per-direction link rate; "
                                      "the apply cannot be faster than this however well it overlaps"}
+    if world_eff > 1 and stages is not None:
         # what the transport saw: the un-overlapped exchange stages of the per-stage profile
         ex = {s[0]: s[1] for s in stages if s[0].startswith("alltoall")}
         out["exchange"] = {"nranks": world_eff, "transport": (multi.transport if multi is not None else "rccl send/recv, pairwise schedule"),
@@ -418,7 +477,7 @@ def main():
                            "achieved_GBps_per_link_per_direction": {k: (per_link / 2) / (v * 1e-3) / 1e9 for k, v in ex.items() if v > 0},
                            "note": "each exchange ships bytes_per_link_per_direction_per_apply / 2 over every one of the P-1 links of a GPU; "
                                    "production applies overlap the exchanges with the y/z passes (K pipeline chunks)"}
-    if world_eff == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world_eff == 1 and rank == 0 and not args.no_cpu_baseline:
         cb = cpu_baseline(n, nu_host, xb.cpu().numpy())
         if cb is not None:
             out["cpu_baseline"] = cb

@@ -210,15 +210,15 @@ def test_multi_device_plan_argument_errors(lsfc):
 
 
 def test_bench_single_process_rehearsal(lsfc):
-    # bench.py --single-process with two logical ranks on device 0 (peer-copy transport): the N > 1 line carries the
-    # exchange object and says that it is a rehearsal
+    # bench.py --full --single-process with two logical ranks on device 0 (peer-copy transport): the N > 1 line carries
+    # the exchange object and says that it is a rehearsal
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--single-process", "--devices", "0,0", "--n", "64",
-                        "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+                        "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and "REHEARSAL" in line["config"]["parallelism"]
