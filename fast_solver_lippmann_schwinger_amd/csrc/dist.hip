@@ -42,7 +42,8 @@ static void phase1(lsfc_plan* p, const cplx* x, bool use_nu, hipStream_t st, int
     const DistState* d = p->dist.get();
     const int64_t all = (int64_t)p->dims[1] * d->lz, nl = part < 0 ? all : all / 2, l0 = part == 1 ? all / 2 : 0;
     // chunk width Wc: storage index s of a line lands in block s / Wc = dest_rank * K + chunk
-    pruned_xfwd(p->pads[0], p->tuning, x + l0 * p->dims[0], use_nu ? p->nu.p + l0 * p->dims[0] : nullptr, d->S1.p + l0 * d->Wc, p->tw[0].p,
+    VecBatch vb{}; vb.x[0] = x + l0 * p->dims[0];
+    pruned_xfwd(p->pads[0], p->tuning, vb, 1, 0, use_nu ? p->nu.p + l0 * p->dims[0] : nullptr, d->S1.p + l0 * d->Wc, p->tw[0].p,
                 nl, d->Wc, d->Wc, p->dims[0], st, all * d->Wc);
 }
 static void phase2_yfwd(lsfc_plan* p, int c, hipStream_t st) {
@@ -53,10 +54,7 @@ static void phase2_yfwd(lsfc_plan* p, int c, hipStream_t st) {
 }
 static void phase2_zfused(lsfc_plan* p, int c, hipStream_t st) {
     const DistState* d = p->dist.get();
-    const int Ly = p->pads[1], Lz = p->pads[2], l = p->dims[2];
-    pruned_zfused(Lz, p->tuning, p->A2.p + (int64_t)c * (d->Wc / 8) * Ly * p->pitch2, p->sym.p + (int64_t)c * d->Wc * p->sym_rows * p->sym_hz, p->tw[2].p, p->twl[2].p, d->Wc, Ly,
-                  (int64_t)p->pitch2 * Ly, (int64_t)p->pitch2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8, p->ytab.p,
-                  p->zmirror.p, l, st);
+    plan_zfused_3d(p, d->Wc, (int64_t)c * (d->Wc / 8) * p->pads[1] * p->pitch2, (int64_t)c * d->Wc * p->sym_rows * p->sym_hz, 1, st);
 }
 static void phase2_yinv(lsfc_plan* p, int c, hipStream_t st) {
     const DistState* d = p->dist.get();
@@ -68,7 +66,8 @@ static void phase2(lsfc_plan* p, int c, hipStream_t st) { phase2_yfwd(p, c, st);
 static void phase3(lsfc_plan* p, const cplx* x, cplx* y, double alpha, double beta, hipStream_t st, int part = -1) {
     const DistState* d = p->dist.get();
     const int64_t all = (int64_t)p->dims[1] * d->lz, nl = part < 0 ? all : all / 2, l0 = part == 1 ? all / 2 : 0;
-    pruned_xinv(p->pads[0], p->tuning, d->S1.p + l0 * d->Wc, x + l0 * p->dims[0], y + l0 * p->dims[0], alpha, beta, p->tw[0].p,
+    VecBatch vb{}; vb.x[0] = x + l0 * p->dims[0]; vb.y[0] = y + l0 * p->dims[0];
+    pruned_xinv(p->pads[0], p->tuning, d->S1.p + l0 * d->Wc, vb, 1, 0, alpha, beta, p->tw[0].p,
                 nl, d->Wc, d->Wc, p->dims[0], st, all * d->Wc);
 }
 

@@ -663,42 +663,41 @@ template <class C, bool SPLIT, int WPE> static void yinv_t(const PrunedTuning& t
     int TG, TZ; ytile(tn, C::L, Lx / LINES, l, TG, TZ);
     hipLaunchKernelGGL(k, dim3((unsigned)((Lx / LINES) * l), (unsigned)nrhs), dim3(C::T * LINES), lds, st, a2, a1, tw, Lx, m, l, TG, TZ, p1, p2, b1, b2);
 }
-template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false> static void zfused_t(cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, int Lx, int nouter,
-                                                    int64_t dTile, int64_t dOuter, int64_t dLine, int64_t sTile, int64_t sOuter, int64_t sLine,
-                                                    const int2* ytab, const int* zm, int nin, hipStream_t st, int nrhs, int64_t dBatch) {
-    // dTile/sTile are strides per XB-tile of x'; a workgroup covers LINES of the XB lines of a tile.
+template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false> static void zfused_t(cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
+                                                    const FusedGeom& g, hipStream_t st, int nrhs, int64_t dBatch) {
+    // g.dTile / g.sTile are strides per XB-tile of x'; a workgroup covers LINES of the XB lines of a tile.
     // twl != NULL: full stage-twiddle table, staged in LDS by the kernel.
     constexpr int LINES = Tune<C>::LINES;
     static_assert(XB % LINES == 0, "LINES must divide XB");
     using LL = LdsLayout<LINES, 3, SPLIT>;
     size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = (nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, false>;
+    auto k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, false>;
     if (twl && lds + (size_t)C::TWLEN * sizeof(cplx) > (size_t)160 * 1024) twl = nullptr;   // table does not fit beside the exchange buffer
     if (twl) {
-        k = (nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, true> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, true>;
+        k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, true> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, true>;
         lds += (size_t)C::TWLEN * sizeof(cplx);
         tw = twl;
     }
     if (nrhs > 1) {
         // batch: one symbol load per tile for all right-hand sides (the symbol is always loaded up front there, so the
         // PREFETCH flavours share one instantiation)
-        if (twl) k = (nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, true, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, true, true>;
-        else     k = (nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, false, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, false, true>;
+        if (twl) k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, true, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, true, true>;
+        else     k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, false, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, false, true>;
     }
     allow_lds(k, lds);
     if (LINES == XB) {
-        hipLaunchKernelGGL(k, dim3((unsigned)((Lx / XB) * nouter)), dim3(C::T * LINES), lds, st, data, sym, tw, nouter,
-                           dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, nrhs, dBatch,
+        hipLaunchKernelGGL(k, dim3((unsigned)((g.Lx / XB) * g.nouter)), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
+                           g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, nrhs, dBatch,
                            // (pairing a row with its mirror row on one XCD here too -- blocks b and b + 8 -- measured neutral on the
                            // one-tile and the multi-right-hand-side forms at 48^3 ... 256^3: left off)
                            0);
     } else {
         // split each tile into XB/LINES sub-groups: sub-group h starts at xi offset h*LINES
         // (tile, sub-group) collapse to one group index only when tiles are XB-contiguous in xi (2D natural layout)
-        LSFC_REQUIRE(dTile == XB && sTile == XB, "sub-tile groups need the natural (2D) layout");
-        hipLaunchKernelGGL(k, dim3((unsigned)((Lx / LINES) * nouter)), dim3(C::T * LINES), lds, st, data, sym, tw, nouter,
-                           (int64_t)LINES, dOuter, dLine, (int64_t)LINES, sOuter, sLine, ytab, zm, nin, nrhs, dBatch,
-                           (XB / LINES == 2 && nouter == 1 && (Lx / LINES) % 16 == 0 && !env_flag_no_sibling_pairs()) ? 1 : 0);
+        LSFC_REQUIRE(g.dTile == XB && g.sTile == XB, "sub-tile groups need the natural (2D) layout");
+        hipLaunchKernelGGL(k, dim3((unsigned)((g.Lx / LINES) * g.nouter)), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
+                           (int64_t)LINES, g.dOuter, g.dLine, (int64_t)LINES, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, nrhs, dBatch,
+                           (XB / LINES == 2 && g.nouter == 1 && (g.Lx / LINES) % 16 == 0 && !env_flag_no_sibling_pairs()) ? 1 : 0);
     }
 }
 
@@ -709,40 +708,39 @@ static int cu_count() {
     return cus;
 }
 static unsigned* ticket_set(hipStream_t st);
-template <class C, bool SPLIT, bool LATE_SYM = false, bool TICKETS = false> static void zfused_persist_t(cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, int Lx, int nouter,
-                                                            int64_t dTile, int64_t dOuter, int64_t dLine, int64_t sTile, int64_t sOuter, int64_t sLine,
-                                                            const int2* ytab, const int* zm, int nin, hipStream_t st, int xl = 0) {
+template <class C, bool SPLIT, bool LATE_SYM = false, bool TICKETS = false> static void zfused_persist_t(cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
+                                                            const FusedGeom& g, hipStream_t st, int xl = 0) {
     constexpr int LINES = XB;
     using LL = LdsLayout<LINES, 3, SPLIT>;
     size_t lds = persist_xbuf_bytes<C, LINES, SPLIT, false>();
     if (twl && lds + (size_t)C::TWLEN * sizeof(cplx) > (size_t)160 * 1024) twl = nullptr;
-    auto k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS>;
+    auto k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS>;
     if (twl) {
-        k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS>;
+        k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS>;
         lds += (size_t)C::TWLEN * sizeof(cplx);
         tw = twl;
     }
     // lane exchanges between stages of equal radix (whole-complex whole tiles, symbol after the first stage: the 512^3 and 256^3 forms)
     if constexpr (xlane_ok<C, LL>() && !SPLIT && LATE_SYM) {
         if (xl == 1) {
-            if (twl) k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
-            else     k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS, 1>;
+            if (twl) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
+            else     k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS, 1>;
         } else if (xl >= 2 && twl) {
             // 3: + mirror symbol values from L2 (XL & 2; measured slower, profiles/r03_experiment_fused_pass_variants.log)
-            if (xl == 5 && TICKETS) k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 5> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 5>;
-            else if (xl == 3) k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 3> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 3>;
-            else k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
+            if (xl == 5 && TICKETS) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 5> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 5>;
+            else if (xl == 3) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 3> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 3>;
+            else k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
         }
     }
     if (TICKETS) lds += 16;                             // the ticket slots
     allow_lds(k, lds);
     const int cus = cu_count();
-    const unsigned ntiles = (unsigned)((Lx / XB) * nouter);
+    const unsigned ntiles = (unsigned)((g.Lx / XB) * g.nouter);
     // workgroups per CU that fit (LDS-limited); the walk stays interleaved so that co-resident workgroups touch neighbouring tiles
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, ((size_t)160 * 1024) / lds));
     const unsigned grid = std::min<unsigned>(ntiles, (unsigned)(cus * per_cu));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, data, sym, tw, nouter,
-                       dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, ntiles, TICKETS ? ticket_set(st) : (unsigned*)nullptr);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
+                       g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, ntiles, TICKETS ? ticket_set(st) : (unsigned*)nullptr);
 }
 // Ticket counters of the half-tile pass: 8 (one per XCD) per launch, zeroed on the launch's stream just before it.  A ring of
 // 64 sets per device, so that launches in flight on different streams (chunks of a distributed plan) never share a set.
@@ -766,16 +764,14 @@ static unsigned* ticket_set(hipStream_t st) {
     return set;
 }
 // the same on half tiles: 4-line workgroups with the twiddle table, as many per CU as the LDS holds (two at L = 1024)
-template <class C> static void zfused_persist_half_t(cplx* data, const cplx* sym, const cplx* twl, int Lx, int nouter,
-                                                     int64_t dTile, int64_t dOuter, int64_t dLine, int64_t sTile, int64_t sOuter, int64_t sLine,
-                                                     const int2* ytab, const int* zm, int nin, hipStream_t st, int xl = 0) {
+template <class C> static void zfused_persist_half_t(cplx* data, const cplx* sym, const cplx* twl, const FusedGeom& g, hipStream_t st, int xl = 0) {
     if constexpr (C::L >= 1024) {
         constexpr int LINES = XB / 2;
         constexpr size_t lds = persist_lds_bytes<C, LINES, false, true, true>() + 16;   // + the ticket slot
         static_assert(lds <= (size_t)160 * 1024, "half-tile persistent pass: exchange buffer exceeds the LDS");
-        auto k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, false, true, true, true, true> : k_zfused_persist<C, LINES, false, false, true, true, true>;
+        auto k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, false, true, true, true, true> : k_zfused_persist<C, LINES, false, false, true, true, true>;
         if constexpr (xlane_ok<C, LdsLayout<LINES, -1, false>>()) {
-            if (xl) k = (nin == C::L / 2) ? k_zfused_persist<C, LINES, false, true, true, true, true, true, 1> : k_zfused_persist<C, LINES, false, false, true, true, true, true, 1>;
+            if (xl) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, false, true, true, true, true, true, 1> : k_zfused_persist<C, LINES, false, false, true, true, true, true, 1>;
         }
         // (tried in round 3: the ONE LDS exchange left per direction run split -- real parts, then imaginary parts, through half the
         // buffer -- so that TWO half-tile workgroups fit a CU at 1280 / 1536 points: without the in-stage stores every output of the
@@ -783,13 +779,13 @@ template <class C> static void zfused_persist_half_t(cplx* data, const cplx* sym
         // at 30.4 ms and 768^3 loses 49.3 -> 60.7 ms; removed, profiles/r03_experiment_lane_exchange_radix4.log)
         LSFC_REQUIRE(twl != nullptr, "half-tile persistent pass: twiddle table missing");
         allow_lds(k, lds);
-        const unsigned ntiles = (unsigned)((Lx / XB) * nouter);
-        LSFC_REQUIRE(ntiles % 16 == 0 && (nouter % 2 == 0 || !ytab), "ticketed half-tile z pass needs a multiple of 16 tiles in row pairs");
+        const unsigned ntiles = (unsigned)((g.Lx / XB) * g.nouter);
+        LSFC_REQUIRE(ntiles % 16 == 0 && (g.nouter % 2 == 0 || !g.ytab), "ticketed half-tile z pass needs a multiple of 16 tiles in row pairs");
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ((size_t)160 * 1024) / lds));
         const unsigned grid = std::min<unsigned>(2 * ntiles, (unsigned)(cu_count() * per_cu));
         unsigned* tickets = ticket_set(st);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, data, sym, twl, nouter,
-                           dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, ntiles, tickets);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, data, sym, twl, g.nouter,
+                           g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, ntiles, tickets);
     } else {
         fail(LSFC_EINVAL, "half-tile persistent pass: lines of %d points run as whole tiles", (int)C::L);
     }
@@ -797,17 +793,16 @@ template <class C> static void zfused_persist_half_t(cplx* data, const cplx* sym
 
 // half-tile z pass (L = 1024 and L = 1536 in the 3D tiled layout only): 4-line workgroups, sibling halves 8 blocks apart
 // (LINES = 2: quarter tiles -- four sibling workgroups per tile, 32 blocks per group of 8 tiles)
-template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false, int LINES = 4> static void zfused_half_t(cplx* data, const cplx* sym, const cplx* tw, int Lx, int nouter,
-                                                         int64_t dTile, int64_t dOuter, int64_t dLine, int64_t sTile, int64_t sOuter, int64_t sLine,
-                                                         const int2* ytab, const int* zm, int nin, hipStream_t st) {
+template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false, int LINES = 4> static void zfused_half_t(cplx* data, const cplx* sym, const cplx* tw,
+                                                         const FusedGeom& g, hipStream_t st) {
     using LL = LdsLayout<LINES, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = (nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, false, false>;
+    auto k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, false, false>;
     allow_lds(k, lds);
-    const int64_t ntiles = (int64_t)(Lx / XB) * nouter;
+    const int64_t ntiles = (int64_t)(g.Lx / XB) * g.nouter;
     LSFC_REQUIRE(ntiles % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
-    hipLaunchKernelGGL(k, dim3((unsigned)((XB / LINES) * ntiles)), dim3(C::T * LINES), lds, st, data, sym, tw, nouter,
-                       dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, 1, (int64_t)0, 0);
+    hipLaunchKernelGGL(k, dim3((unsigned)((XB / LINES) * ntiles)), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
+                       g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, 1, (int64_t)0, 0);
 }
 
 #if LSFC_FAMILY == 2
@@ -898,12 +893,11 @@ void FAM(pruned_twfull)(int L, const cplx* tw, cplx* out) {
     LSFC_DISPATCH_L(L, twfull_table<C>(out, tw));
 }
 
-void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, int Lx, int nouter,
-                   int64_t dTile, int64_t dOuter, int64_t dLine, int64_t sTile, int64_t sOuter, int64_t sLine, const int2* ytab,
-                   const int* zm, int nin, hipStream_t st, int nrhs, int64_t dBatch) {
+void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom& g, hipStream_t st,
+                        int nrhs, int64_t dBatch) {
     // the half-tile forms (below) take one right-hand side per launch: a batch runs through them member by member
-    const bool tiled = dLine == 8 && ((int64_t)(Lx / XB) * nouter) % 8 == 0;
-    const bool half_form = (LSFC_FAMILY == 2 && ((L == 1024 && (tn.z_half >= 0 ? tn.z_half : (zm ? 0 : 2)) > 0 && tiled) || (L == 2048 && dLine == 8)))
+    const bool tiled = g.dLine == 8 && ((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0;
+    const bool half_form = (LSFC_FAMILY == 2 && ((L == 1024 && (tn.z_half >= 0 ? tn.z_half : (g.zm ? 0 : 2)) > 0 && tiled) || (L == 2048 && g.dLine == 8)))
                         || (LSFC_FAMILY == 3 && L == 1536 && (tn.z_half >= 0 ? tn.z_half : 1) > 0 && tiled);
     // persistent pipelined form: z-even symbol, 3D tiled layout, whole 8-line tiles, one right-hand side
     {
@@ -921,47 +915,47 @@ void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* s
         LSFC_DISPATCH_L(L, (eight_lines = Tune<C>::LINES == XB));
         // (worth it only when a workgroup walks over several tiles: below ~4 tiles per resident workgroup -- grids up to 64^3 --
         // the one-tile kernels finish sooner, 35 against 37.5 us per apply at 48^3)
-        const bool enough_tiles = tn.z_persist > 0 || (int64_t)(Lx / XB) * nouter >= (int64_t)4096;
-        const bool half5 = zp == 5 && tiled && twl && L >= 1024 && ((int64_t)(Lx / XB) * nouter) % 16 == 0 && (nouter % 2 == 0 || !ytab);
-        if (zp > 0 && zm && dLine == 8 && nrhs == 1 && (eight_lines || half5) && (!half_form || half5) && enough_tiles) {
+        const bool enough_tiles = tn.z_persist > 0 || (int64_t)(g.Lx / XB) * g.nouter >= (int64_t)4096;
+        const bool half5 = zp == 5 && tiled && twl && L >= 1024 && ((int64_t)(g.Lx / XB) * g.nouter) % 16 == 0 && (g.nouter % 2 == 0 || !g.ytab);
+        if (zp > 0 && g.zm && g.dLine == 8 && nrhs == 1 && (eight_lines || half5) && (!half_form || half5) && enough_tiles) {
             size_t full_lds = 0;
             LSFC_DISPATCH_L(L, (full_lds = (size_t)LdsLayout<XB, 3, false>::line_elems(C::L) * XB * 16));
             const bool split = zp == 2 || zp == 4 || full_lds > (size_t)160 * 1024;
             // 5: half tiles (4-line workgroups, swizzled unpadded exchange buffer + twiddle table), two workgroups per CU at L = 1024
             if (half5) {
-                LSFC_DISPATCH_L(L, (zfused_persist_half_t<C>(data, sym, twl, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st, tn.xlane != 0 ? 1 : 0)));
+                LSFC_DISPATCH_L(L, (zfused_persist_half_t<C>(data, sym, twl, g, st, tn.xlane != 0 ? 1 : 0)));
                 LSFC_HIP(hipGetLastError());
                 return;
             }
             // 6: whole tiles (as 3) handed out by tickets in row pairs per XCD
-            if (zp == 6 && !split && ((int64_t)(Lx / XB) * nouter) % 16 == 0 && nouter % 2 == 0) {
-                LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st, tn.xlane < 0 ? 5 : tn.xlane)));
+            if (zp == 6 && !split && ((int64_t)(g.Lx / XB) * g.nouter) % 16 == 0 && g.nouter % 2 == 0) {
+                LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, tn.xlane < 0 ? 5 : tn.xlane)));
                 LSFC_HIP(hipGetLastError());
                 return;
             }
-            if ((zp == 3 || zp == 6) && !split) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st, tn.xlane < 0 ? 1 : tn.xlane))); }
-            else if (zp >= 3) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st))); }
-            else if (split) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st))); }
-            else       { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false>(data, sym, tw, tn.tw_lds ? twl : nullptr, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st))); }
+            if ((zp == 3 || zp == 6) && !split) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, tn.xlane < 0 ? 1 : tn.xlane))); }
+            else if (zp >= 3) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st))); }
+            else if (split) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st))); }
+            else       { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st))); }
             LSFC_HIP(hipGetLastError());
             return;
         }
     }
     if (nrhs > 1 && half_form) {
         for (int r = 0; r < nrhs; ++r)
-            FAM(pruned_zfused)(L, tn, data + (int64_t)r * dBatch, sym, tw, twl, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st, 1, 0);
+            FAM(pruned_zfused)(L, tn, data + (int64_t)r * dBatch, sym, tw, twl, g, st, 1, 0);
         return;
     }
-#define LSFC_ZF(SP, PF) do { if (zm) { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st, nrhs, dBatch))); } \
-                             else    { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, false>(data, sym, tw, tn.tw_lds ? twl : nullptr, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st, nrhs, dBatch))); } } while (0)
+#define LSFC_ZF(SP, PF) do { if (g.zm) { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, nrhs, dBatch))); } \
+                             else    { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, false>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, nrhs, dBatch))); } } while (0)
     // auto (-1): half-tile, split exchanges, symbol prefetch -- 6.95 -> 6.6 ms at 512^3 (profiles/r01_experiment_half_tile.log)
     // with the z-even half symbol the full-tile form wins (6.05 ms, profiles/r01_experiment_even_z.log)
 #if LSFC_FAMILY == 2
-    const int zh = tn.z_half >= 0 ? tn.z_half : (zm ? 0 : 2);
-    if (L == 1024 && zh > 0 && dLine == 8 && ((int64_t)(Lx / XB) * nouter) % 8 == 0) {
+    const int zh = tn.z_half >= 0 ? tn.z_half : (g.zm ? 0 : 2);
+    if (L == 1024 && zh > 0 && g.dLine == 8 && ((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0) {
         using C = Cfg1024;
-#define LSFC_ZH(SP, PF, W) do { if (zm) zfused_half_t<C, SP, PF, W, true>(data, sym, tw, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st); \
-                                else zfused_half_t<C, SP, PF, W, false>(data, sym, tw, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st); } while (0)
+#define LSFC_ZH(SP, PF, W) do { if (g.zm) zfused_half_t<C, SP, PF, W, true>(data, sym, tw, g, st); \
+                                else zfused_half_t<C, SP, PF, W, false>(data, sym, tw, g, st); } while (0)
         switch (zh) {
         case 1: LSFC_ZH(false, true, 2); break;
         case 2: LSFC_ZH(true, true, 2); break;
@@ -973,17 +967,17 @@ void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* s
         return;
     }
     // the 2048-point line in the 3D tiled layout: a whole 8-line tile does not fit the 160 KiB of LDS, half tiles do
-    if (L == 2048 && dLine == 8) {
-        LSFC_REQUIRE(((int64_t)(Lx / XB) * nouter) % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
+    if (L == 2048 && g.dLine == 8) {
+        LSFC_REQUIRE(((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
         using C = Cfg2048;
         // LSFC_Z_QUARTER=1 (experiment, off): quarter tiles, two 256-thread workgroups per CU (74 KB of LDS each).  Measured on
         // the 2D tiled pass at n = 1024 (256 tiles): 35.4 against 34.2 us -- workgroups that start together run their phases
         // together, so two per CU overlap nothing in a one-tile kernel; the ticketed persistent form (2 half tiles per
         // workgroup) takes 54.8 us there (profiles/r02_2d_half_symbol.jsonl)
-        const bool quarter = zm && env_flag_z_quarter();
-        if (quarter) zfused_half_t<C, false, false, 2, true, 2>(data, sym, tw, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st);
-        else if (zm) zfused_half_t<C, false, false, 2, true>(data, sym, tw, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st);
-        else zfused_half_t<C, false, false, 2, false>(data, sym, tw, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st);
+        const bool quarter = g.zm && env_flag_z_quarter();
+        if (quarter) zfused_half_t<C, false, false, 2, true, 2>(data, sym, tw, g, st);
+        else if (g.zm) zfused_half_t<C, false, false, 2, true>(data, sym, tw, g, st);
+        else zfused_half_t<C, false, false, 2, false>(data, sym, tw, g, st);
         LSFC_HIP(hipGetLastError());
         return;
     }
@@ -993,10 +987,10 @@ void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* s
     // z_half: 0 off, 1 (auto) whole-complex exchange + prefetch, 2 split + prefetch, 3 split, 4 whole-complex
     // (768^3: fused pass 36.7 -> 29.7 ms, apply 64.7 -> 57.4 ms)
     const int zh = tn.z_half >= 0 ? tn.z_half : 1;
-    if (L == 1536 && zh > 0 && dLine == 8 && ((int64_t)(Lx / XB) * nouter) % 8 == 0) {
+    if (L == 1536 && zh > 0 && g.dLine == 8 && ((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0) {
         using C = Cfg1536;
-#define LSFC_ZH(SP, PF) do { if (zm) zfused_half_t<C, SP, PF, 1, true>(data, sym, tw, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st); \
-                             else zfused_half_t<C, SP, PF, 1, false>(data, sym, tw, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st); } while (0)
+#define LSFC_ZH(SP, PF) do { if (g.zm) zfused_half_t<C, SP, PF, 1, true>(data, sym, tw, g, st); \
+                             else zfused_half_t<C, SP, PF, 1, false>(data, sym, tw, g, st); } while (0)
         switch (zh) {
         case 1: LSFC_ZH(false, true); break;
         case 2: LSFC_ZH(true, true); break;

@@ -78,6 +78,12 @@ void RocFft::exec(void* buf, hipStream_t stream) {
 // ---------------------------------------------------------------------------
 // plan construction helpers
 // ---------------------------------------------------------------------------
+// environment switches (developer knobs, read at plan creation): the first character of the value, -1 when not set
+static int env_switch(const char* name) { const char* e = getenv(name); return e ? (unsigned char)e[0] : -1; }
+// LSFC_SYM_EVEN_Y=0 / LSFC_SYM_EVEN_Z=0: store the full symbol although it is even in y / along the fused pass's axis
+static bool sym_even_y_enabled() { return env_switch("LSFC_SYM_EVEN_Y") != '0'; }
+static bool sym_even_z_enabled() { return env_switch("LSFC_SYM_EVEN_Z") != '0'; }
+
 static void select_device(int device) {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -135,8 +141,8 @@ static bool pruned_eligible(const lsfc_plan* p) {
     return ratio <= 4.0;
 }
 
-// working padded grid of the reduced pipelines: pruned_best_length(n) (pruned) or 2n (rocFFT)
-void plan_choose_reduced_grid(lsfc_plan* p) {
+// working padded grid of the reduced pipelines: pruned_best_length(n) (pruned) or 2n (rocFFT); sets p->pads / p->pipeline
+static void plan_choose_reduced_grid(lsfc_plan* p) {
     const bool pr = pruned_eligible(p);
     for (int d = 0; d < 3; ++d) {
         p->crop[d] = 0;
@@ -153,7 +159,8 @@ static void setup_rocfft_pipeline(lsfc_plan* p) {
     p->W.alloc(len[0] * len[1] * len[2]);
 }
 
-void plan_finish_literal(lsfc_plan* p, const cplx* Gd, bool centred) {
+// Finish a plan from a natural-layout symbol already on the device: Gd has p->pads entries; centred => ifftshift is folded in.
+static void plan_finish_literal(lsfc_plan* p, const cplx* Gd, bool centred) {
     // working grid == the caller's padded grid; symbol pre-shifted and pre-scaled once
     const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
     p->sym.alloc((size_t)total);
@@ -165,6 +172,29 @@ void plan_finish_literal(lsfc_plan* p, const cplx* Gd, bool centred) {
     LSFC_HIP(hipStreamSynchronize(p->stream));
 }
 
+// Even symbol along the fused pass's axis: a line of L points stores only the frequencies k <= L/2 -- the storage slots
+// s < L/2 plus the k = L/2 entry at index L/2 -- and the kernel fetches the value of every upper slot from its mirror.
+// perm[s] = frequency held at storage slot s.  Returns the precondition "slot s < L/2 <=> frequency < L/2" (true for every
+// factorisation in fft_configs.hpp); if it holds and zm != NULL, zm[s - L/2] = where the stored line holds frequency
+// (L - perm[s]) mod L, for the L/2 upper slots s.
+static bool mirror_slots(const std::vector<int>& perm, std::vector<int>* zm) {
+    const int L = (int)perm.size();
+    for (int s = 0; s < L; ++s) if ((perm[(size_t)s] < L / 2) != (s < L / 2)) return false;
+    if (!zm) return true;
+    std::vector<int> inv((size_t)L);
+    for (int s = 0; s < L; ++s) inv[(size_t)perm[(size_t)s]] = s;
+    zm->resize((size_t)L / 2);
+    for (int s = L / 2; s < L; ++s) {
+        const int km = (L - perm[(size_t)s]) % L;                    // in [1, L/2]
+        (*zm)[(size_t)(s - L / 2)] = (km == L / 2) ? L / 2 : inv[(size_t)km];
+    }
+    return true;
+}
+static void upload_mirror_slots(lsfc_plan* p, const std::vector<int>& zm) {
+    p->zmirror.alloc(zm.size());
+    LSFC_HIP(hipMemcpy(p->zmirror.p, zm.data(), zm.size() * sizeof(int), hipMemcpyHostToDevice));
+}
+
 void plan_setup_symbol_rows(lsfc_plan* p, const cplx* G2, const std::vector<int>& perm_y, const std::vector<int>& perm_z, DevBuf<int>& pyrow) {
     const int Ly = p->pads[1], Lz = p->pads[2];
     // The Green's symbols of the reference are even in every axis.  When the reduced symbol handed to us is even in
@@ -172,9 +202,8 @@ void plan_setup_symbol_rows(lsfc_plan* p, const cplx* G2, const std::vector<int>
     // are stored, and each row is scheduled right next to its mirror: the second read of the shared symbol row is
     // served on-die by the Infinity Cache, which removes ~1/8 of the apply's HBM traffic.
     bool even = false;
-    const char* env = getenv("LSFC_SYM_EVEN_Y");
     // (G2 == NULL: the caller built the symbol through its symmetry, symbol_gv3d_quarter, and vouches for it)
-    if (!(env && env[0] == '0') && p->ndim == 3 && Ly >= 4) even = !G2 || pw_mirror_deviation(G2, p->pads, 1, p->stream) < 1e-13;
+    if (sym_even_y_enabled() && p->ndim == 3 && Ly >= 4) even = !G2 || pw_mirror_deviation(G2, p->pads, 1, p->stream) < 1e-13;
     std::vector<int> inv((size_t)Ly), rowky;
     for (int s = 0; s < Ly; ++s) inv[perm_y[s]] = s;
     std::vector<int2> tab;
@@ -204,25 +233,14 @@ void plan_setup_symbol_rows(lsfc_plan* p, const cplx* G2, const std::vector<int>
     LSFC_HIP(hipMemcpy(pyrow.p, rowky.data(), rowky.size() * sizeof(int), hipMemcpyHostToDevice));
 
     // z-even symbol: store only kz <= Lz/2 per line; the kernel fetches the mirror values of its upper slots from
-    // the threads that loaded them (through LDS).  Needs: storage slots s < Lz/2 <-> kz < Lz/2 (true for every
-    // factorisation in fft_configs.hpp, re-checked here).
+    // the threads that loaded them (through LDS): mirror_slots.
+    std::vector<int> zm;
     bool zeven = false;
-    const char* envz = getenv("LSFC_SYM_EVEN_Z");
-    if (!(envz && envz[0] == '0') && p->ndim == 3 && Lz >= 32) {
-        bool ok = true;
-        for (int s2 = 0; s2 < Lz; ++s2) if ((perm_z[s2] < Lz / 2) != (s2 < Lz / 2)) ok = false;
-        if (ok) zeven = !G2 || pw_mirror_deviation(G2, p->pads, 2, p->stream) < 1e-13;
-    }
+    if (sym_even_z_enabled() && p->ndim == 3 && Lz >= 32 && mirror_slots(perm_z, &zm))
+        zeven = !G2 || pw_mirror_deviation(G2, p->pads, 2, p->stream) < 1e-13;
     if (zeven) {
-        std::vector<int> invz((size_t)Lz), zm((size_t)Lz / 2);
-        for (int s2 = 0; s2 < Lz; ++s2) invz[perm_z[s2]] = s2;
-        for (int s2 = Lz / 2; s2 < Lz; ++s2) {
-            const int km = (Lz - perm_z[s2]) % Lz;                  // in [1, Lz/2]
-            zm[s2 - Lz / 2] = (km == Lz / 2) ? Lz / 2 : invz[km];
-        }
         p->sym_hz = Lz / 2 + 8;
-        p->zmirror.alloc(zm.size());
-        LSFC_HIP(hipMemcpy(p->zmirror.p, zm.data(), zm.size() * sizeof(int), hipMemcpyHostToDevice));
+        upload_mirror_slots(p, zm);
     } else {
         p->sym_hz = Lz;
         p->zmirror.release();
@@ -232,22 +250,18 @@ void plan_setup_symbol_rows(lsfc_plan* p, const cplx* G2, const std::vector<int>
 // whether the pruned pipeline will store the y-even, z-even quarter of a 3D symbol that is even in every axis
 bool plan_quarter_symbol_ok(const lsfc_plan* p) {
     if (p->ndim != 3) return false;                    // (the caller knows that the plan runs the pruned pipeline)
-    const char* ey = getenv("LSFC_SYM_EVEN_Y"); const char* ez = getenv("LSFC_SYM_EVEN_Z"); const char* full = getenv("LSFC_SYMBOL_FULL");
-    if ((ey && ey[0] == '0') || (ez && ez[0] == '0') || (full && full[0] == '1')) return false;
+    // (LSFC_SYMBOL_FULL=1: evaluate the symbol on the whole grid although its symmetry would do)
+    if (!sym_even_y_enabled() || !sym_even_z_enabled() || env_switch("LSFC_SYMBOL_FULL") == '1') return false;
     const int Ly = p->pads[1], Lz = p->pads[2];
     if (Ly < 4 || Lz < 32 || p->pads[0] % 2 || Ly % 2 || Lz % 2) return false;
     std::vector<int> pz((size_t)Lz);
     pruned_perm(Lz, pz.data());
-    for (int s2 = 0; s2 < Lz; ++s2) if ((pz[(size_t)s2] < Lz / 2) != (s2 < Lz / 2)) return false;
-    return true;
+    return mirror_slots(pz, nullptr);
 }
 
-void plan_finish_from_reduced(lsfc_plan* p, DevBuf<cplx>& G2) { plan_finish_symbol(p, G2, false); }
-void plan_finish_from_quarter(lsfc_plan* p, DevBuf<cplx>& Gq) { plan_finish_symbol(p, Gq, true); }
-
-void plan_finish_symbol(lsfc_plan* p, DevBuf<cplx>& G2, bool quarter) {
-    // G2: natural FFT-order symbol on the grid chosen by plan_choose_reduced_grid; quarter: only its rows ky <= Ly/2 and
-    // planes kz <= Lz/2 (symbol_gv3d_quarter)
+// G2: natural FFT-order symbol on the grid chosen by plan_choose_reduced_grid, unscaled; quarter: only its rows ky <= Ly/2
+// and planes kz <= Lz/2 (symbol_gv3d_quarter)
+static void plan_finish_symbol(lsfc_plan* p, DevBuf<cplx>& G2, bool quarter) {
     const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
     const int64_t have = quarter ? (int64_t)p->pads[0] * (p->pads[1] / 2 + 1) * (p->pads[2] / 2 + 1) : total;
     LSFC_REQUIRE((int64_t)G2.n == have, "internal: reduced symbol has %lld entries, expected %lld", (long long)G2.n, (long long)have);
@@ -255,7 +269,7 @@ void plan_finish_symbol(lsfc_plan* p, DevBuf<cplx>& G2, bool quarter) {
     const double scale = 1.0 / (double)total;
     if (p->pipeline == lsfc_plan::PRUNED) {
         std::vector<int> perm[3];
-        DevBuf<int> dperm[3];
+        DevBuf<int> dperm[3], pyrow, zero, drow;        // tables the queued pw_permute_symbol reads: they live until the synchronisation below
         for (int d = 0; d < p->ndim; ++d) {
             perm[d].resize((size_t)p->pads[d]);
             pruned_perm(p->pads[d], perm[d].data());
@@ -264,7 +278,6 @@ void plan_finish_symbol(lsfc_plan* p, DevBuf<cplx>& G2, bool quarter) {
             plan_make_twiddles(p, d, p->pads[d]);
         }
         if (p->ndim == 3) {
-            DevBuf<int> pyrow;
             plan_setup_symbol_rows(p, quarter ? nullptr : G2.p, perm[1], perm[2], pyrow);
             LSFC_REQUIRE(!quarter || (p->sym_rows == p->pads[1] / 2 + 1 && p->sym_hz == p->pads[2] / 2 + 8), "internal: quarter symbol but full storage");
             p->sym.alloc((size_t)p->pads[0] * p->sym_rows * p->sym_hz);
@@ -275,47 +288,34 @@ void plan_finish_symbol(lsfc_plan* p, DevBuf<cplx>& G2, bool quarter) {
             // frequencies ky <= Ly/2 only -- rows s < Ly/2 in storage order plus the ky = Ly/2 row -- and the fused pass
             // fetches the mirror values through LDS exactly as the 3D pass does along z (half the symbol bytes of the pass).
             const int Ly = p->pads[1];
+            std::vector<int> zm;
             bool even = false;
-            const char* env = getenv("LSFC_SYM_EVEN_Z");
-            if (!(env && env[0] == '0') && Ly >= 32) {
-                bool ok = true;
-                for (int s2 = 0; s2 < Ly; ++s2) if ((perm[1][(size_t)s2] < Ly / 2) != (s2 < Ly / 2)) ok = false;
-                if (ok) even = pw_mirror_deviation(G2.p, p->pads, 1, p->stream) < 1e-13;
-            }
+            if (sym_even_z_enabled() && Ly >= 32 && mirror_slots(perm[1], &zm)) even = pw_mirror_deviation(G2.p, p->pads, 1, p->stream) < 1e-13;
             if (even) {
-                std::vector<int> inv((size_t)Ly), zm((size_t)Ly / 2), rowk((size_t)Ly / 2 + 1);
-                for (int s2 = 0; s2 < Ly; ++s2) inv[(size_t)perm[1][(size_t)s2]] = s2;
-                for (int s2 = Ly / 2; s2 < Ly; ++s2) {
-                    const int km = (Ly - perm[1][(size_t)s2]) % Ly;              // in [1, Ly/2]
-                    zm[(size_t)(s2 - Ly / 2)] = (km == Ly / 2) ? Ly / 2 : inv[(size_t)km];
-                }
-                for (int s2 = 0; s2 < Ly / 2; ++s2) rowk[(size_t)s2] = perm[1][(size_t)s2];
-                rowk[(size_t)Ly / 2] = Ly / 2;
-                p->zmirror.alloc(zm.size());
-                LSFC_HIP(hipMemcpy(p->zmirror.p, zm.data(), zm.size() * sizeof(int), hipMemcpyHostToDevice));
+                upload_mirror_slots(p, zm);
                 // Tiled form (default from Ly = 2048 on; LSFC_2D_TILED=0|1): the x passes write / read the x'-expanded array as
                 // tiles [Lx/8][m][8] -- the chunked output they already have for the slab transposes, chunk width 8 -- so the
                 // fused pass along y finds its eight interleaved lines in ONE contiguous run of 128-B lines, exactly the 3D fused
                 // pass's situation (same kernels, same z-even symbol layout), instead of 64-B pieces a whole row apart.
-                const char* t2 = getenv("LSFC_2D_TILED");
-                const bool tiled = t2 ? t2[0] == '1' : Ly >= 2048;      // (at 1024 points the 8-line tiles are too few for the chip: 128 workgroups)
+                const int t2 = env_switch("LSFC_2D_TILED");
+                const bool tiled = t2 >= 0 ? t2 == '1' : Ly >= 2048;    // (at 1024 points the 8-line tiles are too few for the chip: 128 workgroups)
                 // (the tiled fused pass is the 3D half-tile kernel: whole groups of 8 tiles -- Lx / 8 tiles here; a short x axis,
                 // e.g. n = 80 next to m = 1024, keeps the natural rows)
                 if (tiled && p->pads[0] % 8 == 0 && (p->pads[0] / 8) % 8 == 0 && p->pads[0] <= 2048) {
                     p->sym_hz = Ly / 2 + 8; p->sym_rows = 1;
-                    DevBuf<int> zero; zero.alloc(1);
+                    zero.alloc(1);
                     LSFC_HIP(hipMemset(zero.p, 0, sizeof(int)));
                     const int L3[3] = { p->pads[0], 1, Ly };        // the line axis plays z; one symbol row per tile
                     p->sym.alloc((size_t)p->pads[0] * p->sym_hz);
                     pw_permute_symbol(G2.p, p->sym.p, dperm[0].p, zero.p, dperm[1].p, L3, 1, p->sym_hz, 0, p->pads[0] / 8, scale, p->stream);
-                    LSFC_HIP(hipStreamSynchronize(p->stream));
                     p->tile2d = (int64_t)8 * p->dims[1] + (Ly >= 1024 ? 72 : 0);
                 } else {
-                DevBuf<int> drow; drow.alloc(rowk.size());
-                LSFC_HIP(hipMemcpy(drow.p, rowk.data(), rowk.size() * sizeof(int), hipMemcpyHostToDevice));
-                p->sym.alloc((size_t)p->pads[0] * rowk.size());
-                pw_permute_symbol(G2.p, p->sym.p, dperm[0].p, drow.p, dperm[2].p, p->pads, (int)rowk.size(), 1, 0, p->pads[0] / 8, scale, p->stream);
-                LSFC_HIP(hipStreamSynchronize(p->stream));
+                    std::vector<int> rowk(perm[1].begin(), perm[1].begin() + Ly / 2);     // rows ky < Ly/2 in storage order, then ky = Ly/2
+                    rowk.push_back(Ly / 2);
+                    drow.alloc(rowk.size());
+                    LSFC_HIP(hipMemcpy(drow.p, rowk.data(), rowk.size() * sizeof(int), hipMemcpyHostToDevice));
+                    p->sym.alloc((size_t)p->pads[0] * rowk.size());
+                    pw_permute_symbol(G2.p, p->sym.p, dperm[0].p, drow.p, dperm[2].p, p->pads, (int)rowk.size(), 1, 0, p->pads[0] / 8, scale, p->stream);
                 }
             } else {
                 p->zmirror.release();
@@ -346,7 +346,8 @@ void plan_finish_symbol(lsfc_plan* p, DevBuf<cplx>& G2, bool quarter) {
     }
 }
 
-void plan_finish_reduce(lsfc_plan* p, DevBuf<cplx>& Gd, const int lit[3], bool centred, const int kernel_origin[3]) {
+// reduce a (pe,me,le) symbol (centred or FFT order) to the working grid and pick the pipeline
+static void plan_finish_reduce(lsfc_plan* p, DevBuf<cplx>& Gd, const int lit[3], bool centred, const int kernel_origin[3]) {
     // T = ifft(ifftshift(G)) on the literal grid is the spatial kernel; the cropped convolution only needs its
     // offsets -(n-1)..n-1 per axis, so it is re-sampled on the working grid q and transformed back: G2 = fft(T2).
     //   Greengard-Vico: offset d sits at index d mod lit (kernel_origin = 0), crop window [0, n).
@@ -377,60 +378,95 @@ void plan_finish_reduce(lsfc_plan* p, DevBuf<cplx>& Gd, const int lit[3], bool c
         fwd.exec(Gd.p, p->stream);
         LSFC_HIP(hipStreamSynchronize(p->stream));
     }
-    plan_finish_from_reduced(p, Gd);
+    plan_finish_symbol(p, Gd, false);
 }
 
 // ---------------------------------------------------------------------------
 // the apply
 // ---------------------------------------------------------------------------
-// the three passes of the 2D pipeline (natural rows, or tiles: lsfc_plan::tile2d)
-static void pass2d_xfwd(lsfc_plan* p, const VecBatch& vb, int nrhs, const double* nu, hipStream_t st) {
-    const int Lx = p->pads[0], m = p->dims[1];
-    if (p->tile2d) pruned_xfwd(Lx, p->tuning, vb, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, m, 8, 8, p->dims[0], st, p->tile2d);
-    else pruned_xfwd(Lx, p->tuning, vb, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, m, Lx, p->pitch1, p->dims[0], st);
+// The passes of the single-device pruned pipeline: xfwd -> yfwd -> fused z -> yinv -> xinv in 3D, xfwd -> fused y -> xinv
+// in 2D (natural rows, or tiles: lsfc_plan::tile2d).  Every driver below -- device vectors, batches, the chunked host-vector
+// pipeline, the per-stage profile -- issues these and nothing else.  A one-member launch gets the batch strides a1_elems /
+// a2_elems like any other (the kernels only multiply them by the member index).
+struct Slab { int z0, nz; };            // z planes [z0, z0 + nz) of the grid: the x and y passes work plane by plane
+static Slab whole_grid(const lsfc_plan* p) { return Slab{0, p->dims[2]}; }
+// the members' vectors at the first plane of a slab
+static VecBatch slab_vectors(const lsfc_plan* p, const VecBatch& vb, int nrhs, Slab s) {
+    const int64_t off = (int64_t)s.z0 * p->dims[0] * p->dims[1];
+    VecBatch v = vb;
+    for (int j = 0; j < nrhs; ++j) { v.x[j] += off; v.y[j] += off; }
+    return v;
 }
-static void pass2d_yfused(lsfc_plan* p, int nrhs, hipStream_t st) {
-    const int Lx = p->pads[0], Ly = p->pads[1], m = p->dims[1];
-    if (p->tile2d) pruned_zfused(Ly, p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, Lx, 1, p->tile2d, 0, 8, (int64_t)8 * p->sym_hz, 0, 8,
-                                 nullptr, p->zmirror.p, m, st, nrhs, p->a1_elems);
-    else pruned_zfused(Ly, p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, Lx, 1, 8, 0, p->pitch1, 8, 0, Lx, nullptr, p->zmirror.p, m, st, nrhs, p->a1_elems);
+static cplx* slab_a1(const lsfc_plan* p, Slab s) { return p->A1.p + (int64_t)s.z0 * p->dims[1] * p->pitch1; }
+static cplx* slab_a2(const lsfc_plan* p, Slab s) { return p->A2.p + (int64_t)8 * s.z0; }
+
+static void pass_xfwd(lsfc_plan* p, const VecBatch& vb, int nrhs, const double* nu, Slab s, hipStream_t st) {
+    const int Lx = p->pads[0], n = p->dims[0];
+    const int64_t nlines = (int64_t)p->dims[1] * s.nz;
+    const VecBatch v = slab_vectors(p, vb, nrhs, s);
+    if (nu) nu += (int64_t)s.z0 * n * p->dims[1];
+    if (p->tile2d) pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d);
+    else pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, slab_a1(p, s), p->tw[0].p, nlines, Lx, p->pitch1, n, st);
 }
-static void pass2d_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, double alpha, double beta, hipStream_t st) {
-    const int Lx = p->pads[0], m = p->dims[1];
-    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, vb, nrhs, p->a1_elems, alpha, beta, p->tw[0].p, m, 8, 8, p->dims[0], st, p->tile2d);
-    else pruned_xinv(Lx, p->tuning, p->A1.p, vb, nrhs, p->a1_elems, alpha, beta, p->tw[0].p, m, Lx, p->pitch1, p->dims[0], st);
+static void pass_yfwd(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {         // 3D only
+    pruned_yfwd(p->pads[1], p->tuning, slab_a1(p, s), slab_a2(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
+                nrhs, p->a1_elems, p->a2_elems);
+}
+static void pass_yinv(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {         // 3D only
+    pruned_yinv(p->pads[1], p->tuning, slab_a2(p, s), slab_a1(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
+                nrhs, p->a1_elems, p->a2_elems);
+}
+static void pass_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, double alpha, double beta, Slab s, hipStream_t st) {
+    const int Lx = p->pads[0], n = p->dims[0];
+    const int64_t nlines = (int64_t)p->dims[1] * s.nz;
+    const VecBatch v = slab_vectors(p, vb, nrhs, s);
+    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, v, nrhs, p->a1_elems, alpha, beta, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d);
+    else pruned_xinv(Lx, p->tuning, slab_a1(p, s), v, nrhs, p->a1_elems, alpha, beta, p->tw[0].p, nlines, Lx, p->pitch1, n, st);
+}
+
+// The three geometries of the fused pass.  3D: A2 as tiles [x'/8][Ly][pitch2 >= 8*l] of 8 interleaved z lines, the symbol as
+// [x'/8][sym_rows][sym_hz][8]; `Wc` x' storage indices from the tile that `a2_off` / `sym_off` point to (a chunk of a
+// distributed plan; the whole range on one device).
+void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st) {
+    const int Ly = p->pads[1];
+    const FusedGeom g{Wc, Ly, (int64_t)p->pitch2 * Ly, (int64_t)p->pitch2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8,
+                      p->ytab.p, p->zmirror.p, p->dims[2]};
+    pruned_zfused(p->pads[2], p->tuning, p->A2.p + a2_off, p->sym.p + sym_off, p->tw[2].p, p->twl[2].p, g, st, nrhs, p->a2_elems);
+}
+// 2D, natural rows: A1 as [m][pitch1 >= Lx], the lines along y; the symbol likewise, [rows][Lx]
+static FusedGeom geom_2d_rows(const lsfc_plan* p) {
+    return FusedGeom{p->pads[0], 1, 8, 0, (int64_t)p->pitch1, 8, 0, (int64_t)p->pads[0], nullptr, p->zmirror.p, p->dims[1]};
+}
+// 2D, tiles: A1 as [Lx/8][tile2d >= 8*m] -- the 3D layout with one row per tile; the symbol as [Lx/8][sym_hz][8]
+static FusedGeom geom_2d_tiles(const lsfc_plan* p) {
+    return FusedGeom{p->pads[0], 1, p->tile2d, 0, 8, (int64_t)8 * p->sym_hz, 0, 8, nullptr, p->zmirror.p, p->dims[1]};
+}
+static void pass_fused(lsfc_plan* p, int nrhs, hipStream_t st) {
+    if (p->ndim == 3) { plan_zfused_3d(p, p->pads[0], 0, 0, nrhs, st); return; }
+    pruned_zfused(p->pads[1], p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, p->tile2d ? geom_2d_tiles(p) : geom_2d_rows(p), st, nrhs, p->a1_elems);
+}
+
+// nrhs <= batch_cap right-hand sides through the pruned pipeline on the plan's stream
+static void pruned_convolve(lsfc_plan* p, int nrhs, const VecBatch& vb, bool use_nu, double alpha, double beta) {
+    // (round 3, measured slower and removed again -- profiles/r03_experiment_a1_window.log: the x and y passes chunk by chunk over
+    // groups of z planes through one chunk-sized window of A1, hoping the Infinity Cache would absorb the 2 x 4.3 GB of A1 traffic)
+    hipStream_t st = p->stream;
+    const Slab all = whole_grid(p);
+    pass_xfwd(p, vb, nrhs, use_nu ? p->nu.p : nullptr, all, st);
+    if (p->ndim == 3) pass_yfwd(p, nrhs, all, st);
+    pass_fused(p, nrhs, st);
+    if (p->ndim == 3) pass_yinv(p, nrhs, all, st);
+    pass_xinv(p, vb, nrhs, alpha, beta, all, st);
 }
 
 void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double alpha, double beta) {
-    const double* nu = use_nu ? p->nu.p : nullptr;
-    hipStream_t st = p->stream;
     if (p->dist) { dist_convolve_dev(p, x, y, use_nu, alpha, beta); return; }
     if (p->pipeline == lsfc_plan::PRUNED) {
-        const int Lx = p->pads[0], Ly = p->pads[1], Lz = p->pads[2];
-        const int m = p->dims[1], l = p->dims[2];
-        const int64_t nlines = (int64_t)m * l;
-        if (p->ndim == 2) {
-            VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
-            pass2d_xfwd(p, vb, 1, nu, st);
-            pass2d_yfused(p, 1, st);
-            pass2d_xinv(p, vb, 1, alpha, beta, st);
-            return;
-        }
-        // (round 3, measured slower and removed again -- profiles/r03_experiment_a1_window.log: the x and y passes chunk by chunk over
-        // groups of z planes through one chunk-sized window of A1, hoping the Infinity Cache would absorb the 2 x 4.3 GB of A1 traffic)
-        pruned_xfwd(Lx, p->tuning, x, nu, p->A1.p, p->tw[0].p, nlines, Lx, p->pitch1, p->dims[0], st);
-        if (p->ndim == 3) {
-            const int p1 = p->pitch1, p2 = p->pitch2;
-            pruned_yfwd(Ly, p->tuning, p->A1.p, p->A2.p, p->tw[1].p, Lx, m, l, p1, p2, st);
-            pruned_zfused(Lz, p->tuning, p->A2.p, p->sym.p, p->tw[2].p, p->twl[2].p, Lx, Ly,
-                          (int64_t)p2 * Ly, (int64_t)p2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8, p->ytab.p,
-                          p->zmirror.p, l, st);
-            pruned_yinv(Ly, p->tuning, p->A2.p, p->A1.p, p->tw[1].p, Lx, m, l, p1, p2, st);
-        } else {
-            pruned_zfused(Ly, p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, Lx, 1, 8, 0, p->pitch1, 8, 0, Lx, nullptr, p->zmirror.p, m, st);
-        }
-        pruned_xinv(Lx, p->tuning, p->A1.p, x, y, alpha, beta, p->tw[0].p, nlines, Lx, p->pitch1, p->dims[0], st);
+        VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
+        pruned_convolve(p, 1, vb, use_nu, alpha, beta);
     } else {
+        const double* nu = use_nu ? p->nu.p : nullptr;
+        hipStream_t st = p->stream;
         const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
         pw_embed(x, nu, p->W.p, p->dims, p->pads, st);
         p->fwd->exec(p->W.p, st);
@@ -448,36 +484,14 @@ void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool us
         for (int j = 0; j < nrhs; ++j) plan_convolve_dev(p, vb.x[j], vb.y[j], use_nu, alpha, beta);
         return;
     }
-    hipStream_t st = p->stream;
     if (nrhs > p->batch_cap) {
         // the work arrays hold the batch back to back: grow them (the plan is idle once its stream has drained)
-        LSFC_HIP(hipStreamSynchronize(st));
+        LSFC_HIP(hipStreamSynchronize(p->stream));
         p->A1.alloc((size_t)(p->a1_elems * nrhs));
         if (p->ndim == 3) p->A2.alloc((size_t)(p->a2_elems * nrhs));
         p->batch_cap = nrhs;
     }
-    const double* nu = use_nu ? p->nu.p : nullptr;
-    const int Lx = p->pads[0], Ly = p->pads[1], Lz = p->pads[2];
-    const int m = p->dims[1], l = p->dims[2];
-    const int64_t nlines = (int64_t)m * l;
-    if (p->ndim == 2) {
-        pass2d_xfwd(p, vb, nrhs, nu, st);
-        pass2d_yfused(p, nrhs, st);
-        pass2d_xinv(p, vb, nrhs, alpha, beta, st);
-        return;
-    }
-    pruned_xfwd(Lx, p->tuning, vb, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, nlines, Lx, p->pitch1, p->dims[0], st);
-    if (p->ndim == 3) {
-        const int p1 = p->pitch1, p2 = p->pitch2;
-        pruned_yfwd(Ly, p->tuning, p->A1.p, p->A2.p, p->tw[1].p, Lx, m, l, p1, p2, st, nrhs, p->a1_elems, p->a2_elems);
-        pruned_zfused(Lz, p->tuning, p->A2.p, p->sym.p, p->tw[2].p, p->twl[2].p, Lx, Ly,
-                      (int64_t)p2 * Ly, (int64_t)p2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8, p->ytab.p,
-                      p->zmirror.p, l, st, nrhs, p->a2_elems);
-        pruned_yinv(Ly, p->tuning, p->A2.p, p->A1.p, p->tw[1].p, Lx, m, l, p1, p2, st, nrhs, p->a1_elems, p->a2_elems);
-    } else {
-        pruned_zfused(Ly, p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, Lx, 1, 8, 0, p->pitch1, 8, 0, Lx, nullptr, p->zmirror.p, m, st, nrhs, p->a1_elems);
-    }
-    pruned_xinv(Lx, p->tuning, p->A1.p, vb, nrhs, p->a1_elems, alpha, beta, p->tw[0].p, nlines, Lx, p->pitch1, p->dims[0], st);
+    pruned_convolve(p, nrhs, vb, use_nu, alpha, beta);
 }
 
 static void ensure_staging(lsfc_plan* p, int64_t count) {
@@ -535,10 +549,8 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
     if (p->xs.n < (size_t)(slots * p->N)) { LSFC_HIP(hipStreamSynchronize(p->stream)); p->xs.alloc((size_t)(slots * p->N)); p->ys.alloc((size_t)(slots * p->N)); }
     const double* nu = use_nu ? p->nu.p : nullptr;
     hipStream_t st = p->stream;
-    const int Lx = p->pads[0], Ly = p->pads[1], Lz = p->pads[2];
-    const int n = p->dims[0], m = p->dims[1], l = p->dims[2], lz = l / K;
-    const int p1 = p->pitch1, p2 = p->pitch2;
-    const int64_t chunk = (int64_t)n * m * lz, lines = (int64_t)m * lz;
+    const int lz = p->dims[2] / K;
+    const int64_t chunk = (int64_t)p->dims[0] * p->dims[1] * lz;
     // the staging buffers may still be read by work queued earlier on the plan's stream (device-memory calls are asynchronous)
     LSFC_HIP(hipEventRecord(hp->ev_free, st));
     LSFC_HIP(hipStreamWaitEvent(hp->up, hp->ev_free, 0));
@@ -572,6 +584,7 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
         const int sl = (int)(j % slots);
         const cplx* xj = x + j * p->N; cplx* yj = y + j * p->N;
         cplx* xs = p->xs.p + (int64_t)sl * p->N; cplx* ys = p->ys.p + (int64_t)sl * p->N;
+        VecBatch sv{}; sv.x[0] = xs; sv.y[0] = ys;
         // slot sl was last used by right-hand side j - 2: its inverse x pass (which reads xs) and its downloads (which read ys) must be over
         if (j >= slots) {
             LSFC_HIP(hipStreamWaitEvent(hp->up, hp->ev_xfree[sl], 0));
@@ -589,18 +602,15 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
             LSFC_HIP(hipMemcpyAsync(xs + off, xj + off, (size_t)chunk * sizeof(cplx), hipMemcpyHostToDevice, hp->up));
             LSFC_HIP(hipEventRecord(ev, hp->up));
             LSFC_HIP(hipStreamWaitEvent(st, ev, 0));
-            cplx* a1 = p->A1.p + (int64_t)c * lines * p1;
-            pruned_xfwd(Lx, p->tuning, xs + off, nu ? nu + off : nullptr, a1, p->tw[0].p, lines, Lx, p1, n, st);
-            pruned_yfwd(Ly, p->tuning, a1, p->A2.p + (int64_t)8 * c * lz, p->tw[1].p, Lx, m, lz, p1, p2, st);
+            pass_xfwd(p, sv, 1, nu, Slab{c * lz, lz}, st);
+            pass_yfwd(p, 1, Slab{c * lz, lz}, st);
         }
-        pruned_zfused(Lz, p->tuning, p->A2.p, p->sym.p, p->tw[2].p, p->twl[2].p, Lx, Ly,
-                      (int64_t)p2 * Ly, (int64_t)p2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8, p->ytab.p, p->zmirror.p, l, st);
+        pass_fused(p, 1, st);
         for (int c = 0; c < K; ++c) {
             const int64_t off = c * chunk;
             hipEvent_t ev = hp->ev_down[(size_t)(sl * K + c)];
-            cplx* a1 = p->A1.p + (int64_t)c * lines * p1;
-            pruned_yinv(Ly, p->tuning, p->A2.p + (int64_t)8 * c * lz, a1, p->tw[1].p, Lx, m, lz, p1, p2, st);
-            pruned_xinv(Lx, p->tuning, a1, xs + off, ys + off, alpha, beta, p->tw[0].p, lines, Lx, p1, n, st);
+            pass_yinv(p, 1, Slab{c * lz, lz}, st);
+            pass_xinv(p, sv, 1, alpha, beta, Slab{c * lz, lz}, st);
             LSFC_HIP(hipEventRecord(ev, st));
             if (helper) {
                 { std::lock_guard<std::mutex> lk(dmu); dq.push_back(Down{ev, yj + off, ys + off, sl, c == K - 1, j}); }
@@ -655,7 +665,7 @@ static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs,
     }
     // LSFC_HOST_COPY=sync (developer switch, diagnostics of the round-2 first-apply fault): the round-2 workaround, a
     // synchronous copy behind a drained stream, instead of the stream-ordered copy
-    static const bool sync_copy = [] { const char* e = getenv("LSFC_HOST_COPY"); return e && e[0] == 's'; }();
+    static const bool sync_copy = env_switch("LSFC_HOST_COPY") == 's';
     for (int64_t j0 = 0; j0 < nrhs; j0 += group) {
         const int cnt = (int)std::min<int64_t>(group, nrhs - j0);
         const size_t bytes = (size_t)cnt * p->N * sizeof(cplx);
@@ -751,11 +761,11 @@ int lsfc_plan_create_gv3d(lsfc_plan** out, int64_t n, int64_t m, int64_t l, doub
         if (p->pipeline == lsfc_plan::PRUNED && plan_quarter_symbol_ok(p.get())) {
             symbol_gv3d_quarter(p.get(), box, G2);
             pt.mark("symbol (total; through its symmetry)");
-            plan_finish_from_quarter(p.get(), G2);
+            plan_finish_symbol(p.get(), G2, true);
         } else {
             symbol_gv3d_reduced(p.get(), box, G2);
             pt.mark("symbol (total)");
-            plan_finish_from_reduced(p.get(), G2);
+            plan_finish_symbol(p.get(), G2, false);
         }
         pt.mark("tables, symbol permutation, work arrays");
         *out = p.release();
@@ -1020,27 +1030,15 @@ int lsfc_profile_apply(lsfc_plan* plan, const double* x_dev, double* y_dev, int 
         if (p->dist) {
             dist_profile_stages(p, x, y, stages_add_fn(stages));
         } else if (p->pipeline == lsfc_plan::PRUNED) {
-            const int Lx = p->pads[0], Ly = p->pads[1], Lz = p->pads[2];
-            const int m = p->dims[1], l = p->dims[2];
-            const int64_t nlines = (int64_t)m * l;
-            if (p->ndim == 2) {
-                VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
-                stages.push_back({"xfwd", N * (C + 8) + 2 * N * C, [=] { pass2d_xfwd(p, vb, 1, p->nu.p, st); }});
-                stages.push_back({"yfused", (2 + 4 + 2) * N * C, [=] { pass2d_yfused(p, 1, st); }});
-                stages.push_back({"xinv", (2 + 1 + 1) * N * C, [=] { pass2d_xinv(p, vb, 1, 1.0, om2, st); }});
-            } else {
-            stages.push_back({"xfwd", N * (C + 8) + 2 * N * C, [=] { pruned_xfwd(Lx, p->tuning, x, p->nu.p, p->A1.p, p->tw[0].p, nlines, Lx, p->pitch1, p->dims[0], st); }});
-            if (p->ndim == 3) {
-                stages.push_back({"yfwd", (2 + 4) * N * C, [=] { pruned_yfwd(Ly, p->tuning, p->A1.p, p->A2.p, p->tw[1].p, Lx, m, l, p->pitch1, p->pitch2, st); }});
-                stages.push_back({"zfused", (4 + 8 + 4) * N * C, [=] { pruned_zfused(Lz, p->tuning, p->A2.p, p->sym.p, p->tw[2].p, p->twl[2].p, Lx, Ly,
-                                  (int64_t)p->pitch2 * Ly, (int64_t)p->pitch2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8,
-                                  p->ytab.p, p->zmirror.p, l, st); }});
-                stages.push_back({"yinv", (4 + 2) * N * C, [=] { pruned_yinv(Ly, p->tuning, p->A2.p, p->A1.p, p->tw[1].p, Lx, m, l, p->pitch1, p->pitch2, st); }});
-            } else {
-                stages.push_back({"yfused", (2 + 4 + 2) * N * C, [=] { pruned_zfused(Ly, p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, Lx, 1, 8, 0, p->pitch1, 8, 0, Lx, nullptr, p->zmirror.p, m, st); }});
-            }
-            stages.push_back({"xinv", (2 + 1 + 1) * N * C, [=] { pruned_xinv(Lx, p->tuning, p->A1.p, x, y, 1.0, om2, p->tw[0].p, nlines, Lx, p->pitch1, p->dims[0], st); }});
-            }
+            // the production passes, one stage each
+            VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
+            const Slab all = whole_grid(p);
+            const bool d3 = p->ndim == 3;
+            stages.push_back({"xfwd", N * (C + 8) + 2 * N * C, [=] { pass_xfwd(p, vb, 1, p->nu.p, all, st); }});
+            if (d3) stages.push_back({"yfwd", (2 + 4) * N * C, [=] { pass_yfwd(p, 1, all, st); }});
+            stages.push_back({d3 ? "zfused" : "yfused", d3 ? (4 + 8 + 4) * N * C : (2 + 4 + 2) * N * C, [=] { pass_fused(p, 1, st); }});
+            if (d3) stages.push_back({"yinv", (4 + 2) * N * C, [=] { pass_yinv(p, 1, all, st); }});
+            stages.push_back({"xinv", (2 + 1 + 1) * N * C, [=] { pass_xinv(p, vb, 1, 1.0, om2, all, st); }});
         } else {
             const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
             const double P = (double)total;

@@ -157,15 +157,9 @@ void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool us
 // the operator M = I + omega^2 G nu
 inline void plan_apply_dev(lsfc_plan* p, const cplx* x, cplx* y) { plan_convolve_dev(p, x, y, true, 1.0, p->omega * p->omega); }
 
-// Finish a plan from a natural-layout symbol already on the device.
-//   literal: Gd has p->pads entries; centred => ifftshift is folded in.  Takes ownership of nothing.
-void plan_finish_literal(lsfc_plan* p, const cplx* Gd, bool centred);
-//   reduce a (pe,me,le) symbol (centred or FFT order) to the (2n,2m,2l) grid and pick the pipeline
-void plan_finish_reduce(lsfc_plan* p, DevBuf<cplx>& Gd, const int lit[3], bool centred, const int kernel_origin[3]);
-//   picks pruned (pruned_best_length(n)) or rocFFT (2n) and sets p->pads / p->pipeline
-void plan_choose_reduced_grid(lsfc_plan* p);
-//   G2 natural FFT order on the (2n,2m,2l) grid, unscaled
-void plan_finish_from_reduced(lsfc_plan* p, DevBuf<cplx>& G2);
+// The fused z pass of the 3D tiled layout on `Wc` x' storage indices, starting at the tile that the offsets into A2 and
+// the symbol point to (the whole range on one device; dist.hip: one chunk of the owned range)
+void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st);
 
 void plan_common_init(lsfc_plan* p, int ndim, int64_t n, int64_t m, int64_t l, const double* nu_host, double omega,
                       int quad_rule, unsigned flags, int device);
@@ -174,8 +168,6 @@ void plan_common_init(lsfc_plan* p, int ndim, int64_t n, int64_t m, int64_t l, c
 void symbol_gv3d_reduced(lsfc_plan* p, double box, DevBuf<cplx>& G2);                  // -> (2n,2m,2l) FFT order, unscaled
 void symbol_gv3d_quarter(lsfc_plan* p, double box, DevBuf<cplx>& Gq);                  // -> [Q0][Q1/2+1][Q2/2+1] (ky, kz >= 0 only), unscaled
 bool plan_quarter_symbol_ok(const lsfc_plan* p);                                       // the stored symbol is the y-even, z-even quarter
-void plan_finish_from_quarter(lsfc_plan* p, DevBuf<cplx>& Gq);
-void plan_finish_symbol(lsfc_plan* p, DevBuf<cplx>& G2, bool quarter);
 void symbol_gv2d_literal(lsfc_plan* p, double box, DevBuf<cplx>& G, int lit[3]);       // -> (4n,4m) centred
 void symbol_trap2d_literal(lsfc_plan* p, double x0, double y0, double h, cplx d0, DevBuf<cplx>& G); // -> fft(Ge), (2n-1,2m-1)
 
@@ -185,10 +177,10 @@ void dist_allreduce_sum(lsfc_plan* p, cplx* dev, int count);           // no-op 
 void dist_profile_stages(lsfc_plan* p, const cplx* x, cplx* y,
                          std::function<void(const char*, double, std::function<void()>)> add);
 
-// symbol rows / block order of the z pass for a (possibly) y-even symbol: fills p->sym_rows, p->ytab, returns the
-// device table of the y frequency of every stored row (plan.hip)
 // roots of unity of one axis: the per-line table tw[] and the full stage-twiddle table twl[] (pruned_twfull)
 void plan_make_twiddles(lsfc_plan* p, int axis, int L);
+// symbol rows / block order of the z pass for a (possibly) y-even, z-even symbol: fills p->sym_rows, p->ytab, p->sym_hz,
+// p->zmirror and returns in pyrow the device table of the y frequency of every stored row (plan.hip)
 void plan_setup_symbol_rows(lsfc_plan* p, const cplx* G2, const std::vector<int>& perm_y, const std::vector<int>& perm_z, DevBuf<int>& pyrow);
 
 // single-process multi-device plan (dist.hip): x[r], y[r] = device pointers of rank r's slab on devices[r]

@@ -13,8 +13,7 @@ namespace lsfc {
     void pruned_xinv_f##F(int, const PrunedTuning&, const cplx*, const VecBatch&, int, int64_t, double, double, const cplx*, int64_t, int, int, int, hipStream_t, int64_t); \
     void pruned_yfwd_f##F(int, const PrunedTuning&, const cplx*, cplx*, const cplx*, int, int, int, int, int, hipStream_t, int, int64_t, int64_t);     \
     void pruned_yinv_f##F(int, const PrunedTuning&, const cplx*, cplx*, const cplx*, int, int, int, int, int, hipStream_t, int, int64_t, int64_t);     \
-    void pruned_zfused_f##F(int, const PrunedTuning&, cplx*, const cplx*, const cplx*, const cplx*, int, int, int64_t, int64_t, int64_t, \
-                            int64_t, int64_t, int64_t, const int2*, const int*, int, hipStream_t, int, int64_t);                \
+    void pruned_zfused_f##F(int, const PrunedTuning&, cplx*, const cplx*, const cplx*, const cplx*, const FusedGeom&, hipStream_t, int, int64_t); \
     void pruned_perm_f##F(int, int*);                                                                                     \
     void pruned_warmup_f##F();                                                                                         \
     int pruned_twfull_len_f##F(int);                                                                                            \
@@ -87,10 +86,8 @@ void pruned_yfwd(int L, const PrunedTuning& tn, const cplx* a1, cplx* a2, const 
 void pruned_yinv(int L, const PrunedTuning& tn, const cplx* a2, cplx* a1, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
     LSFC_ROUTE(L, pruned_yinv, L, tn, a2, a1, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2);
 }
-void pruned_zfused(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, int Lx, int nouter,
-                   int64_t dTile, int64_t dOuter, int64_t dLine, int64_t sTile, int64_t sOuter, int64_t sLine, const int2* ytab,
-                   const int* zm, int nin, hipStream_t st, int nrhs, int64_t dBatch) {
-    LSFC_ROUTE(L, pruned_zfused, L, tn, data, sym, tw, twl, Lx, nouter, dTile, dOuter, dLine, sTile, sOuter, sLine, ytab, zm, nin, st, nrhs, dBatch);
+void pruned_zfused(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom& g, hipStream_t st, int nrhs, int64_t dBatch) {
+    LSFC_ROUTE(L, pruned_zfused, L, tn, data, sym, tw, twl, g, st, nrhs, dBatch);
 }
 void pruned_perm(int L, int* freq_of_storage) {
     switch (family(L)) {

@@ -53,16 +53,6 @@ void pruned_xfwd(int L, const PrunedTuning&, const VecBatch& vb, int nrhs, int64
                  int64_t bstride = 0);     // bstride: distance between chunks of the storage axis (0: dense, Wp * nlines)
 void pruned_xinv(int L, const PrunedTuning&, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta,
                  const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t, int64_t bstride = 0);
-inline void pruned_xfwd(int L, const PrunedTuning& tn, const cplx* x, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st,
-                        int64_t bstride = 0) {
-    VecBatch vb{}; vb.x[0] = x;
-    pruned_xfwd(L, tn, vb, 1, 0, nu, out, tw, nlines, W, Wp, n, st, bstride);
-}
-inline void pruned_xinv(int L, const PrunedTuning& tn, const cplx* in, const cplx* xorig, cplx* y, double alpha, double beta,
-                        const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride = 0) {
-    VecBatch vb{}; vb.x[0] = xorig; vb.y[0] = y;
-    pruned_xinv(L, tn, in, vb, 1, 0, alpha, beta, tw, nlines, W, Wp, n, st, bstride);
-}
 // p1: row pitch of A1 (>= Lx), p2: pitch of one storage-y row of an A2 tile (>= 8*l); both multiples of 8 elements
 void pruned_yfwd(int L, const PrunedTuning&, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t,
                  int nrhs = 1, int64_t batch1 = 0, int64_t batch2 = 0);
@@ -71,11 +61,21 @@ void pruned_yinv(int L, const PrunedTuning&, const cplx* a2, cplx* a1, const cpl
 // full stage-twiddle table of the factorisation used for length L (host side; tw[j] = exp(-2 pi i j / L))
 int pruned_twfull_len(int L);
 void pruned_twfull(int L, const cplx* tw, cplx* out);
-void pruned_zfused(int L, const PrunedTuning&, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl /* full table or NULL */, int Lx, int nouter,
-                   int64_t dTile, int64_t dOuter, int64_t dLine, int64_t sTile, int64_t sOuter, int64_t sLine,
-                   const int2* ytab /* block order -> (data row, symbol row); NULL: identity */,
-                   const int* zm /* z-even symbol: partner storage index of every upper-half slot; NULL: full symbol lines */,
-                   int nin /* valid entries per line (<= L/2) */, hipStream_t,
-                   int nrhs = 1, int64_t dBatch = 0 /* distance between the batch members in `data` */);
+// Geometry of one fused pass (forward transform along the line, multiply by the symbol, inverse transform, in place).
+// Lines come in tiles of 8 consecutive x' storage indices; `nouter` lines of the other transformed axis share a tile.
+// Line (tile g, row o, xi in 0..7): element j at data[g*dTile + o*dOuter + xi + dLine*j], the symbol value of storage
+// index j at sym[g*sTile + so*sOuter + xi + sLine*j]; block b of a tile takes (o, so) = ytab[b], or (b, b) without a table.
+struct FusedGeom {
+    int Lx;                 // x' storage indices covered (a multiple of 8): Lx / 8 tiles
+    int nouter;             // lines per (tile, xi): Ly in 3D, 1 in 2D
+    int64_t dTile, dOuter, dLine;   // strides of `data` per tile, per outer line, per element of a line
+    int64_t sTile, sOuter, sLine;   // the same for the symbol
+    const int2* ytab;       // block order -> (data row, symbol row); NULL: identity
+    const int* zm;          // even symbol: partner storage index of every upper-half slot; NULL: full symbol lines
+    int nin;                // valid entries per line (<= L/2)
+};
+// twl: full stage-twiddle table or NULL; dBatch: distance between the batch members in `data`
+void pruned_zfused(int L, const PrunedTuning&, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom&, hipStream_t,
+                   int nrhs = 1, int64_t dBatch = 0);
 
 } // namespace lsfc
