@@ -64,6 +64,10 @@ SIGNATURES = {
     "lsfc_precond_callback": (_I, [_P, _P, _L]),
     "lsfc_precond_stats": (_I, [_P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L)]),
     "lsfc_precond_schedule": (_I, [_P, _I, C.POINTER(_L)]),
+    "lsfc_precond_create_blocktri": (_I, [_PP, _L, _L, _P, _P, _P, _P, _I, _I]),
+    "lsfc_precond_create_from_plan": (_I, [_PP, _P]),
+    "lsfc_precond_blocktri_info": (_I, [_P, C.POINTER(_L), C.POINTER(_D)]),
+    "lsfc_precond_blocktri_get_block": (_I, [_P, _L, _P, _L]),
     "lsfc_sparsify_pattern": (_I, [_L, _L, _L, C.POINTER(_L), _P, _P, _P]),
     "lsfc_sparsify_build": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_plan_set_stream": (_I, [_P, _P]),

@@ -1,0 +1,515 @@
+// Factorisation of Msp on the device and the apply of Msp^{-1} from it.
+//
+// As, AG and Msp of the sparsifying preconditioner (src/preconditioner.jl:27-58; examples/example3D.jl:57-68) carry the
+// full 9-point / 27-point stencil of an n x m (x l) grid, x fastest.  With the slowest axis as block index Msp is
+// block tridiagonal: K blocks of b = N / K rows, diagonal blocks D_k, couplings L_k (block k to k-1), U_k (k to k+1).
+// Exact block elimination
+//     S_0 = D_0,   S_k = D_k - L_k S_{k-1}^{-1} U_{k-1}
+//     forward   z_k = S_k^{-1} (w_k - L_k z_{k-1})
+//     backward  x_{K-1} = z_{K-1},   x_k = z_k - S_k^{-1} (U_k x_{k+1})
+// with the explicit inverses S_k^{-1} stored dense (column-major, K b^2 16 B).  The reference has UMFPACK's lu(Msp) here.
+//
+// Set-up, per block:  Schur update as two sparse gathers (W = L_k S_{k-1}^{-1}; S_k = D_k - W U_{k-1}, U by columns),
+// then a blocked in-place Gauss-Jordan inversion without pivoting, panels of 32 columns:
+//     P = A_JJ^{-1}                       one workgroup, in LDS; |pivot| / max|S_k| is monitored
+//     A_J: <- P A_J:,  A_:J <- -A_:J P    panel kernels (VALU), the old column panel and the new row panel are kept aside
+//     A_ij <- A_ij - A_iJ(old) A_Jj(new)  the trailing update: complex fp64 GEMM on v_mfma_f64_16x16x4_f64
+// No float atomics anywhere and every sum in a fixed order: two factorisations of one input are bitwise equal.
+//
+// Apply: one kernel per step of the two sweeps; a workgroup forms the stencil product (L_k z_{k-1} or U_k x_{k+1}) in
+// LDS and multiplies 16 rows of S_k^{-1} with it (16 B loads, 32 column slots folded through LDS in a fixed order).
+// Planes of at most 96 rows are walked inside one launch by a single workgroup.
+#include "blocktri.hpp"
+#include <algorithm>
+#include <chrono>
+#include <memory>
+#include <vector>
+
+namespace lsfc {
+
+static constexpr int NB = 32;             // panel width of the inversion = tile edge of the trailing update
+static constexpr int AP_ROWS = 16;        // apply: rows of S_k^{-1} per workgroup ...
+static constexpr int AP_SLOTS = 32;       // ... times column slots = 512 threads
+static constexpr int AP_CHUNK = 2048;     // apply: entries of the stencil product staged in LDS at a time
+static constexpr int WALK_B = 96;         // planes of at most this many rows: both sweeps inside one launch
+
+struct BtStatus { int bad_block, bad_row; double bad_ratio, min_ratio, smax; int bad_band, bad_format; };
+
+__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ void cfma(cplx& s, cplx a, cplx b) { s.x += a.x * b.x - a.y * b.y; s.y += a.x * b.y + a.y * b.x; }
+
+// ---- set-up: pattern ---------------------------------------------------------------------------------------------
+
+// one thread per row: checks the row (columns ascending, in range, inside the three block diagonals), splits it at the
+// block boundaries (rlo: first entry of the diagonal block, rhi: first entry of the upper coupling), narrows the columns
+// to 32 bits and counts the entries of the upper couplings per column
+__global__ void k_bt_check(int64_t N, int64_t b, int64_t nnz, const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                           int64_t* __restrict__ rlo, int64_t* __restrict__ rhi, int* __restrict__ col32, int* __restrict__ ucnt, BtStatus* st) {
+    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const int64_t s = rowptr[r], e = rowptr[r + 1], k = r / b;
+    if (s < 0 || e < s || e > nnz) { atomicMin(&st->bad_format, (int)r); return; }
+    int64_t prev = -1, lo = e, hi = e;
+    bool fmt = true, band = true;
+    for (int64_t q = s; q < e; ++q) {
+        const int64_t c = col[q];
+        if (c <= prev || c >= N) { fmt = false; break; }
+        prev = c;
+        const int64_t cb = c / b;
+        if (cb < k - 1 || cb > k + 1) { band = false; continue; }
+        if (cb >= k && lo == e) lo = q;
+        if (cb > k && hi == e) hi = q;
+        col32[q] = (int)c;
+    }
+    if (!fmt) { atomicMin(&st->bad_format, (int)r); return; }
+    if (!band) { atomicMin(&st->bad_band, (int)r); return; }
+    if (lo > hi) lo = hi;                                  // no entry in the diagonal block
+    rlo[r] = lo; rhi[r] = hi;
+    for (int64_t q = hi; q < e; ++q) atomicAdd(&ucnt[col32[q]], 1);
+}
+
+// upper couplings by columns: slots handed out by an integer counter, then every column sorted by row, so the result
+// does not depend on the order in which the counter was served
+__global__ void k_bt_ufill(int64_t N, const int64_t* __restrict__ rowptr, const int64_t* __restrict__ rhi, const int* __restrict__ col32,
+                           const int64_t* __restrict__ ucolptr, int* __restrict__ ucur, int* __restrict__ urow, int64_t* __restrict__ uidx) {
+    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    for (int64_t q = rhi[r]; q < rowptr[r + 1]; ++q) {
+        const int c = col32[q];
+        const int64_t at = ucolptr[c] + atomicAdd(&ucur[c], 1);
+        urow[at] = (int)r; uidx[at] = q;
+    }
+}
+
+__global__ void k_bt_usort(int64_t N, const int64_t* __restrict__ ucolptr, int* __restrict__ urow, int64_t* __restrict__ uidx,
+                           const cplx* __restrict__ val, cplx* __restrict__ uval) {
+    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const int64_t s = ucolptr[c], e = ucolptr[c + 1];
+    for (int64_t i = s + 1; i < e; ++i) {                  // insertion sort: a column holds a handful of entries
+        const int r = urow[i]; const int64_t x = uidx[i];
+        int64_t j = i;
+        while (j > s && urow[j - 1] > r) { urow[j] = urow[j - 1]; uidx[j] = uidx[j - 1]; --j; }
+        urow[j] = r; uidx[j] = x;
+    }
+    for (int64_t i = s; i < e; ++i) uval[i] = val[uidx[i]];
+}
+
+// ---- set-up: Schur update ------------------------------------------------------------------------------------------
+
+// W = L_k S_{k-1}^{-1}: W[i, r] = sum over the lower coupling of row i
+__global__ void k_bt_schur_left(int64_t b, int64_t k, const int64_t* __restrict__ rowptr, const int64_t* __restrict__ rlo, const int* __restrict__ col32,
+                                const cplx* __restrict__ val, const cplx* __restrict__ Sprev, cplx* __restrict__ W) {
+    const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (idx >= b * b) return;
+    const int64_t i = idx % b, r = idx / b, g = k * b + i, base = (k - 1) * b;
+    cplx s = make_double2(0.0, 0.0);
+    for (int64_t q = rowptr[g]; q < rlo[g]; ++q) cfma(s, val[q], Sprev[(col32[q] - base) + r * b]);
+    W[idx] = s;
+}
+
+// S = -W U_{k-1}: S[i, j] = -sum over column j of the upper coupling of block k-1
+__global__ void k_bt_schur_right(int64_t b, int64_t k, const int64_t* __restrict__ ucolptr, const int* __restrict__ urow, const cplx* __restrict__ uval,
+                                 const cplx* __restrict__ W, cplx* __restrict__ S) {
+    const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (idx >= b * b) return;
+    const int64_t i = idx % b, j = idx / b, g = k * b + j, base = (k - 1) * b;
+    cplx s = make_double2(0.0, 0.0);
+    for (int64_t q = ucolptr[g]; q < ucolptr[g + 1]; ++q) cfma(s, W[i + (urow[q] - base) * b], uval[q]);
+    S[idx] = make_double2(-s.x, -s.y);
+}
+
+// S += D_k (every stored entry of the diagonal block once: columns are strictly ascending)
+__global__ void k_bt_add_diag(int64_t b, int64_t k, const int64_t* __restrict__ rlo, const int64_t* __restrict__ rhi, const int* __restrict__ col32,
+                              const cplx* __restrict__ val, cplx* __restrict__ S) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= b) return;
+    const int64_t g = k * b + i;
+    for (int64_t q = rlo[g]; q < rhi[g]; ++q) {
+        cplx& d = S[i + (col32[q] - k * b) * b];
+        d.x += val[q].x; d.y += val[q].y;
+    }
+}
+
+// max |S_ij|^2 in two steps (a maximum does not depend on the order)
+__global__ __launch_bounds__(256) void k_bt_absmax_part(int64_t n, const cplx* __restrict__ S, double* __restrict__ part) {
+    __shared__ double red[256];
+    double m = 0.0;
+    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) { const cplx v = S[i]; m = fmax(m, v.x * v.x + v.y * v.y); }
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+__global__ __launch_bounds__(256) void k_bt_absmax_fin(int nparts, const double* __restrict__ part, BtStatus* st) {
+    __shared__ double red[256];
+    red[threadIdx.x] = (int)threadIdx.x < nparts ? part[threadIdx.x] : 0.0;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
+    if (threadIdx.x == 0) st->smax = sqrt(red[0]);
+}
+
+// ---- set-up: blocked Gauss-Jordan inversion, in place, no pivoting ------------------------------------------------
+
+// P = A_JJ^{-1} (nb x nb, nb <= 32) by one workgroup of 32 x 32 threads, thread (r, c) owns one entry in LDS.
+// Monitor: |pivot| / max|S_k|; the first pivot below `thr` (or not a number) is recorded with block and row.
+__global__ __launch_bounds__(1024) void k_bt_diag(const cplx* __restrict__ A, int64_t b, int j0, int nb, cplx* __restrict__ P, BtStatus* st,
+                                                  int block, double thr) {
+    __shared__ cplx M[NB][NB + 1];
+    const int c = threadIdx.x & 31, r = threadIdx.x >> 5;
+    M[r][c] = (r < nb && c < nb) ? A[(j0 + r) + (int64_t)(j0 + c) * b] : make_double2(r == c ? 1.0 : 0.0, 0.0);
+    __syncthreads();
+    const double smax = st->smax;
+    double minr = 1e300, badr = 0.0; int bad = -1;
+    for (int p = 0; p < nb; ++p) {
+        const cplx piv = M[p][p], f = M[r][p], v = M[r][c], rp = M[p][c];
+        __syncthreads();
+        const double a2 = piv.x * piv.x + piv.y * piv.y;
+        const double ratio = sqrt(a2) / smax;
+        if (!(ratio >= thr) && bad < 0) { bad = p; badr = ratio; }
+        if (ratio < minr) minr = ratio;
+        const cplx ip = make_double2(piv.x / a2, -piv.y / a2);
+        const cplx sp = c == p ? ip : cmul(rp, ip);                          // row p of the step's result
+        cplx nv;
+        if (r == p) nv = sp;
+        else { const cplx t = cmul(f, sp); nv = c == p ? make_double2(-t.x, -t.y) : make_double2(v.x - t.x, v.y - t.y); }
+        M[r][c] = nv;
+        __syncthreads();
+    }
+    P[r + c * NB] = M[r][c];
+    if (threadIdx.x == 0) {
+        if (minr < st->min_ratio) st->min_ratio = minr;
+        if (bad >= 0 && st->bad_block < 0) { st->bad_block = block; st->bad_row = j0 + bad; st->bad_ratio = badr; }
+    }
+}
+
+// Both panels of one step.  Workgroups [0, nx): the row panel, a thread per column j outside J: A_Jj <- P A_Jj, kept
+// aside in R (32 x b, rows beyond nb zero).  Workgroups [nx, 2 nx): the column panel, a thread per row i outside J:
+// C_i <- A_iJ (b x 32, columns beyond nb zero), A_iJ <- -A_iJ P; rows inside J: A_JJ <- P.
+__global__ __launch_bounds__(256) void k_bt_panels(cplx* __restrict__ A, int64_t b, int j0, int nb, const cplx* __restrict__ P,
+                                                   cplx* __restrict__ R, cplx* __restrict__ Cb, int nx) {
+    __shared__ cplx Ps[NB][NB + 1];                                         // Ps[r][c] = P[r, c]
+    for (int t = threadIdx.x; t < NB * NB; t += 256) Ps[t % NB][t / NB] = P[t];
+    __syncthreads();
+    const bool rowpart = (int)blockIdx.x < nx;
+    const int64_t t = (int64_t)(rowpart ? blockIdx.x : blockIdx.x - nx) * 256 + threadIdx.x;
+    if (t >= b) return;
+    const bool inJ = t >= j0 && t < j0 + nb;
+    cplx a[NB];
+    if (rowpart) {
+        if (inJ) return;
+#pragma unroll
+        for (int c = 0; c < NB; ++c) a[c] = c < nb ? A[(j0 + c) + t * b] : make_double2(0.0, 0.0);
+        for (int r = 0; r < NB; ++r) {
+            cplx s = make_double2(0.0, 0.0);
+            if (r < nb) {
+#pragma unroll
+                for (int c = 0; c < NB; ++c) cfma(s, Ps[r][c], a[c]);
+                A[(j0 + r) + t * b] = s;
+            }
+            R[r + t * NB] = s;
+        }
+    } else {
+        if (inJ) {
+            for (int c = 0; c < NB; ++c) { Cb[t + (int64_t)c * b] = make_double2(0.0, 0.0); if (c < nb) A[t + (int64_t)(j0 + c) * b] = Ps[t - j0][c]; }
+            return;
+        }
+#pragma unroll
+        for (int c = 0; c < NB; ++c) { a[c] = c < nb ? A[t + (int64_t)(j0 + c) * b] : make_double2(0.0, 0.0); Cb[t + (int64_t)c * b] = a[c]; }
+        for (int c = 0; c < nb; ++c) {
+            cplx s = make_double2(0.0, 0.0);
+#pragma unroll
+            for (int q = 0; q < NB; ++q) cfma(s, a[q], Ps[q][c]);             // (rows q >= nb of a are zero)
+            A[t + (int64_t)(j0 + c) * b] = make_double2(-s.x, -s.y);
+        }
+    }
+}
+
+// Trailing update A_ij <- A_ij - C_i R_j over all 32 x 32 tiles outside panel row / panel column J: one wave per tile,
+// 2 x 2 MFMA tiles of 16 x 16, each complex product as four real v_mfma_f64_16x16x4_f64.  The product is formed
+// transposed (MFMA rows = matrix columns j, MFMA columns = matrix rows i) so that the 16 lanes of a result register
+// sit on 16 consecutive rows of the column-major matrix: 256 B per access.
+// Lane maps (cdna_hip_programming.md): A operand [row = lane & 15][k = lane >> 4], B operand [k = lane >> 4][col = lane & 15],
+// result register g: [row = (lane >> 4) + 4 g][col = lane & 15].
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void k_bt_trail(cplx* __restrict__ A, int64_t b, int J, int nt, const cplx* __restrict__ R, const cplx* __restrict__ Cb) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= (int64_t)nt * nt) return;                                      // (whole waves leave together)
+    const int ti = (int)(w % nt), tj = (int)(w / nt);
+    if (ti == J || tj == J) return;
+    const int c16 = lane & 15, q = lane >> 4;
+    d4 re[2][2], im[2][2];                                                  // [sj][si]
+#pragma unroll
+    for (int sj = 0; sj < 2; ++sj)
+#pragma unroll
+        for (int si = 0; si < 2; ++si) {
+            const int64_t i = (int64_t)ti * NB + si * 16 + c16;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int64_t j = (int64_t)tj * NB + sj * 16 + q + 4 * g;
+                const cplx v = (i < b && j < b) ? A[i + j * b] : make_double2(0.0, 0.0);
+                re[sj][si][g] = v.x; im[sj][si][g] = v.y;
+            }
+        }
+#pragma unroll
+    for (int k0 = 0; k0 < NB; k0 += 4) {
+        const int kk = k0 + q;
+        cplx cn[2], rv[2];
+#pragma unroll
+        for (int si = 0; si < 2; ++si) {
+            const int64_t i = (int64_t)ti * NB + si * 16 + c16;
+            const cplx v = i < b ? Cb[i + (int64_t)kk * b] : make_double2(0.0, 0.0);
+            cn[si] = make_double2(-v.x, -v.y);
+        }
+#pragma unroll
+        for (int sj = 0; sj < 2; ++sj) {
+            const int64_t j = (int64_t)tj * NB + sj * 16 + c16;
+            rv[sj] = j < b ? R[kk + j * NB] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int sj = 0; sj < 2; ++sj)
+#pragma unroll
+            for (int si = 0; si < 2; ++si) {
+                re[sj][si] = __builtin_amdgcn_mfma_f64_16x16x4f64(rv[sj].x, cn[si].x, re[sj][si], 0, 0, 0);
+                re[sj][si] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rv[sj].y, cn[si].y, re[sj][si], 0, 0, 0);
+                im[sj][si] = __builtin_amdgcn_mfma_f64_16x16x4f64(rv[sj].x, cn[si].y, im[sj][si], 0, 0, 0);
+                im[sj][si] = __builtin_amdgcn_mfma_f64_16x16x4f64(rv[sj].y, cn[si].x, im[sj][si], 0, 0, 0);
+            }
+    }
+#pragma unroll
+    for (int sj = 0; sj < 2; ++sj)
+#pragma unroll
+        for (int si = 0; si < 2; ++si) {
+            const int64_t i = (int64_t)ti * NB + si * 16 + c16;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int64_t j = (int64_t)tj * NB + sj * 16 + q + 4 * g;
+                if (i < b && j < b) A[i + j * b] = make_double2(re[sj][si][g], im[sj][si][g]);
+            }
+        }
+}
+
+// ---- the apply -----------------------------------------------------------------------------------------------------
+
+struct BtApply {                   // what the sweep kernels read
+    int64_t b; int K;
+    const int64_t* rowptr; const int64_t* rlo; const int64_t* rhi; const int* col; const cplx* val;
+    const cplx* S;
+};
+
+// entries [jc, jc + n) of the right-hand side of step k into LDS: w_k - L_k z_{k-1} (forward) or U_k x_{k+1} (backward)
+template <bool FWD>
+__device__ __forceinline__ void bt_stage(const BtApply& a, int k, int64_t jc, int n, const cplx* __restrict__ w, const cplx* x, cplx* t) {
+    for (int jj = threadIdx.x; jj < n; jj += AP_ROWS * AP_SLOTS) {
+        const int64_t g = (int64_t)k * a.b + jc + jj;
+        cplx s;
+        if (FWD) {
+            s = w[g];
+            if (k > 0) { cplx u = make_double2(0.0, 0.0); for (int64_t q = a.rowptr[g]; q < a.rlo[g]; ++q) cfma(u, a.val[q], x[a.col[q]]); s.x -= u.x; s.y -= u.y; }
+        } else {
+            s = make_double2(0.0, 0.0);
+            for (int64_t q = a.rhi[g]; q < a.rowptr[g + 1]; ++q) cfma(s, a.val[q], x[a.col[q]]);
+        }
+        t[jj] = s;
+    }
+}
+
+// this thread's share of (S_k^{-1} t)[i]: columns jc + slot, jc + slot + 32, ...
+__device__ __forceinline__ void bt_accum(const cplx* __restrict__ Sk, int64_t b, int64_t i, int64_t jc, int n, int slot, const cplx* t, cplx& acc) {
+    if (i >= b) return;
+    const cplx* p = Sk + i + (jc + slot) * b;
+#pragma unroll 4
+    for (int jj = slot; jj < n; jj += AP_SLOTS, p += (int64_t)AP_SLOTS * b) cfma(acc, *p, t[jj]);
+}
+
+// fold the 32 column slots of every row in slot order; the sum is valid on the threads of slot 0
+__device__ __forceinline__ cplx bt_fold(cplx acc, cplx* red) {
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    cplx s = make_double2(0.0, 0.0);
+    if (threadIdx.x < AP_ROWS) for (int q = 0; q < AP_SLOTS; ++q) { const cplx v = red[q * AP_ROWS + threadIdx.x]; s.x += v.x; s.y += v.y; }
+    __syncthreads();
+    return s;
+}
+
+// one step of a sweep over many workgroups, 16 rows each: forward writes z_k, backward updates it in place to x_k
+// (a workgroup writes rows of block k only and reads block k -+ 1 only)
+template <bool FWD>
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step(BtApply a, int k, const cplx* __restrict__ w, cplx* x) {
+    __shared__ cplx t[AP_CHUNK], red[AP_ROWS * AP_SLOTS];
+    const int r = threadIdx.x & (AP_ROWS - 1), slot = threadIdx.x / AP_ROWS;
+    const int64_t i = (int64_t)blockIdx.x * AP_ROWS + r;
+    const cplx* Sk = a.S + (int64_t)k * a.b * a.b;
+    cplx acc = make_double2(0.0, 0.0);
+    for (int64_t jc = 0; jc < a.b; jc += AP_CHUNK) {
+        const int n = (int)(a.b - jc < AP_CHUNK ? a.b - jc : AP_CHUNK);
+        bt_stage<FWD>(a, k, jc, n, w, x, t);
+        __syncthreads();
+        bt_accum(Sk, a.b, i, jc, n, slot, t, acc);
+        __syncthreads();
+    }
+    const cplx s = bt_fold(acc, red);
+    if (slot == 0 && i < a.b) {
+        cplx& o = x[(int64_t)k * a.b + i];
+        if (FWD) o = s; else { o.x -= s.x; o.y -= s.y; }
+    }
+}
+
+// small planes (b <= WALK_B): both sweeps by ONE workgroup, a barrier between steps
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_walk(BtApply a, const cplx* __restrict__ w, cplx* x) {
+    __shared__ cplx t[WALK_B], red[AP_ROWS * AP_SLOTS];
+    const int r = threadIdx.x & (AP_ROWS - 1), slot = threadIdx.x / AP_ROWS;
+    const int b = (int)a.b;
+    for (int step = 0; step < 2 * a.K - 1; ++step) {
+        const bool fwd = step < a.K;
+        const int k = fwd ? step : 2 * a.K - 2 - step;
+        if (fwd) bt_stage<true>(a, k, 0, b, w, x, t); else bt_stage<false>(a, k, 0, b, w, x, t);
+        __syncthreads();
+        const cplx* Sk = a.S + (int64_t)k * b * b;
+        for (int i0 = 0; i0 < b; i0 += AP_ROWS) {
+            cplx acc = make_double2(0.0, 0.0);
+            bt_accum(Sk, b, i0 + r, 0, b, slot, t, acc);
+            const cplx s = bt_fold(acc, red);
+            if (slot == 0 && i0 + r < b) {
+                cplx& o = x[(int64_t)k * b + i0 + r];
+                if (fwd) o = s; else { o.x -= s.x; o.y -= s.y; }
+            }
+        }
+        __syncthreads();                          // this step's rows are visible to the next step (same workgroup)
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+struct BlockTri {
+    int64_t N = 0, K = 0, b = 0, nnz = 0;
+    DevBuf<int64_t> rowptr, rlo, rhi; DevBuf<int> col; DevBuf<cplx> val;     // private CSR of Msp, split at the block boundaries
+    DevBuf<cplx> S;                                                          // S_k^{-1}, k = 0 .. K-1
+    int64_t factor_us = 0; double min_ratio = 0.0;
+    int launches() const { return b <= WALK_B ? 1 : (int)(2 * K - 1); }
+};
+
+static double work_bytes(int64_t N, int64_t K) {
+    const double b = (double)(N / K);
+    return b * b * 16.0 + 2.0 * b * NB * 16.0 + 64.0 * (double)N;            // W, the two panels, row tables and vectors
+}
+
+void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who) {
+    const double b = (double)(N / K), factors = (double)K * b * b * 16.0, need = factors + work_bytes(N, K) + extra;
+    size_t free_b = 0, total_b = 0;
+    LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (need > (double)free_b)
+        fail(LSFC_ENOMEM, "%s: %lld blocks of %lld x %lld complex need %.3f GB for the inverses S_k^{-1} (K b^2 16 B) and %.3f GB of work space, "
+             "%.3f GB of device memory are free", who, (long long)K, (long long)(N / K), (long long)(N / K), factors / 1e9, (need - factors) / 1e9,
+             (double)free_b / 1e9);
+}
+
+static inline unsigned nblk(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t b = N / K;
+    LSFC_REQUIRE(b * b < ((int64_t)1 << 40), "block-tridiagonal preconditioner: block size %lld out of range", (long long)b);
+    hipStream_t st = nullptr;
+    std::unique_ptr<BlockTri> bt(new BlockTri());
+    bt->N = N; bt->K = K; bt->b = b;
+    int64_t nnz = 0;
+    LSFC_HIP(hipMemcpy(&nnz, rowptr + N, sizeof nnz, hipMemcpyDeviceToHost));
+    LSFC_REQUIRE(nnz >= 1 && nnz < ((int64_t)1 << 40), "block-tridiagonal preconditioner: rowptr[N] = %lld is not a plausible entry count", (long long)nnz);
+    bt->nnz = nnz;
+    // pattern: check, split, upper couplings by columns
+    bt->rowptr.alloc((size_t)N + 1); bt->rlo.alloc((size_t)N); bt->rhi.alloc((size_t)N); bt->col.alloc((size_t)nnz); bt->val.alloc((size_t)nnz);
+    LSFC_HIP(hipMemcpyAsync(bt->rowptr.p, rowptr, ((size_t)N + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    LSFC_HIP(hipMemcpyAsync(bt->val.p, msp, (size_t)nnz * sizeof(cplx), hipMemcpyDeviceToDevice, st));
+    DevBuf<BtStatus> dstat; dstat.alloc(1);
+    BtStatus hs{};
+    hs.bad_block = -1; hs.bad_row = -1; hs.min_ratio = 1e300; hs.smax = 0.0; hs.bad_band = hs.bad_format = 0x7fffffff;
+    LSFC_HIP(hipMemcpyAsync(dstat.p, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+    DevBuf<int> ucnt; ucnt.alloc((size_t)N);
+    LSFC_HIP(hipMemsetAsync(ucnt.p, 0, ucnt.bytes(), st));
+    hipLaunchKernelGGL(k_bt_check, dim3(nblk(N, 256)), dim3(256), 0, st, N, b, nnz, bt->rowptr.p, col, bt->rlo.p, bt->rhi.p, bt->col.p, ucnt.p, dstat.p);
+    LSFC_HIP(hipGetLastError());
+    std::vector<int> hcnt((size_t)N);
+    LSFC_HIP(hipMemcpyAsync(hcnt.data(), ucnt.p, ucnt.bytes(), hipMemcpyDeviceToHost, st));
+    LSFC_HIP(hipMemcpyAsync(&hs, dstat.p, sizeof hs, hipMemcpyDeviceToHost, st));
+    LSFC_HIP(hipStreamSynchronize(st));
+    LSFC_REQUIRE(hs.bad_format == 0x7fffffff, "block-tridiagonal preconditioner: row %d is not a CSR row with ascending columns in [0, N)", hs.bad_format);
+    LSFC_REQUIRE(hs.bad_band == 0x7fffffff, "block-tridiagonal preconditioner: row %d (block %lld) has an entry outside the three block diagonals "
+                 "of %lld blocks of %lld rows", hs.bad_band, (long long)(hs.bad_band / b), (long long)K, (long long)b);
+    std::vector<int64_t> hptr((size_t)N + 1, 0);
+    for (int64_t c = 0; c < N; ++c) hptr[(size_t)c + 1] = hptr[(size_t)c] + hcnt[(size_t)c];
+    const int64_t nnzU = hptr[(size_t)N];
+    DevBuf<int64_t> ucolptr, uidx; DevBuf<int> urow; DevBuf<cplx> uval;
+    ucolptr.alloc((size_t)N + 1); uidx.alloc((size_t)nnzU); urow.alloc((size_t)nnzU); uval.alloc((size_t)nnzU);
+    LSFC_HIP(hipMemcpyAsync(ucolptr.p, hptr.data(), hptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    LSFC_HIP(hipMemsetAsync(ucnt.p, 0, ucnt.bytes(), st));
+    if (nnzU) {
+        hipLaunchKernelGGL(k_bt_ufill, dim3(nblk(N, 256)), dim3(256), 0, st, N, bt->rowptr.p, bt->rhi.p, bt->col.p, ucolptr.p, ucnt.p, urow.p, uidx.p);
+        LSFC_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_bt_usort, dim3(nblk(N, 256)), dim3(256), 0, st, N, ucolptr.p, urow.p, uidx.p, bt->val.p, uval.p);
+        LSFC_HIP(hipGetLastError());
+    }
+    // the blocks
+    bt->S.alloc((size_t)(K * b * b));
+    DevBuf<cplx> W, P, R, Cb; DevBuf<double> part;
+    if (K > 1) W.alloc((size_t)(b * b));
+    P.alloc(NB * NB); R.alloc((size_t)(NB * b)); Cb.alloc((size_t)(b * NB)); part.alloc(256);
+    const int nt = (int)((b + NB - 1) / NB), nx = (int)nblk(b, 256);
+    const unsigned ebl = nblk(b * b, 256);
+    for (int64_t k = 0; k < K; ++k) {
+        cplx* Sk = bt->S.p + k * b * b;
+        if (k == 0) LSFC_HIP(hipMemsetAsync(Sk, 0, (size_t)(b * b) * sizeof(cplx), st));
+        else {
+            hipLaunchKernelGGL(k_bt_schur_left, dim3(ebl), dim3(256), 0, st, b, k, bt->rowptr.p, bt->rlo.p, bt->col.p, bt->val.p, Sk - b * b, W.p);
+            hipLaunchKernelGGL(k_bt_schur_right, dim3(ebl), dim3(256), 0, st, b, k, ucolptr.p, urow.p, uval.p, W.p, Sk);
+        }
+        hipLaunchKernelGGL(k_bt_add_diag, dim3(nblk(b, 256)), dim3(256), 0, st, b, k, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p, Sk);
+        hipLaunchKernelGGL(k_bt_absmax_part, dim3(256), dim3(256), 0, st, b * b, Sk, part.p);
+        hipLaunchKernelGGL(k_bt_absmax_fin, dim3(1), dim3(256), 0, st, 256, part.p, dstat.p);
+        for (int J = 0; J < nt; ++J) {
+            const int j0 = J * NB, nb = (int)std::min<int64_t>(NB, b - j0);
+            hipLaunchKernelGGL(k_bt_diag, dim3(1), dim3(1024), 0, st, Sk, b, j0, nb, P.p, dstat.p, (int)k, BLOCKTRI_PIVOT_MIN);
+            hipLaunchKernelGGL(k_bt_panels, dim3(2 * nx), dim3(256), 0, st, Sk, b, j0, nb, P.p, R.p, Cb.p, nx);
+            if (nt > 1) hipLaunchKernelGGL(k_bt_trail, dim3(nblk((int64_t)nt * nt, 4)), dim3(256), 0, st, Sk, b, J, nt, R.p, Cb.p);
+        }
+        LSFC_HIP(hipGetLastError());
+    }
+    LSFC_HIP(hipMemcpyAsync(&hs, dstat.p, sizeof hs, hipMemcpyDeviceToHost, st));
+    LSFC_HIP(hipStreamSynchronize(st));
+    LSFC_REQUIRE(hs.bad_block < 0, "block-tridiagonal preconditioner: breakdown in block %d at row %lld (row %d of the block): |pivot| / max|S_k| = %.3e is below %.1e "
+                 "-- the Schur block is singular or needs pivoting; use the host LU route (lsfc_precond_create)", hs.bad_block,
+                 (long long)(hs.bad_block * b + hs.bad_row), hs.bad_row, hs.bad_ratio, BLOCKTRI_PIVOT_MIN);
+    bt->min_ratio = hs.min_ratio;
+    bt->factor_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    return bt.release();
+}
+
+void blocktri_destroy(BlockTri* bt) { delete bt; }
+const int* blocktri_col32(const BlockTri* bt) { return bt->col.p; }
+int64_t blocktri_nnz(const BlockTri* bt) { return bt->nnz; }
+
+void blocktri_enqueue(const BlockTri* bt, const cplx* w, cplx* x, hipStream_t st) {
+    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p, bt->S.p};
+    if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk, dim3(1), dim3(AP_ROWS * AP_SLOTS), 0, st, a, w, x); return; }
+    const unsigned g = nblk(bt->b, AP_ROWS);
+    for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(k_bt_step<true>, dim3(g), dim3(AP_ROWS * AP_SLOTS), 0, st, a, k, w, x);
+    for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(k_bt_step<false>, dim3(g), dim3(AP_ROWS * AP_SLOTS), 0, st, a, k, w, x);
+}
+
+BlockTriInfo blocktri_info(const BlockTri* bt) {
+    return BlockTriInfo{bt->K, bt->b, (int64_t)bt->S.bytes(), bt->launches(), bt->factor_us, 0, bt->min_ratio};
+}
+
+void blocktri_get_block(const BlockTri* bt, int64_t k, cplx* host_out) {
+    LSFC_HIP(hipMemcpy(host_out, bt->S.p + k * bt->b * bt->b, (size_t)(bt->b * bt->b) * sizeof(cplx), hipMemcpyDeviceToHost));
+}
+
+__global__ void k_warmup_blocktri(int* p) { if (p) *p = 0; }
+void warmup_blocktri() {
+    hipLaunchKernelGGL(k_warmup_blocktri, dim3(1), dim3(64), 0, 0, (int*)nullptr);
+    LSFC_HIP(hipGetLastError());
+}
+
+} // namespace lsfc

@@ -1,0 +1,32 @@
+// Host-side interface of the block-tridiagonal factorisation of Msp (blocktri.hip), used by precond.hip.
+#pragma once
+#include "common.hpp"
+
+namespace lsfc {
+
+struct BlockTri;       // K explicit inverses S_k^{-1} (b x b, column-major) and a private copy of the CSR of Msp
+
+struct BlockTriInfo {
+    int64_t K, b, factor_bytes, launches, factor_us;
+    int pivoting;
+    double min_pivot_ratio;
+};
+
+// |pivot| / max|S_k| below which the pivot-free inversion of a Schur block is refused (include/lsfc.h)
+static constexpr double BLOCKTRI_PIVOT_MIN = 1e-8;
+
+// LSFC_ENOMEM unless K b^2 16 B of factors plus the work space fit into the free memory of the current device;
+// `extra` = bytes the caller is about to allocate besides.  From the dimensions alone: nothing is allocated or read.
+void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who);
+// Factorise: rowptr / col / msp are DEVICE arrays (CSR, 0-based, columns ascending, N rows).  Synchronous.
+BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp);
+void blocktri_destroy(BlockTri*);
+const int* blocktri_col32(const BlockTri*);          // the columns as 32-bit integers (device), nnz of them
+int64_t blocktri_nnz(const BlockTri*);
+// x <- Msp^{-1} w (device vectors of N, w != x), enqueued on st as a single chain of launches
+void blocktri_enqueue(const BlockTri*, const cplx* w, cplx* x, hipStream_t st);
+BlockTriInfo blocktri_info(const BlockTri*);
+void blocktri_get_block(const BlockTri*, int64_t k, cplx* host_out);
+void warmup_blocktri();
+
+} // namespace lsfc

@@ -18,8 +18,13 @@
 //                                        forward substitution (the trailing separator blocks of the factor)
 // The whole sequence SpMV -> L solve -> U solve -> scatter is captured once in a hipGraph on fixed internal buffers
 // and replayed per apply.
+//
+// A second kind of object is factorised on the device (blocktri.hip; lsfc_precond_create_blocktri / _from_plan at the end
+// of this file): its apply is the same SpMV followed by the block-tridiagonal sweeps, captured and replayed the same way.
 #include "common.hpp"
 #include "pruned.hpp"
+#include "plan.hpp"
+#include "blocktri.hpp"
 #include <algorithm>
 #include <complex>
 #include <cstring>
@@ -477,10 +482,11 @@ struct lsfc_precond {
     lsfc::DevBuf<int64_t> a_rowptr; lsfc::DevBuf<int> a_col; lsfc::DevBuf<lsfc::cplx> a_val;     // As, CSR
     lsfc::DevBuf<int> rgather, cscatter; lsfc::DevBuf<double> rscale;
     lsfc::TriFactor L, U;
+    lsfc::BlockTri* bt = nullptr;      // block-tridiagonal factorisation (blocktri.hip) instead of L, U
     lsfc::DevBuf<lsfc::cplx> vin, y0, z, w, vout, hstage;
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; hipStream_t captured_on = nullptr;
     int launches = 0;
-    ~lsfc_precond() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }
+    ~lsfc_precond() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); lsfc::blocktri_destroy(bt); }
 };
 
 namespace lsfc {
@@ -489,6 +495,7 @@ static void enqueue_all(lsfc_precond* pc, hipStream_t st) {
     const int N = (int)pc->N;
     hipLaunchKernelGGL(k_spmv_gather<8>, dim3((unsigned)(((int64_t)N * 8 + 255) / 256)), dim3(256), 0, st, pc->a_rowptr.p, pc->a_col.p, pc->a_val.p,
                        pc->rgather.p, pc->rscale.p, pc->vin.p, pc->y0.p, N);
+    if (pc->bt) { blocktri_enqueue(pc->bt, pc->y0.p, pc->vout.p, st); return; }
     launch_factor(pc->L, pc->y0.p, pc->z.p, st);
     launch_factor(pc->U, pc->z.p, pc->w.p, st);
     hipLaunchKernelGGL(k_scatter, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, pc->w.p, pc->cscatter.p, pc->vout.p, N);
@@ -623,8 +630,8 @@ int lsfc_precond_callback(void* user, double* v, int64_t n) {
 int lsfc_precond_stats(const lsfc_precond* pc, int64_t* levels_L, int64_t* levels_U, int64_t* launches) {
     return guarded([&] {
         LSFC_REQUIRE(pc, "NULL preconditioner");
-        if (levels_L) *levels_L = pc->L.nlevels;
-        if (levels_U) *levels_U = pc->U.nlevels;
+        if (levels_L) *levels_L = pc->bt ? blocktri_info(pc->bt).K : pc->L.nlevels;
+        if (levels_U) *levels_U = pc->bt ? blocktri_info(pc->bt).K : pc->U.nlevels;
         if (launches) *launches = pc->launches;
     });
 }
@@ -633,8 +640,108 @@ int lsfc_precond_schedule(const lsfc_precond* pc, int factor, int64_t out[10]) {
     return guarded([&] {
         LSFC_REQUIRE(pc && out, "NULL argument");
         LSFC_REQUIRE(factor == 0 || factor == 1, "bad factor %d (0 = L, 1 = U)", factor);
+        LSFC_REQUIRE(!pc->bt, "a block-tridiagonal preconditioner has no level schedule (see lsfc_precond_blocktri_info)");
         const lsfc::TriFactor& F = factor == 0 ? pc->L : pc->U;
         for (int i = 0; i < 10; ++i) out[i] = F.sched[i];
+    });
+}
+
+} // extern "C"
+
+// ---- block-tridiagonal route: factorised on the device (blocktri.hip) ----------------------------------------------
+
+namespace lsfc {
+
+// the object from DEVICE arrays of one shared pattern; the current device is `device`
+static lsfc_precond* create_blocktri_dev(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* As, const cplx* Msp, int device) {
+    std::unique_ptr<lsfc_precond> pc(new lsfc_precond());
+    pc->device = device; pc->N = N;
+    pc->bt = blocktri_factor(N, K, rowptr, col, Msp);
+    const int64_t nnz = blocktri_nnz(pc->bt);
+    pc->a_rowptr.alloc((size_t)N + 1); pc->a_col.alloc((size_t)nnz); pc->a_val.alloc((size_t)nnz);
+    LSFC_HIP(hipMemcpy(pc->a_rowptr.p, rowptr, ((size_t)N + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
+    LSFC_HIP(hipMemcpy(pc->a_col.p, blocktri_col32(pc->bt), (size_t)nnz * sizeof(int), hipMemcpyDeviceToDevice));
+    LSFC_HIP(hipMemcpy(pc->a_val.p, As, (size_t)nnz * sizeof(cplx), hipMemcpyDeviceToDevice));
+    for (DevBuf<cplx>* b : { &pc->vin, &pc->y0, &pc->vout }) { b->alloc((size_t)N); LSFC_HIP(hipMemset(b->p, 0, b->bytes())); }
+    pc->launches = 1 + (int)blocktri_info(pc->bt).launches;
+    LSFC_HIP(hipDeviceSynchronize());
+    return pc.release();
+}
+
+static void select_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) fail(LSFC_ENODEV, "no HIP device available: the preconditioner has no CPU fallback");
+    LSFC_REQUIRE(device >= 0 && device < count, "device %d out of range (have %d)", device, count);
+    LSFC_HIP(hipSetDevice(device));
+    pruned_warmup(device);
+}
+
+} // namespace lsfc
+
+extern "C" {
+
+int lsfc_precond_create_blocktri(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
+                                 const double* As_val, const double* Msp_val, int memspace, int device) {
+    return guarded([&] {
+        LSFC_REQUIRE(out, "NULL argument"); *out = nullptr;
+        LSFC_REQUIRE(rowptr && col && As_val && Msp_val, "NULL argument");
+        LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "bad memspace %d", memspace);
+        LSFC_REQUIRE(N >= 1 && N < ((int64_t)1 << 31), "preconditioner: N out of range");
+        LSFC_REQUIRE(nblocks >= 1 && N % nblocks == 0, "block-tridiagonal preconditioner: N = %lld is not divisible by nblocks = %lld", (long long)N, (long long)nblocks);
+        select_device(device);
+        blocktri_require_memory(N, nblocks, 0.0, "lsfc_precond_create_blocktri");      // from the dimensions alone, before any array is read
+        if (memspace == LSFC_MEM_DEVICE) { *out = create_blocktri_dev(N, nblocks, rowptr, col, (const cplx*)As_val, (const cplx*)Msp_val, device); return; }
+        const int64_t nnz = rowptr[N];
+        LSFC_REQUIRE(nnz >= 0, "block-tridiagonal preconditioner: rowptr[N] is negative");
+        DevBuf<int64_t> drp, dcol; DevBuf<cplx> das, dmsp;
+        drp.alloc((size_t)N + 1); dcol.alloc((size_t)nnz); das.alloc((size_t)nnz); dmsp.alloc((size_t)nnz);
+        LSFC_HIP(hipMemcpy(drp.p, rowptr, ((size_t)N + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (nnz) {
+            LSFC_HIP(hipMemcpy(dcol.p, col, (size_t)nnz * sizeof(int64_t), hipMemcpyHostToDevice));
+            LSFC_HIP(hipMemcpy(das.p, As_val, (size_t)nnz * sizeof(cplx), hipMemcpyHostToDevice));
+            LSFC_HIP(hipMemcpy(dmsp.p, Msp_val, (size_t)nnz * sizeof(cplx), hipMemcpyHostToDevice));
+        }
+        *out = create_blocktri_dev(N, nblocks, drp.p, dcol.p, das.p, dmsp.p, device);
+    });
+}
+
+int lsfc_precond_create_from_plan(lsfc_precond** out, lsfc_plan* plan) {
+    return guarded([&] {
+        LSFC_REQUIRE(out, "NULL argument"); *out = nullptr;
+        LSFC_REQUIRE(plan, "NULL plan");
+        LSFC_REQUIRE(!plan->dist && !plan->multi, "block-tridiagonal preconditioner: not available on a distributed or multi-device plan");
+        const int64_t n = plan->dims[0], m = plan->dims[1], l = plan->ndim == 2 ? 1 : plan->dims[2];
+        const int64_t N = n * m * l, K = plan->ndim == 2 ? m : l;
+        int64_t nnz = 0;
+        if (int rc = lsfc_sparsify_pattern(n, m, l, &nnz, nullptr, nullptr, nullptr)) fail(rc, "%s", lsfc_last_error());
+        select_device(plan->device);
+        blocktri_require_memory(N, K, (double)nnz * 40.0, "lsfc_precond_create_from_plan");
+        DevBuf<int64_t> drp, dcol; DevBuf<cplx> das, dmsp;
+        drp.alloc((size_t)N + 1); dcol.alloc((size_t)nnz); das.alloc((size_t)nnz); dmsp.alloc((size_t)nnz);
+        if (int rc = lsfc_sparsify_build(plan, drp.p, dcol.p, (double*)das.p, nullptr, (double*)dmsp.p, nullptr, LSFC_MEM_DEVICE)) fail(rc, "%s", lsfc_last_error());
+        *out = create_blocktri_dev(N, K, drp.p, dcol.p, das.p, dmsp.p, plan->device);
+    });
+}
+
+int lsfc_precond_blocktri_info(const lsfc_precond* pc, int64_t out[6], double* min_pivot_ratio) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && out, "NULL argument");
+        LSFC_REQUIRE(pc->bt, "not a block-tridiagonal preconditioner (made by lsfc_precond_create)");
+        const BlockTriInfo i = blocktri_info(pc->bt);
+        out[0] = i.K; out[1] = i.b; out[2] = i.factor_bytes; out[3] = pc->launches; out[4] = i.factor_us; out[5] = i.pivoting;
+        if (min_pivot_ratio) *min_pivot_ratio = i.min_pivot_ratio;
+    });
+}
+
+int lsfc_precond_blocktri_get_block(const lsfc_precond* pc, int64_t k, double* out, int64_t capacity_complex) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && out, "NULL argument");
+        LSFC_REQUIRE(pc->bt, "not a block-tridiagonal preconditioner (made by lsfc_precond_create)");
+        const BlockTriInfo i = blocktri_info(pc->bt);
+        LSFC_REQUIRE(k >= 0 && k < i.K, "block %lld out of range (have %lld)", (long long)k, (long long)i.K);
+        LSFC_REQUIRE(capacity_complex >= i.b * i.b, "capacity %lld is less than the %lld entries of a block", (long long)capacity_complex, (long long)(i.b * i.b));
+        LSFC_HIP(hipSetDevice(pc->device));
+        blocktri_get_block(pc->bt, k, (cplx*)out);
     });
 }
 

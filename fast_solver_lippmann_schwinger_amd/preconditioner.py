@@ -6,7 +6,13 @@
 The sparse LU stays on the host, as in the reference (UMFPACK there; scipy's SuperLU here -- any LU of Msp gives
 the same operator).  Its factors and As are uploaded once; `ldiv_` then runs entirely on the device (csrc/precond.hip:
 CSR SpMV + two level-scheduled sparse triangular solves replayed from one hipGraph), so under `gmres_` the Krylov
-vector never crosses PCIe.  Msp / As are assembled on the device by sparsify.py (src/SparsifyingMatrix*.jl)."""
+vector never crosses PCIe.  Msp / As are assembled on the device by sparsify.py (src/SparsifyingMatrix*.jl).
+
+A second route factorises on the device as well (csrc/blocktri.hip, lsfc_precond_create_blocktri): with the slowest grid
+axis as block index Msp is block tridiagonal, and exact block elimination with dense explicit inverses of the Schur
+blocks replaces the sparse LU.  `SparsifyingPreconditioner(Msp, As, factor="blocktri", nblocks=...)` takes host
+matrices; `SparsifyingPreconditioner.from_operator(M)` assembles and factorises from the plan of a FastM / FastM3D
+without the matrices ever leaving the device (examples/example3D.jl:57-68 in one call)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,6 +25,8 @@ from . import _lib as L
 # lsfc_precond_schedule's ten counts (include/lsfc.h), in order
 SCHEDULE_FIELDS = ("level8", "level16", "level32", "level64", "chains", "chain_groups", "heavy_groups", "run_pieces",
                    "run_max", "run_min")
+# lsfc_precond_blocktri_info's six counts, in order
+BLOCKTRI_FIELDS = ("blocks", "block_size", "factor_bytes", "launches", "factor_us", "pivoting")
 
 
 def _csr_arrays(A):
@@ -30,19 +38,40 @@ def _csr_arrays(A):
 
 class SparsifyingPreconditioner:
     """SparsifyingPreconditioner(Msp, As; solverType="UMFPACK") -- src/preconditioner.jl:27-58.
-    Msp, As: scipy.sparse matrices (N x N, complex).  ``lu``: optional pre-computed scipy.sparse.linalg.SuperLU of Msp."""
+    Msp, As: scipy.sparse matrices (N x N, complex).  ``lu``: optional pre-computed scipy.sparse.linalg.SuperLU of Msp.
+    ``factor``: "host" (default) -- sparse LU of Msp on the host, level-scheduled triangular solves on the device;
+    "blocktri" -- block-tridiagonal factorisation on the device with ``nblocks`` blocks (the slowest grid axis: m in 2D,
+    l in 3D); Msp and As must share one pattern, as the pair of `sparsifying_pair` does."""
 
-    def __init__(self, Msp, As, solverType="UMFPACK", device=0, lu=None):
+    def __init__(self, Msp, As, solverType="UMFPACK", device=0, lu=None, factor="host", nblocks=None):
         import scipy.sparse as sp
         import scipy.sparse.linalg as spla
         if solverType not in ("UMFPACK", "MKLPARDISO"):
             raise NameError(f"UndefVarError: unknown solverType {solverType!r}")
+        if factor not in ("host", "blocktri"):
+            raise ValueError(f"factor must be 'host' or 'blocktri', not {factor!r}")
         Msp = sp.csc_matrix(Msp, dtype=np.complex128)
         As = sp.csr_matrix(As, dtype=np.complex128)
         N = Msp.shape[0]
         if Msp.shape != (N, N) or As.shape != (N, N):
             raise ValueError("DimensionMismatch: Msp and As must be square and of the same size")
         self.Msp, self.As, self.solverType, self.N = Msp, As, solverType, N
+        self.factor = factor
+        if factor == "blocktri":
+            if nblocks is None:
+                raise ValueError("factor='blocktri' needs nblocks (the slowest grid axis)")
+            if lu is not None:
+                raise ValueError("factor='blocktri' factorises on the device: lu does not apply")
+            a_ptr, a_col, a_val = _csr_arrays(As)
+            m_ptr, m_col, m_val = _csr_arrays(Msp)
+            if not (np.array_equal(a_ptr, m_ptr) and np.array_equal(a_col, m_col)):
+                raise ValueError("factor='blocktri': Msp and As must share one sparsity pattern (every stencil entry stored)")
+            pc = C.c_void_p()
+            p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+            L.check(L.load().lsfc_precond_create_blocktri(C.byref(pc), N, int(nblocks), p(m_ptr), p(m_col), p(a_val), p(m_val),
+                                                          L.LSFC_MEM_HOST, int(device)))
+            self._pc = pc
+            return
         if lu is None:
             lu = spla.splu(Msp)                      # Pr * Msp * Pc = L * U, no row scaling
         # scipy: Pr Msp Pc = L U with row i of Msp -> row perm_r[i] of L U, column j of Msp -> column perm_c[j] of L U;
@@ -60,6 +89,36 @@ class SparsifyingPreconditioner:
         L.check(L.load().lsfc_precond_create(C.byref(pc), N, p(a_ptr), p(a_col), p(a_val), p(l_ptr), p(l_col), p(l_val),
                                              p(u_ptr), p(u_col), p(u_val), p(row_gather), p(col_scatter), None, int(device)))
         self._pc = pc
+
+    @classmethod
+    def from_operator(cls, M):
+        """The preconditioner of a FastM / FastM3D in one device call (lsfc_precond_create_from_plan): As and
+        Msp = As + k^2 AG diag(nu) are assembled into device memory from the plan's kernel, nu and k, and factorised
+        there with the slowest axis as block index.  ``Msp`` / ``As`` of the object are None: nothing is downloaded."""
+        self = cls.__new__(cls)
+        pc = C.c_void_p()
+        L.check(L.load().lsfc_precond_create_from_plan(C.byref(pc), M._plan))
+        self._pc = pc
+        self.Msp = self.As = None
+        self.solverType, self.factor = "UMFPACK", "blocktri"
+        self.N = int(self.blocktri_info()["blocks"] * self.blocktri_info()["block_size"])
+        return self
+
+    def blocktri_info(self):
+        """lsfc_precond_blocktri_info as a dict (BLOCKTRI_FIELDS and min_pivot_ratio)"""
+        out = (C.c_int64 * len(BLOCKTRI_FIELDS))()
+        ratio = C.c_double(0.0)
+        L.check(L.load().lsfc_precond_blocktri_info(self._pc, out, C.byref(ratio)))
+        info = dict(zip(BLOCKTRI_FIELDS, (int(v) for v in out)))
+        info["min_pivot_ratio"] = ratio.value
+        return info
+
+    def blocktri_block(self, k):
+        """S_k^{-1} (b x b) of a block-tridiagonal object (lsfc_precond_blocktri_get_block; debugging and tests)"""
+        b = self.blocktri_info()["block_size"]
+        out = np.empty(b * b, dtype=np.complex128)
+        L.check(L.load().lsfc_precond_blocktri_get_block(self._pc, int(k), out.ctypes.data_as(C.c_void_p), b * b))
+        return out.reshape((b, b), order="F")
 
     # -- ldiv!(P, b) / P \\ b -- src/preconditioner.jl:132-170 ---------------------------------------------------------
     def ldiv_(self, v):
@@ -89,10 +148,13 @@ class SparsifyingPreconditioner:
 
     def stats(self):
         """dependency levels of the L and U solves, kernel launches captured in the graph, and what the launch schedule
-        of each solve reached (schedule_L / schedule_U, SCHEDULE_FIELDS of lsfc_precond_schedule)"""
+        of each solve reached (schedule_L / schedule_U, SCHEDULE_FIELDS of lsfc_precond_schedule).  A block-tridiagonal
+        object has no levels: levels_L = levels_U = its blocks, and the fields of `blocktri_info` take the schedule's place."""
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         lib = L.load()
         L.check(lib.lsfc_precond_stats(self._pc, C.byref(a), C.byref(b), C.byref(c)))
+        if self.factor == "blocktri":
+            return {"levels_L": a.value, "levels_U": b.value, **self.blocktri_info(), "launches": c.value}
         st = {"levels_L": a.value, "levels_U": b.value, "launches": c.value, "nnz_L": self.nnz_L, "nnz_U": self.nnz_U}
         for factor, name in ((0, "schedule_L"), (1, "schedule_U")):
             out = (C.c_int64 * len(SCHEDULE_FIELDS))()

@@ -238,6 +238,35 @@ int lsfc_precond_stats(const lsfc_precond* pc, int64_t* levels_L, int64_t* level
  * LSFC_EINVAL: NULL pc or out, factor not 0 or 1. */
 int lsfc_precond_schedule(const lsfc_precond* pc, int factor, int64_t out[10]);
 
+/* The same object factorised ON THE DEVICE, in place of the host's lu(Msp) (src/preconditioner.jl:35;
+ * examples/example3D.jl:57-68 build As, AG, Msp and call SparsifyingPreconditioner(Msp, As)).  As and Msp share one
+ * pattern, as lsfc_sparsify_build returns it (CSR, 0-based, columns ascending, values interleaved complex); with the
+ * slowest grid axis as block index Msp is block tridiagonal: nblocks blocks of b = N / nblocks rows.  Exact block
+ * elimination S_0 = D_0, S_k = D_k - L_k S_{k-1}^{-1} U_{k-1} with the explicit inverses S_k^{-1} kept dense
+ * (nblocks * b^2 * 16 bytes of device memory); the apply is As v, then 2 nblocks - 1 dense b x b products.
+ * memspace: LSFC_MEM_HOST or LSFC_MEM_DEVICE for the four arrays (the device output of lsfc_sparsify_build is taken as it is).
+ * The Schur blocks are inverted WITHOUT pivoting (they are well conditioned: |pivot| / max|S_k| >= 0.5 observed); every
+ * pivot is monitored and |pivot| / max|S_k| < 1e-8 (or a pivot that is not a number) is a breakdown: LSFC_EINVAL with
+ * block and row in lsfc_last_error, no object is returned.
+ * LSFC_EINVAL: NULL pointer, N not divisible by nblocks, a row that is not sorted CSR, an entry outside the three block
+ * diagonals (the row is named), breakdown.  LSFC_ENOMEM (decided from N and nblocks alone, before an array is read or
+ * anything is allocated): inverses plus work space exceed the free device memory; the message has the figures.
+ * Two factorisations of the same input are bitwise equal. */
+int lsfc_precond_create_blocktri(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
+                                 const double* As_val, const double* Msp_val, int memspace, int device);
+/* lsfc_sparsify_build into device memory, then lsfc_precond_create_blocktri with nblocks = the slowest axis (m in 2D,
+ * l in 3D), on the plan's device: examples/example3D.jl:57-68 in one call.  Restrictions of lsfc_sparsify_build. */
+int lsfc_precond_create_from_plan(lsfc_precond** out, lsfc_plan* plan);
+/* out: blocks, block size b, bytes of the stored inverses, kernel launches per apply, factorisation time in
+ * microseconds, 1 if pivoting was used (always 0); min_pivot_ratio (may be NULL): smallest |pivot| / max|S_k| met.
+ * LSFC_EINVAL on an object made by lsfc_precond_create. */
+int lsfc_precond_blocktri_info(const lsfc_precond* pc, int64_t out[6], double* min_pivot_ratio);
+/* Debug / test access in the spirit of lsfc_plan_get_symbol: S_k^{-1} (b x b, column-major) to the host.
+ * LSFC_EINVAL: object made by lsfc_precond_create, k out of range, capacity_complex < b^2. */
+int lsfc_precond_blocktri_get_block(const lsfc_precond* pc, int64_t k, double* out, int64_t capacity_complex);
+/* On such an object lsfc_precond_apply / _callback / _set_stream / _destroy work as on any other; lsfc_precond_stats
+ * returns nblocks, nblocks and the launch count; lsfc_precond_schedule returns LSFC_EINVAL (there are no levels). */
+
 /* ---- assembly of the sparsifying matrices (As, As*G, Msp) ------------------- */
 
 /* The reference builds the two matrices of SparsifyingPreconditioner(Msp, As) with buildSparseA / buildSparseAG

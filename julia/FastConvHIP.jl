@@ -191,6 +191,41 @@ function SparsifyingPreconditionerHIP(Msp::SparseMatrixCSC{Complex{Float64},Int6
     finalizer(P -> ccall((:lsfc_precond_destroy, liblsfc), Cint, (Ptr{Cvoid},), P.pc), P)
     return P
 end
+# The same object factorised ON THE DEVICE (lsfc_precond_create_blocktri / lsfc_precond_create_from_plan): block-tridiagonal
+# elimination with the slowest grid axis as block index instead of lu(Msp).  Msp and As must share one pattern, as
+# buildSparseA* / buildSparseAG* return it.  examples/example3D.jl:57-68 in one call: SparsifyingPreconditionerHIP(fastconv).
+function _wrap_precond(pc::Ptr{Cvoid}, N)
+    P = SparsifyingPreconditionerHIP(pc, N)
+    finalizer(P -> ccall((:lsfc_precond_destroy, liblsfc), Cint, (Ptr{Cvoid},), P.pc), P)
+    return P
+end
+function SparsifyingPreconditionerHIP(Msp::SparseMatrixCSC{Complex{Float64},Int64}, As::SparseMatrixCSC{Complex{Float64},Int64}, nblocks::Integer; device=0)
+    N = size(Msp, 1)
+    (mp, mc, mv) = _csr(Msp); (ap, ac, av) = _csr(As)
+    (mp == ap && mc == ac) || throw(DimensionMismatch("Msp and As must share one sparsity pattern"))
+    pc = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:lsfc_precond_create_blocktri, liblsfc), Cint,
+                (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Cint, Cint),
+                pc, N, nblocks, mp, mc, av, mv, 0, device))
+    return _wrap_precond(pc[], N)
+end
+function SparsifyingPreconditionerHIP(M::FastMHIP)
+    pc = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:lsfc_precond_create_from_plan, liblsfc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}), pc, M.plan))
+    return _wrap_precond(pc[], size(M, 1))
+end
+# (blocks, block size, bytes of the inverses, launches per apply, factorisation microseconds, pivoting used), min |pivot| / max|S_k|
+function blocktri_info(P::SparsifyingPreconditionerHIP)
+    out = zeros(Int64, 6); r = Ref{Float64}(0.0)
+    check(ccall((:lsfc_precond_blocktri_info, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ref{Float64}), P.pc, out, r))
+    return out, r[]
+end
+# S_k^{-1} (k 0-based), b x b
+function blocktri_block(P::SparsifyingPreconditionerHIP, k::Integer)
+    b = blocktri_info(P)[1][2]; S = Matrix{Complex{Float64}}(undef, b, b)
+    check(ccall((:lsfc_precond_blocktri_get_block, liblsfc), Cint, (Ptr{Cvoid}, Int64, Ptr{Complex{Float64}}, Int64), P.pc, k, S, b * b))
+    return S
+end
 # ldiv!(P, b): host vector in, host vector out (staged over PCIe); inside gmres_hip! the device path is used instead
 function LinearAlgebra.ldiv!(P::SparsifyingPreconditionerHIP, b::Vector{Complex{Float64}})
     check(ccall((:lsfc_precond_apply, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Complex{Float64}}, Cint), P.pc, b, 0)); b

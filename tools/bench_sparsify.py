@@ -6,7 +6,14 @@ value spread of the classes; where it fits, the route a Python user had before (
 one numpy SVD per class); at 3D 48^3 the host LU of Msp (scipy splu, in a child process under a time limit).
 One JSON line per measurement on stdout and appended to --out.
 
-    python tools/bench_sparsify.py --out profiles/sparsify_timing.jsonl"""
+    python tools/bench_sparsify.py --out profiles/sparsify_timing.jsonl
+
+--factor: the preconditioner factorised on the device instead (SparsifyingPreconditioner.from_operator: assembly plus
+block-tridiagonal factorisation, csrc/blocktri.hip) -- set-up time, time per apply beside its byte floor
+2 K b^2 16 B / 6.29 TB/s, and, where scipy's splu of the same Msp is affordable (2D, 3D up to 24^3), the host-LU route
+with its level-scheduled apply on the same pair.
+
+    python tools/bench_sparsify.py --factor --out profiles/precond_blocktri.jsonl"""
 import argparse
 import json
 import os
@@ -122,6 +129,54 @@ def splu_time(a, limit, tmpdir):
         os.remove(path)
 
 
+def apply_ms(P, N, reps=20):
+    import torch
+    v = torch.from_numpy(np.random.default_rng(0).standard_normal(N) + 0j).cuda()
+    P.ldiv_(v)                                             # captures the graph
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        P.ldiv_(v)
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / reps
+
+
+def factor_mode(args):
+    import scipy.sparse.linalg as spla
+    import torch
+    import fast_solver_lippmann_schwinger_amd as pkg
+    for spec in args.cases.split(","):
+        ndim, n = (int(v) for v in spec.split(":"))
+        N = n ** ndim
+        M = operator(ndim, n)
+        pkg.sparsify_arrays(M, ("As",))                    # warm: the plan's spatial kernel
+        t0 = time.perf_counter()
+        P = pkg.SparsifyingPreconditioner.from_operator(M)
+        setup = time.perf_counter() - t0
+        st = P.stats()
+        floor_ms = 1e3 * 2 * st["factor_bytes"] / 6.29e12
+        rec = {"case": f"{ndim}D n={n}", "N": N, "blocks": st["blocks"], "block_size": st["block_size"],
+               "factor_GB": round(st["factor_bytes"] / 1e9, 3), "assembly_plus_factor_s": round(setup, 4),
+               "factor_s": round(st["factor_us"] / 1e6, 4), "min_pivot_ratio": round(st["min_pivot_ratio"], 4),
+               "launches": st["launches"], "apply_ms": round(apply_ms(P, N), 4), "apply_floor_ms": round(floor_ms, 4)}
+        if ndim == 2 or n <= 24:
+            Msp, As = pkg.sparsifying_pair(M)
+            t0 = time.perf_counter()
+            lu = spla.splu(Msp)
+            rec["host_splu_s"] = round(time.perf_counter() - t0, 3)
+            Ph = pkg.SparsifyingPreconditioner(Msp, As, lu=lu)
+            rec["host_route_apply_ms"] = round(apply_ms(Ph, N), 4)
+            rec["host_route_launches"] = Ph.stats()["launches"]
+            b = np.random.default_rng(1).standard_normal(N) + 1j * np.random.default_rng(2).standard_normal(N)
+            xh = Ph.solve(b)
+            rec["rel_diff_to_host_route"] = float(np.linalg.norm(P.solve(b) - xh) / np.linalg.norm(xh))
+            Ph.close()
+        emit(args.out, rec)
+        P.close()
+        del M
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -129,7 +184,12 @@ def main():
     ap.add_argument("--cases", default="2:201,3:48,3:128,3:256")
     ap.add_argument("--splu-limit", type=float, default=240.0)
     ap.add_argument("--device-only", action="store_true", help="only the device builds (for a kernel trace)")
+    ap.add_argument("--factor", action="store_true", help="time the device-factorised preconditioner (see the module docstring)")
     args = ap.parse_args()
+    if args.factor:
+        if args.cases == ap.get_default("cases"):
+            args.cases = "2:201,2:257,2:513,3:24,3:48,3:64"
+        return factor_mode(args)
     import torch
     import fast_solver_lippmann_schwinger_amd as pkg
     for spec in args.cases.split(","):
