@@ -61,6 +61,8 @@ SIGNATURES = {
     "lsfc_precond_destroy": (_I, [_P]),
     "lsfc_precond_set_stream": (_I, [_P, _P]),
     "lsfc_precond_apply": (_I, [_P, _P, _I]),
+    "lsfc_precond_apply_batch": (_I, [_P, _P, _L, _I]),
+    "lsfc_precond_batch_info": (_I, [_P, C.POINTER(_L)]),
     "lsfc_precond_callback": (_I, [_P, _P, _L]),
     "lsfc_precond_stats": (_I, [_P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L)]),
     "lsfc_precond_schedule": (_I, [_P, _I, C.POINTER(_L)]),

@@ -19,6 +19,11 @@
 // Apply: one kernel per step of the two sweeps; a workgroup forms the stencil product (L_k z_{k-1} or U_k x_{k+1}) in
 // LDS and multiplies 16 rows of S_k^{-1} with it (16 B loads, 32 column slots folded through LDS in a fixed order).
 // Planes of at most 96 rows are walked inside one launch by a single workgroup.
+//
+// Apply to a GROUP of up to 8 right-hand sides (blocktri_enqueue_batch): three launches per step.  A small kernel forms the
+// stencil product once for all members (b x R), the product kernel reads S_k^{-1} once and applies every loaded entry to
+// all R members (tiles of 64 rows x a range of columns, so that one step fills the device), a third kernel folds the
+// column ranges in a fixed order.  What is summed for one member, and in which order, is fixed by b alone.
 #include "blocktri.hpp"
 #include <algorithm>
 #include <chrono>
@@ -381,6 +386,97 @@ __global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_walk(BtApply a, const
     }
 }
 
+// ---- the apply for a group of right-hand sides -------------------------------------------------------------------------
+//
+// Vectors of a group are member-major (member r at offset r N); the stencil product t is b x R with the R values of a row
+// next to each other.  A member's result must not depend on its companions (a lock-step GMRES drops converged members):
+// the tiling below comes from b alone, every member has its own accumulators, and the complex multiply-adds are spelled
+// as fused multiply-adds, so no instantiation contracts them differently from another.
+
+static constexpr int BB_ROWS = 64;        // rows of S_k^{-1} per workgroup: one wave along a column, 1 KiB per load ...
+static constexpr int BB_SLOTS = 4;        // ... times column slots (waves) = 256 threads
+static constexpr int BB_COLS_MAX = 128;   // columns of S_k^{-1} per workgroup at most
+
+// columns per workgroup (from b alone): b / 64 row tiles times b / cols column ranges keep 256 CUs busy from b ~ 600 on
+static int bb_cols(int64_t b) { return b < 1024 ? 32 : (b < 2048 ? 64 : BB_COLS_MAX); }
+
+__device__ __forceinline__ void cfma_x(cplx& s, cplx a, cplx b) {
+    s.x = fma(a.x, b.x, s.x); s.x = fma(-a.y, b.y, s.x);
+    s.y = fma(a.x, b.y, s.y); s.y = fma(a.y, b.x, s.y);
+}
+
+// t[j, r] = (w_r)_k[j] - (L_k (z_r)_{k-1})[j] (forward) or (U_k (x_r)_{k+1})[j] (backward): a thread per row and member
+template <bool FWD>
+__global__ __launch_bounds__(256) void k_btb_stage(BtApply a, int k, int R, int64_t N, const cplx* __restrict__ w, const cplx* __restrict__ x,
+                                                   cplx* __restrict__ t) {
+    const int64_t idx = blockIdx.x * (int64_t)256 + threadIdx.x;
+    if (idx >= a.b * R) return;
+    const int r = (int)(idx % R);
+    const int64_t g = (int64_t)k * a.b + idx / R;
+    const cplx* xr = x + (int64_t)r * N;
+    cplx s;
+    if (FWD) {
+        s = w[(int64_t)r * N + g];
+        if (k > 0) { cplx u = make_double2(0.0, 0.0); for (int64_t q = a.rowptr[g]; q < a.rlo[g]; ++q) cfma_x(u, a.val[q], xr[a.col[q]]); s.x -= u.x; s.y -= u.y; }
+    } else {
+        s = make_double2(0.0, 0.0);
+        for (int64_t q = a.rhi[g]; q < a.rowptr[g + 1]; ++q) cfma_x(s, a.val[q], xr[a.col[q]]);
+    }
+    t[idx] = s;
+}
+
+// part[c, r, i] = sum over the columns j of range c of S_k^{-1}[i, j] t[j, r].  Workgroup (row tile, column range): the
+// range's rows of t go to LDS, wave `slot` takes the columns slot, slot + 4, ... of the range, lane = row: a wave reads
+// 64 consecutive rows of one column (16 B per lane) and applies the entry to the R members (R accumulators, the R values
+// of t read from LDS at one address for the whole wave).  The four slots are folded through LDS in slot order.
+template <int R>
+__global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product(const cplx* __restrict__ Sk, int64_t b, int cols, const cplx* __restrict__ t,
+                                                                    cplx* __restrict__ part) {
+    __shared__ cplx ts[BB_COLS_MAX * R], red[(BB_SLOTS - 1) * R * BB_ROWS];
+    const int lane = threadIdx.x & (BB_ROWS - 1), slot = threadIdx.x / BB_ROWS;
+    const int64_t i = (int64_t)blockIdx.x * BB_ROWS + lane, jc = (int64_t)blockIdx.y * cols;
+    const int n = (int)(b - jc < cols ? b - jc : cols);
+    for (int e = threadIdx.x; e < n * R; e += BB_ROWS * BB_SLOTS) ts[e] = t[jc * R + e];
+    __syncthreads();
+    cplx acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = make_double2(0.0, 0.0);
+    if (i < b) {
+        const cplx* p = Sk + i + (jc + slot) * b;
+#pragma unroll 4
+        for (int jj = slot; jj < n; jj += BB_SLOTS, p += (int64_t)BB_SLOTS * b) {
+            const cplx s = *p;
+#pragma unroll
+            for (int r = 0; r < R; ++r) cfma_x(acc[r], s, ts[jj * R + r]);
+        }
+    }
+    if (slot > 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) red[((slot - 1) * R + r) * BB_ROWS + lane] = acc[r];
+    }
+    __syncthreads();
+    if (slot == 0 && i < b) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            cplx s = acc[r];
+            for (int q = 0; q < BB_SLOTS - 1; ++q) { const cplx v = red[(q * R + r) * BB_ROWS + lane]; s.x += v.x; s.y += v.y; }
+            part[((int64_t)blockIdx.y * R + r) * b + i] = s;
+        }
+    }
+}
+
+// the column ranges in range order: forward writes (z_r)_k, backward updates it in place to (x_r)_k
+template <bool FWD>
+__global__ __launch_bounds__(256) void k_btb_fold(int64_t b, int k, int R, int nranges, int64_t N, const cplx* __restrict__ part, cplx* __restrict__ x) {
+    const int64_t idx = blockIdx.x * (int64_t)256 + threadIdx.x;
+    if (idx >= b * R) return;
+    const int64_t i = idx % b, r = idx / b;
+    cplx s = make_double2(0.0, 0.0);
+    for (int c = 0; c < nranges; ++c) { const cplx v = part[((int64_t)c * R + r) * b + i]; s.x += v.x; s.y += v.y; }
+    cplx& o = x[r * N + (int64_t)k * b + i];
+    if (FWD) o = s; else { o.x -= s.x; o.y -= s.y; }
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------
 
 struct BlockTri {
@@ -388,6 +484,7 @@ struct BlockTri {
     DevBuf<int64_t> rowptr, rlo, rhi; DevBuf<int> col; DevBuf<cplx> val;     // private CSR of Msp, split at the block boundaries
     DevBuf<cplx> S;                                                          // S_k^{-1}, k = 0 .. K-1
     int64_t factor_us = 0; double min_ratio = 0.0;
+    DevBuf<cplx> bt_t, bt_part; int batch_cap = 0;                           // group apply: stencil products (b x R), partial sums (ranges x R x b)
     int launches() const { return b <= WALK_B ? 1 : (int)(2 * K - 1); }
 };
 
@@ -496,6 +593,52 @@ void blocktri_enqueue(const BlockTri* bt, const cplx* w, cplx* x, hipStream_t st
     const unsigned g = nblk(bt->b, AP_ROWS);
     for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(k_bt_step<true>, dim3(g), dim3(AP_ROWS * AP_SLOTS), 0, st, a, k, w, x);
     for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(k_bt_step<false>, dim3(g), dim3(AP_ROWS * AP_SLOTS), 0, st, a, k, w, x);
+}
+
+int64_t blocktri_batch_reserve(BlockTri* bt, int R) {
+    if (R > bt->batch_cap) {
+        const int64_t nranges = (bt->b + bb_cols(bt->b) - 1) / bb_cols(bt->b);
+        bt->bt_t.alloc((size_t)(bt->b * R)); bt->bt_part.alloc((size_t)(nranges * R * bt->b));
+        bt->batch_cap = R;
+    }
+    return (int64_t)(bt->bt_t.bytes() + bt->bt_part.bytes());
+}
+
+template <int R>
+static void launch_product(const cplx* Sk, int64_t b, int cols, const cplx* t, cplx* part, hipStream_t st) {
+    hipLaunchKernelGGL(k_btb_product<R>, dim3(nblk(b, BB_ROWS), nblk(b, cols)), dim3(BB_ROWS * BB_SLOTS), 0, st, Sk, b, cols, t, part);
+}
+
+void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, hipStream_t st) {
+    LSFC_REQUIRE(R >= 1 && R <= 8 && R <= bt->batch_cap, "internal: group of %d right-hand sides, work space for %d", R, bt->batch_cap);
+    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p, bt->S.p};
+    const int64_t b = bt->b, N = bt->N;
+    const int cols = bb_cols(b), nranges = (int)nblk(b, cols);
+    const unsigned g = nblk(b * R, 256);
+    cplx* t = bt->bt_t.p; cplx* part = bt->bt_part.p;
+    auto product = [&](int k) {
+        const cplx* Sk = bt->S.p + (int64_t)k * b * b;
+        switch (R) {
+            case 1: launch_product<1>(Sk, b, cols, t, part, st); break;
+            case 2: launch_product<2>(Sk, b, cols, t, part, st); break;
+            case 3: launch_product<3>(Sk, b, cols, t, part, st); break;
+            case 4: launch_product<4>(Sk, b, cols, t, part, st); break;
+            case 5: launch_product<5>(Sk, b, cols, t, part, st); break;
+            case 6: launch_product<6>(Sk, b, cols, t, part, st); break;
+            case 7: launch_product<7>(Sk, b, cols, t, part, st); break;
+            default: launch_product<8>(Sk, b, cols, t, part, st); break;
+        }
+    };
+    for (int k = 0; k < (int)bt->K; ++k) {
+        hipLaunchKernelGGL(k_btb_stage<true>, dim3(g), dim3(256), 0, st, a, k, R, N, w, (const cplx*)x, t);
+        product(k);
+        hipLaunchKernelGGL(k_btb_fold<true>, dim3(g), dim3(256), 0, st, b, k, R, nranges, N, (const cplx*)part, x);
+    }
+    for (int k = (int)bt->K - 2; k >= 0; --k) {
+        hipLaunchKernelGGL(k_btb_stage<false>, dim3(g), dim3(256), 0, st, a, k, R, N, w, (const cplx*)x, t);
+        product(k);
+        hipLaunchKernelGGL(k_btb_fold<false>, dim3(g), dim3(256), 0, st, b, k, R, nranges, N, (const cplx*)part, x);
+    }
 }
 
 BlockTriInfo blocktri_info(const BlockTri* bt) {

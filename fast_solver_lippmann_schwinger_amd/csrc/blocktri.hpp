@@ -25,8 +25,19 @@ const int* blocktri_col32(const BlockTri*);          // the columns as 32-bit in
 int64_t blocktri_nnz(const BlockTri*);
 // x <- Msp^{-1} w (device vectors of N, w != x), enqueued on st as a single chain of launches
 void blocktri_enqueue(const BlockTri*, const cplx* w, cplx* x, hipStream_t st);
+// The same for a group of R <= 8 right-hand sides, member r at w + r N and x + r N: every S_k^{-1} is read once per group.
+// The bits of a member's result do not depend on R or on r.  blocktri_batch_reserve(bt, R) first (it allocates: not
+// inside a stream capture); it returns the bytes of the group work space.
+int64_t blocktri_batch_reserve(BlockTri*, int R);
+void blocktri_enqueue_batch(const BlockTri*, int R, const cplx* w, cplx* x, hipStream_t st);
 BlockTriInfo blocktri_info(const BlockTri*);
 void blocktri_get_block(const BlockTri*, int64_t k, cplx* host_out);
 void warmup_blocktri();
+
+// precond.hip: pc applied to cnt >= 1 device vectors at arbitrary addresses, in place, stream-ordered on st.  A
+// block-tridiagonal object takes them in groups of up to 8 through blocktri_enqueue_batch; an object of
+// lsfc_precond_create member by member through the single-vector path.
+void precond_apply_batch_dev(lsfc_precond* pc, cplx* const* v, int cnt, hipStream_t st);
+int64_t precond_size(const lsfc_precond* pc);
 
 } // namespace lsfc

@@ -6,6 +6,7 @@
 // only O(restart) scalars per step cross to the host.
 #include "plan.hpp"
 #include "pointwise.hpp"
+#include "blocktri.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <complex>
@@ -127,12 +128,46 @@ struct ApplyBatcher {
     }
 };
 
+// The second meeting point of lsfc_gmres_batch, for the library's own device preconditioner (lsfc_precond_callback): the
+// last member to arrive applies it to the Krylov columns of all waiting members in group sweeps (precond_apply_batch_dev),
+// on the plan's stream.  Every member applies the operator and the preconditioner in the same alternation, so the two
+// meeting points never wait for each other.
+struct PrecondBatcher {
+    lsfc_plan* p; lsfc_precond* pc; int active;
+    std::mutex mu;
+    std::condition_variable cv;
+    int waiting = 0; uint64_t gen = 0;
+    std::vector<cplx*> v;
+    std::exception_ptr err;
+    void run_locked() {
+        try {
+            LSFC_HIP(hipSetDevice(p->device));
+            precond_apply_batch_dev(pc, v.data(), (int)v.size(), p->stream);
+        } catch (...) { err = std::current_exception(); }
+        v.clear(); waiting = 0; ++gen;
+        cv.notify_all();
+    }
+    void apply(cplx* x) {
+        std::unique_lock<std::mutex> lk(mu);
+        v.push_back(x); ++waiting;
+        if (waiting == active) run_locked();
+        else { const uint64_t g = gen; cv.wait(lk, [&] { return gen != g; }); }
+        if (err) std::rethrow_exception(err);
+    }
+    void leave() {
+        std::unique_lock<std::mutex> lk(mu);
+        --active;
+        if (active > 0 && waiting == active) run_locked();
+    }
+};
+
 struct Team {
     lsfc_plan* root;
     std::vector<Member> mem;
     bool reduce = false;                // local inner products are partial sums
     GmresWorkspace* rootw = nullptr;    // pinned host vector of the preconditioner callback
     ApplyBatcher* batcher = nullptr;    // lsfc_gmres_batch: operator applications go through the rendezvous
+    PrecondBatcher* pbatcher = nullptr; // ... and so do applications of the library's own device preconditioner
 
     static void dev(const Member& m) { LSFC_HIP(hipSetDevice(m.p->device)); }
     static cplx* V(const Member& m, int j) { return m.w->V.p + (size_t)j * (size_t)m.p->N; }
@@ -177,6 +212,7 @@ void solve(Team& T, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap
 
     auto precondition = [&](int col) {
         if (!o.precond) return;
+        if (T.pbatcher) { T.pbatcher->apply(Team::V(T.mem[0], col)); return; }
         std::unique_lock<std::mutex> cb_lock;
         if (T.batcher) cb_lock = std::unique_lock<std::mutex>(T.batcher->cb_mu);
         if (o.precond_on_device) {
@@ -451,6 +487,12 @@ void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_
     }
     LSFC_HIP(hipStreamSynchronize(p->stream));
     ApplyBatcher batcher; batcher.p = p; batcher.active = nrhs;
+    // the library's own device preconditioner is applied to all members at once; any other callback one member at a time
+    const bool own_precond = r.o.precond_on_device && r.o.precond == &lsfc_precond_callback;
+    PrecondBatcher pbatcher; pbatcher.p = p; pbatcher.pc = (lsfc_precond*)r.o.precond_user; pbatcher.active = nrhs;
+    if (own_precond)
+        LSFC_REQUIRE(pbatcher.pc && precond_size(pbatcher.pc) == p->N, "preconditioner: size mismatch (%lld vs %lld)",
+                     (long long)p->N, pbatcher.pc ? (long long)precond_size(pbatcher.pc) : -1LL);
     std::vector<std::exception_ptr> errs((size_t)nrhs);
     std::vector<std::thread> th;
     for (int j = 0; j < nrhs; ++j)
@@ -458,12 +500,14 @@ void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_
             try {
                 LSFC_HIP(hipSetDevice(p->device));
                 Team T; T.root = p; T.batcher = &batcher;
+                if (own_precond) T.pbatcher = &pbatcher;
                 GmresWorkspace* w = p->gmres_batch[(size_t)j].get();
                 T.mem.push_back({p, w, x + (int64_t)j * p->N, b + (int64_t)j * p->N});
                 T.rootw = w;
                 solve(T, opts_in, resnorm ? resnorm + (int64_t)j * cap : nullptr, cap, res + j, r.restart, r.maxiter, r.reltol, r.abstol, r.o);
             } catch (...) { errs[(size_t)j] = std::current_exception(); }
             batcher.leave();
+            pbatcher.leave();
         });
     for (auto& t : th) t.join();
     LSFC_HIP(hipSetDevice(p->device));

@@ -21,6 +21,8 @@
 //
 // A second kind of object is factorised on the device (blocktri.hip; lsfc_precond_create_blocktri / _from_plan at the end
 // of this file): its apply is the same SpMV followed by the block-tridiagonal sweeps, captured and replayed the same way.
+// Such an object also takes GROUPS of up to 8 vectors (precond_apply_batch_dev, lsfc_precond_apply_batch): one SpMV launch
+// and one sweep per group, As and every S_k^{-1} read once per group; one captured graph per group size.
 #include "common.hpp"
 #include "pruned.hpp"
 #include "plan.hpp"
@@ -51,6 +53,46 @@ __global__ void k_spmv_gather(const int64_t* __restrict__ rowptr, const int* __r
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) { sx += __shfl_xor(sx, o, LPR); sy += __shfl_xor(sy, o, LPR); }
     if (lane == 0) { const double s = scale ? scale[row] : 1.0; y[g] = make_double2(s * sx, s * sy); }
+}
+
+// The same for R vectors (member-major, member r at x + r n and y + r n; no gather, no scale): the row of the matrix is
+// read once and applied to every member.  Multiply-adds spelled out, one set of sums per member: the bits of a member's
+// result do not depend on R or on its place in the group.
+template <int R>
+__global__ void k_spmv_batch(const int64_t* __restrict__ rowptr, const int* __restrict__ col, const cplx* __restrict__ val,
+                             const cplx* __restrict__ x, cplx* __restrict__ y, int nrows) {
+    constexpr int LPR = 8;
+    const int row = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / LPR), lane = threadIdx.x % LPR;
+    if (row >= nrows) return;                     // (whole LPR-groups leave together: blockDim is a multiple of LPR)
+    double sx[R], sy[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { sx[r] = 0.0; sy[r] = 0.0; }
+    for (int64_t e = rowptr[row] + lane; e < rowptr[row + 1]; e += LPR) {
+        const cplx a = val[e];
+        const int c = col[e];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const cplx b = x[(int64_t)r * nrows + c];
+            sx[r] = fma(a.x, b.x, sx[r]); sx[r] = fma(-a.y, b.y, sx[r]);
+            sy[r] = fma(a.x, b.y, sy[r]); sy[r] = fma(a.y, b.x, sy[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) { sx[r] += __shfl_xor(sx[r], o, LPR); sy[r] += __shfl_xor(sy[r], o, LPR); }
+        if (lane == 0) y[(int64_t)r * nrows + row] = make_double2(sx[r], sy[r]);
+    }
+}
+
+// the vectors of a group, wherever they live, into / out of the member-major work buffer (TO_WORK: work <- v, else v <- work)
+struct GroupPtrs { cplx* v[LSFC_MAX_BATCH]; };
+template <bool TO_WORK>
+__global__ void k_group_copy(GroupPtrs g, cplx* __restrict__ work, int64_t n) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    cplx* v = g.v[blockIdx.y];
+    if (TO_WORK) work[(int64_t)blockIdx.y * n + i] = v[i]; else v[i] = work[(int64_t)blockIdx.y * n + i];
 }
 
 // one row of a triangular solve, LANES lanes: x[row] = (b[row] - sum_{j != row} a_j x[col_j]) * inv_diag
@@ -486,7 +528,23 @@ struct lsfc_precond {
     lsfc::DevBuf<lsfc::cplx> vin, y0, z, w, vout, hstage;
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; hipStream_t captured_on = nullptr;
     int launches = 0;
-    ~lsfc_precond() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); lsfc::blocktri_destroy(bt); }
+    // groups of right-hand sides (block-tridiagonal objects): member-major work buffers for bcap members, one graph per group size
+    lsfc::DevBuf<lsfc::cplx> bvin, by0, bvout, bhstage;
+    int bcap = 0;
+    hipGraph_t bgraph[lsfc::LSFC_MAX_BATCH + 1] = {}; hipGraphExec_t bexec[lsfc::LSFC_MAX_BATCH + 1] = {};
+    int64_t bsweeps = 0, bvectors = 0, blargest = 0, bwork_bytes = 0;
+    void drop_group_graphs() {
+        for (int r = 0; r <= lsfc::LSFC_MAX_BATCH; ++r) {
+            if (bexec[r]) { (void)hipGraphExecDestroy(bexec[r]); bexec[r] = nullptr; }
+            if (bgraph[r]) { (void)hipGraphDestroy(bgraph[r]); bgraph[r] = nullptr; }
+        }
+    }
+    ~lsfc_precond() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        drop_group_graphs();
+        lsfc::blocktri_destroy(bt);
+    }
 };
 
 namespace lsfc {
@@ -528,6 +586,62 @@ static void precond_apply_dev(lsfc_precond* pc, cplx* v, hipStream_t st) {
     LSFC_HIP(hipGraphLaunch(pc->exec, st));
     LSFC_HIP(hipMemcpyAsync(v, pc->vout.p, bytes, hipMemcpyDeviceToDevice, st));
 }
+
+// the fixed part of a group apply, on internal buffers only: SpMV for R members, then the group sweep
+static void enqueue_group(lsfc_precond* pc, int R, hipStream_t st) {
+    const int N = (int)pc->N;
+    const dim3 grid((unsigned)(((int64_t)N * 8 + 255) / 256)), block(256);
+#define LSFC_SPMV(RR) hipLaunchKernelGGL(k_spmv_batch<RR>, grid, block, 0, st, pc->a_rowptr.p, pc->a_col.p, pc->a_val.p, (const cplx*)pc->bvin.p, pc->by0.p, N)
+    switch (R) {
+        case 1: LSFC_SPMV(1); break; case 2: LSFC_SPMV(2); break; case 3: LSFC_SPMV(3); break; case 4: LSFC_SPMV(4); break;
+        case 5: LSFC_SPMV(5); break; case 6: LSFC_SPMV(6); break; case 7: LSFC_SPMV(7); break; default: LSFC_SPMV(8); break;
+    }
+#undef LSFC_SPMV
+    blocktri_enqueue_batch(pc->bt, R, pc->by0.p, pc->bvout.p, st);
+}
+
+// one group of R <= LSFC_MAX_BATCH vectors of a block-tridiagonal object
+static void precond_apply_group(lsfc_precond* pc, cplx* const* v, int R, hipStream_t st) {
+    if (R > pc->bcap) {
+        // work space on first use (and when a larger group comes): the captured graphs hold the old addresses
+        LSFC_HIP(hipDeviceSynchronize());
+        pc->drop_group_graphs();
+        const size_t n = (size_t)R * (size_t)pc->N;
+        pc->bvin.alloc(n); pc->by0.alloc(n); pc->bvout.alloc(n);
+        pc->bwork_bytes = (int64_t)(3 * n * sizeof(cplx)) + blocktri_batch_reserve(pc->bt, R);
+        pc->bcap = R;
+    }
+    GroupPtrs g{};
+    for (int r = 0; r < R; ++r) g.v[r] = v[r];
+    const dim3 cgrid((unsigned)((pc->N + 255) / 256), (unsigned)R);
+    hipLaunchKernelGGL(k_group_copy<true>, cgrid, dim3(256), 0, st, g, pc->bvin.p, pc->N);
+    static const bool no_graph = getenv("LSFC_PRECOND_GRAPH") && getenv("LSFC_PRECOND_GRAPH")[0] == '0';
+    if (no_graph) enqueue_group(pc, R, st);
+    else {
+        if (!pc->bexec[R]) {
+            hipStream_t cs; LSFC_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+            hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+            if (e == hipSuccess) {
+                enqueue_group(pc, R, cs);
+                e = hipStreamEndCapture(cs, &pc->bgraph[R]);
+            }
+            if (e == hipSuccess) e = hipGraphInstantiate(&pc->bexec[R], pc->bgraph[R], nullptr, nullptr, 0);
+            (void)hipStreamDestroy(cs);
+            if (e != hipSuccess) { (void)hipGetLastError(); fail(LSFC_EHIP, "preconditioner: graph capture of a group of %d failed: %s", R, hipGetErrorString(e)); }
+        }
+        LSFC_HIP(hipGraphLaunch(pc->bexec[R], st));
+    }
+    hipLaunchKernelGGL(k_group_copy<false>, cgrid, dim3(256), 0, st, g, pc->bvout.p, pc->N);
+    LSFC_HIP(hipGetLastError());
+    ++pc->bsweeps; pc->bvectors += R; pc->blargest = std::max<int64_t>(pc->blargest, R);
+}
+
+void precond_apply_batch_dev(lsfc_precond* pc, cplx* const* v, int cnt, hipStream_t st) {
+    if (!pc->bt) { for (int j = 0; j < cnt; ++j) precond_apply_dev(pc, v[j], st); return; }
+    for (int j0 = 0; j0 < cnt; j0 += LSFC_MAX_BATCH) precond_apply_group(pc, v + j0, std::min(LSFC_MAX_BATCH, cnt - j0), st);
+}
+
+int64_t precond_size(const lsfc_precond* pc) { return pc->N; }
 
 // loads this translation unit's code object on the current device (pruned.hip: pruned_warmup -- every code object of the library is
 // resident before the first transfer or pass of a process exists; DESIGN 3, "The round-2 first-apply GPU fault")
@@ -616,6 +730,41 @@ int lsfc_precond_apply(lsfc_precond* pc, double* v, int memspace) {
         precond_apply_dev(pc, pc->hstage.p, pc->stream);
         LSFC_HIP(hipMemcpyAsync(v, pc->hstage.p, bytes, hipMemcpyDeviceToHost, pc->stream));
         LSFC_HIP(hipStreamSynchronize(pc->stream));
+    });
+}
+
+int lsfc_precond_apply_batch(lsfc_precond* pc, double* v, int64_t nrhs, int memspace) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && v, "NULL argument");
+        LSFC_REQUIRE(nrhs >= 1 && nrhs < ((int64_t)1 << 31), "nrhs = %lld: need at least one right-hand side", (long long)nrhs);
+        LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "bad memspace %d", memspace);
+        LSFC_HIP(hipSetDevice(pc->device));
+        const int64_t N = pc->N;
+        std::vector<cplx*> ptr((size_t)nrhs);
+        if (memspace == LSFC_MEM_DEVICE) {
+            for (int64_t j = 0; j < nrhs; ++j) ptr[(size_t)j] = (cplx*)v + j * N;
+            precond_apply_batch_dev(pc, ptr.data(), (int)nrhs, pc->stream);
+            return;
+        }
+        // host vectors: staged through device memory a group at a time
+        const int64_t grp = std::min<int64_t>(nrhs, LSFC_MAX_BATCH);
+        if (pc->bhstage.n < (size_t)(grp * N)) pc->bhstage.alloc((size_t)(grp * N));
+        for (int64_t j0 = 0; j0 < nrhs; j0 += grp) {
+            const int cnt = (int)std::min<int64_t>(grp, nrhs - j0);
+            const size_t bytes = (size_t)cnt * (size_t)N * sizeof(cplx);
+            LSFC_HIP(hipMemcpyAsync(pc->bhstage.p, (cplx*)v + j0 * N, bytes, hipMemcpyHostToDevice, pc->stream));
+            for (int j = 0; j < cnt; ++j) ptr[(size_t)j] = pc->bhstage.p + (int64_t)j * N;
+            precond_apply_batch_dev(pc, ptr.data(), cnt, pc->stream);
+            LSFC_HIP(hipMemcpyAsync((cplx*)v + j0 * N, pc->bhstage.p, bytes, hipMemcpyDeviceToHost, pc->stream));
+        }
+        LSFC_HIP(hipStreamSynchronize(pc->stream));
+    });
+}
+
+int lsfc_precond_batch_info(const lsfc_precond* pc, int64_t out[4]) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && out, "NULL argument");
+        out[0] = pc->bsweeps; out[1] = pc->bvectors; out[2] = pc->blargest; out[3] = pc->bwork_bytes;
     });
 }
 

@@ -436,7 +436,9 @@ def gmres_batch_(X, A, B, Pl=None, abstol=0.0, reltol=None, restart=None, maxite
     """``gmres!`` for several right-hand sides at once (rows of B, solutions in the rows of X, updated in place): the
     solves of tests/plasma_example.jl:160-176 (two incident directions, one after the other in the reference) run in
     lock step, one batched operator application per Arnoldi step.  Each row's iterates are those of ``gmres_`` on that
-    row alone.  Returns X or (X, [ConvergenceHistory per row])."""
+    row alone.  ``Pl``: a SparsifyingPreconditioner is applied on the device to all unconverged rows at once (one group
+    sweep per step for a block-tridiagonal object); any other callable ``v -> None`` gets one host vector at a time.
+    Returns X or (X, [ConvergenceHistory per row])."""
     torch_in = _is_torch(X)
     if torch_in:
         nrhs = X.shape[0]
@@ -462,7 +464,20 @@ def gmres_batch_(X, A, B, Pl=None, abstol=0.0, reltol=None, restart=None, maxite
     opts.orth = _ORTH[orth_meth]
     opts.initially_zero = 1 if initially_zero else 0
     err = []
-    if Pl is not None:
+    native_pc = getattr(Pl, "_pc", None) if Pl is not None else None
+    if native_pc is not None:
+        # device-resident SparsifyingPreconditioner, as in gmres_: called by the library on the device vectors; the
+        # right-hand sides meet at it and a block-tridiagonal object takes their Krylov vectors in one group sweep
+        if sx == L.LSFC_MEM_DEVICE:
+            import torch
+            Pl.set_stream(torch.cuda.current_stream(X.device).cuda_stream)
+        else:
+            L.check(L.load().lsfc_plan_set_stream(A._plan, None))
+            Pl.set_stream(0)
+        opts.precond = C.cast(L.load().lsfc_precond_callback, L.PRECOND_FN)
+        opts.precond_user = native_pc
+        opts.precond_on_device = 1
+    elif Pl is not None:
         def _cb(user, v, n):
             try:
                 Pl(np.ctypeslib.as_array(C.cast(v, C.POINTER(C.c_double)), shape=(2 * n,)).view(np.complex128))

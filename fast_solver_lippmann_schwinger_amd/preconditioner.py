@@ -27,6 +27,8 @@ SCHEDULE_FIELDS = ("level8", "level16", "level32", "level64", "chains", "chain_g
                    "run_max", "run_min")
 # lsfc_precond_blocktri_info's six counts, in order
 BLOCKTRI_FIELDS = ("blocks", "block_size", "factor_bytes", "launches", "factor_us", "pivoting")
+# lsfc_precond_batch_info's four counts, in order
+BATCH_FIELDS = ("sweeps", "vectors", "largest_group", "work_bytes")
 
 
 def _csr_arrays(A):
@@ -142,6 +144,43 @@ class SparsifyingPreconditioner:
         from .operators import _is_torch
         v = b.clone() if _is_torch(b) else np.array(b, dtype=np.complex128)
         return self.ldiv_(v)
+
+    # -- several right-hand sides at once (lsfc_precond_apply_batch) -----------------------------------------------------
+    def ldiv_batch_(self, V):
+        """in place: every row of V (nrhs, N) <- Msp^{-1} (As row).  numpy array (staged over PCIe) or torch CUDA tensor
+        (stays on the device, enqueued on torch's current stream).  A block-tridiagonal object takes groups of up to 8 rows
+        through one sweep that reads every S_k^{-1} once per group; a row's result does not depend on the other rows.
+        An object of the host-LU route applies row by row: the bits of `ldiv_` per row."""
+        from .operators import _is_torch
+        if _is_torch(V):
+            import torch
+            if V.dtype != torch.complex128 or V.dim() != 2 or V.shape[1] != self.N or V.shape[0] < 1 or not V.is_contiguous():
+                raise TypeError(f"V: need a contiguous complex128 tensor of shape (nrhs >= 1, {self.N}), not {tuple(V.shape)} {V.dtype}")
+            space = L.LSFC_MEM_DEVICE if V.is_cuda else L.LSFC_MEM_HOST
+            if V.is_cuda:
+                self.set_stream(torch.cuda.current_stream(V.device).cuda_stream)
+            pv = C.c_void_p(V.data_ptr())
+        else:
+            if not (isinstance(V, np.ndarray) and V.dtype == np.complex128 and V.flags.c_contiguous):
+                raise TypeError("V must be a C-contiguous complex128 array (it is updated in place)")
+            if V.ndim != 2 or V.shape[1] != self.N or V.shape[0] < 1:
+                raise ValueError(f"DimensionMismatch: V has shape {V.shape}, need (nrhs >= 1, {self.N})")
+            space, pv = L.LSFC_MEM_HOST, V.ctypes.data_as(C.c_void_p)
+        L.check(L.load().lsfc_precond_apply_batch(self._pc, pv, int(V.shape[0]), space))
+        return V
+
+    def solve_batch(self, B):
+        """rows of P \\ B (out of place)"""
+        from .operators import _is_torch
+        V = B.clone().contiguous() if _is_torch(B) else np.array(B, dtype=np.complex128, order="C")
+        return self.ldiv_batch_(V)
+
+    def batch_info(self):
+        """lsfc_precond_batch_info as a dict (BATCH_FIELDS): group sweeps enqueued, vectors that went through them, the
+        largest group and the bytes of group work buffers; all 0 on an object of the host-LU route"""
+        out = (C.c_int64 * len(BATCH_FIELDS))()
+        L.check(L.load().lsfc_precond_batch_info(self._pc, out))
+        return dict(zip(BATCH_FIELDS, (int(v) for v in out)))
 
     def set_stream(self, stream):
         L.check(L.load().lsfc_precond_set_stream(self._pc, C.c_void_p(int(stream))))

@@ -188,8 +188,10 @@ int lsfc_gmres(lsfc_plan* plan, double* x, const double* b, const lsfc_gmres_opt
  * resnorm_cap entries; results[nrhs]).  Replaces the back-to-back gmres! calls for several incident directions
  * (tests/plasma_example.jl:160-176): each right-hand side keeps its own Krylov basis, Hessenberg matrix and stopping
  * test -- its iterates are those of lsfc_gmres on that right-hand side alone -- but every Arnoldi step applies the
- * operator to all unconverged right-hand sides in one batched pass (see lsfc_apply_batch).  Host preconditioner
- * callbacks are invoked one at a time.  Returns LSFC_OK even if some right-hand side hit maxiter: check
+ * operator to all unconverged right-hand sides in one batched pass (see lsfc_apply_batch).  With precond =
+ * lsfc_precond_callback and precond_on_device = 1 the right-hand sides meet at the preconditioner as well: one
+ * lsfc_precond_apply_batch-style group sweep over the Krylov vectors of all unconverged right-hand sides per step.  Any
+ * other callback (host, or the caller's own device callback) is invoked for one right-hand side at a time.  Returns LSFC_OK even if some right-hand side hit maxiter: check
  * results[j].converged.  Device memory: nrhs * (restart + 2) vectors of N complex for the duration of the call (checked
  * against the free memory up front: LSFC_ENOMEM with the figures; released on return). */
 int lsfc_gmres_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_gmres_opts* opts,
@@ -221,6 +223,16 @@ int lsfc_precond_destroy(lsfc_precond* pc);
 int lsfc_precond_set_stream(lsfc_precond* pc, void* stream);
 /* v <- Msp^{-1} (As v); LSFC_MEM_DEVICE: stream-ordered, returns without synchronising */
 int lsfc_precond_apply(lsfc_precond* pc, double* v, int memspace);
+/* nrhs vectors back to back (v + j*N), each overwritten with Msp^{-1} (As v_j).  Block-tridiagonal objects: groups of
+ * up to 8 go through ONE sweep that reads every S_k^{-1} once per group.  Objects of lsfc_precond_create: member by member.
+ * The bits of a vector's result do not depend on nrhs, on its place among the others or on what the others hold; on an
+ * object of lsfc_precond_create they are those of lsfc_precond_apply.  Work buffers (three of R*N complex for the largest
+ * group R so far, plus the sweep's own) are allocated on first use.  LSFC_MEM_HOST: staged through device memory,
+ * synchronises; LSFC_MEM_DEVICE: stream-ordered.  LSFC_EINVAL (before any device call): NULL argument, nrhs < 1, bad memspace. */
+int lsfc_precond_apply_batch(lsfc_precond* pc, double* v, int64_t nrhs, int memspace);
+/* out[0] group sweeps enqueued since creation, out[1] vectors that went through them, out[2] largest group so far,
+ * out[3] bytes of batch work buffers.  All 0 on an object of lsfc_precond_create. */
+int lsfc_precond_batch_info(const lsfc_precond* pc, int64_t out[4]);
 /* lsfc_precond_fn for lsfc_gmres_opts: precond = lsfc_precond_callback, precond_user = pc, precond_on_device = 1 */
 int lsfc_precond_callback(void* user, double* v, int64_t n);
 /* dependency levels of the two triangular solves and kernel launches captured in the graph */

@@ -231,6 +231,18 @@ function LinearAlgebra.ldiv!(P::SparsifyingPreconditionerHIP, b::Vector{Complex{
     check(ccall((:lsfc_precond_apply, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Complex{Float64}}, Cint), P.pc, b, 0)); b
 end
 Base.:\(P::SparsifyingPreconditionerHIP, b::Vector{Complex{Float64}}) = ldiv!(P, copy(b))
+# ldiv_batch!(P, B): every column of B (N x nrhs) <- Msp^{-1} (As column), lsfc_precond_apply_batch: a block-tridiagonal object
+# takes groups of up to 8 columns through one sweep that reads every S_k^{-1} once; a column's result does not depend on the others
+function ldiv_batch!(P::SparsifyingPreconditionerHIP, B::Matrix{Complex{Float64}})
+    size(B, 1) == P.N && size(B, 2) >= 1 || throw(DimensionMismatch("B must be $(P.N) x nrhs with nrhs >= 1"))
+    check(ccall((:lsfc_precond_apply_batch, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Complex{Float64}}, Int64, Cint), P.pc, B, size(B, 2), 0)); B
+end
+# (group sweeps enqueued, vectors that went through them, largest group, bytes of group work buffers)
+function batch_info(P::SparsifyingPreconditionerHIP)
+    out = zeros(Int64, 4)
+    check(ccall((:lsfc_precond_batch_info, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Int64}), P.pc, out))
+    return Tuple(out)
+end
 
 # Device-side GMRES with a host preconditioner: Pl is anything with the two-argument ldiv!(Pl, v)
 # (src/preconditioner.jl:147-170), passed through @cfunction.
@@ -268,6 +280,30 @@ function gmres_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Complex{
         (rc == 0 || rc == -5) || check(rc)
     end
     x, resnorm[1:res[].iters]
+end
+
+# The solves of several incident directions (tests/plasma_example.jl:160-176) in lock step, lsfc_gmres_batch: columns of B,
+# solutions in the columns of X.  A SparsifyingPreconditionerHIP is applied on the device to all unconverged columns at
+# once (one group sweep per step for a block-tridiagonal object); any other Pl gets one host vector at a time.
+function gmres_batch_hip!(X::Matrix{Complex{Float64}}, M::FastMHIP, B::Matrix{Complex{Float64}}; Pl=nothing, restart=min(20, size(B, 1)),
+                          maxiter=size(B, 1), reltol=sqrt(eps(Float64)), abstol=0.0, initially_zero=false)
+    size(X) == size(B) || throw(DimensionMismatch("X and B"))
+    nrhs = size(B, 2)
+    box = Ref{Any}(Pl)
+    if Pl isa SparsifyingPreconditionerHIP
+        cb = cglobal((:lsfc_precond_callback, liblsfc)); user = Pl.pc; ondev = Cint(1)
+    else
+        cb = Pl === nothing ? C_NULL : @cfunction(_precond_trampoline, Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64))
+        user = Pl === nothing ? C_NULL : pointer_from_objref(box); ondev = Cint(0)
+    end
+    opts = Ref(GmresOpts(restart, maxiter, reltol, abstol, 0, initially_zero ? 1 : 0, cb, user, ondev))
+    res = fill(GmresResult(0, 0, 0, 0.0), nrhs); resnorm = zeros(Float64, maxiter, nrhs)
+    GC.@preserve box begin
+        check(ccall((:lsfc_gmres_batch, liblsfc), Cint,
+                    (Ptr{Cvoid}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Int64, Ref{GmresOpts}, Ptr{Float64}, Int64, Ptr{GmresResult}, Cint),
+                    M.plan, X, B, nrhs, opts, resnorm, maxiter, res, 0))
+    end
+    X, [resnorm[1:res[j].iters, j] for j in 1:nrhs]
 end
 
 end # module

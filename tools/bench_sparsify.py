@@ -13,7 +13,14 @@ block-tridiagonal factorisation, csrc/blocktri.hip) -- set-up time, time per app
 2 K b^2 16 B / 6.29 TB/s, and, where scipy's splu of the same Msp is affordable (2D, 3D up to 24^3), the host-LU route
 with its level-scheduled apply on the same pair.
 
-    python tools/bench_sparsify.py --factor --out profiles/precond_blocktri.jsonl"""
+    python tools/bench_sparsify.py --factor --out profiles/precond_blocktri.jsonl
+
+--nrhs R[,R...]: the device-factorised preconditioner applied to R right-hand sides at once (ldiv_batch_: one group sweep
+that reads every S_k^{-1} once) against R single applies of the same object in the same process, with the rate the
+batched time implies on the byte model 2 K b^2 16 B per group.  --gmres adds, for the largest R, a preconditioned
+gmres_batch_ of R incident directions against R back-to-back gmres_ calls with the same object.
+
+    python tools/bench_sparsify.py --nrhs 1,2,4,8 --gmres --out profiles/precond_batch.jsonl"""
 import argparse
 import json
 import os
@@ -177,6 +184,76 @@ def factor_mode(args):
         torch.cuda.empty_cache()
 
 
+def median_ms(fn, reps):
+    import torch
+    fn()                                                   # warm-up (captures the graph, allocates work buffers)
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append(1e3 * (time.perf_counter() - t0))
+    return float(np.median(ms))
+
+
+def nrhs_mode(args):
+    import torch
+    import fast_solver_lippmann_schwinger_amd as pkg
+    groups = [int(v) for v in args.nrhs.split(",")]
+    for spec in args.cases.split(","):
+        ndim, n = (int(v) for v in spec.split(":"))
+        N = n ** ndim
+        M = operator(ndim, n)
+        P = pkg.SparsifyingPreconditioner.from_operator(M)
+        st = P.stats()
+        rng = np.random.default_rng(0)
+        B = torch.from_numpy(rng.standard_normal((max(groups), N)) + 1j * rng.standard_normal((max(groups), N))).cuda()
+        single_ms = median_ms(lambda: P.ldiv_(B[0].clone()), args.reps)
+        for R in groups:
+            def singles():
+                W = B[:R].clone()
+                for j in range(R):
+                    P.ldiv_(W[j])
+            batched_ms = median_ms(lambda: P.ldiv_batch_(B[:R].clone()), args.reps)
+            singles_ms = median_ms(singles, args.reps)
+            groups_of_8 = (R + 7) // 8
+            emit(args.out, {"case": f"{ndim}D n={n}", "N": N, "blocks": st["blocks"], "block_size": st["block_size"], "nrhs": R,
+                            "batched_ms": round(batched_ms, 4), "singles_ms": round(singles_ms, 4), "single_apply_ms": round(single_ms, 4),
+                            "per_vector_ms": round(batched_ms / R, 4), "ratio_batched_over_singles": round(batched_ms / singles_ms, 4),
+                            "model_GB": round(groups_of_8 * 2 * st["factor_bytes"] / 1e9, 3),
+                            "implied_TBps": round(groups_of_8 * 2 * st["factor_bytes"] / (batched_ms * 1e-3) / 1e12, 3)})
+        if args.gmres:
+            R = max(groups)
+            h = 1.0 / (n - 1) if ndim == 2 else 1.0 / n
+            k = 1.0 / h
+            x = -0.5 + h * np.arange(n)
+            grids = np.meshgrid(*(ndim * [x]), indexing="ij")
+            X = [g.reshape(-1, order="F") for g in grids]
+            rng = np.random.default_rng(1)
+            RHS = []
+            for _ in range(R):                             # R incident plane waves, random directions
+                d = rng.standard_normal(ndim)
+                d /= np.linalg.norm(d)
+                u_inc = np.exp(1j * k * sum(di * Xi for di, Xi in zip(d, X)))
+                RHS.append(-(M * u_inc - u_inc))
+            RHS = np.ascontiguousarray(np.stack(RHS))
+            t0 = time.perf_counter()
+            _, hb = pkg.gmres_batch_(np.zeros_like(RHS), M, RHS, Pl=P, reltol=1e-6, log=True)
+            tb = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            hs = [pkg.gmres_(np.zeros(N, dtype=np.complex128), M, RHS[j], Pl=P, reltol=1e-6, log=True)[1] for j in range(R)]
+            ts = time.perf_counter() - t0
+            steps_b, steps_s = max(h.iters for h in hb), sum(h.iters for h in hs)
+            emit(args.out, {"case": f"{ndim}D n={n}", "gmres_nrhs": R, "batch_s": round(tb, 4), "back_to_back_s": round(ts, 4),
+                            "batch_iters": [h.iters for h in hb], "single_iters": [h.iters for h in hs],
+                            "batch_ms_per_lockstep_step": round(1e3 * tb / steps_b, 3),
+                            "single_ms_per_step": round(1e3 * ts / steps_s, 3), "batch_info": P.batch_info()})
+        P.close()
+        del M, B
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -185,7 +262,13 @@ def main():
     ap.add_argument("--splu-limit", type=float, default=240.0)
     ap.add_argument("--device-only", action="store_true", help="only the device builds (for a kernel trace)")
     ap.add_argument("--factor", action="store_true", help="time the device-factorised preconditioner (see the module docstring)")
+    ap.add_argument("--nrhs", default="", help="group sizes, e.g. 1,2,4,8: batched apply against single applies (see the module docstring)")
+    ap.add_argument("--gmres", action="store_true", help="with --nrhs: also a preconditioned gmres_batch_ against back-to-back gmres_")
     args = ap.parse_args()
+    if args.nrhs:
+        if args.cases == ap.get_default("cases"):
+            args.cases = "2:513,3:24,3:48,3:64"
+        return nrhs_mode(args)
     if args.factor:
         if args.cases == ap.get_default("cases"):
             args.cases = "2:201,2:257,2:513,3:24,3:48,3:64"
