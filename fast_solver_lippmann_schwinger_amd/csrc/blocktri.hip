@@ -9,6 +9,11 @@
 //     backward  x_{K-1} = z_{K-1},   x_k = z_k - S_k^{-1} (U_k x_{k+1})
 // with the explicit inverses S_k^{-1} stored dense (column-major, K b^2 16 B).  The reference has UMFPACK's lu(Msp) here.
 //
+// Storage of the inverses: complex double, or (LSFC_PRECOND_INV_F32) interleaved float pairs, K b^2 8 B.  The elimination
+// is the same fp64 arithmetic either way: at float storage block k is inverted in one of two fp64 work blocks (the Schur
+// update of block k + 1 reads it there), then rounded once to nearest-even into the float array.  The sweeps widen every
+// stored entry to fp64 on load and sum in fp64 in the order of the fp64 object; they are templates over the stored type.
+//
 // Set-up, per block:  Schur update as two sparse gathers (W = L_k S_{k-1}^{-1}; S_k = D_k - W U_{k-1}, U by columns),
 // then a blocked in-place Gauss-Jordan inversion without pivoting, panels of 32 columns:
 //     P = A_JJ^{-1}                       one workgroup, in LDS; |pivot| / max|S_k| is monitored
@@ -301,8 +306,21 @@ __global__ __launch_bounds__(256) void k_bt_trail(cplx* __restrict__ A, int64_t 
 struct BtApply {                   // what the sweep kernels read
     int64_t b; int K;
     const int64_t* rowptr; const int64_t* rlo; const int64_t* rhi; const int* col; const cplx* val;
-    const cplx* S;
 };
+
+// a stored entry of S_k^{-1} as fp64: the float form is widened (exact), all arithmetic after it is fp64
+typedef float2 cplx32;
+typedef float f4u __attribute__((ext_vector_type(4), aligned(8)));           // two consecutive float pairs of one column
+__device__ __forceinline__ cplx bt_ld(const cplx* p) { return *p; }
+__device__ __forceinline__ cplx bt_ld(const cplx32* p) { const cplx32 v = *p; return make_double2((double)v.x, (double)v.y); }
+
+// fp64 work block -> float storage, round to nearest even, once per block
+__global__ __launch_bounds__(256) void k_bt_round(int64_t n, const cplx* __restrict__ A, cplx32* __restrict__ S32) {
+    const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;
+    if (i >= n) return;
+    const cplx v = A[i];
+    S32[i] = make_float2(__double2float_rn(v.x), __double2float_rn(v.y));
+}
 
 // entries [jc, jc + n) of the right-hand side of step k into LDS: w_k - L_k z_{k-1} (forward) or U_k x_{k+1} (backward)
 template <bool FWD>
@@ -322,11 +340,25 @@ __device__ __forceinline__ void bt_stage(const BtApply& a, int k, int64_t jc, in
 }
 
 // this thread's share of (S_k^{-1} t)[i]: columns jc + slot, jc + slot + 32, ...
-__device__ __forceinline__ void bt_accum(const cplx* __restrict__ Sk, int64_t b, int64_t i, int64_t jc, int n, int slot, const cplx* t, cplx& acc) {
+template <typename T>
+__device__ __forceinline__ void bt_accum(const T* __restrict__ Sk, int64_t b, int64_t i, int64_t jc, int n, int slot, const cplx* t, cplx& acc) {
     if (i >= b) return;
-    const cplx* p = Sk + i + (jc + slot) * b;
+    const T* p = Sk + i + (jc + slot) * b;
 #pragma unroll 4
-    for (int jj = slot; jj < n; jj += AP_SLOTS, p += (int64_t)AP_SLOTS * b) cfma(acc, *p, t[jj]);
+    for (int jj = slot; jj < n; jj += AP_SLOTS, p += (int64_t)AP_SLOTS * b) cfma(acc, bt_ld(p), t[jj]);
+}
+
+// float storage: rows i and i + 1 of the same columns from one 16 B load (i + 1 < b), each row summed as bt_accum sums it
+__device__ __forceinline__ void bt_accum2(const cplx32* __restrict__ Sk, int64_t b, int64_t i, int64_t jc, int n, int slot, const cplx* t,
+                                          cplx& acc0, cplx& acc1) {
+    const cplx32* p = Sk + i + (jc + slot) * b;
+#pragma unroll 4
+    for (int jj = slot; jj < n; jj += AP_SLOTS, p += (int64_t)AP_SLOTS * b) {
+        const f4u v = *(const f4u*)p;
+        const cplx tj = t[jj];
+        cfma(acc0, make_double2((double)v.x, (double)v.y), tj);
+        cfma(acc1, make_double2((double)v.z, (double)v.w), tj);
+    }
 }
 
 // fold the 32 column slots of every row in slot order; the sum is valid on the threads of slot 0
@@ -342,11 +374,11 @@ __device__ __forceinline__ cplx bt_fold(cplx acc, cplx* red) {
 // one step of a sweep over many workgroups, 16 rows each: forward writes z_k, backward updates it in place to x_k
 // (a workgroup writes rows of block k only and reads block k -+ 1 only)
 template <bool FWD>
-__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step(BtApply a, int k, const cplx* __restrict__ w, cplx* x) {
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step(BtApply a, const cplx* __restrict__ S, int k, const cplx* __restrict__ w, cplx* x) {
     __shared__ cplx t[AP_CHUNK], red[AP_ROWS * AP_SLOTS];
     const int r = threadIdx.x & (AP_ROWS - 1), slot = threadIdx.x / AP_ROWS;
     const int64_t i = (int64_t)blockIdx.x * AP_ROWS + r;
-    const cplx* Sk = a.S + (int64_t)k * a.b * a.b;
+    const cplx* Sk = S + (int64_t)k * a.b * a.b;
     cplx acc = make_double2(0.0, 0.0);
     for (int64_t jc = 0; jc < a.b; jc += AP_CHUNK) {
         const int n = (int)(a.b - jc < AP_CHUNK ? a.b - jc : AP_CHUNK);
@@ -362,8 +394,35 @@ __global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step(BtApply a, int k
     }
 }
 
-// small planes (b <= WALK_B): both sweeps by ONE workgroup, a barrier between steps
-__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_walk(BtApply a, const cplx* __restrict__ w, cplx* x) {
+// the same step at float storage: 32 rows per workgroup, a thread takes rows i, i + 1 of its columns with one 16 B load
+// (a quarter wave reads 256 B of a column, as above); a row's sum runs over the same columns and slots in the same order
+template <bool FWD>
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step32(BtApply a, const cplx32* __restrict__ S, int k, const cplx* __restrict__ w, cplx* x) {
+    __shared__ cplx t[AP_CHUNK], red[AP_ROWS * AP_SLOTS];
+    const int r = threadIdx.x & (AP_ROWS - 1), slot = threadIdx.x / AP_ROWS;
+    const int64_t i = (int64_t)blockIdx.x * (2 * AP_ROWS) + 2 * r;
+    const cplx32* Sk = S + (int64_t)k * a.b * a.b;
+    cplx acc0 = make_double2(0.0, 0.0), acc1 = make_double2(0.0, 0.0);
+    for (int64_t jc = 0; jc < a.b; jc += AP_CHUNK) {
+        const int n = (int)(a.b - jc < AP_CHUNK ? a.b - jc : AP_CHUNK);
+        bt_stage<FWD>(a, k, jc, n, w, x, t);
+        __syncthreads();
+        if (i + 1 < a.b) bt_accum2(Sk, a.b, i, jc, n, slot, t, acc0, acc1);
+        else bt_accum(Sk, a.b, i, jc, n, slot, t, acc0);                    // the last row of an odd plane, or none
+        __syncthreads();
+    }
+    const cplx s0 = bt_fold(acc0, red), s1 = bt_fold(acc1, red);
+    if (slot == 0) {
+        cplx* o = x + (int64_t)k * a.b + i;
+        if (i < a.b) { if (FWD) o[0] = s0; else { o[0].x -= s0.x; o[0].y -= s0.y; } }
+        if (i + 1 < a.b) { if (FWD) o[1] = s1; else { o[1].x -= s1.x; o[1].y -= s1.y; } }
+    }
+}
+
+// small planes (b <= WALK_B): both sweeps by ONE workgroup, a barrier between steps.  One shape for both storages: a
+// single workgroup waits on the chain of steps, not on bytes, so the float form keeps one row per thread (8 B loads).
+template <typename T>
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_walk(BtApply a, const T* __restrict__ S, const cplx* __restrict__ w, cplx* x) {
     __shared__ cplx t[WALK_B], red[AP_ROWS * AP_SLOTS];
     const int r = threadIdx.x & (AP_ROWS - 1), slot = threadIdx.x / AP_ROWS;
     const int b = (int)a.b;
@@ -372,7 +431,7 @@ __global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_walk(BtApply a, const
         const int k = fwd ? step : 2 * a.K - 2 - step;
         if (fwd) bt_stage<true>(a, k, 0, b, w, x, t); else bt_stage<false>(a, k, 0, b, w, x, t);
         __syncthreads();
-        const cplx* Sk = a.S + (int64_t)k * b * b;
+        const T* Sk = S + (int64_t)k * b * b;
         for (int i0 = 0; i0 < b; i0 += AP_ROWS) {
             cplx acc = make_double2(0.0, 0.0);
             bt_accum(Sk, b, i0 + r, 0, b, slot, t, acc);
@@ -465,6 +524,60 @@ __global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product(const cplx* 
     }
 }
 
+// The product at float storage.  Workgroup (tile of 128 rows, column range): a lane takes rows i, i + 1 of a column
+// with one 16 B load, so a wave still reads 1 KiB of a column per instruction.  Both rows have their own R accumulators;
+// a row's sum runs over the columns, slots and ranges of the fp64 form in the same order, and the tiling is a function
+// of b alone, so a member's bits do not depend on its companions here either.  The slots are folded row half by row
+// half through the LDS of the fp64 form.
+template <int R>
+__global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product32(const cplx32* __restrict__ Sk, int64_t b, int cols, const cplx* __restrict__ t,
+                                                                      cplx* __restrict__ part) {
+    __shared__ cplx ts[BB_COLS_MAX * R], red[(BB_SLOTS - 1) * R * BB_ROWS];
+    const int lane = threadIdx.x & (BB_ROWS - 1), slot = threadIdx.x / BB_ROWS;
+    const int64_t i = (int64_t)blockIdx.x * (2 * BB_ROWS) + 2 * lane, jc = (int64_t)blockIdx.y * cols;
+    const int n = (int)(b - jc < cols ? b - jc : cols);
+    for (int e = threadIdx.x; e < n * R; e += BB_ROWS * BB_SLOTS) ts[e] = t[jc * R + e];
+    __syncthreads();
+    cplx acc[2][R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[0][r] = acc[1][r] = make_double2(0.0, 0.0);
+    if (i + 1 < b) {
+        const cplx32* p = Sk + i + (jc + slot) * b;
+#pragma unroll 4
+        for (int jj = slot; jj < n; jj += BB_SLOTS, p += (int64_t)BB_SLOTS * b) {
+            const f4u v = *(const f4u*)p;
+            const cplx s0 = make_double2((double)v.x, (double)v.y), s1 = make_double2((double)v.z, (double)v.w);
+#pragma unroll
+            for (int r = 0; r < R; ++r) { const cplx tj = ts[jj * R + r]; cfma_x(acc[0][r], s0, tj); cfma_x(acc[1][r], s1, tj); }
+        }
+    } else if (i < b) {                                                       // the last row of an odd plane
+        const cplx32* p = Sk + i + (jc + slot) * b;
+#pragma unroll 4
+        for (int jj = slot; jj < n; jj += BB_SLOTS, p += (int64_t)BB_SLOTS * b) {
+            const cplx s0 = bt_ld(p);
+#pragma unroll
+            for (int r = 0; r < R; ++r) cfma_x(acc[0][r], s0, ts[jj * R + r]);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (slot > 0) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) red[((slot - 1) * R + r) * BB_ROWS + lane] = acc[h][r];
+        }
+        __syncthreads();
+        if (slot == 0 && i + h < b) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                cplx s = acc[h][r];
+                for (int q = 0; q < BB_SLOTS - 1; ++q) { const cplx v = red[(q * R + r) * BB_ROWS + lane]; s.x += v.x; s.y += v.y; }
+                part[((int64_t)blockIdx.y * R + r) * b + i + h] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // the column ranges in range order: forward writes (z_r)_k, backward updates it in place to (x_r)_k
 template <bool FWD>
 __global__ __launch_bounds__(256) void k_btb_fold(int64_t b, int k, int R, int nranges, int64_t N, const cplx* __restrict__ part, cplx* __restrict__ x) {
@@ -482,36 +595,47 @@ __global__ __launch_bounds__(256) void k_btb_fold(int64_t b, int k, int R, int n
 struct BlockTri {
     int64_t N = 0, K = 0, b = 0, nnz = 0;
     DevBuf<int64_t> rowptr, rlo, rhi; DevBuf<int> col; DevBuf<cplx> val;     // private CSR of Msp, split at the block boundaries
-    DevBuf<cplx> S;                                                          // S_k^{-1}, k = 0 .. K-1
+    int prec = BLOCKTRI_INV_F64;
+    DevBuf<cplx> S;                                                          // S_k^{-1}, k = 0 .. K-1 (fp64 storage) ...
+    DevBuf<cplx32> S32;                                                      // ... or the same blocks rounded to float pairs
     int64_t factor_us = 0; double min_ratio = 0.0;
     DevBuf<cplx> bt_t, bt_part; int batch_cap = 0;                           // group apply: stencil products (b x R), partial sums (ranges x R x b)
     int launches() const { return b <= WALK_B ? 1 : (int)(2 * K - 1); }
 };
 
-static double work_bytes(int64_t N, int64_t K) {
+static double entry_bytes(int prec) { return prec == BLOCKTRI_INV_F32 ? 8.0 : 16.0; }
+
+static double work_bytes(int64_t N, int64_t K, int prec) {
     const double b = (double)(N / K);
-    return b * b * 16.0 + 2.0 * b * NB * 16.0 + 64.0 * (double)N;            // W, the two panels, row tables and vectors
+    const double blocks = prec == BLOCKTRI_INV_F32 ? 2.0 * b * b * 16.0 : 0.0;    // float storage: current and previous block in fp64
+    return blocks + b * b * 16.0 + 2.0 * b * NB * 16.0 + 64.0 * (double)N;   // W, the two panels, row tables and vectors
 }
 
-void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who) {
-    const double b = (double)(N / K), factors = (double)K * b * b * 16.0, need = factors + work_bytes(N, K) + extra;
+BlockTriNeed blocktri_memory_need(int64_t N, int64_t K, int prec) {
+    const double b = (double)(N / K);
+    return BlockTriNeed{(double)K * b * b * entry_bytes(prec), work_bytes(N, K, prec)};
+}
+
+void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who, int prec) {
+    const BlockTriNeed nd = blocktri_memory_need(N, K, prec);
+    const double factors = nd.inverse_bytes, need = factors + nd.work_bytes + extra;
     size_t free_b = 0, total_b = 0;
     LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
     if (need > (double)free_b)
-        fail(LSFC_ENOMEM, "%s: %lld blocks of %lld x %lld complex need %.3f GB for the inverses S_k^{-1} (K b^2 16 B) and %.3f GB of work space, "
-             "%.3f GB of device memory are free", who, (long long)K, (long long)(N / K), (long long)(N / K), factors / 1e9, (need - factors) / 1e9,
-             (double)free_b / 1e9);
+        fail(LSFC_ENOMEM, "%s: %lld blocks of %lld x %lld complex need %.3f GB for the inverses S_k^{-1} stored as %s (K b^2 %d B) and %.3f GB of "
+             "work space, %.3f GB of device memory are free", who, (long long)K, (long long)(N / K), (long long)(N / K), factors / 1e9,
+             prec == BLOCKTRI_INV_F32 ? "complex64" : "complex128", (int)entry_bytes(prec), (need - factors) / 1e9, (double)free_b / 1e9);
 }
 
 static inline unsigned nblk(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp) {
+BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp, int prec) {
     const auto t0 = std::chrono::steady_clock::now();
     const int64_t b = N / K;
     LSFC_REQUIRE(b * b < ((int64_t)1 << 40), "block-tridiagonal preconditioner: block size %lld out of range", (long long)b);
     hipStream_t st = nullptr;
     std::unique_ptr<BlockTri> bt(new BlockTri());
-    bt->N = N; bt->K = K; bt->b = b;
+    bt->N = N; bt->K = K; bt->b = b; bt->prec = prec;
     int64_t nnz = 0;
     LSFC_HIP(hipMemcpy(&nnz, rowptr + N, sizeof nnz, hipMemcpyDeviceToHost));
     LSFC_REQUIRE(nnz >= 1 && nnz < ((int64_t)1 << 40), "block-tridiagonal preconditioner: rowptr[N] = %lld is not a plausible entry count", (long long)nnz);
@@ -549,17 +673,21 @@ BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int
         LSFC_HIP(hipGetLastError());
     }
     // the blocks
-    bt->S.alloc((size_t)(K * b * b));
+    const bool f32 = prec == BLOCKTRI_INV_F32;
+    DevBuf<cplx> work[2];                                                   // float storage: block k is inverted in work[k & 1] ...
+    if (f32) { bt->S32.alloc((size_t)(K * b * b)); work[0].alloc((size_t)(b * b)); if (K > 1) work[1].alloc((size_t)(b * b)); }
+    else bt->S.alloc((size_t)(K * b * b));
     DevBuf<cplx> W, P, R, Cb; DevBuf<double> part;
     if (K > 1) W.alloc((size_t)(b * b));
     P.alloc(NB * NB); R.alloc((size_t)(NB * b)); Cb.alloc((size_t)(b * NB)); part.alloc(256);
     const int nt = (int)((b + NB - 1) / NB), nx = (int)nblk(b, 256);
     const unsigned ebl = nblk(b * b, 256);
     for (int64_t k = 0; k < K; ++k) {
-        cplx* Sk = bt->S.p + k * b * b;
+        cplx* Sk = f32 ? work[k & 1].p : bt->S.p + k * b * b;
+        const cplx* Sprev = f32 ? work[(k + 1) & 1].p : Sk - b * b;           // ... and block k + 1 reads it there: fp64 S_k^{-1} either way
         if (k == 0) LSFC_HIP(hipMemsetAsync(Sk, 0, (size_t)(b * b) * sizeof(cplx), st));
         else {
-            hipLaunchKernelGGL(k_bt_schur_left, dim3(ebl), dim3(256), 0, st, b, k, bt->rowptr.p, bt->rlo.p, bt->col.p, bt->val.p, Sk - b * b, W.p);
+            hipLaunchKernelGGL(k_bt_schur_left, dim3(ebl), dim3(256), 0, st, b, k, bt->rowptr.p, bt->rlo.p, bt->col.p, bt->val.p, Sprev, W.p);
             hipLaunchKernelGGL(k_bt_schur_right, dim3(ebl), dim3(256), 0, st, b, k, ucolptr.p, urow.p, uval.p, W.p, Sk);
         }
         hipLaunchKernelGGL(k_bt_add_diag, dim3(nblk(b, 256)), dim3(256), 0, st, b, k, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p, Sk);
@@ -571,6 +699,7 @@ BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int
             hipLaunchKernelGGL(k_bt_panels, dim3(2 * nx), dim3(256), 0, st, Sk, b, j0, nb, P.p, R.p, Cb.p, nx);
             if (nt > 1) hipLaunchKernelGGL(k_bt_trail, dim3(nblk((int64_t)nt * nt, 4)), dim3(256), 0, st, Sk, b, J, nt, R.p, Cb.p);
         }
+        if (f32) hipLaunchKernelGGL(k_bt_round, dim3(ebl), dim3(256), 0, st, b * b, (const cplx*)Sk, bt->S32.p + k * b * b);
         LSFC_HIP(hipGetLastError());
     }
     LSFC_HIP(hipMemcpyAsync(&hs, dstat.p, sizeof hs, hipMemcpyDeviceToHost, st));
@@ -588,11 +717,21 @@ const int* blocktri_col32(const BlockTri* bt) { return bt->col.p; }
 int64_t blocktri_nnz(const BlockTri* bt) { return bt->nnz; }
 
 void blocktri_enqueue(const BlockTri* bt, const cplx* w, cplx* x, hipStream_t st) {
-    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p, bt->S.p};
-    if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk, dim3(1), dim3(AP_ROWS * AP_SLOTS), 0, st, a, w, x); return; }
+    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p};
+    const dim3 wg(AP_ROWS * AP_SLOTS);
+    if (bt->prec == BLOCKTRI_INV_F32) {
+        const cplx32* S = bt->S32.p;
+        if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk<cplx32>, dim3(1), wg, 0, st, a, S, w, x); return; }
+        const unsigned g = nblk(bt->b, 2 * AP_ROWS);
+        for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(k_bt_step32<true>, dim3(g), wg, 0, st, a, S, k, w, x);
+        for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(k_bt_step32<false>, dim3(g), wg, 0, st, a, S, k, w, x);
+        return;
+    }
+    const cplx* S = bt->S.p;
+    if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk<cplx>, dim3(1), wg, 0, st, a, S, w, x); return; }
     const unsigned g = nblk(bt->b, AP_ROWS);
-    for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(k_bt_step<true>, dim3(g), dim3(AP_ROWS * AP_SLOTS), 0, st, a, k, w, x);
-    for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(k_bt_step<false>, dim3(g), dim3(AP_ROWS * AP_SLOTS), 0, st, a, k, w, x);
+    for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(k_bt_step<true>, dim3(g), wg, 0, st, a, S, k, w, x);
+    for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(k_bt_step<false>, dim3(g), wg, 0, st, a, S, k, w, x);
 }
 
 int64_t blocktri_batch_reserve(BlockTri* bt, int R) {
@@ -605,28 +744,33 @@ int64_t blocktri_batch_reserve(BlockTri* bt, int R) {
 }
 
 template <int R>
-static void launch_product(const cplx* Sk, int64_t b, int cols, const cplx* t, cplx* part, hipStream_t st) {
-    hipLaunchKernelGGL(k_btb_product<R>, dim3(nblk(b, BB_ROWS), nblk(b, cols)), dim3(BB_ROWS * BB_SLOTS), 0, st, Sk, b, cols, t, part);
+static void launch_product(const BlockTri* bt, int k, int cols, const cplx* t, cplx* part, hipStream_t st) {
+    const int64_t b = bt->b;
+    if (bt->prec == BLOCKTRI_INV_F32)
+        hipLaunchKernelGGL(k_btb_product32<R>, dim3(nblk(b, 2 * BB_ROWS), nblk(b, cols)), dim3(BB_ROWS * BB_SLOTS), 0, st,
+                           (const cplx32*)(bt->S32.p + (int64_t)k * b * b), b, cols, t, part);
+    else
+        hipLaunchKernelGGL(k_btb_product<R>, dim3(nblk(b, BB_ROWS), nblk(b, cols)), dim3(BB_ROWS * BB_SLOTS), 0, st,
+                           (const cplx*)(bt->S.p + (int64_t)k * b * b), b, cols, t, part);
 }
 
 void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, hipStream_t st) {
     LSFC_REQUIRE(R >= 1 && R <= 8 && R <= bt->batch_cap, "internal: group of %d right-hand sides, work space for %d", R, bt->batch_cap);
-    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p, bt->S.p};
+    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p};
     const int64_t b = bt->b, N = bt->N;
     const int cols = bb_cols(b), nranges = (int)nblk(b, cols);
     const unsigned g = nblk(b * R, 256);
     cplx* t = bt->bt_t.p; cplx* part = bt->bt_part.p;
     auto product = [&](int k) {
-        const cplx* Sk = bt->S.p + (int64_t)k * b * b;
         switch (R) {
-            case 1: launch_product<1>(Sk, b, cols, t, part, st); break;
-            case 2: launch_product<2>(Sk, b, cols, t, part, st); break;
-            case 3: launch_product<3>(Sk, b, cols, t, part, st); break;
-            case 4: launch_product<4>(Sk, b, cols, t, part, st); break;
-            case 5: launch_product<5>(Sk, b, cols, t, part, st); break;
-            case 6: launch_product<6>(Sk, b, cols, t, part, st); break;
-            case 7: launch_product<7>(Sk, b, cols, t, part, st); break;
-            default: launch_product<8>(Sk, b, cols, t, part, st); break;
+            case 1: launch_product<1>(bt, k, cols, t, part, st); break;
+            case 2: launch_product<2>(bt, k, cols, t, part, st); break;
+            case 3: launch_product<3>(bt, k, cols, t, part, st); break;
+            case 4: launch_product<4>(bt, k, cols, t, part, st); break;
+            case 5: launch_product<5>(bt, k, cols, t, part, st); break;
+            case 6: launch_product<6>(bt, k, cols, t, part, st); break;
+            case 7: launch_product<7>(bt, k, cols, t, part, st); break;
+            default: launch_product<8>(bt, k, cols, t, part, st); break;
         }
     };
     for (int k = 0; k < (int)bt->K; ++k) {
@@ -642,11 +786,21 @@ void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, h
 }
 
 BlockTriInfo blocktri_info(const BlockTri* bt) {
-    return BlockTriInfo{bt->K, bt->b, (int64_t)bt->S.bytes(), bt->launches(), bt->factor_us, 0, bt->min_ratio};
+    const int64_t bytes = (int64_t)(bt->prec == BLOCKTRI_INV_F32 ? bt->S32.bytes() : bt->S.bytes());
+    return BlockTriInfo{bt->K, bt->b, bytes, bt->launches(), bt->factor_us, 0, bt->min_ratio};
 }
 
+int blocktri_precision(const BlockTri* bt) { return bt->prec; }
+
 void blocktri_get_block(const BlockTri* bt, int64_t k, cplx* host_out) {
-    LSFC_HIP(hipMemcpy(host_out, bt->S.p + k * bt->b * bt->b, (size_t)(bt->b * bt->b) * sizeof(cplx), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)(bt->b * bt->b);
+    if (bt->prec == BLOCKTRI_INV_F32) {                                      // the stored float pairs, widened on the host
+        std::vector<cplx32> h(n);
+        LSFC_HIP(hipMemcpy(h.data(), bt->S32.p + k * bt->b * bt->b, n * sizeof(cplx32), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) host_out[i] = make_double2((double)h[i].x, (double)h[i].y);
+        return;
+    }
+    LSFC_HIP(hipMemcpy(host_out, bt->S.p + k * bt->b * bt->b, n * sizeof(cplx), hipMemcpyDeviceToHost));
 }
 
 __global__ void k_warmup_blocktri(int* p) { if (p) *p = 0; }

@@ -6,6 +6,10 @@ namespace lsfc {
 
 struct BlockTri;       // K explicit inverses S_k^{-1} (b x b, column-major) and a private copy of the CSR of Msp
 
+// how the inverses are stored (LSFC_PRECOND_INV_F64 / _F32 of include/lsfc.h): complex double, or interleaved float pairs
+// rounded once from the fp64 block; the elimination itself is fp64 either way
+static constexpr int BLOCKTRI_INV_F64 = 0, BLOCKTRI_INV_F32 = 1;
+
 struct BlockTriInfo {
     int64_t K, b, factor_bytes, launches, factor_us;
     int pivoting;
@@ -15,11 +19,15 @@ struct BlockTriInfo {
 // |pivot| / max|S_k| below which the pivot-free inversion of a Schur block is refused (include/lsfc.h)
 static constexpr double BLOCKTRI_PIVOT_MIN = 1e-8;
 
-// LSFC_ENOMEM unless K b^2 16 B of factors plus the work space fit into the free memory of the current device;
-// `extra` = bytes the caller is about to allocate besides.  From the dimensions alone: nothing is allocated or read.
-void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who);
+// LSFC_ENOMEM unless K b^2 16 B (8 B at float storage) of factors plus the work space fit into the free memory of the
+// current device; `extra` = bytes the caller is about to allocate besides.  From the dimensions and the precision alone:
+// nothing is allocated or read.  blocktri_memory_need is the arithmetic of it.
+struct BlockTriNeed { double inverse_bytes, work_bytes; };
+BlockTriNeed blocktri_memory_need(int64_t N, int64_t K, int prec);
+void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who, int prec);
 // Factorise: rowptr / col / msp are DEVICE arrays (CSR, 0-based, columns ascending, N rows).  Synchronous.
-BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp);
+BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp, int prec);
+int blocktri_precision(const BlockTri*);
 void blocktri_destroy(BlockTri*);
 const int* blocktri_col32(const BlockTri*);          // the columns as 32-bit integers (device), nnz of them
 int64_t blocktri_nnz(const BlockTri*);
@@ -31,7 +39,7 @@ void blocktri_enqueue(const BlockTri*, const cplx* w, cplx* x, hipStream_t st);
 int64_t blocktri_batch_reserve(BlockTri*, int R);
 void blocktri_enqueue_batch(const BlockTri*, int R, const cplx* w, cplx* x, hipStream_t st);
 BlockTriInfo blocktri_info(const BlockTri*);
-void blocktri_get_block(const BlockTri*, int64_t k, cplx* host_out);
+void blocktri_get_block(const BlockTri*, int64_t k, cplx* host_out);  // the stored block, widened to double at float storage
 void warmup_blocktri();
 
 // precond.hip: pc applied to cnt >= 1 device vectors at arbitrary addresses, in place, stream-ordered on st.  A

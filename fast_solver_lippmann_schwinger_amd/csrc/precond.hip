@@ -802,10 +802,11 @@ int lsfc_precond_schedule(const lsfc_precond* pc, int factor, int64_t out[10]) {
 namespace lsfc {
 
 // the object from DEVICE arrays of one shared pattern; the current device is `device`
-static lsfc_precond* create_blocktri_dev(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* As, const cplx* Msp, int device) {
+static lsfc_precond* create_blocktri_dev(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* As, const cplx* Msp, int device,
+                                         int prec) {
     std::unique_ptr<lsfc_precond> pc(new lsfc_precond());
     pc->device = device; pc->N = N;
-    pc->bt = blocktri_factor(N, K, rowptr, col, Msp);
+    pc->bt = blocktri_factor(N, K, rowptr, col, Msp, prec);
     const int64_t nnz = blocktri_nnz(pc->bt);
     pc->a_rowptr.alloc((size_t)N + 1); pc->a_col.alloc((size_t)nnz); pc->a_val.alloc((size_t)nnz);
     LSFC_HIP(hipMemcpy(pc->a_rowptr.p, rowptr, ((size_t)N + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
@@ -831,15 +832,22 @@ extern "C" {
 
 int lsfc_precond_create_blocktri(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
                                  const double* As_val, const double* Msp_val, int memspace, int device) {
+    return lsfc_precond_create_blocktri_prec(out, N, nblocks, rowptr, col, As_val, Msp_val, memspace, device, LSFC_PRECOND_INV_F64);
+}
+
+int lsfc_precond_create_blocktri_prec(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
+                                      const double* As_val, const double* Msp_val, int memspace, int device, int inverse_precision) {
+    const int prec = inverse_precision;
     return guarded([&] {
         LSFC_REQUIRE(out, "NULL argument"); *out = nullptr;
+        LSFC_REQUIRE(prec == LSFC_PRECOND_INV_F64 || prec == LSFC_PRECOND_INV_F32, "bad inverse_precision %d (LSFC_PRECOND_INV_F64 or _F32)", prec);
         LSFC_REQUIRE(rowptr && col && As_val && Msp_val, "NULL argument");
         LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "bad memspace %d", memspace);
         LSFC_REQUIRE(N >= 1 && N < ((int64_t)1 << 31), "preconditioner: N out of range");
         LSFC_REQUIRE(nblocks >= 1 && N % nblocks == 0, "block-tridiagonal preconditioner: N = %lld is not divisible by nblocks = %lld", (long long)N, (long long)nblocks);
         select_device(device);
-        blocktri_require_memory(N, nblocks, 0.0, "lsfc_precond_create_blocktri");      // from the dimensions alone, before any array is read
-        if (memspace == LSFC_MEM_DEVICE) { *out = create_blocktri_dev(N, nblocks, rowptr, col, (const cplx*)As_val, (const cplx*)Msp_val, device); return; }
+        blocktri_require_memory(N, nblocks, 0.0, "lsfc_precond_create_blocktri", prec);   // from the dimensions alone, before any array is read
+        if (memspace == LSFC_MEM_DEVICE) { *out = create_blocktri_dev(N, nblocks, rowptr, col, (const cplx*)As_val, (const cplx*)Msp_val, device, prec); return; }
         const int64_t nnz = rowptr[N];
         LSFC_REQUIRE(nnz >= 0, "block-tridiagonal preconditioner: rowptr[N] is negative");
         DevBuf<int64_t> drp, dcol; DevBuf<cplx> das, dmsp;
@@ -850,13 +858,17 @@ int lsfc_precond_create_blocktri(lsfc_precond** out, int64_t N, int64_t nblocks,
             LSFC_HIP(hipMemcpy(das.p, As_val, (size_t)nnz * sizeof(cplx), hipMemcpyHostToDevice));
             LSFC_HIP(hipMemcpy(dmsp.p, Msp_val, (size_t)nnz * sizeof(cplx), hipMemcpyHostToDevice));
         }
-        *out = create_blocktri_dev(N, nblocks, drp.p, dcol.p, das.p, dmsp.p, device);
+        *out = create_blocktri_dev(N, nblocks, drp.p, dcol.p, das.p, dmsp.p, device, prec);
     });
 }
 
-int lsfc_precond_create_from_plan(lsfc_precond** out, lsfc_plan* plan) {
+int lsfc_precond_create_from_plan(lsfc_precond** out, lsfc_plan* plan) { return lsfc_precond_create_from_plan_prec(out, plan, LSFC_PRECOND_INV_F64); }
+
+int lsfc_precond_create_from_plan_prec(lsfc_precond** out, lsfc_plan* plan, int inverse_precision) {
+    const int prec = inverse_precision;
     return guarded([&] {
         LSFC_REQUIRE(out, "NULL argument"); *out = nullptr;
+        LSFC_REQUIRE(prec == LSFC_PRECOND_INV_F64 || prec == LSFC_PRECOND_INV_F32, "bad inverse_precision %d (LSFC_PRECOND_INV_F64 or _F32)", prec);
         LSFC_REQUIRE(plan, "NULL plan");
         LSFC_REQUIRE(!plan->dist && !plan->multi, "block-tridiagonal preconditioner: not available on a distributed or multi-device plan");
         const int64_t n = plan->dims[0], m = plan->dims[1], l = plan->ndim == 2 ? 1 : plan->dims[2];
@@ -864,11 +876,11 @@ int lsfc_precond_create_from_plan(lsfc_precond** out, lsfc_plan* plan) {
         int64_t nnz = 0;
         if (int rc = lsfc_sparsify_pattern(n, m, l, &nnz, nullptr, nullptr, nullptr)) fail(rc, "%s", lsfc_last_error());
         select_device(plan->device);
-        blocktri_require_memory(N, K, (double)nnz * 40.0, "lsfc_precond_create_from_plan");
+        blocktri_require_memory(N, K, (double)nnz * 40.0, "lsfc_precond_create_from_plan", prec);
         DevBuf<int64_t> drp, dcol; DevBuf<cplx> das, dmsp;
         drp.alloc((size_t)N + 1); dcol.alloc((size_t)nnz); das.alloc((size_t)nnz); dmsp.alloc((size_t)nnz);
         if (int rc = lsfc_sparsify_build(plan, drp.p, dcol.p, (double*)das.p, nullptr, (double*)dmsp.p, nullptr, LSFC_MEM_DEVICE)) fail(rc, "%s", lsfc_last_error());
-        *out = create_blocktri_dev(N, K, drp.p, dcol.p, das.p, dmsp.p, plan->device);
+        *out = create_blocktri_dev(N, K, drp.p, dcol.p, das.p, dmsp.p, plan->device, prec);
     });
 }
 
@@ -879,6 +891,14 @@ int lsfc_precond_blocktri_info(const lsfc_precond* pc, int64_t out[6], double* m
         const BlockTriInfo i = blocktri_info(pc->bt);
         out[0] = i.K; out[1] = i.b; out[2] = i.factor_bytes; out[3] = pc->launches; out[4] = i.factor_us; out[5] = i.pivoting;
         if (min_pivot_ratio) *min_pivot_ratio = i.min_pivot_ratio;
+    });
+}
+
+int lsfc_precond_inverse_precision(const lsfc_precond* pc, int* precision) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && precision, "NULL argument");
+        LSFC_REQUIRE(pc->bt, "not a block-tridiagonal preconditioner (made by lsfc_precond_create)");
+        *precision = blocktri_precision(pc->bt);
     });
 }
 

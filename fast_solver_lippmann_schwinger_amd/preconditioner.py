@@ -12,7 +12,9 @@ A second route factorises on the device as well (csrc/blocktri.hip, lsfc_precond
 axis as block index Msp is block tridiagonal, and exact block elimination with dense explicit inverses of the Schur
 blocks replaces the sparse LU.  `SparsifyingPreconditioner(Msp, As, factor="blocktri", nblocks=...)` takes host
 matrices; `SparsifyingPreconditioner.from_operator(M)` assembles and factorises from the plan of a FastM / FastM3D
-without the matrices ever leaving the device (examples/example3D.jl:57-68 in one call)."""
+without the matrices ever leaving the device (examples/example3D.jl:57-68 in one call).  ``inverse_dtype="complex64"``
+keeps the dense inverses as float pairs (half the memory and half the bytes per apply): the factorisation is the fp64
+one, each inverse is rounded once when it is stored, and the applies widen on load and sum in fp64."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,6 +31,14 @@ SCHEDULE_FIELDS = ("level8", "level16", "level32", "level64", "chains", "chain_g
 BLOCKTRI_FIELDS = ("blocks", "block_size", "factor_bytes", "launches", "factor_us", "pivoting")
 # lsfc_precond_batch_info's four counts, in order
 BATCH_FIELDS = ("sweeps", "vectors", "largest_group", "work_bytes")
+# inverse_dtype -> LSFC_PRECOND_INV_*
+INVERSE_DTYPES = {"complex128": L.LSFC_PRECOND_INV_F64, "complex64": L.LSFC_PRECOND_INV_F32}
+
+
+def _inverse_precision(inverse_dtype):
+    if not isinstance(inverse_dtype, str) or inverse_dtype not in INVERSE_DTYPES:
+        raise ValueError(f"inverse_dtype must be 'complex128' or 'complex64', not {inverse_dtype!r}")
+    return INVERSE_DTYPES[inverse_dtype]
 
 
 def _csr_arrays(A):
@@ -43,15 +53,20 @@ class SparsifyingPreconditioner:
     Msp, As: scipy.sparse matrices (N x N, complex).  ``lu``: optional pre-computed scipy.sparse.linalg.SuperLU of Msp.
     ``factor``: "host" (default) -- sparse LU of Msp on the host, level-scheduled triangular solves on the device;
     "blocktri" -- block-tridiagonal factorisation on the device with ``nblocks`` blocks (the slowest grid axis: m in 2D,
-    l in 3D); Msp and As must share one pattern, as the pair of `sparsifying_pair` does."""
+    l in 3D); Msp and As must share one pattern, as the pair of `sparsifying_pair` does.
+    ``inverse_dtype`` (factor="blocktri" only): "complex128" (default) or "complex64", the storage of the dense inverses
+    S_k^{-1}; the factorisation and the sums of the apply are fp64 either way."""
 
-    def __init__(self, Msp, As, solverType="UMFPACK", device=0, lu=None, factor="host", nblocks=None):
+    def __init__(self, Msp, As, solverType="UMFPACK", device=0, lu=None, factor="host", nblocks=None, inverse_dtype="complex128"):
         import scipy.sparse as sp
         import scipy.sparse.linalg as spla
         if solverType not in ("UMFPACK", "MKLPARDISO"):
             raise NameError(f"UndefVarError: unknown solverType {solverType!r}")
         if factor not in ("host", "blocktri"):
             raise ValueError(f"factor must be 'host' or 'blocktri', not {factor!r}")
+        precision = _inverse_precision(inverse_dtype)
+        if factor == "host" and precision != L.LSFC_PRECOND_INV_F64:
+            raise ValueError("inverse_dtype='complex64' needs factor='blocktri': the host LU keeps no dense inverses")
         Msp = sp.csc_matrix(Msp, dtype=np.complex128)
         As = sp.csr_matrix(As, dtype=np.complex128)
         N = Msp.shape[0]
@@ -70,8 +85,8 @@ class SparsifyingPreconditioner:
                 raise ValueError("factor='blocktri': Msp and As must share one sparsity pattern (every stencil entry stored)")
             pc = C.c_void_p()
             p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-            L.check(L.load().lsfc_precond_create_blocktri(C.byref(pc), N, int(nblocks), p(m_ptr), p(m_col), p(a_val), p(m_val),
-                                                          L.LSFC_MEM_HOST, int(device)))
+            L.check(L.load().lsfc_precond_create_blocktri_prec(C.byref(pc), N, int(nblocks), p(m_ptr), p(m_col), p(a_val), p(m_val),
+                                                               L.LSFC_MEM_HOST, int(device), precision))
             self._pc = pc
             return
         if lu is None:
@@ -93,18 +108,30 @@ class SparsifyingPreconditioner:
         self._pc = pc
 
     @classmethod
-    def from_operator(cls, M):
+    def from_operator(cls, M, inverse_dtype="complex128"):
         """The preconditioner of a FastM / FastM3D in one device call (lsfc_precond_create_from_plan): As and
         Msp = As + k^2 AG diag(nu) are assembled into device memory from the plan's kernel, nu and k, and factorised
-        there with the slowest axis as block index.  ``Msp`` / ``As`` of the object are None: nothing is downloaded."""
+        there with the slowest axis as block index.  ``Msp`` / ``As`` of the object are None: nothing is downloaded.
+        ``inverse_dtype``: storage of the dense inverses, as in the constructor."""
+        precision = _inverse_precision(inverse_dtype)
         self = cls.__new__(cls)
         pc = C.c_void_p()
-        L.check(L.load().lsfc_precond_create_from_plan(C.byref(pc), M._plan))
+        L.check(L.load().lsfc_precond_create_from_plan_prec(C.byref(pc), M._plan, precision))
         self._pc = pc
         self.Msp = self.As = None
         self.solverType, self.factor = "UMFPACK", "blocktri"
         self.N = int(self.blocktri_info()["blocks"] * self.blocktri_info()["block_size"])
         return self
+
+    @property
+    def inverse_dtype(self):
+        """storage of the dense inverses of a block-tridiagonal object (lsfc_precond_inverse_precision): "complex128" or
+        "complex64"; None on an object of the host-LU route, which keeps none"""
+        if self.factor != "blocktri":
+            return None
+        prec = C.c_int(-1)
+        L.check(L.load().lsfc_precond_inverse_precision(self._pc, C.byref(prec)))
+        return {v: k for k, v in INVERSE_DTYPES.items()}[prec.value]
 
     def blocktri_info(self):
         """lsfc_precond_blocktri_info as a dict (BLOCKTRI_FIELDS and min_pivot_ratio)"""
@@ -116,7 +143,8 @@ class SparsifyingPreconditioner:
         return info
 
     def blocktri_block(self, k):
-        """S_k^{-1} (b x b) of a block-tridiagonal object (lsfc_precond_blocktri_get_block; debugging and tests)"""
+        """S_k^{-1} (b x b) of a block-tridiagonal object as stored, widened to complex128 at float storage
+        (lsfc_precond_blocktri_get_block; debugging and tests)"""
         b = self.blocktri_info()["block_size"]
         out = np.empty(b * b, dtype=np.complex128)
         L.check(L.load().lsfc_precond_blocktri_get_block(self._pc, int(k), out.ctypes.data_as(C.c_void_p), b * b))

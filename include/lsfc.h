@@ -269,14 +269,33 @@ int lsfc_precond_create_blocktri(lsfc_precond** out, int64_t N, int64_t nblocks,
 /* lsfc_sparsify_build into device memory, then lsfc_precond_create_blocktri with nblocks = the slowest axis (m in 2D,
  * l in 3D), on the plan's device: examples/example3D.jl:57-68 in one call.  Restrictions of lsfc_sparsify_build. */
 int lsfc_precond_create_from_plan(lsfc_precond** out, lsfc_plan* plan);
-/* out: blocks, block size b, bytes of the stored inverses, kernel launches per apply, factorisation time in
+/* The same two constructors with the storage of the inverses chosen: the functions above are the LSFC_PRECOND_INV_F64 case.
+ * LSFC_PRECOND_INV_F32 keeps every S_k^{-1} as interleaved float pairs, nblocks * b^2 * 8 bytes: half the memory rule and
+ * half the bytes an apply reads.  The elimination is the fp64 one, unchanged: S_k^{-1} is computed in an fp64 work block
+ * (the Schur update of block k + 1 reads it there), then rounded ONCE to nearest-even and stored, so the stored blocks
+ * are bit for bit the fp64 object's blocks cast to float, and min_pivot_ratio is that of the fp64 object.  The applies
+ * widen every entry to fp64 on load and sum in fp64 in the fp64 object's order.  The object is a fixed linear operator
+ * about 1e-7 (relative) away from the fp64 one: left-preconditioned GMRES solves A x = b to the same tolerance with it.
+ * Work space during the factorisation: two more fp64 blocks (2 b^2 16 bytes).  LSFC_ENOMEM as above, decided from N,
+ * nblocks and the precision alone; the message names the precision.
+ * LSFC_EINVAL (before any device call): inverse_precision is neither constant. */
+#define LSFC_PRECOND_INV_F64 0   /* as today */
+#define LSFC_PRECOND_INV_F32 1   /* S_k^{-1} stored as interleaved float pairs */
+int lsfc_precond_create_blocktri_prec(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
+                                      const double* As_val, const double* Msp_val, int memspace, int device, int inverse_precision);
+int lsfc_precond_create_from_plan_prec(lsfc_precond** out, lsfc_plan* plan, int inverse_precision);
+/* precision: LSFC_PRECOND_INV_F64 or _F32, as the object was made.  LSFC_EINVAL on an object of lsfc_precond_create. */
+int lsfc_precond_inverse_precision(const lsfc_precond* pc, int* precision);
+/* out: blocks, block size b, bytes of the stored inverses (nblocks b^2 16, or 8 at float storage), kernel launches per apply, factorisation time in
  * microseconds, 1 if pivoting was used (always 0); min_pivot_ratio (may be NULL): smallest |pivot| / max|S_k| met.
  * LSFC_EINVAL on an object made by lsfc_precond_create. */
 int lsfc_precond_blocktri_info(const lsfc_precond* pc, int64_t out[6], double* min_pivot_ratio);
-/* Debug / test access in the spirit of lsfc_plan_get_symbol: S_k^{-1} (b x b, column-major) to the host.
+/* Debug / test access in the spirit of lsfc_plan_get_symbol: S_k^{-1} (b x b, column-major) to the host, as stored
+ * (at float storage: the stored float pairs widened to double).
  * LSFC_EINVAL: object made by lsfc_precond_create, k out of range, capacity_complex < b^2. */
 int lsfc_precond_blocktri_get_block(const lsfc_precond* pc, int64_t k, double* out, int64_t capacity_complex);
-/* On such an object lsfc_precond_apply / _callback / _set_stream / _destroy work as on any other; lsfc_precond_stats
+/* On such an object, at either storage, lsfc_precond_apply / _apply_batch / _batch_info / _callback / _set_stream /
+ * _destroy work as on any other, and lsfc_gmres_batch groups its members' applies as before; lsfc_precond_stats
  * returns nblocks, nblocks and the launch count; lsfc_precond_schedule returns LSFC_EINVAL (there are no levels). */
 
 /* ---- assembly of the sparsifying matrices (As, As*G, Msp) ------------------- */

@@ -199,20 +199,36 @@ function _wrap_precond(pc::Ptr{Cvoid}, N)
     finalizer(P -> ccall((:lsfc_precond_destroy, liblsfc), Cint, (Ptr{Cvoid},), P.pc), P)
     return P
 end
-function SparsifyingPreconditionerHIP(Msp::SparseMatrixCSC{Complex{Float64},Int64}, As::SparseMatrixCSC{Complex{Float64},Int64}, nblocks::Integer; device=0)
+# inverse_type: Complex{Float64} (default, LSFC_PRECOND_INV_F64) or Complex{Float32} (LSFC_PRECOND_INV_F32): the storage of the
+# dense inverses S_k^{-1}.  The factorisation is fp64 either way; float storage rounds each inverse once and halves the memory.
+function _inverse_precision(T)
+    T === Complex{Float64} && return Cint(0)
+    T === Complex{Float32} && return Cint(1)
+    throw(ArgumentError("inverse_type must be Complex{Float64} or Complex{Float32}"))
+end
+function SparsifyingPreconditionerHIP(Msp::SparseMatrixCSC{Complex{Float64},Int64}, As::SparseMatrixCSC{Complex{Float64},Int64}, nblocks::Integer;
+                                      device=0, inverse_type=Complex{Float64})
+    prec = _inverse_precision(inverse_type)
     N = size(Msp, 1)
     (mp, mc, mv) = _csr(Msp); (ap, ac, av) = _csr(As)
     (mp == ap && mc == ac) || throw(DimensionMismatch("Msp and As must share one sparsity pattern"))
     pc = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:lsfc_precond_create_blocktri, liblsfc), Cint,
-                (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Cint, Cint),
-                pc, N, nblocks, mp, mc, av, mv, 0, device))
+    check(ccall((:lsfc_precond_create_blocktri_prec, liblsfc), Cint,
+                (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Cint, Cint, Cint),
+                pc, N, nblocks, mp, mc, av, mv, 0, device, prec))
     return _wrap_precond(pc[], N)
 end
-function SparsifyingPreconditionerHIP(M::FastMHIP)
+function SparsifyingPreconditionerHIP(M::FastMHIP; inverse_type=Complex{Float64})
+    prec = _inverse_precision(inverse_type)
     pc = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:lsfc_precond_create_from_plan, liblsfc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}), pc, M.plan))
+    check(ccall((:lsfc_precond_create_from_plan_prec, liblsfc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Cint), pc, M.plan, prec))
     return _wrap_precond(pc[], size(M, 1))
+end
+# Complex{Float64} or Complex{Float32}: how the object stores its inverses (lsfc_precond_inverse_precision)
+function inverse_type(P::SparsifyingPreconditionerHIP)
+    prec = Ref{Cint}(-1)
+    check(ccall((:lsfc_precond_inverse_precision, liblsfc), Cint, (Ptr{Cvoid}, Ref{Cint}), P.pc, prec))
+    return prec[] == 1 ? Complex{Float32} : Complex{Float64}
 end
 # (blocks, block size, bytes of the inverses, launches per apply, factorisation microseconds, pivoting used), min |pivot| / max|S_k|
 function blocktri_info(P::SparsifyingPreconditionerHIP)
@@ -220,7 +236,7 @@ function blocktri_info(P::SparsifyingPreconditionerHIP)
     check(ccall((:lsfc_precond_blocktri_info, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ref{Float64}), P.pc, out, r))
     return out, r[]
 end
-# S_k^{-1} (k 0-based), b x b
+# S_k^{-1} (k 0-based), b x b, as stored (float storage: widened to Complex{Float64})
 function blocktri_block(P::SparsifyingPreconditionerHIP, k::Integer)
     b = blocktri_info(P)[1][2]; S = Matrix{Complex{Float64}}(undef, b, b)
     check(ccall((:lsfc_precond_blocktri_get_block, liblsfc), Cint, (Ptr{Cvoid}, Int64, Ptr{Complex{Float64}}, Int64), P.pc, k, S, b * b))

@@ -20,7 +20,13 @@ that reads every S_k^{-1} once) against R single applies of the same object in t
 batched time implies on the byte model 2 K b^2 16 B per group.  --gmres adds, for the largest R, a preconditioned
 gmres_batch_ of R incident directions against R back-to-back gmres_ calls with the same object.
 
-    python tools/bench_sparsify.py --nrhs 1,2,4,8 --gmres --out profiles/precond_batch.jsonl"""
+    python tools/bench_sparsify.py --nrhs 1,2,4,8 --gmres --out profiles/precond_batch.jsonl
+
+--inverse-dtype complex128[,complex64] (with --nrhs): the same rows once per storage of the inverses, both objects timed
+in one process; the byte model is 2 K b^2 times the bytes of a stored entry, and every row also has the factorisation
+time of its object and the spread (min, max) of the timed single applies.
+
+    python tools/bench_sparsify.py --inverse-dtype complex128,complex64 --nrhs 1,8 --out profiles/precond_f32.jsonl"""
 import argparse
 import json
 import os
@@ -184,7 +190,7 @@ def factor_mode(args):
         torch.cuda.empty_cache()
 
 
-def median_ms(fn, reps):
+def timed_ms(fn, reps):
     import torch
     fn()                                                   # warm-up (captures the graph, allocates work buffers)
     ms = []
@@ -194,7 +200,37 @@ def median_ms(fn, reps):
         fn()
         torch.cuda.synchronize()
         ms.append(1e3 * (time.perf_counter() - t0))
-    return float(np.median(ms))
+    return ms
+
+
+def median_ms(fn, reps):
+    return float(np.median(timed_ms(fn, reps)))
+
+
+def nrhs_rows(args, pkg, M, B, groups, name, inverse_dtype):
+    """one row per group size for an object of the given storage; returns (object, its stats)"""
+    N = B.shape[1]
+    P = pkg.SparsifyingPreconditioner.from_operator(M, inverse_dtype=inverse_dtype)
+    st = P.stats()
+    single = timed_ms(lambda: P.ldiv_(B[0].clone()), args.reps)
+    for R in groups:
+        def singles():
+            W = B[:R].clone()
+            for j in range(R):
+                P.ldiv_(W[j])
+        batched_ms = median_ms(lambda: P.ldiv_batch_(B[:R].clone()), args.reps)
+        singles_ms = median_ms(singles, args.reps)
+        groups_of_8 = (R + 7) // 8
+        emit(args.out, {"case": name, "N": N, "blocks": st["blocks"], "block_size": st["block_size"], "inverse_dtype": inverse_dtype,
+                        "factor_GB": round(st["factor_bytes"] / 1e9, 3), "factor_s": round(st["factor_us"] / 1e6, 4), "nrhs": R,
+                        "batched_ms": round(batched_ms, 4), "singles_ms": round(singles_ms, 4),
+                        "single_apply_ms": round(float(np.median(single)), 4),
+                        "single_apply_ms_min_max": [round(min(single), 4), round(max(single), 4)],
+                        "single_apply_TBps": round(2 * st["factor_bytes"] / (float(np.median(single)) * 1e-3) / 1e12, 3),
+                        "per_vector_ms": round(batched_ms / R, 4), "ratio_batched_over_singles": round(batched_ms / singles_ms, 4),
+                        "model_GB": round(groups_of_8 * 2 * st["factor_bytes"] / 1e9, 3),
+                        "implied_TBps": round(groups_of_8 * 2 * st["factor_bytes"] / (batched_ms * 1e-3) / 1e12, 3)})
+    return P, st
 
 
 def nrhs_mode(args):
@@ -205,24 +241,11 @@ def nrhs_mode(args):
         ndim, n = (int(v) for v in spec.split(":"))
         N = n ** ndim
         M = operator(ndim, n)
-        P = pkg.SparsifyingPreconditioner.from_operator(M)
-        st = P.stats()
         rng = np.random.default_rng(0)
         B = torch.from_numpy(rng.standard_normal((max(groups), N)) + 1j * rng.standard_normal((max(groups), N))).cuda()
-        single_ms = median_ms(lambda: P.ldiv_(B[0].clone()), args.reps)
-        for R in groups:
-            def singles():
-                W = B[:R].clone()
-                for j in range(R):
-                    P.ldiv_(W[j])
-            batched_ms = median_ms(lambda: P.ldiv_batch_(B[:R].clone()), args.reps)
-            singles_ms = median_ms(singles, args.reps)
-            groups_of_8 = (R + 7) // 8
-            emit(args.out, {"case": f"{ndim}D n={n}", "N": N, "blocks": st["blocks"], "block_size": st["block_size"], "nrhs": R,
-                            "batched_ms": round(batched_ms, 4), "singles_ms": round(singles_ms, 4), "single_apply_ms": round(single_ms, 4),
-                            "per_vector_ms": round(batched_ms / R, 4), "ratio_batched_over_singles": round(batched_ms / singles_ms, 4),
-                            "model_GB": round(groups_of_8 * 2 * st["factor_bytes"] / 1e9, 3),
-                            "implied_TBps": round(groups_of_8 * 2 * st["factor_bytes"] / (batched_ms * 1e-3) / 1e12, 3)})
+        for inverse_dtype in args.inverse_dtype.split(",")[:-1]:            # all but the last storage: apply rows only
+            nrhs_rows(args, pkg, M, B, groups, f"{ndim}D n={n}", inverse_dtype)[0].close()
+        P, st = nrhs_rows(args, pkg, M, B, groups, f"{ndim}D n={n}", args.inverse_dtype.split(",")[-1])
         if args.gmres:
             R = max(groups)
             h = 1.0 / (n - 1) if ndim == 2 else 1.0 / n
@@ -263,6 +286,8 @@ def main():
     ap.add_argument("--device-only", action="store_true", help="only the device builds (for a kernel trace)")
     ap.add_argument("--factor", action="store_true", help="time the device-factorised preconditioner (see the module docstring)")
     ap.add_argument("--nrhs", default="", help="group sizes, e.g. 1,2,4,8: batched apply against single applies (see the module docstring)")
+    ap.add_argument("--inverse-dtype", default="complex128", help="with --nrhs: storages of the inverses to time in one process, "
+                    "complex128 and / or complex64, comma separated")
     ap.add_argument("--gmres", action="store_true", help="with --nrhs: also a preconditioned gmres_batch_ against back-to-back gmres_")
     args = ap.parse_args()
     if args.nrhs:
