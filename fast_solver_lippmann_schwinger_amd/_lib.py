@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("LSFC_LIBRARY") or os.path.join(_HERE, "liblsfc.so")
 LSFC_QUAD_TRAPEZOIDAL, LSFC_QUAD_GREENGARD_VICO = 0, 1
 LSFC_MEM_HOST, LSFC_MEM_DEVICE = 0, 1
 LSFC_PRECOND_INV_F64, LSFC_PRECOND_INV_F32 = 0, 1
+LSFC_PRECOND_PIVOT_NONE, LSFC_PRECOND_PIVOT_PARTIAL, LSFC_PRECOND_PIVOT_AUTO = 0, 1, 2
 LSFC_FLAG_DEFAULT, LSFC_FLAG_LITERAL_PAD, LSFC_FLAG_FORCE_ROCFFT, LSFC_FLAG_PATCH_SINGULAR = 0, 1, 2, 4
 LSFC_ORTH_MGS, LSFC_ORTH_CGS, LSFC_ORTH_DGKS = 0, 1, 2
 LSFC_ENODEV, LSFC_ENOTCONV = -2, -5
@@ -29,6 +30,10 @@ class GmresOpts(C.Structure):
 
 class GmresResult(C.Structure):
     _fields_ = [("iters", C.c_int64), ("mvps", C.c_int64), ("converged", C.c_int), ("final_resnorm", C.c_double)]
+
+
+class BlocktriOpts(C.Structure):                   # lsfc_blocktri_opts
+    _fields_ = [("inverse_precision", C.c_int), ("pivoting", C.c_int), ("reserved", C.c_int * 6)]
 
 
 class LsfcError(RuntimeError):
@@ -71,6 +76,9 @@ SIGNATURES = {
     "lsfc_precond_create_from_plan": (_I, [_PP, _P]),
     "lsfc_precond_create_blocktri_prec": (_I, [_PP, _L, _L, _P, _P, _P, _P, _I, _I, _I]),
     "lsfc_precond_create_from_plan_prec": (_I, [_PP, _P, _I]),
+    "lsfc_precond_create_blocktri_opts": (_I, [_PP, _L, _L, _P, _P, _P, _P, _I, _I, _P]),
+    "lsfc_precond_create_from_plan_opts": (_I, [_PP, _P, _P]),
+    "lsfc_precond_blocktri_get_pivots": (_I, [_P, _L, _P, _L]),
     "lsfc_precond_inverse_precision": (_I, [_P, C.POINTER(_I)]),
     "lsfc_precond_blocktri_info": (_I, [_P, C.POINTER(_L), C.POINTER(_D)]),
     "lsfc_precond_blocktri_get_block": (_I, [_P, _L, _P, _L]),

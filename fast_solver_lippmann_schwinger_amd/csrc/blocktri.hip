@@ -21,6 +21,13 @@
 //     A_ij <- A_ij - A_iJ(old) A_Jj(new)  the trailing update: complex fp64 GEMM on v_mfma_f64_16x16x4_f64
 // No float atomics anywhere and every sum in a fixed order: two factorisations of one input are bitwise equal.
 //
+// Partial row pivoting inside a Schur block (BLOCKTRI_PIVOT_PARTIAL): before the three kernels of a step, one workgroup
+// factorises a scratch copy of the tall panel (rows j0 .. b-1) by LU with row interchanges -- rows >= p of column p are the
+// same in Gauss-Jordan and in LU at step p -- and composes the panel's interchanges into one list of row moves; a second
+// kernel applies the moves to whole rows of the block.  The step then runs on the permuted block as it stands.  After the
+// last panel the block is (Pi S_k)^{-1}; its columns are put back once through W, so that S_k^{-1} itself is stored and
+// nothing after the inversion knows of the pivoting.
+//
 // Apply: one kernel per step of the two sweeps; a workgroup forms the stencil product (L_k z_{k-1} or U_k x_{k+1}) in
 // LDS and multiplies 16 rows of S_k^{-1} with it (16 B loads, 32 column slots folded through LDS in a fixed order).
 // Planes of at most 96 rows are walked inside one launch by a single workgroup.
@@ -299,6 +306,113 @@ __global__ __launch_bounds__(256) void k_bt_trail(cplx* __restrict__ A, int64_t 
                 if (i < b && j < b) A[i + j * b] = make_double2(re[sj][si][g], im[sj][si][g]);
             }
         }
+}
+
+// ---- set-up: partial row pivoting ------------------------------------------------------------------------------------
+
+static constexpr int PV_THREADS = 1024;   // the panel factorisation: one workgroup, thread t owns rows t, t + 1024, ...
+static constexpr int PV_MOVES = 2 * NB;   // rows that the interchanges of one panel can touch
+
+// (|v|^2, row) of a pivot candidate: the larger modulus wins, on a tie the lower row (a total order, so the result does
+// not depend on the order in which candidates are compared); a modulus that is not a number never wins
+__device__ __forceinline__ void pv_better(double& bm, int& bi, double m, int i) { if (m > bm || (m == bm && i < bi)) { bm = m; bi = i; } }
+__device__ __forceinline__ double pv_abs2(cplx v) { return __dadd_rn(__dmul_rn(v.x, v.x), __dmul_rn(v.y, v.y)); }
+
+// The pivots of panel J = [j0, j0 + nb): LU with partial pivoting of the tall panel A[j0 .. b-1, J] on the scratch copy T
+// (h = b - j0 rows, leading dimension b), with the arithmetic of k_bt_diag, by ONE workgroup.  A thread keeps its rows
+// for the whole panel, so per step only the two interchanged rows pass between threads: two barriers per step.  The
+// modulus of the next column is taken while that column is updated.  Thread 0 composes the interchanges: mpos / mval is
+// a map "position -> row now there" over the <= 64 positions touched.  Out: nmoves and moves[2 i] = position,
+// moves[2 i + 1] = row that goes there (both relative to j0, only where they differ); perm (b entries of this block,
+// perm[i] = row of S_k now at position i) is set to the identity by the first panel and updated by every panel.
+__global__ __launch_bounds__(PV_THREADS) void k_bt_pivot_panel(const cplx* __restrict__ A, int64_t b, int j0, int nb, cplx* T,
+                                                               int* __restrict__ moves, int* perm) {
+    __shared__ double rm[PV_THREADS / 64]; __shared__ int ri[PV_THREADS / 64];
+    __shared__ cplx prow[NB];
+    __shared__ int mpos[PV_MOVES], mval[PV_MOVES], mcnt, oldp[PV_MOVES];
+    const int tid = threadIdx.x, h = (int)(b - j0);
+    if (j0 == 0) for (int i = tid; i < h; i += PV_THREADS) perm[i] = i;
+    if (tid == 0) mcnt = 0;
+    double bm = -1.0; int bi = 0;
+    for (int i = tid; i < h; i += PV_THREADS) {
+        for (int c = 0; c < nb; ++c) {
+            const cplx v = A[(j0 + i) + (int64_t)(j0 + c) * b];
+            T[i + (int64_t)c * b] = v;
+            if (c == 0) pv_better(bm, bi, pv_abs2(v), i);
+        }
+    }
+    for (int p = 0; p < nb; ++p) {
+        // the pivot of column p among rows p .. h-1: lanes, then waves (every thread folds the 16 wave results itself)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const double m = __shfl_xor(bm, o, 64); const int i = __shfl_xor(bi, o, 64); pv_better(bm, bi, m, i); }
+        if ((tid & 63) == 0) { rm[tid >> 6] = bm; ri[tid >> 6] = bi; }
+        __syncthreads();
+        double qm = -1.0; int q = p;
+        for (int w = 0; w < PV_THREADS / 64; ++w) pv_better(qm, q, rm[w], ri[w]);
+        if (qm < 0.0) q = p;                                                 // no candidate is a number: k_bt_diag reports the pivot
+        if (tid < nb) {                                                      // interchange rows p and q of T; the new row p aside
+            const cplx vq = T[q + (int64_t)tid * b];
+            if (q != p) { T[q + (int64_t)tid * b] = T[p + (int64_t)tid * b]; T[p + (int64_t)tid * b] = vq; }
+            prow[tid] = vq;
+        }
+        if (tid == 0 && q != p) {
+            int ip = -1, iq = -1;
+            for (int e = 0; e < mcnt; ++e) { if (mpos[e] == p) ip = e; if (mpos[e] == q) iq = e; }
+            if (ip < 0) { ip = mcnt++; mpos[ip] = p; mval[ip] = p; }
+            if (iq < 0) { iq = mcnt++; mpos[iq] = q; mval[iq] = q; }
+            const int t = mval[ip]; mval[ip] = mval[iq]; mval[iq] = t;
+        }
+        __syncthreads();
+        bm = -1.0; bi = 0;
+        if (p + 1 < nb) {
+            const cplx piv = prow[p];
+            const double a2 = piv.x * piv.x + piv.y * piv.y;
+            const cplx ip = make_double2(piv.x / a2, -piv.y / a2);
+            for (int i = tid; i < h; i += PV_THREADS) {
+                if (i <= p) continue;
+                const cplx f = T[i + (int64_t)p * b];
+                for (int c = p + 1; c < nb; ++c) {
+                    const cplx t = cmul(f, cmul(prow[c], ip)), v = T[i + (int64_t)c * b];
+                    const cplx nv = make_double2(v.x - t.x, v.y - t.y);
+                    T[i + (int64_t)c * b] = nv;
+                    if (c == p + 1) pv_better(bm, bi, pv_abs2(nv), i);
+                }
+            }
+        }
+    }
+    // the moves of this panel, and perm after them
+    const int n = mcnt;
+    if (tid < PV_MOVES) oldp[tid] = tid < n ? perm[j0 + mval[tid]] : 0;
+    __syncthreads();
+    if (tid < n) perm[j0 + mpos[tid]] = oldp[tid];
+    if (tid == 0) {
+        int cnt = 0;
+        for (int e = 0; e < n; ++e) if (mval[e] != mpos[e]) { moves[1 + 2 * cnt] = mpos[e]; moves[2 + 2 * cnt] = mval[e]; ++cnt; }
+        moves[0] = cnt;
+    }
+}
+
+// The moves of one panel applied to whole rows of the block: one wave per column, lane e reads the entry that goes to
+// position moves[e] and writes it there after the whole wave has read (4 columns per workgroup; the rows of a panel's own
+// positions are consecutive, so half of the stores of a wave fall into 512 consecutive bytes).
+__global__ __launch_bounds__(256) void k_bt_swap_rows(cplx* __restrict__ A, int64_t b, int j0, const int* __restrict__ moves) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int n = moves[0];
+    const bool on = lane < n && c < b;
+    cplx v = make_double2(0.0, 0.0);
+    int dst = 0;
+    if (on) { dst = moves[1 + 2 * lane]; v = A[(j0 + moves[2 + 2 * lane]) + c * b]; }
+    __syncthreads();
+    if (on) A[(j0 + dst) + c * b] = v;
+}
+
+// columns back in place after the last panel: B = (Pi S)^{-1} in A, S^{-1} = B Pi, column perm[j] of S^{-1} = column j of B
+__global__ __launch_bounds__(256) void k_bt_unscramble(int64_t b, const cplx* __restrict__ A, const int* __restrict__ perm, cplx* __restrict__ W) {
+    const int64_t idx = blockIdx.x * (int64_t)256 + threadIdx.x;
+    if (idx >= b * b) return;
+    const int64_t i = idx % b, j = idx / b;
+    W[i + (int64_t)perm[j] * b] = A[idx];
 }
 
 // ---- the apply -----------------------------------------------------------------------------------------------------
@@ -599,25 +713,28 @@ struct BlockTri {
     DevBuf<cplx> S;                                                          // S_k^{-1}, k = 0 .. K-1 (fp64 storage) ...
     DevBuf<cplx32> S32;                                                      // ... or the same blocks rounded to float pairs
     int64_t factor_us = 0; double min_ratio = 0.0;
+    bool pivoted = false; DevBuf<int> perm;                                  // partial pivoting: perm[k b + i] = row of S_k that became pivot row i
     DevBuf<cplx> bt_t, bt_part; int batch_cap = 0;                           // group apply: stencil products (b x R), partial sums (ranges x R x b)
     int launches() const { return b <= WALK_B ? 1 : (int)(2 * K - 1); }
 };
 
 static double entry_bytes(int prec) { return prec == BLOCKTRI_INV_F32 ? 8.0 : 16.0; }
 
-static double work_bytes(int64_t N, int64_t K, int prec) {
+static double work_bytes(int64_t N, int64_t K, int prec, int pivoting) {
     const double b = (double)(N / K);
     const double blocks = prec == BLOCKTRI_INV_F32 ? 2.0 * b * b * 16.0 : 0.0;    // float storage: current and previous block in fp64
-    return blocks + b * b * 16.0 + 2.0 * b * NB * 16.0 + 64.0 * (double)N;   // W, the two panels, row tables and vectors
+    // pivoting (PARTIAL, and AUTO, which may come to it): the scratch copy of the tall panel, the pivots (K b 4 B), the moves
+    const double pivot = pivoting == BLOCKTRI_PIVOT_NONE ? 0.0 : b * NB * 16.0 + 4.0 * (double)N + 4.0 * (1 + 2 * PV_MOVES);
+    return blocks + b * b * 16.0 + 2.0 * b * NB * 16.0 + 64.0 * (double)N + pivot;   // W, the two panels, row tables and vectors
 }
 
-BlockTriNeed blocktri_memory_need(int64_t N, int64_t K, int prec) {
+BlockTriNeed blocktri_memory_need(int64_t N, int64_t K, int prec, int pivoting) {
     const double b = (double)(N / K);
-    return BlockTriNeed{(double)K * b * b * entry_bytes(prec), work_bytes(N, K, prec)};
+    return BlockTriNeed{(double)K * b * b * entry_bytes(prec), work_bytes(N, K, prec, pivoting)};
 }
 
-void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who, int prec) {
-    const BlockTriNeed nd = blocktri_memory_need(N, K, prec);
+void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who, int prec, int pivoting) {
+    const BlockTriNeed nd = blocktri_memory_need(N, K, prec, pivoting);
     const double factors = nd.inverse_bytes, need = factors + nd.work_bytes + extra;
     size_t free_b = 0, total_b = 0;
     LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -629,7 +746,9 @@ void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who
 
 static inline unsigned nblk(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp, int prec) {
+// one factorisation, with partial pivoting in every block or without any.  `breakdown` (may be NULL): a pivot below the
+// threshold sets it and returns no object instead of failing -- BLOCKTRI_PIVOT_AUTO then repeats with pivoting.
+static BlockTri* factor_once(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp, int prec, bool pivot, bool* breakdown) {
     const auto t0 = std::chrono::steady_clock::now();
     const int64_t b = N / K;
     LSFC_REQUIRE(b * b < ((int64_t)1 << 40), "block-tridiagonal preconditioner: block size %lld out of range", (long long)b);
@@ -678,7 +797,9 @@ BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int
     if (f32) { bt->S32.alloc((size_t)(K * b * b)); work[0].alloc((size_t)(b * b)); if (K > 1) work[1].alloc((size_t)(b * b)); }
     else bt->S.alloc((size_t)(K * b * b));
     DevBuf<cplx> W, P, R, Cb; DevBuf<double> part;
-    if (K > 1) W.alloc((size_t)(b * b));
+    if (K > 1 || pivot) W.alloc((size_t)(b * b));                           // (pivoting: the columns go back in place through W)
+    DevBuf<cplx> T; DevBuf<int> moves;
+    if (pivot) { T.alloc((size_t)(b * NB)); moves.alloc(1 + 2 * PV_MOVES); bt->perm.alloc((size_t)N); bt->pivoted = true; }
     P.alloc(NB * NB); R.alloc((size_t)(NB * b)); Cb.alloc((size_t)(b * NB)); part.alloc(256);
     const int nt = (int)((b + NB - 1) / NB), nx = (int)nblk(b, 256);
     const unsigned ebl = nblk(b * b, 256);
@@ -695,21 +816,41 @@ BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int
         hipLaunchKernelGGL(k_bt_absmax_fin, dim3(1), dim3(256), 0, st, 256, part.p, dstat.p);
         for (int J = 0; J < nt; ++J) {
             const int j0 = J * NB, nb = (int)std::min<int64_t>(NB, b - j0);
+            if (pivot) {
+                hipLaunchKernelGGL(k_bt_pivot_panel, dim3(1), dim3(PV_THREADS), 0, st, (const cplx*)Sk, b, j0, nb, T.p, moves.p, bt->perm.p + k * b);
+                hipLaunchKernelGGL(k_bt_swap_rows, dim3(nblk(b, 4)), dim3(256), 0, st, Sk, b, j0, (const int*)moves.p);
+            }
             hipLaunchKernelGGL(k_bt_diag, dim3(1), dim3(1024), 0, st, Sk, b, j0, nb, P.p, dstat.p, (int)k, BLOCKTRI_PIVOT_MIN);
             hipLaunchKernelGGL(k_bt_panels, dim3(2 * nx), dim3(256), 0, st, Sk, b, j0, nb, P.p, R.p, Cb.p, nx);
             if (nt > 1) hipLaunchKernelGGL(k_bt_trail, dim3(nblk((int64_t)nt * nt, 4)), dim3(256), 0, st, Sk, b, J, nt, R.p, Cb.p);
+        }
+        if (pivot) {
+            hipLaunchKernelGGL(k_bt_unscramble, dim3(ebl), dim3(256), 0, st, b, (const cplx*)Sk, (const int*)(bt->perm.p + k * b), W.p);
+            LSFC_HIP(hipMemcpyAsync(Sk, W.p, (size_t)(b * b) * sizeof(cplx), hipMemcpyDeviceToDevice, st));
         }
         if (f32) hipLaunchKernelGGL(k_bt_round, dim3(ebl), dim3(256), 0, st, b * b, (const cplx*)Sk, bt->S32.p + k * b * b);
         LSFC_HIP(hipGetLastError());
     }
     LSFC_HIP(hipMemcpyAsync(&hs, dstat.p, sizeof hs, hipMemcpyDeviceToHost, st));
     LSFC_HIP(hipStreamSynchronize(st));
+    if (hs.bad_block >= 0 && breakdown) { *breakdown = true; return nullptr; }
+    if (pivot)
+        LSFC_REQUIRE(hs.bad_block < 0, "block-tridiagonal preconditioner: breakdown in block %d at row %lld (pivot %d of the block): the largest candidate has "
+                     "|pivot| / max|S_k| = %.3e, below %.1e -- the Schur block is singular to working precision (partial pivoting inside the block)",
+                     hs.bad_block, (long long)(hs.bad_block * b + hs.bad_row), hs.bad_row, hs.bad_ratio, BLOCKTRI_PIVOT_MIN);
     LSFC_REQUIRE(hs.bad_block < 0, "block-tridiagonal preconditioner: breakdown in block %d at row %lld (row %d of the block): |pivot| / max|S_k| = %.3e is below %.1e "
                  "-- the Schur block is singular or needs pivoting; use the host LU route (lsfc_precond_create)", hs.bad_block,
                  (long long)(hs.bad_block * b + hs.bad_row), hs.bad_row, hs.bad_ratio, BLOCKTRI_PIVOT_MIN);
     bt->min_ratio = hs.min_ratio;
     bt->factor_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     return bt.release();
+}
+
+BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp, int prec, int pivoting) {
+    if (pivoting != BLOCKTRI_PIVOT_AUTO) return factor_once(N, K, rowptr, col, msp, prec, pivoting == BLOCKTRI_PIVOT_PARTIAL, nullptr);
+    bool breakdown = false;
+    if (BlockTri* bt = factor_once(N, K, rowptr, col, msp, prec, false, &breakdown)) return bt;
+    return factor_once(N, K, rowptr, col, msp, prec, true, nullptr);          // the whole factorisation again, pivoting in every block
 }
 
 void blocktri_destroy(BlockTri* bt) { delete bt; }
@@ -787,7 +928,14 @@ void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, h
 
 BlockTriInfo blocktri_info(const BlockTri* bt) {
     const int64_t bytes = (int64_t)(bt->prec == BLOCKTRI_INV_F32 ? bt->S32.bytes() : bt->S.bytes());
-    return BlockTriInfo{bt->K, bt->b, bytes, bt->launches(), bt->factor_us, 0, bt->min_ratio};
+    return BlockTriInfo{bt->K, bt->b, bytes, bt->launches(), bt->factor_us, bt->pivoted ? 1 : 0, bt->min_ratio};
+}
+
+void blocktri_get_pivots(const BlockTri* bt, int64_t k, int64_t* host_out) {
+    if (!bt->pivoted) { for (int64_t i = 0; i < bt->b; ++i) host_out[i] = i; return; }
+    std::vector<int> h((size_t)bt->b);
+    LSFC_HIP(hipMemcpy(h.data(), bt->perm.p + k * bt->b, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < bt->b; ++i) host_out[i] = h[(size_t)i];
 }
 
 int blocktri_precision(const BlockTri* bt) { return bt->prec; }

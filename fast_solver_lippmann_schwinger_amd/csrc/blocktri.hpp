@@ -10,23 +10,27 @@ struct BlockTri;       // K explicit inverses S_k^{-1} (b x b, column-major) and
 // rounded once from the fp64 block; the elimination itself is fp64 either way
 static constexpr int BLOCKTRI_INV_F64 = 0, BLOCKTRI_INV_F32 = 1;
 
+// pivoting inside the Schur blocks (LSFC_PRECOND_PIVOT_* of include/lsfc.h): none; partial row pivoting in every block;
+// without first and, if that breaks down, the whole factorisation again with partial pivoting
+static constexpr int BLOCKTRI_PIVOT_NONE = 0, BLOCKTRI_PIVOT_PARTIAL = 1, BLOCKTRI_PIVOT_AUTO = 2;
+
 struct BlockTriInfo {
     int64_t K, b, factor_bytes, launches, factor_us;
     int pivoting;
     double min_pivot_ratio;
 };
 
-// |pivot| / max|S_k| below which the pivot-free inversion of a Schur block is refused (include/lsfc.h)
+// |pivot| / max|S_k| below which the inversion of a Schur block is refused, with or without pivoting (include/lsfc.h)
 static constexpr double BLOCKTRI_PIVOT_MIN = 1e-8;
 
 // LSFC_ENOMEM unless K b^2 16 B (8 B at float storage) of factors plus the work space fit into the free memory of the
-// current device; `extra` = bytes the caller is about to allocate besides.  From the dimensions and the precision alone:
-// nothing is allocated or read.  blocktri_memory_need is the arithmetic of it.
+// current device; `extra` = bytes the caller is about to allocate besides.  From the dimensions, the precision and the
+// pivoting mode alone: nothing is allocated or read.  blocktri_memory_need is the arithmetic of it.
 struct BlockTriNeed { double inverse_bytes, work_bytes; };
-BlockTriNeed blocktri_memory_need(int64_t N, int64_t K, int prec);
-void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who, int prec);
+BlockTriNeed blocktri_memory_need(int64_t N, int64_t K, int prec, int pivoting = BLOCKTRI_PIVOT_NONE);
+void blocktri_require_memory(int64_t N, int64_t K, double extra, const char* who, int prec, int pivoting = BLOCKTRI_PIVOT_NONE);
 // Factorise: rowptr / col / msp are DEVICE arrays (CSR, 0-based, columns ascending, N rows).  Synchronous.
-BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp, int prec);
+BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* msp, int prec, int pivoting = BLOCKTRI_PIVOT_NONE);
 int blocktri_precision(const BlockTri*);
 void blocktri_destroy(BlockTri*);
 const int* blocktri_col32(const BlockTri*);          // the columns as 32-bit integers (device), nnz of them
@@ -40,6 +44,8 @@ int64_t blocktri_batch_reserve(BlockTri*, int R);
 void blocktri_enqueue_batch(const BlockTri*, int R, const cplx* w, cplx* x, hipStream_t st);
 BlockTriInfo blocktri_info(const BlockTri*);
 void blocktri_get_block(const BlockTri*, int64_t k, cplx* host_out);  // the stored block, widened to double at float storage
+// perm[i] = row of S_k that became pivot row i, b entries to the host (the identity on an object factorised without pivoting)
+void blocktri_get_pivots(const BlockTri*, int64_t k, int64_t* host_out);
 void warmup_blocktri();
 
 // precond.hip: pc applied to cnt >= 1 device vectors at arbitrary addresses, in place, stream-ordered on st.  A

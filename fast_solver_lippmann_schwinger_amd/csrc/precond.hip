@@ -803,10 +803,10 @@ namespace lsfc {
 
 // the object from DEVICE arrays of one shared pattern; the current device is `device`
 static lsfc_precond* create_blocktri_dev(int64_t N, int64_t K, const int64_t* rowptr, const int64_t* col, const cplx* As, const cplx* Msp, int device,
-                                         int prec) {
+                                         int prec, int pivoting) {
     std::unique_ptr<lsfc_precond> pc(new lsfc_precond());
     pc->device = device; pc->N = N;
-    pc->bt = blocktri_factor(N, K, rowptr, col, Msp, prec);
+    pc->bt = blocktri_factor(N, K, rowptr, col, Msp, prec, pivoting);
     const int64_t nnz = blocktri_nnz(pc->bt);
     pc->a_rowptr.alloc((size_t)N + 1); pc->a_col.alloc((size_t)nnz); pc->a_val.alloc((size_t)nnz);
     LSFC_HIP(hipMemcpy(pc->a_rowptr.p, rowptr, ((size_t)N + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
@@ -826,6 +826,23 @@ static void select_device(int device) {
     pruned_warmup(device);
 }
 
+// the options of the two _opts constructors, checked before any device call; NULL: fp64 storage, no pivoting
+struct BtOpts { int prec, pivoting; };
+static BtOpts checked_opts(const lsfc_blocktri_opts* o) {
+    if (!o) return BtOpts{LSFC_PRECOND_INV_F64, LSFC_PRECOND_PIVOT_NONE};
+    LSFC_REQUIRE(o->inverse_precision == LSFC_PRECOND_INV_F64 || o->inverse_precision == LSFC_PRECOND_INV_F32,
+                 "bad inverse_precision %d (LSFC_PRECOND_INV_F64 or _F32)", o->inverse_precision);
+    LSFC_REQUIRE(o->pivoting == LSFC_PRECOND_PIVOT_NONE || o->pivoting == LSFC_PRECOND_PIVOT_PARTIAL || o->pivoting == LSFC_PRECOND_PIVOT_AUTO,
+                 "bad pivoting %d (LSFC_PRECOND_PIVOT_NONE, _PARTIAL or _AUTO)", o->pivoting);
+    for (int i = 0; i < 6; ++i) LSFC_REQUIRE(o->reserved[i] == 0, "lsfc_blocktri_opts: reserved[%d] = %d must be zero", i, o->reserved[i]);
+    return BtOpts{o->inverse_precision, o->pivoting};
+}
+static lsfc_blocktri_opts opts_of_precision(int inverse_precision) {
+    lsfc_blocktri_opts o{};
+    o.inverse_precision = inverse_precision; o.pivoting = LSFC_PRECOND_PIVOT_NONE;
+    return o;
+}
+
 } // namespace lsfc
 
 extern "C" {
@@ -837,17 +854,23 @@ int lsfc_precond_create_blocktri(lsfc_precond** out, int64_t N, int64_t nblocks,
 
 int lsfc_precond_create_blocktri_prec(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
                                       const double* As_val, const double* Msp_val, int memspace, int device, int inverse_precision) {
-    const int prec = inverse_precision;
+    const lsfc_blocktri_opts o = opts_of_precision(inverse_precision);
+    return lsfc_precond_create_blocktri_opts(out, N, nblocks, rowptr, col, As_val, Msp_val, memspace, device, &o);
+}
+
+int lsfc_precond_create_blocktri_opts(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
+                                      const double* As_val, const double* Msp_val, int memspace, int device, const lsfc_blocktri_opts* opts) {
     return guarded([&] {
         LSFC_REQUIRE(out, "NULL argument"); *out = nullptr;
-        LSFC_REQUIRE(prec == LSFC_PRECOND_INV_F64 || prec == LSFC_PRECOND_INV_F32, "bad inverse_precision %d (LSFC_PRECOND_INV_F64 or _F32)", prec);
+        const BtOpts bo = checked_opts(opts);
+        const int prec = bo.prec, piv = bo.pivoting;
         LSFC_REQUIRE(rowptr && col && As_val && Msp_val, "NULL argument");
         LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "bad memspace %d", memspace);
         LSFC_REQUIRE(N >= 1 && N < ((int64_t)1 << 31), "preconditioner: N out of range");
         LSFC_REQUIRE(nblocks >= 1 && N % nblocks == 0, "block-tridiagonal preconditioner: N = %lld is not divisible by nblocks = %lld", (long long)N, (long long)nblocks);
         select_device(device);
-        blocktri_require_memory(N, nblocks, 0.0, "lsfc_precond_create_blocktri", prec);   // from the dimensions alone, before any array is read
-        if (memspace == LSFC_MEM_DEVICE) { *out = create_blocktri_dev(N, nblocks, rowptr, col, (const cplx*)As_val, (const cplx*)Msp_val, device, prec); return; }
+        blocktri_require_memory(N, nblocks, 0.0, "lsfc_precond_create_blocktri", prec, piv);   // from the dimensions and options alone, before any array is read
+        if (memspace == LSFC_MEM_DEVICE) { *out = create_blocktri_dev(N, nblocks, rowptr, col, (const cplx*)As_val, (const cplx*)Msp_val, device, prec, piv); return; }
         const int64_t nnz = rowptr[N];
         LSFC_REQUIRE(nnz >= 0, "block-tridiagonal preconditioner: rowptr[N] is negative");
         DevBuf<int64_t> drp, dcol; DevBuf<cplx> das, dmsp;
@@ -858,17 +881,22 @@ int lsfc_precond_create_blocktri_prec(lsfc_precond** out, int64_t N, int64_t nbl
             LSFC_HIP(hipMemcpy(das.p, As_val, (size_t)nnz * sizeof(cplx), hipMemcpyHostToDevice));
             LSFC_HIP(hipMemcpy(dmsp.p, Msp_val, (size_t)nnz * sizeof(cplx), hipMemcpyHostToDevice));
         }
-        *out = create_blocktri_dev(N, nblocks, drp.p, dcol.p, das.p, dmsp.p, device, prec);
+        *out = create_blocktri_dev(N, nblocks, drp.p, dcol.p, das.p, dmsp.p, device, prec, piv);
     });
 }
 
 int lsfc_precond_create_from_plan(lsfc_precond** out, lsfc_plan* plan) { return lsfc_precond_create_from_plan_prec(out, plan, LSFC_PRECOND_INV_F64); }
 
 int lsfc_precond_create_from_plan_prec(lsfc_precond** out, lsfc_plan* plan, int inverse_precision) {
-    const int prec = inverse_precision;
+    const lsfc_blocktri_opts o = opts_of_precision(inverse_precision);
+    return lsfc_precond_create_from_plan_opts(out, plan, &o);
+}
+
+int lsfc_precond_create_from_plan_opts(lsfc_precond** out, lsfc_plan* plan, const lsfc_blocktri_opts* opts) {
     return guarded([&] {
         LSFC_REQUIRE(out, "NULL argument"); *out = nullptr;
-        LSFC_REQUIRE(prec == LSFC_PRECOND_INV_F64 || prec == LSFC_PRECOND_INV_F32, "bad inverse_precision %d (LSFC_PRECOND_INV_F64 or _F32)", prec);
+        const BtOpts bo = checked_opts(opts);
+        const int prec = bo.prec, piv = bo.pivoting;
         LSFC_REQUIRE(plan, "NULL plan");
         LSFC_REQUIRE(!plan->dist && !plan->multi, "block-tridiagonal preconditioner: not available on a distributed or multi-device plan");
         const int64_t n = plan->dims[0], m = plan->dims[1], l = plan->ndim == 2 ? 1 : plan->dims[2];
@@ -876,11 +904,11 @@ int lsfc_precond_create_from_plan_prec(lsfc_precond** out, lsfc_plan* plan, int 
         int64_t nnz = 0;
         if (int rc = lsfc_sparsify_pattern(n, m, l, &nnz, nullptr, nullptr, nullptr)) fail(rc, "%s", lsfc_last_error());
         select_device(plan->device);
-        blocktri_require_memory(N, K, (double)nnz * 40.0, "lsfc_precond_create_from_plan", prec);
+        blocktri_require_memory(N, K, (double)nnz * 40.0, "lsfc_precond_create_from_plan", prec, piv);
         DevBuf<int64_t> drp, dcol; DevBuf<cplx> das, dmsp;
         drp.alloc((size_t)N + 1); dcol.alloc((size_t)nnz); das.alloc((size_t)nnz); dmsp.alloc((size_t)nnz);
         if (int rc = lsfc_sparsify_build(plan, drp.p, dcol.p, (double*)das.p, nullptr, (double*)dmsp.p, nullptr, LSFC_MEM_DEVICE)) fail(rc, "%s", lsfc_last_error());
-        *out = create_blocktri_dev(N, K, drp.p, dcol.p, das.p, dmsp.p, plan->device, prec);
+        *out = create_blocktri_dev(N, K, drp.p, dcol.p, das.p, dmsp.p, plan->device, prec, piv);
     });
 }
 
@@ -911,6 +939,18 @@ int lsfc_precond_blocktri_get_block(const lsfc_precond* pc, int64_t k, double* o
         LSFC_REQUIRE(capacity_complex >= i.b * i.b, "capacity %lld is less than the %lld entries of a block", (long long)capacity_complex, (long long)(i.b * i.b));
         LSFC_HIP(hipSetDevice(pc->device));
         blocktri_get_block(pc->bt, k, (cplx*)out);
+    });
+}
+
+int lsfc_precond_blocktri_get_pivots(const lsfc_precond* pc, int64_t k, int64_t* perm, int64_t capacity) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && perm, "NULL argument");
+        LSFC_REQUIRE(pc->bt, "not a block-tridiagonal preconditioner (made by lsfc_precond_create)");
+        const BlockTriInfo i = blocktri_info(pc->bt);
+        LSFC_REQUIRE(k >= 0 && k < i.K, "block %lld out of range (have %lld)", (long long)k, (long long)i.K);
+        LSFC_REQUIRE(capacity >= i.b, "capacity %lld is less than the %lld rows of a block", (long long)capacity, (long long)i.b);
+        LSFC_HIP(hipSetDevice(pc->device));
+        blocktri_get_pivots(pc->bt, k, perm);
     });
 }
 

@@ -14,7 +14,9 @@ blocks replaces the sparse LU.  `SparsifyingPreconditioner(Msp, As, factor="bloc
 matrices; `SparsifyingPreconditioner.from_operator(M)` assembles and factorises from the plan of a FastM / FastM3D
 without the matrices ever leaving the device (examples/example3D.jl:57-68 in one call).  ``inverse_dtype="complex64"``
 keeps the dense inverses as float pairs (half the memory and half the bytes per apply): the factorisation is the fp64
-one, each inverse is rounded once when it is stored, and the applies widen on load and sum in fp64."""
+one, each inverse is rounded once when it is stored, and the applies widen on load and sum in fp64.  ``pivoting="partial"``
+inverts every Schur block with partial row pivoting (``"auto"``: only after the pivot-free factorisation broke down); the
+stored blocks are the inverses themselves either way, so the applies do not change."""
 from __future__ import annotations
 
 import ctypes as C
@@ -41,6 +43,16 @@ def _inverse_precision(inverse_dtype):
     return INVERSE_DTYPES[inverse_dtype]
 
 
+# pivoting -> LSFC_PRECOND_PIVOT_*
+PIVOTING = {"none": L.LSFC_PRECOND_PIVOT_NONE, "partial": L.LSFC_PRECOND_PIVOT_PARTIAL, "auto": L.LSFC_PRECOND_PIVOT_AUTO}
+
+
+def _pivoting(pivoting):
+    if not isinstance(pivoting, str) or pivoting not in PIVOTING:
+        raise ValueError(f"pivoting must be 'none', 'partial' or 'auto', not {pivoting!r}")
+    return PIVOTING[pivoting]
+
+
 def _csr_arrays(A):
     A = A.tocsr()
     A.sort_indices()
@@ -55,9 +67,12 @@ class SparsifyingPreconditioner:
     "blocktri" -- block-tridiagonal factorisation on the device with ``nblocks`` blocks (the slowest grid axis: m in 2D,
     l in 3D); Msp and As must share one pattern, as the pair of `sparsifying_pair` does.
     ``inverse_dtype`` (factor="blocktri" only): "complex128" (default) or "complex64", the storage of the dense inverses
-    S_k^{-1}; the factorisation and the sums of the apply are fp64 either way."""
+    S_k^{-1}; the factorisation and the sums of the apply are fp64 either way.
+    ``pivoting`` (factor="blocktri" only): "none" (default), "partial" -- partial row pivoting inside every Schur block --
+    or "auto" -- without pivoting first and, after a breakdown, the whole factorisation again with "partial"."""
 
-    def __init__(self, Msp, As, solverType="UMFPACK", device=0, lu=None, factor="host", nblocks=None, inverse_dtype="complex128"):
+    def __init__(self, Msp, As, solverType="UMFPACK", device=0, lu=None, factor="host", nblocks=None, inverse_dtype="complex128",
+                 pivoting="none"):
         import scipy.sparse as sp
         import scipy.sparse.linalg as spla
         if solverType not in ("UMFPACK", "MKLPARDISO"):
@@ -67,6 +82,9 @@ class SparsifyingPreconditioner:
         precision = _inverse_precision(inverse_dtype)
         if factor == "host" and precision != L.LSFC_PRECOND_INV_F64:
             raise ValueError("inverse_dtype='complex64' needs factor='blocktri': the host LU keeps no dense inverses")
+        pivot = _pivoting(pivoting)
+        if factor == "host" and pivot != L.LSFC_PRECOND_PIVOT_NONE:
+            raise ValueError(f"pivoting={pivoting!r} needs factor='blocktri': the host LU pivots on its own")
         Msp = sp.csc_matrix(Msp, dtype=np.complex128)
         As = sp.csr_matrix(As, dtype=np.complex128)
         N = Msp.shape[0]
@@ -85,8 +103,9 @@ class SparsifyingPreconditioner:
                 raise ValueError("factor='blocktri': Msp and As must share one sparsity pattern (every stencil entry stored)")
             pc = C.c_void_p()
             p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-            L.check(L.load().lsfc_precond_create_blocktri_prec(C.byref(pc), N, int(nblocks), p(m_ptr), p(m_col), p(a_val), p(m_val),
-                                                               L.LSFC_MEM_HOST, int(device), precision))
+            opts = L.BlocktriOpts(inverse_precision=precision, pivoting=pivot)
+            L.check(L.load().lsfc_precond_create_blocktri_opts(C.byref(pc), N, int(nblocks), p(m_ptr), p(m_col), p(a_val), p(m_val),
+                                                               L.LSFC_MEM_HOST, int(device), C.byref(opts)))
             self._pc = pc
             return
         if lu is None:
@@ -108,15 +127,15 @@ class SparsifyingPreconditioner:
         self._pc = pc
 
     @classmethod
-    def from_operator(cls, M, inverse_dtype="complex128"):
+    def from_operator(cls, M, inverse_dtype="complex128", pivoting="none"):
         """The preconditioner of a FastM / FastM3D in one device call (lsfc_precond_create_from_plan): As and
         Msp = As + k^2 AG diag(nu) are assembled into device memory from the plan's kernel, nu and k, and factorised
         there with the slowest axis as block index.  ``Msp`` / ``As`` of the object are None: nothing is downloaded.
-        ``inverse_dtype``: storage of the dense inverses, as in the constructor."""
-        precision = _inverse_precision(inverse_dtype)
+        ``inverse_dtype``: storage of the dense inverses, ``pivoting``: "none", "partial" or "auto", as in the constructor."""
+        opts = L.BlocktriOpts(inverse_precision=_inverse_precision(inverse_dtype), pivoting=_pivoting(pivoting))
         self = cls.__new__(cls)
         pc = C.c_void_p()
-        L.check(L.load().lsfc_precond_create_from_plan_prec(C.byref(pc), M._plan, precision))
+        L.check(L.load().lsfc_precond_create_from_plan_opts(C.byref(pc), M._plan, C.byref(opts)))
         self._pc = pc
         self.Msp = self.As = None
         self.solverType, self.factor = "UMFPACK", "blocktri"
@@ -149,6 +168,14 @@ class SparsifyingPreconditioner:
         out = np.empty(b * b, dtype=np.complex128)
         L.check(L.load().lsfc_precond_blocktri_get_block(self._pc, int(k), out.ctypes.data_as(C.c_void_p), b * b))
         return out.reshape((b, b), order="F")
+
+    def blocktri_pivots(self, k):
+        """perm of block k of a block-tridiagonal object (lsfc_precond_blocktri_get_pivots): perm[i] = row of S_k that became
+        pivot row i; the identity on an object factorised without pivoting"""
+        b = self.blocktri_info()["block_size"]
+        out = np.empty(b, dtype=np.int64)
+        L.check(L.load().lsfc_precond_blocktri_get_pivots(self._pc, int(k), out.ctypes.data_as(C.c_void_p), b))
+        return out
 
     # -- ldiv!(P, b) / P \\ b -- src/preconditioner.jl:132-170 ---------------------------------------------------------
     def ldiv_(self, v):

@@ -286,8 +286,34 @@ int lsfc_precond_create_blocktri_prec(lsfc_precond** out, int64_t N, int64_t nbl
 int lsfc_precond_create_from_plan_prec(lsfc_precond** out, lsfc_plan* plan, int inverse_precision);
 /* precision: LSFC_PRECOND_INV_F64 or _F32, as the object was made.  LSFC_EINVAL on an object of lsfc_precond_create. */
 int lsfc_precond_inverse_precision(const lsfc_precond* pc, int* precision);
+/* The same two constructors with options.  opts == NULL is the LSFC_PRECOND_INV_F64 / LSFC_PRECOND_PIVOT_NONE case, and the
+ * four constructors above are calls of these two.  pivoting:
+ *     LSFC_PRECOND_PIVOT_NONE     the inversion without pivoting described above (the default)
+ *     LSFC_PRECOND_PIVOT_PARTIAL  partial ROW pivoting inside every Schur block (never across blocks): at elimination step p
+ *                                 the pivot is the row among p .. b-1 with the largest x*x + y*y (fp64) in column p, the
+ *                                 lowest such row on a tie.  Gauss-Jordan with interchanges inverts Pi_k S_k; the columns
+ *                                 are put back once, so the stored block is S_k^{-1} itself and the applies, the float
+ *                                 storage and the memory of the inverses are as without pivoting.  Work space during the
+ *                                 factorisation: one more panel (b * 32 * 16 bytes); the pivots are kept (nblocks * b * 4 bytes).
+ *     LSFC_PRECOND_PIVOT_AUTO     without pivoting first; after a breakdown the whole factorisation again with _PARTIAL:
+ *                                 the object is bit for bit the _NONE object or the _PARTIAL object of the same input
+ * The monitor is the same: min_pivot_ratio is the smallest chosen |pivot| / max|S_k|; a chosen pivot below 1e-8 (or not a
+ * number) under _PARTIAL means the block is singular to working precision: LSFC_EINVAL with block and row, no object.
+ * LSFC_ENOMEM as above, from N, nblocks and the options alone (_AUTO counts as _PARTIAL).
+ * LSFC_EINVAL (before any device call): unknown inverse_precision or pivoting, a reserved word that is not zero. */
+#define LSFC_PRECOND_PIVOT_NONE 0
+#define LSFC_PRECOND_PIVOT_PARTIAL 1
+#define LSFC_PRECOND_PIVOT_AUTO 2
+typedef struct lsfc_blocktri_opts { int inverse_precision; int pivoting; int reserved[6]; } lsfc_blocktri_opts; /* reserved: zero */
+int lsfc_precond_create_blocktri_opts(lsfc_precond** out, int64_t N, int64_t nblocks, const int64_t* rowptr, const int64_t* col,
+                                      const double* As_val, const double* Msp_val, int memspace, int device, const lsfc_blocktri_opts* opts);
+int lsfc_precond_create_from_plan_opts(lsfc_precond** out, lsfc_plan* plan, const lsfc_blocktri_opts* opts);
+/* perm[i] = row of S_k that became pivot row i (identity on an object factorised without pivoting); b entries.
+ * LSFC_EINVAL: object made by lsfc_precond_create, k out of range, capacity < b. */
+int lsfc_precond_blocktri_get_pivots(const lsfc_precond* pc, int64_t k, int64_t* perm, int64_t capacity);
 /* out: blocks, block size b, bytes of the stored inverses (nblocks b^2 16, or 8 at float storage), kernel launches per apply, factorisation time in
- * microseconds, 1 if pivoting was used (always 0); min_pivot_ratio (may be NULL): smallest |pivot| / max|S_k| met.
+ * microseconds, 1 if the stored blocks come from the pivoted elimination (LSFC_PRECOND_PIVOT_PARTIAL, or _AUTO after it fell
+ * back), else 0; min_pivot_ratio (may be NULL): smallest |pivot| / max|S_k| met.
  * LSFC_EINVAL on an object made by lsfc_precond_create. */
 int lsfc_precond_blocktri_info(const lsfc_precond* pc, int64_t out[6], double* min_pivot_ratio);
 /* Debug / test access in the spirit of lsfc_plan_get_symbol: S_k^{-1} (b x b, column-major) to the host, as stored

@@ -206,22 +206,30 @@ function _inverse_precision(T)
     T === Complex{Float32} && return Cint(1)
     throw(ArgumentError("inverse_type must be Complex{Float64} or Complex{Float32}"))
 end
+# pivoting: :none (default, LSFC_PRECOND_PIVOT_NONE), :partial (partial row pivoting inside every Schur block) or :auto (without
+# pivoting first; after a breakdown the whole factorisation again with :partial).  The options travel as lsfc_blocktri_opts:
+# eight Cints (inverse_precision, pivoting, six reserved zeros).
+function _blocktri_opts(inverse_type, pivoting)
+    piv = pivoting === :none ? Cint(0) : pivoting === :partial ? Cint(1) : pivoting === :auto ? Cint(2) :
+          throw(ArgumentError("pivoting must be :none, :partial or :auto"))
+    return Cint[_inverse_precision(inverse_type), piv, 0, 0, 0, 0, 0, 0]
+end
 function SparsifyingPreconditionerHIP(Msp::SparseMatrixCSC{Complex{Float64},Int64}, As::SparseMatrixCSC{Complex{Float64},Int64}, nblocks::Integer;
-                                      device=0, inverse_type=Complex{Float64})
-    prec = _inverse_precision(inverse_type)
+                                      device=0, inverse_type=Complex{Float64}, pivoting=:none)
+    opts = _blocktri_opts(inverse_type, pivoting)
     N = size(Msp, 1)
     (mp, mc, mv) = _csr(Msp); (ap, ac, av) = _csr(As)
     (mp == ap && mc == ac) || throw(DimensionMismatch("Msp and As must share one sparsity pattern"))
     pc = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:lsfc_precond_create_blocktri_prec, liblsfc), Cint,
-                (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Cint, Cint, Cint),
-                pc, N, nblocks, mp, mc, av, mv, 0, device, prec))
+    check(ccall((:lsfc_precond_create_blocktri_opts, liblsfc), Cint,
+                (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Cint, Cint, Ptr{Cint}),
+                pc, N, nblocks, mp, mc, av, mv, 0, device, opts))
     return _wrap_precond(pc[], N)
 end
-function SparsifyingPreconditionerHIP(M::FastMHIP; inverse_type=Complex{Float64})
-    prec = _inverse_precision(inverse_type)
+function SparsifyingPreconditionerHIP(M::FastMHIP; inverse_type=Complex{Float64}, pivoting=:none)
+    opts = _blocktri_opts(inverse_type, pivoting)
     pc = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:lsfc_precond_create_from_plan_prec, liblsfc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Cint), pc, M.plan, prec))
+    check(ccall((:lsfc_precond_create_from_plan_opts, liblsfc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cint}), pc, M.plan, opts))
     return _wrap_precond(pc[], size(M, 1))
 end
 # Complex{Float64} or Complex{Float32}: how the object stores its inverses (lsfc_precond_inverse_precision)
@@ -241,6 +249,12 @@ function blocktri_block(P::SparsifyingPreconditionerHIP, k::Integer)
     b = blocktri_info(P)[1][2]; S = Matrix{Complex{Float64}}(undef, b, b)
     check(ccall((:lsfc_precond_blocktri_get_block, liblsfc), Cint, (Ptr{Cvoid}, Int64, Ptr{Complex{Float64}}, Int64), P.pc, k, S, b * b))
     return S
+end
+# perm of block k (k 0-based, entries 0-based): perm[i + 1] = row of S_k that became pivot row i; the identity without pivoting
+function blocktri_pivots(P::SparsifyingPreconditionerHIP, k::Integer)
+    b = blocktri_info(P)[1][2]; perm = Vector{Int64}(undef, b)
+    check(ccall((:lsfc_precond_blocktri_get_pivots, liblsfc), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64), P.pc, k, perm, b))
+    return perm
 end
 # ldiv!(P, b): host vector in, host vector out (staged over PCIe); inside gmres_hip! the device path is used instead
 function LinearAlgebra.ldiv!(P::SparsifyingPreconditionerHIP, b::Vector{Complex{Float64}})

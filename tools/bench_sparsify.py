@@ -26,7 +26,13 @@ gmres_batch_ of R incident directions against R back-to-back gmres_ calls with t
 in one process; the byte model is 2 K b^2 times the bytes of a stored entry, and every row also has the factorisation
 time of its object and the spread (min, max) of the timed single applies.
 
-    python tools/bench_sparsify.py --inverse-dtype complex128,complex64 --nrhs 1,8 --out profiles/precond_f32.jsonl"""
+    python tools/bench_sparsify.py --inverse-dtype complex128,complex64 --nrhs 1,8 --out profiles/precond_f32.jsonl
+
+--pivoting none,partial: the factorisation (from_operator, fp64 storage) once per pivoting mode in one process: after a
+warm-up object per mode, --reps objects each; median, minimum and maximum of the factorisation time the library reports
+(factor_us: pattern, Schur updates and inversions, no assembly) and of the apply time of the last object.
+
+    python tools/bench_sparsify.py --pivoting none,partial --out profiles/precond_pivot.jsonl"""
 import argparse
 import json
 import os
@@ -190,6 +196,37 @@ def factor_mode(args):
         torch.cuda.empty_cache()
 
 
+def pivoting_mode(args):
+    import torch
+    import fast_solver_lippmann_schwinger_amd as pkg
+    modes = args.pivoting.split(",")
+    for spec in args.cases.split(","):
+        ndim, n = (int(v) for v in spec.split(":"))
+        N = n ** ndim
+        M = operator(ndim, n)
+        pkg.sparsify_arrays(M, ("As",))                    # warm: the plan's spatial kernel
+        for mode in modes:                                 # warm-up: one object per mode
+            pkg.SparsifyingPreconditioner.from_operator(M, pivoting=mode).close()
+        for mode in modes:
+            factor_s, P = [], None
+            for _ in range(args.reps):
+                if P is not None:
+                    P.close()
+                P = pkg.SparsifyingPreconditioner.from_operator(M, pivoting=mode)
+                factor_s.append(P.stats()["factor_us"] / 1e6)
+            st = P.stats()
+            applies = [apply_ms(P, N) for _ in range(args.reps)]
+            emit(args.out, {"case": f"{ndim}D n={n}", "N": N, "blocks": st["blocks"], "block_size": st["block_size"], "pivoting": mode,
+                            "pivoted": st["pivoting"], "reps": args.reps, "factor_s_median": round(float(np.median(factor_s)), 4),
+                            "factor_s_min_max": [round(min(factor_s), 4), round(max(factor_s), 4)],
+                            "apply_ms_median": round(float(np.median(applies)), 4),
+                            "apply_ms_min_max": [round(min(applies), 4), round(max(applies), 4)],
+                            "min_pivot_ratio": round(st["min_pivot_ratio"], 4)})
+            P.close()
+        del M
+        torch.cuda.empty_cache()
+
+
 def timed_ms(fn, reps):
     import torch
     fn()                                                   # warm-up (captures the graph, allocates work buffers)
@@ -289,7 +326,12 @@ def main():
     ap.add_argument("--inverse-dtype", default="complex128", help="with --nrhs: storages of the inverses to time in one process, "
                     "complex128 and / or complex64, comma separated")
     ap.add_argument("--gmres", action="store_true", help="with --nrhs: also a preconditioned gmres_batch_ against back-to-back gmres_")
+    ap.add_argument("--pivoting", default="", help="pivoting modes to time in one process, e.g. none,partial (see the module docstring)")
     args = ap.parse_args()
+    if args.pivoting:
+        if args.cases == ap.get_default("cases"):
+            args.cases = "2:513,3:24,3:48"
+        return pivoting_mode(args)
     if args.nrhs:
         if args.cases == ap.get_default("cases"):
             args.cases = "2:513,3:24,3:48,3:64"
