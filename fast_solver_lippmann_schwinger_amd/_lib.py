@@ -16,7 +16,7 @@ LSFC_PRECOND_INV_F64, LSFC_PRECOND_INV_F32 = 0, 1
 LSFC_PRECOND_PIVOT_NONE, LSFC_PRECOND_PIVOT_PARTIAL, LSFC_PRECOND_PIVOT_AUTO = 0, 1, 2
 LSFC_FLAG_DEFAULT, LSFC_FLAG_LITERAL_PAD, LSFC_FLAG_FORCE_ROCFFT, LSFC_FLAG_PATCH_SINGULAR = 0, 1, 2, 4
 LSFC_ORTH_MGS, LSFC_ORTH_CGS, LSFC_ORTH_DGKS = 0, 1, 2
-LSFC_ENODEV, LSFC_ENOTCONV = -2, -5
+LSFC_EINVAL, LSFC_ENODEV, LSFC_ENOMEM, LSFC_ENOTCONV = -1, -2, -3, -5
 LSFC_UNIQUE_ID_BYTES = 128
 
 PRECOND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
@@ -30,6 +30,12 @@ class GmresOpts(C.Structure):
 
 class GmresResult(C.Structure):
     _fields_ = [("iters", C.c_int64), ("mvps", C.c_int64), ("converged", C.c_int), ("final_resnorm", C.c_double)]
+
+
+class BicgstablOpts(C.Structure):                  # lsfc_bicgstabl_opts
+    _fields_ = [("l", C.c_int), ("max_mv_products", C.c_int64), ("reltol", C.c_double), ("abstol", C.c_double),
+                ("initially_zero", C.c_int), ("precond", PRECOND_FN), ("precond_user", C.c_void_p),
+                ("precond_on_device", C.c_int), ("r_shadow", C.c_void_p), ("reserved", C.c_int * 4)]
 
 
 class BlocktriOpts(C.Structure):                   # lsfc_blocktri_opts
@@ -63,6 +69,7 @@ SIGNATURES = {
     "lsfc_sample_sources": (_I, [_P, _P, _L, _P, _I]),
     "lsfc_gmres": (_I, [_P, _P, _P, C.POINTER(GmresOpts), _P, _L, C.POINTER(GmresResult), _I]),
     "lsfc_gmres_batch": (_I, [_P, _P, _P, _L, C.POINTER(GmresOpts), _P, _L, C.POINTER(GmresResult), _I]),
+    "lsfc_bicgstabl": (_I, [_P, _P, _P, C.POINTER(BicgstablOpts), _P, _L, C.POINTER(GmresResult), _I]),
     "lsfc_precond_create": (_I, [_PP, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_precond_destroy": (_I, [_P]),
     "lsfc_precond_set_stream": (_I, [_P, _P]),

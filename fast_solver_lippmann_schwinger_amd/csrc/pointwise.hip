@@ -4,6 +4,7 @@
 // reductions with a fixed-order second stage (bitwise reproducible, no float atomics).
 #include "common.hpp"
 #include "pointwise.hpp"
+#include "reduce.hpp"
 #include <algorithm>
 #include <vector>
 
@@ -235,35 +236,7 @@ void pw_gather_sources(const cplx* K, cplx* out, const int64_t* src, int nsrc, c
 }
 
 // ---- GMRES BLAS-1 ------------------------------------------------------------
-// Reductions: each block accumulates a grid-stride slice, reduces across its four
-// waves (shuffle, then LDS), and writes one partial; a single-wave finisher sums
-// the partials in index order.  RED_BLOCKS is fixed so results do not depend on N
-// beyond the slice boundaries -> run-to-run bitwise reproducible.
-
-static constexpr int RED_BLOCKS = 1024;
-static constexpr int RED_THREADS = 256;
-// blocks actually launched for a vector of n entries: at least ~4 entries per thread (a 48^3 grid gets 108 blocks, not 1024
-// blocks of mostly idle threads); a function of n only, so results stay run-to-run reproducible
-static inline int red_blocks(int64_t n) {
-    const int64_t b = (n + (int64_t)RED_THREADS * 4 - 1) / ((int64_t)RED_THREADS * 4);
-    return (int)(b < 1 ? 1 : (b > RED_BLOCKS ? RED_BLOCKS : b));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ cplx block_sum(cplx acc, cplx* sh) {
-    acc.x = wave_sum(acc.x); acc.y = wave_sum(acc.y);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    cplx r = make_double2(0.0, 0.0);
-    if (threadIdx.x == 0) { for (int w = 0; w < RED_THREADS / 64; ++w) { r.x += sh[w].x; r.y += sh[w].y; } }
-    return r;   // valid in thread 0
-}
+// Reductions: the two-stage fixed-order tree of reduce.hpp (RED_BLOCKS, block_sum, finish_in_wave).
 
 // partial[b] = sum_i conj(a[i]) * b[i]   (Julia dot(a, b))
 __global__ __launch_bounds__(RED_THREADS) void k_dot_partial(const cplx* __restrict__ a, const cplx* __restrict__ b, cplx* __restrict__ partial, int64_t n) {
@@ -381,14 +354,6 @@ __global__ void k_scale_inv_dev(cplx* __restrict__ a, const cplx* __restrict__ s
 // of the CONSUMING kernel sums the producer's block partials itself (<= 1024 values from L2, in exactly the order
 // k_finish uses, so every block -- and the host -- sees bit-identical scalars), and block 0 publishes the scalar for the
 // host.  A modified Gram-Schmidt sweep over k vectors is then k + 2 launches instead of 2k + 4, a classical one 3.
-__device__ __forceinline__ cplx finish_in_wave(const cplx* __restrict__ partial, int count) {      // all 64 lanes of one wave
-    cplx acc = make_double2(0.0, 0.0);
-    const int lane = threadIdx.x & 63;
-    for (int i = lane; i < count; i += 64) { acc.x += partial[i].x; acc.y += partial[i].y; }
-    acc.x = wave_sum(acc.x); acc.y = wave_sum(acc.y);
-    return make_double2(__shfl(acc.x, 0, 64), __shfl(acc.y, 0, 64));
-}
-
 // w -= h * v with h = sum(hpartial[0..nb)); then partial[b] = sum conj(vnext) * w (or |w|^2 when vnext == NULL); block 0: *hout = h
 __global__ __launch_bounds__(RED_THREADS) void k_axpy_dot_fused(cplx* __restrict__ w, const cplx* __restrict__ v, const cplx* __restrict__ hpartial, int nb,
                                                                  cplx* __restrict__ hout, const cplx* __restrict__ vnext, cplx* __restrict__ partial, int64_t n) {

@@ -12,6 +12,7 @@ Names, argument meaning and error behaviour follow the Julia reference
   referenceValsTrapRule               src/FastConvolution.jl:407-415
   sampleGConv / sampleG3D             src/FastConvolution.jl:278-306, src/FastConvolution3D.jl:136-160
   gmres_ (= gmres!)                   IterativeSolvers.jl, call sites examples/example.jl:85,91
+  bicgstabl_ (= bicgstabl!)           IterativeSolvers.jl (the short-recurrence alternative; same Pl hook)
 
 Vectors are flat complex128 arrays in column-major (x fastest) order: numpy
 arrays (host memory, copied through PCIe inside the call) or torch CUDA tensors
@@ -410,6 +411,93 @@ def gmres_(x, A, b, Pl=None, abstol=0.0, reltol=None, restart=None, maxiter=None
         L.check(rc)
     if log:
         return x, ConvergenceHistory(resnorm[:min(res.iters, cap)].copy(), int(res.iters), int(res.mvps), bool(res.converged))
+    return x
+
+
+def _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err):
+    """fill precond / precond_user / precond_on_device of a solver's option struct (gmres_ documents the three routes);
+    returns what must stay alive for the duration of the call"""
+    native_pc = getattr(Pl, "_pc", None) if Pl is not None else None
+    if native_pc is not None:
+        if sx == L.LSFC_MEM_DEVICE:
+            import torch
+            Pl.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        else:
+            L.check(L.load().lsfc_plan_set_stream(A._plan, None))
+            Pl.set_stream(0)
+        opts.precond = C.cast(L.load().lsfc_precond_callback, L.PRECOND_FN)
+        opts.precond_user = native_pc
+        opts.precond_on_device = 1
+        return None
+    if Pl is None:
+        return None
+
+    def _cb(user, v, n):
+        try:
+            if Pl_on_device:
+                Pl(_device_view(C.cast(v, C.c_void_p).value, n))
+                return 0
+            Pl(np.ctypeslib.as_array(C.cast(v, C.POINTER(C.c_double)), shape=(2 * n,)).view(np.complex128))
+            return 0
+        except Exception as e:      # never let a Python exception cross the C boundary
+            err.append(e)
+            return 1
+    cb = L.PRECOND_FN(_cb)
+    opts.precond = cb
+    opts.precond_on_device = 1 if Pl_on_device else 0
+    return cb
+
+
+def bicgstabl_(x, A, b, l=2, Pl=None, max_mv_products=None, abstol=0.0, reltol=None, log=False, Pl_on_device=False,
+               r_shadow=None, initially_zero=False):
+    """bicgstabl!(x, A, b, l; Pl, max_mv_products, abstol, reltol, log): left-preconditioned BiCGStab(l) on the device
+    (lsfc_bicgstabl).  2 l + 3 work vectors whatever the iteration count, where gmres_ keeps restart + 2.
+
+    ``Pl`` as in ``gmres_``: a callable on a host numpy vector, on a torch CUDA tensor (``Pl_on_device=True``), or a
+    ``SparsifyingPreconditioner`` (applied by the library on the device, no host code inside the BiCG part).
+    Defaults: l = 2 (1..8), reltol sqrt(eps), abstol 0, max_mv_products N.  The history has one residual norm per cycle
+    (``iters`` counts cycles of l BiCG steps and one minimal-residual step, 2 l operator applications).
+    Departure from IterativeSolvers: the shadow residual is the preconditioned initial residual, not ``rand`` -- or
+    ``r_shadow`` (N complex, in the memory space of x), so that a solve is reproducible bit for bit.
+    A breakdown (rho, sigma or gamma zero where it divides, or not finite) ends the solve with x the last finite iterate;
+    the history then reports ``isconverged == False`` unless that iterate is within the tolerance already.  x is
+    updated in place."""
+    N = A.N
+    px, sx, keepx = _vec(x, N, "x", plan=A._plan)
+    pb, sb, keepb = _vec(b, N, "b")
+    if sx != sb:
+        raise TypeError("x and b must live in the same memory space")
+    if not _is_torch(x) and keepx is not x:
+        raise TypeError("x must be a contiguous complex128 array (it is updated in place)")
+    opts = L.BicgstablOpts()
+    opts.l = int(l)
+    opts.max_mv_products = int(max_mv_products) if max_mv_products is not None else 0
+    opts.reltol = float(reltol) if reltol is not None else -1.0
+    opts.abstol = float(abstol)
+    opts.initially_zero = 1 if initially_zero else 0
+    keeps = None
+    if r_shadow is not None:
+        ps, ss, keeps = _vec(r_shadow, N, "r_shadow")
+        if ss != sx:
+            raise TypeError("r_shadow and x must live in the same memory space")
+        opts.r_shadow = ps
+    err = []
+    cb = _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err)
+    # one history entry per cycle of 2 l operator applications (capped like gmres_)
+    cap = (opts.max_mv_products if opts.max_mv_products > 0 else N) // (2 * max(opts.l, 1)) + 2
+    cap = max(1, min(cap, 1 << 20))
+    res = L.GmresResult()
+    resnorm = np.zeros(cap, dtype=np.float64)
+    rc = L.load().lsfc_bicgstabl(A._plan, px, pb, C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, C.byref(res), sx)
+    del cb, keeps, keepb
+    if err:
+        raise err[0]
+    if rc not in (0, L.LSFC_ENOTCONV):
+        L.check(rc)
+    if log:
+        hist = ConvergenceHistory(resnorm[:min(res.iters, cap)].copy(), int(res.iters), int(res.mvps), bool(res.converged))
+        hist.message = L.load().lsfc_last_error().decode(errors="replace") if rc == L.LSFC_ENOTCONV else ""
+        return x, hist
     return x
 
 

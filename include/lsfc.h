@@ -39,7 +39,7 @@ typedef struct lsfc_plan lsfc_plan;
 #define LSFC_ENODEV   -2   /* no HIP device */
 #define LSFC_ENOMEM   -3
 #define LSFC_EHIP     -4   /* HIP / rocFFT / RCCL runtime failure */
-#define LSFC_ENOTCONV -5   /* GMRES hit maxiter without converging (x still updated, like gmres!) */
+#define LSFC_ENOTCONV -5   /* GMRES hit maxiter without converging (x still updated, like gmres!); BiCGStab(l): cap or breakdown */
 
 /* quadRule (src/FastConvolution.jl:20, src/FastConvolution3D.jl:21) */
 #define LSFC_QUAD_TRAPEZOIDAL     0   /* "trapezoidal"    */
@@ -196,6 +196,44 @@ int lsfc_gmres(lsfc_plan* plan, double* x, const double* b, const lsfc_gmres_opt
  * against the free memory up front: LSFC_ENOMEM with the figures; released on return). */
 int lsfc_gmres_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_gmres_opts* opts,
                      double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int memspace);
+
+/* ---- BiCGStab(l) ------------------------------------------------------------ */
+
+/* Replaces IterativeSolvers.bicgstabl!(x, A, b, l; Pl, max_mv_products, abstol, reltol, log=true): the short-recurrence
+ * alternative to lsfc_gmres for grids whose Krylov basis does not fit.  Left-preconditioned (it solves Pl^-1 A x = Pl^-1 b;
+ * the residuals below are preconditioned residuals).  One cycle = l BiCG steps (2 operator applications each) and one
+ * minimal-residual step over the l + 1 residual vectors; result->iters counts cycles, resnorm has one entry per cycle
+ * (||rs[0]|| after the cycle, computed from the vector), result->mvps counts operator applications (1 for the initial
+ * residual, 0 with initially_zero, 2 l per cycle).  The cycle loop runs while the residual is above
+ * max(reltol * ||Pl^-1 r0||, abstol) and mvps < max_mv_products, so mvps may pass the cap by less than one cycle.
+ * DEPARTURE from upstream: the shadow residual is not rand -- it is the preconditioned initial residual, or r_shadow.
+ * Two solves of the same input are bitwise equal.
+ * Memory rule: 2 l + 3 work vectors of N complex (rs[0..l], us[0..l], the shadow residual) for the duration of the call,
+ * whatever the iteration count (5 at l = 1, 7 at l = 2); with LSFC_MEM_HOST the staged x and b on top, as in lsfc_gmres.
+ * Checked against the free device memory before anything is allocated: LSFC_ENOMEM with the figures.
+ * Exhausted Krylov space: a cycle whose Gram matrix has G[0,0] = ||rs[0]||^2 <= tol^2 records sqrt(G[0,0]) and stops
+ * converged without the minimal-residual solve.
+ * Breakdown: a rho, sigma or gamma that is zero where it divides, or not finite, ends the solve; every update whose scalar
+ * is affected is skipped on the device, so x stays the last finite iterate and rs[0] its residual.  If that residual is
+ * already within the tolerance the solve has converged; otherwise LSFC_ENOTCONV, and lsfc_last_error names the scalar and
+ * the cycle.  LSFC_ENOTCONV also when max_mv_products is reached (x still updated).
+ * LSFC_EINVAL, before any device call: NULL opts, l outside 1..8, a non-zero reserved word, a bad memspace, NULL plan, x,
+ * b or result, a distributed or multi-device plan.
+ * Out of scope: multi-device / distributed plans, and a lock-step batch form like lsfc_gmres_batch. */
+typedef struct lsfc_bicgstabl_opts {
+    int     l;               /* 1..8; IterativeSolvers' default is 2                                   */
+    int64_t max_mv_products; /* <=0: N                                                                 */
+    double  reltol;          /* <0: sqrt(eps)                                                          */
+    double  abstol;          /* default 0                                                              */
+    int     initially_zero;  /* skip the initial A*x0 (x0 == 0)                                        */
+    lsfc_precond_fn precond; void* precond_user;  /* NULL: Identity(); as in lsfc_gmres_opts           */
+    int     precond_on_device; /* as in lsfc_gmres_opts; lsfc_precond_callback with 1: no host code inside the BiCG part */
+    const double* r_shadow;  /* NULL: the preconditioned initial residual; else N complex in `memspace` */
+    int     reserved[4];     /* zero */
+} lsfc_bicgstabl_opts;
+
+int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts,
+                   double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* result, int memspace);
 
 /* ---- device-resident SparsifyingPreconditioner apply ------------------------ */
 

@@ -336,4 +336,42 @@ function gmres_batch_hip!(X::Matrix{Complex{Float64}}, M::FastMHIP, B::Matrix{Co
     X, [resnorm[1:res[j].iters, j] for j in 1:nrhs]
 end
 
+# Device-side BiCGStab(l), lsfc_bicgstabl: IterativeSolvers.bicgstabl!(x, A, b, l; Pl, max_mv_products, abstol, reltol) with
+# the upstream keyword names.  2 l + 3 device work vectors whatever the iteration count (gmres_hip! keeps restart + 2): the
+# solver for grids whose Krylov basis does not fit.  Defaults as upstream: l = 2 (1..8 here), reltol sqrt(eps), abstol 0,
+# max_mv_products = length(b).  DEPARTURE: the shadow residual is the preconditioned initial residual, not rand -- or the
+# keyword r_shadow -- so a solve is reproducible bit for bit.  Returns x and one residual norm per cycle (l BiCG steps and one
+# minimal-residual step, 2 l operator applications).  A breakdown (rho, sigma or gamma zero where it divides, or not finite)
+# ends the solve with x the last finite iterate; like the cap it shows as a history that stops above the tolerance (rc -5).
+# `log` is accepted for the upstream signature: true (the default here, as gmres_hip! always does) returns (x, history), false x alone.
+# ABI-LAYOUT lsfc_bicgstabl_opts size=88 l:0 max_mv_products:8 reltol:16 abstol:24 initially_zero:32 precond:40 precond_user:48 precond_on_device:56 r_shadow:64 reserved:72
+struct BicgstablOpts
+    l::Cint; max_mv_products::Int64; reltol::Float64; abstol::Float64; initially_zero::Cint
+    precond::Ptr{Cvoid}; precond_user::Ptr{Cvoid}; precond_on_device::Cint; r_shadow::Ptr{Cvoid}; reserved::NTuple{4, Cint}
+end
+function bicgstabl_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Complex{Float64}}, l::Int=2; Pl=nothing,
+                        max_mv_products=length(b), abstol=0.0, reltol=sqrt(eps(Float64)), log::Bool=true, initially_zero=false, r_shadow=nothing)
+    box = Ref{Any}(Pl)
+    if Pl isa SparsifyingPreconditionerHIP        # applied on the device by the library itself: no host code inside the BiCG part
+        cb = cglobal((:lsfc_precond_callback, liblsfc)); user = Pl.pc; ondev = Cint(1)
+    else
+        cb = Pl === nothing ? C_NULL : @cfunction(_precond_trampoline, Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64))
+        user = Pl === nothing ? C_NULL : pointer_from_objref(box); ondev = Cint(0)
+    end
+    shadow = r_shadow === nothing ? Complex{Float64}[] : convert(Vector{Complex{Float64}}, r_shadow)
+    r_shadow === nothing || length(shadow) == length(b) || throw(DimensionMismatch("r_shadow"))
+    # one history entry per cycle of 2 l operator applications, capped as the Python surface caps it
+    cap = max(1, min(div(max_mv_products > 0 ? max_mv_products : length(b), 2 * max(l, 1)) + 2, 1 << 20))
+    res = Ref(GmresResult(0, 0, 0, 0.0)); resnorm = zeros(Float64, cap)
+    GC.@preserve box shadow begin
+        opts = Ref(BicgstablOpts(l, max_mv_products, reltol, abstol, initially_zero ? 1 : 0, cb, user, ondev,
+                                 r_shadow === nothing ? C_NULL : Ptr{Cvoid}(pointer(shadow)), (Cint(0), Cint(0), Cint(0), Cint(0))))
+        rc = ccall((:lsfc_bicgstabl, liblsfc), Cint,
+                   (Ptr{Cvoid}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Ref{BicgstablOpts}, Ptr{Float64}, Int64, Ref{GmresResult}, Cint),
+                   M.plan, x, b, opts, resnorm, cap, res, 0)
+        (rc == 0 || rc == -5) || check(rc)
+    end
+    log ? (x, resnorm[1:min(res[].iters, cap)]) : x
+end
+
 end # module
