@@ -94,6 +94,7 @@ SIGNATURES = {
     "lsfc_plan_set_stream": (_I, [_P, _P]),
     "lsfc_plan_synchronize": (_I, [_P]),
     "lsfc_plan_set_tuning": (_I, [_P, C.c_char_p, _I]),
+    "lsfc_plan_describe_passes": (_I, [_P, _I, C.c_char_p, _L, C.POINTER(_L)]),
     "lsfc_time_apply": (_I, [_P, _P, _P, _I, C.POINTER(_D)]),
     "lsfc_profile_apply": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_char_p), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I)]),
     "lsfc_device_count": (_I, [C.POINTER(_I)]),

@@ -25,6 +25,7 @@
 #include <set>
 #include <map>
 #include <utility>
+#include <cstring>
 
 // This file is compiled once per family of line lengths (Makefile: -DLSFC_FAMILY=2 | 3 | 5): the power-of-two lines,
 // the lines with one factor 3 and the lines with one factor 5.  pruned.hip routes each call to the family of its L.
@@ -193,6 +194,15 @@ void k_yinv(const cplx* __restrict__ a2, cplx* __restrict__ a1, const cplx* __re
 // fetched through LDS (zm[s - L/2] = storage index of the partner).  Halves the symbol bytes of the pass again.
 // TWL: the full stage-twiddle table (tw points to it) is staged in LDS behind the exchange buffer and read instead of
 // computing the power trees (-18 % fp64 instructions, +40 % LDS reads).
+// Whether the one-tile kernel of LINES lines exchanges between stages of equal radix through the lanes of the wavefront (whole-complex
+// exchanges, whole wavefronts only).  One definition for the kernel (XL1) and for the description of the pass (PassForm::xl).
+template <class C, int LINES, bool SPLIT> constexpr bool xl_one_tile() {
+#ifdef LSFC_NO_XLANE_ONE_TILE
+    return false;
+#else
+    return !SPLIT && xlane_ok<C, LdsLayout<LINES, 3, SPLIT>>() && (C::T * LINES) % 64 == 0;
+#endif
+}
 // MULTI (several right-hand sides, lsfc_apply_batch): the workgroup runs the tile of every batch member in turn with
 // ONE load of its symbol tile -- the symbol's share of the pass (8 of 16 complex per point in the byte model, 4 with
 // the half symbol) is paid once per batch instead of once per right-hand side.
@@ -236,11 +246,7 @@ void k_zfused(cplx* __restrict__ data, const cplx* __restrict__ sym, const cplx*
     // ... and the exchanges between stages of equal radix through the lanes of the wavefront where the line and the layout allow it
     // (fft_core.hpp xlane_stage_ok; whole wavefronts only): one LDS round trip and two workgroup barriers less per direction in a
     // kernel that is a chain of latencies on the small grids and in 2D
-#ifdef LSFC_NO_XLANE_ONE_TILE
-    constexpr bool XL1 = false;
-#else
-    constexpr bool XL1 = !SPLIT && xlane_ok<C, LL>() && (C::T * LINES) % 64 == 0;
-#endif
+    constexpr bool XL1 = xl_one_tile<C, LINES, SPLIT>();
     auto fwd = [&](cplx (&w)[E]) {
         if constexpr (!SPLIT) fft_forward_ws<C, LL, true, TWL, false, XL1>(w, t, tw, smem, 0, li, [] {});
         else fft_forward<C, LL, true, TWL>(w, t, tw, smem, 0, li);
@@ -384,6 +390,11 @@ template <class C, int LINES, bool SPLIT, bool HALF> constexpr size_t persist_xb
 template <class C, int LINES, bool SPLIT, bool TWL, bool HALF> constexpr size_t persist_lds_bytes() {
     return persist_xbuf_bytes<C, LINES, SPLIT, HALF>() + (TWL ? (size_t)C::TWLEN * sizeof(cplx) : 0);
 }
+// workgroups per CU a persistent kernel is bounded for: two half-tile workgroups where the LDS holds them (one definition for the
+// kernel's launch bounds and for PassForm::wpe)
+template <class C, int LINES, bool SPLIT, bool TWL, bool HALF> constexpr int persist_wpe() {
+    return (HALF && 2 * persist_lds_bytes<C, LINES, SPLIT, TWL, HALF>() <= (size_t)160 * 1024) ? 2 : 1;
+}
 // TICKETS without HALF: whole tiles handed out the same way, in pairs (row, mirror row) per XCD queue.
 // XL (round 3) is a set of bits, chosen by the run-time knob "xlane" (0, 1, 3, 5; -1 = 5 where available, else 1):
 // XL & 1: the exchange between the two radix-8 stages of the line runs through the lanes of the wavefront (fft_core.hpp:
@@ -393,7 +404,7 @@ template <class C, int LINES, bool SPLIT, bool TWL, bool HALF> constexpr size_t 
 // thread that needs them, a second read of lines this workgroup fetches anyway (L2 hits), instead of being staged through
 // LDS by the threads that hold them: 8 ds_write_b128 + 8 ds_read_b128 per thread and one of the two barriers around them go.
 template <class C, int LINES, bool SPLIT, bool EXACT, bool TWL, bool LATE_SYM = false, bool HALF = false, bool TICKETS = HALF, int XL = 0>
-__global__ __launch_bounds__(C::T * LINES, (HALF && 2 * persist_lds_bytes<C, LINES, SPLIT, TWL, HALF>() <= (size_t)160 * 1024) ? 2 : 1)
+__global__ __launch_bounds__(C::T * LINES, (persist_wpe<C, LINES, SPLIT, TWL, HALF>()))
 void k_zfused_persist(cplx* __restrict__ data, const cplx* __restrict__ sym, const cplx* __restrict__ tw,
                       int nouter, int64_t dGrp, int64_t dOuter, int64_t dLine, int64_t sGrp, int64_t sOuter, int64_t sLine,
                       const int2* __restrict__ ytab, const int* __restrict__ zm, int nin, unsigned ntiles, unsigned* __restrict__ tickets) {
@@ -622,19 +633,19 @@ template <class C> struct Tune {
 #endif
 };
 
-template <class C, bool SPLIT> static void xfwd_t(const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st) {
+template <class C, bool SPLIT> static void xfwd_t(const PassForm& f, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st) {
     constexpr int LPW = Tune<C>::LPW;
     using LL = LdsLayout<1, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
-    auto k = (n == C::L / 2) ? k_xfwd<C, LPW, SPLIT, true> : k_xfwd<C, LPW, SPLIT, false>;
+    auto k = f.full ? k_xfwd<C, LPW, SPLIT, true> : k_xfwd<C, LPW, SPLIT, false>;
     allow_lds(k, lds);
     hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, vb, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride);
 }
-template <class C, bool SPLIT> static void xinv_t(const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st) {
+template <class C, bool SPLIT> static void xinv_t(const PassForm& f, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st) {
     constexpr int LPW = Tune<C>::LPW;
     using LL = LdsLayout<1, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
-    auto k = (n == C::L / 2) ? k_xinv<C, LPW, SPLIT, true> : k_xinv<C, LPW, SPLIT, false>;
+    auto k = f.full ? k_xinv<C, LPW, SPLIT, true> : k_xinv<C, LPW, SPLIT, false>;
     allow_lds(k, lds);
     hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride);
 }
@@ -645,25 +656,25 @@ static void ytile(const PrunedTuning& tn, int L, int ngrp, int l, int& TG, int& 
     TG = tn.ytile_g > 0 ? tn.ytile_g : ag; if (TG > ngrp) TG = ngrp; while (ngrp % TG) --TG;
     TZ = tn.ytile_z > 0 ? tn.ytile_z : az; if (TZ > l) TZ = l;       while (l % TZ) --TZ;
 }
-template <class C, bool SPLIT, int WPE> static void yfwd_t(const PrunedTuning& tn, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
+template <class C, bool SPLIT, int WPE> static void yfwd_t(const PassForm& f, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
     constexpr int LINES = Tune<C>::YLINES;
     using LL = LdsLayout<LINES, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = (m == C::L / 2) ? k_yfwd<C, LINES, SPLIT, WPE, true> : k_yfwd<C, LINES, SPLIT, WPE, false>;
+    auto k = f.full ? k_yfwd<C, LINES, SPLIT, WPE, true> : k_yfwd<C, LINES, SPLIT, WPE, false>;
     allow_lds(k, lds);
-    int TG, TZ; ytile(tn, C::L, Lx / LINES, l, TG, TZ);
+    const int TG = f.tg, TZ = f.tz;
     hipLaunchKernelGGL(k, dim3((unsigned)((Lx / LINES) * l), (unsigned)nrhs), dim3(C::T * LINES), lds, st, a1, a2, tw, Lx, m, l, TG, TZ, p1, p2, b1, b2);
 }
-template <class C, bool SPLIT, int WPE> static void yinv_t(const PrunedTuning& tn, const cplx* a2, cplx* a1, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
+template <class C, bool SPLIT, int WPE> static void yinv_t(const PassForm& f, const cplx* a2, cplx* a1, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
     constexpr int LINES = Tune<C>::YLINES;
     using LL = LdsLayout<LINES, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = (m == C::L / 2) ? k_yinv<C, LINES, SPLIT, WPE, true> : k_yinv<C, LINES, SPLIT, WPE, false>;
+    auto k = f.full ? k_yinv<C, LINES, SPLIT, WPE, true> : k_yinv<C, LINES, SPLIT, WPE, false>;
     allow_lds(k, lds);
-    int TG, TZ; ytile(tn, C::L, Lx / LINES, l, TG, TZ);
+    const int TG = f.tg, TZ = f.tz;
     hipLaunchKernelGGL(k, dim3((unsigned)((Lx / LINES) * l), (unsigned)nrhs), dim3(C::T * LINES), lds, st, a2, a1, tw, Lx, m, l, TG, TZ, p1, p2, b1, b2);
 }
-template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false> static void zfused_t(cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
+template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false> static void zfused_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
                                                     const FusedGeom& g, hipStream_t st, int nrhs, int64_t dBatch) {
     // g.dTile / g.sTile are strides per XB-tile of x'; a workgroup covers LINES of the XB lines of a tile.
     // twl != NULL: full stage-twiddle table, staged in LDS by the kernel.
@@ -671,18 +682,18 @@ template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false> static v
     static_assert(XB % LINES == 0, "LINES must divide XB");
     using LL = LdsLayout<LINES, 3, SPLIT>;
     size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, false>;
-    if (twl && lds + (size_t)C::TWLEN * sizeof(cplx) > (size_t)160 * 1024) twl = nullptr;   // table does not fit beside the exchange buffer
+    auto k = f.full ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, false>;
+    if (!f.twl) twl = nullptr;               // (switched off, or the table does not fit beside the exchange buffer: z_form)
     if (twl) {
-        k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, true> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, true>;
+        k = f.full ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, true> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, true>;
         lds += (size_t)C::TWLEN * sizeof(cplx);
         tw = twl;
     }
-    if (nrhs > 1) {
+    if (f.batch) {
         // batch: one symbol load per tile for all right-hand sides (the symbol is always loaded up front there, so the
         // PREFETCH flavours share one instantiation)
-        if (twl) k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, true, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, true, true>;
-        else     k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, false, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, false, true>;
+        if (twl) k = f.full ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, true, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, true, true>;
+        else     k = f.full ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, false, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, false, true>;
     }
     allow_lds(k, lds);
     if (LINES == XB) {
@@ -708,30 +719,31 @@ static int cu_count() {
     return cus;
 }
 static unsigned* ticket_set(hipStream_t st);
-template <class C, bool SPLIT, bool LATE_SYM = false, bool TICKETS = false> static void zfused_persist_t(cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
-                                                            const FusedGeom& g, hipStream_t st, int xl = 0) {
+template <class C, bool SPLIT, bool LATE_SYM = false, bool TICKETS = false> static void zfused_persist_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
+                                                            const FusedGeom& g, hipStream_t st) {
     constexpr int LINES = XB;
     using LL = LdsLayout<LINES, 3, SPLIT>;
     size_t lds = persist_xbuf_bytes<C, LINES, SPLIT, false>();
-    if (twl && lds + (size_t)C::TWLEN * sizeof(cplx) > (size_t)160 * 1024) twl = nullptr;
-    auto k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS>;
+    if (!f.twl) twl = nullptr;
+    const int xl = f.xl;                     // resolved by z_form: 0, 1, and with the table 3 or (ticketed) 5
+    auto k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS>;
     if (twl) {
-        k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS>;
+        k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS>;
         lds += (size_t)C::TWLEN * sizeof(cplx);
         tw = twl;
     }
     // lane exchanges between stages of equal radix (whole-complex whole tiles, symbol after the first stage: the 512^3 and 256^3 forms)
     if constexpr (xlane_ok<C, LL>() && !SPLIT && LATE_SYM) {
         if (xl == 1) {
-            if (twl) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
-            else     k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS, 1>;
+            if (twl) k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
+            else     k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS, 1>;
         } else if (xl >= 2 && twl) {
             // 3: + mirror symbol values from L2 (XL & 2; measured slower, profiles/r03_experiment_fused_pass_variants.log)
-            if (xl == 5 && TICKETS) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 5> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 5>;
-            else if (xl == 3) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 3> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 3>;
-            else k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
+            if (xl == 5 && TICKETS) k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 5> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 5>;
+            else if (xl == 3) k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 3> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 3>;
+            else fail(LSFC_EINVAL, "internal: persistent fused pass with lane-exchange form %d", xl);
         }
-    }
+    } else LSFC_REQUIRE(xl == 0, "internal: lane exchanges requested from a persistent form that has none");
     if (TICKETS) lds += 16;                             // the ticket slots
     allow_lds(k, lds);
     const int cus = cu_count();
@@ -764,14 +776,14 @@ static unsigned* ticket_set(hipStream_t st) {
     return set;
 }
 // the same on half tiles: 4-line workgroups with the twiddle table, as many per CU as the LDS holds (two at L = 1024)
-template <class C> static void zfused_persist_half_t(cplx* data, const cplx* sym, const cplx* twl, const FusedGeom& g, hipStream_t st, int xl = 0) {
+template <class C> static void zfused_persist_half_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* twl, const FusedGeom& g, hipStream_t st) {
     if constexpr (C::L >= 1024) {
         constexpr int LINES = XB / 2;
         constexpr size_t lds = persist_lds_bytes<C, LINES, false, true, true>() + 16;   // + the ticket slot
         static_assert(lds <= (size_t)160 * 1024, "half-tile persistent pass: exchange buffer exceeds the LDS");
-        auto k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, false, true, true, true, true> : k_zfused_persist<C, LINES, false, false, true, true, true>;
+        auto k = f.full ? k_zfused_persist<C, LINES, false, true, true, true, true> : k_zfused_persist<C, LINES, false, false, true, true, true>;
         if constexpr (xlane_ok<C, LdsLayout<LINES, -1, false>>()) {
-            if (xl) k = (g.nin == C::L / 2) ? k_zfused_persist<C, LINES, false, true, true, true, true, true, 1> : k_zfused_persist<C, LINES, false, false, true, true, true, true, 1>;
+            if (f.xl) k = f.full ? k_zfused_persist<C, LINES, false, true, true, true, true, true, 1> : k_zfused_persist<C, LINES, false, false, true, true, true, true, 1>;
         }
         // (tried in round 3: the ONE LDS exchange left per direction run split -- real parts, then imaginary parts, through half the
         // buffer -- so that TWO half-tile workgroups fit a CU at 1280 / 1536 points: without the in-stage stores every output of the
@@ -793,11 +805,11 @@ template <class C> static void zfused_persist_half_t(cplx* data, const cplx* sym
 
 // half-tile z pass (L = 1024 and L = 1536 in the 3D tiled layout only): 4-line workgroups, sibling halves 8 blocks apart
 // (LINES = 2: quarter tiles -- four sibling workgroups per tile, 32 blocks per group of 8 tiles)
-template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false, int LINES = 4> static void zfused_half_t(cplx* data, const cplx* sym, const cplx* tw,
+template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false, int LINES = 4> static void zfused_half_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* tw,
                                                          const FusedGeom& g, hipStream_t st) {
     using LL = LdsLayout<LINES, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = (g.nin == C::L / 2) ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, false, false>;
+    auto k = f.full ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, false, false>;
     allow_lds(k, lds);
     const int64_t ntiles = (int64_t)(g.Lx / XB) * g.nouter;
     LSFC_REQUIRE(ntiles % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
@@ -850,6 +862,63 @@ void FAM(pruned_perm)(int L, int* freq_of_storage) {
     LSFC_DISPATCH_L(L, perm_table<C>(freq_of_storage));
 }
 
+// ---------------------------------------------------------------------------
+// Which kernel a pass runs: pure host functions from what a dispatcher knows (line length, tuning, geometry, number of
+// right-hand sides) to a PassForm (pruned.hpp).  The launchers below switch on the PassForm and decide nothing themselves.
+// ---------------------------------------------------------------------------
+static constexpr size_t LDS_BYTES = (size_t)160 * 1024;
+// the compile-time facts of a line length that the choice depends on
+struct LineTraits {
+    int lines, ylines, twlen;
+    size_t tile_lds[2];          // exchange buffer of a one-tile workgroup (`lines` lines): [0] whole complex, [1] split
+    size_t persist_lds[2];       // ... of a persistent 8-line workgroup
+    size_t xb_full_lds;          // whole-complex exchange of 8 lines
+    size_t y_full_lds;           // whole-complex exchange of the y passes' workgroup
+    bool xl_tile, xl_half, xl_quarter;   // one-tile kernels: the lane exchange is compiled in (whole-complex exchanges only)
+    bool xl_persist;             // persistent whole tiles: lane exchanges available
+    bool xl_persist_half;        // ticketed half tiles likewise
+    int persist_half_wpe;        // ticketed half tiles: workgroups per CU
+};
+template <class C> static LineTraits line_traits_t() {
+    LineTraits t{};
+    constexpr int LINES = Tune<C>::LINES, YLINES = Tune<C>::YLINES;
+    t.lines = LINES; t.ylines = YLINES; t.twlen = C::TWLEN;
+    t.tile_lds[0] = (size_t)LdsLayout<LINES, 3, false>::line_elems(C::L) * LINES * LdsLayout<LINES, 3, false>::elem_bytes();
+    t.tile_lds[1] = (size_t)LdsLayout<LINES, 3, true>::line_elems(C::L) * LINES * LdsLayout<LINES, 3, true>::elem_bytes();
+    t.persist_lds[0] = persist_xbuf_bytes<C, XB, false, false>();
+    t.persist_lds[1] = persist_xbuf_bytes<C, XB, true, false>();
+    t.xb_full_lds = (size_t)LdsLayout<XB, 3, false>::line_elems(C::L) * XB * 16;
+    t.y_full_lds = (size_t)LdsLayout<YLINES, 3, false>::line_elems(C::L) * YLINES * 16;
+    t.xl_tile = xl_one_tile<C, LINES, false>(); t.xl_half = xl_one_tile<C, 4, false>(); t.xl_quarter = xl_one_tile<C, 2, false>();
+    t.xl_persist = xlane_ok<C, LdsLayout<XB, 3, false>>();
+    if constexpr (C::L >= 1024) {
+        t.xl_persist_half = xlane_ok<C, LdsLayout<XB / 2, -1, false>>();
+        t.persist_half_wpe = persist_wpe<C, XB / 2, false, true, true>();
+    }
+    return t;
+}
+static LineTraits line_traits(int L) {
+    LineTraits t{};
+    LSFC_DISPATCH_L(L, t = line_traits_t<C>());
+    return t;
+}
+
+PassForm FAM(pruned_xform)(PassFamily family, int L, const PrunedTuning& tn, int n) {
+    PassForm f;
+    f.family = family; f.L = L; f.split = tn.split_x; f.full = n == L / 2;
+    return f;
+}
+PassForm FAM(pruned_yform)(PassFamily family, int L, const PrunedTuning& tn, int Lx, int m, int l) {
+    const LineTraits t = line_traits(L);
+    PassForm f;
+    f.family = family; f.L = L; f.full = m == L / 2; f.lines = t.ylines;
+    // whole-complex exchange buffers of the longest lines exceed the 160 KiB of LDS: those run split whatever split_s says
+    f.forced_split = t.y_full_lds > LDS_BYTES;
+    f.split = tn.split_s || f.forced_split;
+    ytile(tn, L, Lx / t.ylines, l, f.tg, f.tz);
+    return f;
+}
+
 // chunk addressing of the x passes: s / W by multiplication with wmagic = floor(2^22 / W) + 1 (exact for s < 2048:
 // s * (wmagic * W - 2^22) <= s * W < 2^22; the product s * wmagic stays below 2^32 for W >= 2)
 static int chunk_magic(int L, int W) {
@@ -859,29 +928,29 @@ static int chunk_magic(int L, int W) {
 void FAM(pruned_xfwd)(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride) {
     const int wmagic = chunk_magic(L, W);
     if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
-    if (tn.split_x) { LSFC_DISPATCH_L(L, (xfwd_t<C, true>(vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
-    else            { LSFC_DISPATCH_L(L, (xfwd_t<C, false>(vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
+    const PassForm f = FAM(pruned_xform)(PassFamily::XFWD, L, tn, n);
+    if (f.split) { LSFC_DISPATCH_L(L, (xfwd_t<C, true>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
+    else         { LSFC_DISPATCH_L(L, (xfwd_t<C, false>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
     LSFC_HIP(hipGetLastError());
 }
 void FAM(pruned_xinv)(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride) {
     const int wmagic = chunk_magic(L, W);
     if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
-    if (tn.split_x) { LSFC_DISPATCH_L(L, (xinv_t<C, true>(in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
-    else            { LSFC_DISPATCH_L(L, (xinv_t<C, false>(in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
+    const PassForm f = FAM(pruned_xform)(PassFamily::XINV, L, tn, n);
+    if (f.split) { LSFC_DISPATCH_L(L, (xinv_t<C, true>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
+    else         { LSFC_DISPATCH_L(L, (xinv_t<C, false>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
     LSFC_HIP(hipGetLastError());
 }
 void FAM(pruned_yfwd)(int L, const PrunedTuning& tn, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
-    size_t full_lds = 0;
-    LSFC_DISPATCH_L(L, (full_lds = (size_t)LdsLayout<Tune<C>::YLINES, 3, false>::line_elems(C::L) * Tune<C>::YLINES * 16));
-    if (tn.split_s || full_lds > (size_t)160 * 1024) { LSFC_DISPATCH_L(L, (yfwd_t<C, true, 1>(tn, a1, a2, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
-    else            { LSFC_DISPATCH_L(L, (yfwd_t<C, false, 1>(tn, a1, a2, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
+    const PassForm f = FAM(pruned_yform)(PassFamily::YFWD, L, tn, Lx, m, l);
+    if (f.split) { LSFC_DISPATCH_L(L, (yfwd_t<C, true, 1>(f, a1, a2, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
+    else         { LSFC_DISPATCH_L(L, (yfwd_t<C, false, 1>(f, a1, a2, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
     LSFC_HIP(hipGetLastError());
 }
 void FAM(pruned_yinv)(int L, const PrunedTuning& tn, const cplx* a2, cplx* a1, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
-    size_t full_lds = 0;
-    LSFC_DISPATCH_L(L, (full_lds = (size_t)LdsLayout<Tune<C>::YLINES, 3, false>::line_elems(C::L) * Tune<C>::YLINES * 16));
-    if (tn.split_s || full_lds > (size_t)160 * 1024) { LSFC_DISPATCH_L(L, (yinv_t<C, true, 1>(tn, a2, a1, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
-    else            { LSFC_DISPATCH_L(L, (yinv_t<C, false, 1>(tn, a2, a1, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
+    const PassForm f = FAM(pruned_yform)(PassFamily::YINV, L, tn, Lx, m, l);
+    if (f.split) { LSFC_DISPATCH_L(L, (yinv_t<C, true, 1>(f, a2, a1, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
+    else         { LSFC_DISPATCH_L(L, (yinv_t<C, false, 1>(f, a2, a1, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
     LSFC_HIP(hipGetLastError());
 }
 int FAM(pruned_twfull_len)(int L) {
@@ -893,12 +962,34 @@ void FAM(pruned_twfull)(int L, const cplx* tw, cplx* out) {
     LSFC_DISPATCH_L(L, twfull_table<C>(out, tw));
 }
 
-void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom& g, hipStream_t st,
-                        int nrhs, int64_t dBatch) {
+// the lane-exchange form a persistent whole-tile kernel runs for the request `req` (knob "xlane")
+static int persist_xl(int req, bool available, bool twl, bool tickets) {
+    if (!available) return 0;
+    if (req == 1) return 1;
+    // 3 (+ mirror symbol values from L2) and 5 (+ row pairs as work items, ticketed form only) exist with the twiddle table only;
+    // any other request >= 2 runs as 1 with the table, and through LDS without it
+    if (req >= 2 && twl) return (req == 5 && tickets) ? 5 : (req == 3 ? 3 : 1);
+    return 0;
+}
+PassForm FAM(pruned_zfused_form)(int L, const PrunedTuning& tn, const FusedGeom& g, bool have_twl, int nrhs) {
+    const LineTraits t = line_traits(L);
+    const int64_t ntiles = (int64_t)(g.Lx / XB) * g.nouter;
+    PassForm f;
+    f.L = L; f.ze = g.zm != nullptr; f.full = g.nin == L / 2;
     // the half-tile forms (below) take one right-hand side per launch: a batch runs through them member by member
-    const bool tiled = g.dLine == 8 && ((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0;
-    const bool half_form = (LSFC_FAMILY == 2 && ((L == 1024 && (tn.z_half >= 0 ? tn.z_half : (g.zm ? 0 : 2)) > 0 && tiled) || (L == 2048 && g.dLine == 8)))
-                        || (LSFC_FAMILY == 3 && L == 1536 && (tn.z_half >= 0 ? tn.z_half : 1) > 0 && tiled);
+    const bool tiled = g.dLine == 8 && ntiles % 8 == 0;
+    // z_half, the flavour of the half-tile one-tile kernels: 0 whole tiles, 1 whole-complex exchange + prefetch, 2 split + prefetch,
+    // 3 split, 4 (and above) whole-complex.  auto (-1) at L = 1024: half-tile, split exchanges, symbol prefetch -- 6.95 -> 6.6 ms at
+    // 512^3 (profiles/r01_experiment_half_tile.log); with the z-even half symbol the full-tile form wins (6.05 ms,
+    // profiles/r01_experiment_even_z.log).  At L = 1536 (24 elements per thread: in 8-line, 512-thread workgroups the fused pass is
+    // capped at 256 registers and spills; half tiles, 4 lines, 256 threads, one wave per SIMD, lift the cap) auto is 1
+    // (768^3: fused pass 36.7 -> 29.7 ms, apply 64.7 -> 57.4 ms)
+    int zh = 0;
+    if (LSFC_FAMILY == 2 && L == 1024 && tiled) zh = tn.z_half >= 0 ? tn.z_half : (g.zm ? 0 : 2);
+    if (LSFC_FAMILY == 3 && L == 1536 && tiled) zh = tn.z_half >= 0 ? tn.z_half : 1;
+    // the 2048-point line in the 3D tiled layout: a whole 8-line tile does not fit the 160 KiB of LDS, half tiles do
+    const bool half2048 = LSFC_FAMILY == 2 && L == 2048 && g.dLine == 8;
+    const bool half_form = zh > 0 || half2048;
     // persistent pipelined form: z-even symbol, 3D tiled layout, whole 8-line tiles, one right-hand side
     {
         // z_persist: 1 whole-complex exchanges, 2 split exchanges, 3 / 4 the same with the symbol loaded after the first forward
@@ -911,97 +1002,56 @@ void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* s
         // 6 = 3 with the tiles handed out by the same tickets (row pairs per XCD: both reads of a symbol row meet in one L2):
         // 512^3 apply 12.95 -> 12.86 ms over three A/B rounds of bench.py, neutral at 256^3; auto from L = 1024 on
         const int zp = tn.z_persist >= 0 ? tn.z_persist : ((L == 1536 || L == 1280 || L == 2048) ? 5 : (L >= 1024 ? 6 : 3));   // (2048: 1024^3 fused pass 58.8 -> 47.0 ms)
-        bool eight_lines = false;
-        LSFC_DISPATCH_L(L, (eight_lines = Tune<C>::LINES == XB));
+        const bool eight_lines = t.lines == XB;
         // (worth it only when a workgroup walks over several tiles: below ~4 tiles per resident workgroup -- grids up to 64^3 --
         // the one-tile kernels finish sooner, 35 against 37.5 us per apply at 48^3)
-        const bool enough_tiles = tn.z_persist > 0 || (int64_t)(g.Lx / XB) * g.nouter >= (int64_t)4096;
-        const bool half5 = zp == 5 && tiled && twl && L >= 1024 && ((int64_t)(g.Lx / XB) * g.nouter) % 16 == 0 && (g.nouter % 2 == 0 || !g.ytab);
+        const bool enough_tiles = tn.z_persist > 0 || ntiles >= (int64_t)4096;
+        // 5: half tiles (4-line workgroups, swizzled unpadded exchange buffer + twiddle table), two workgroups per CU at L = 1024;
+        // below 1024 points (whole tiles only) and on grids without a multiple of 16 tiles in row pairs a request for 5 runs as 4
+        const bool half5 = zp == 5 && tiled && have_twl && L >= 1024 && ntiles % 16 == 0 && (g.nouter % 2 == 0 || !g.ytab);
         if (zp > 0 && g.zm && g.dLine == 8 && nrhs == 1 && (eight_lines || half5) && (!half_form || half5) && enough_tiles) {
-            size_t full_lds = 0;
-            LSFC_DISPATCH_L(L, (full_lds = (size_t)LdsLayout<XB, 3, false>::line_elems(C::L) * XB * 16));
-            const bool split = zp == 2 || zp == 4 || full_lds > (size_t)160 * 1024;
-            // 5: half tiles (4-line workgroups, swizzled unpadded exchange buffer + twiddle table), two workgroups per CU at L = 1024
             if (half5) {
-                LSFC_DISPATCH_L(L, (zfused_persist_half_t<C>(data, sym, twl, g, st, tn.xlane != 0 ? 1 : 0)));
-                LSFC_HIP(hipGetLastError());
-                return;
+                f.family = PassFamily::ZFUSED_PERSIST_HALF; f.lines = XB / 2; f.wpe = t.persist_half_wpe;
+                f.twl = f.late_sym = f.tickets = true;
+                f.xl = (tn.xlane != 0 && t.xl_persist_half) ? 1 : 0;
+                return f;
             }
-            // 6: whole tiles (as 3) handed out by tickets in row pairs per XCD
-            if (zp == 6 && !split && ((int64_t)(g.Lx / XB) * g.nouter) % 16 == 0 && g.nouter % 2 == 0) {
-                LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, tn.xlane < 0 ? 5 : tn.xlane)));
-                LSFC_HIP(hipGetLastError());
-                return;
-            }
-            if ((zp == 3 || zp == 6) && !split) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, tn.xlane < 0 ? 1 : tn.xlane))); }
-            else if (zp >= 3) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st))); }
-            else if (split) { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st))); }
-            else       { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st))); }
-            LSFC_HIP(hipGetLastError());
-            return;
+            f.family = PassFamily::ZFUSED_PERSIST; f.lines = XB;
+            const bool split = zp == 2 || zp == 4 || t.xb_full_lds > LDS_BYTES;
+            int xlreq = 0;
+            // 6: whole tiles (as 3) handed out by tickets in row pairs per XCD; without a multiple of 16 tiles in row pairs it runs as 3
+            if (zp == 6 && !split && ntiles % 16 == 0 && g.nouter % 2 == 0) { f.late_sym = f.tickets = true; xlreq = tn.xlane < 0 ? 5 : tn.xlane; }
+            else if ((zp == 3 || zp == 6) && !split) { f.late_sym = true; xlreq = tn.xlane < 0 ? 1 : tn.xlane; }
+            else if (zp >= 3) { f.split = f.late_sym = true; }
+            else f.split = split;
+            f.twl = tn.tw_lds && have_twl && t.persist_lds[f.split] + (size_t)t.twlen * sizeof(cplx) <= LDS_BYTES;
+            // lane exchanges between stages of equal radix (whole-complex whole tiles, symbol after the first stage: the 512^3 and 256^3 forms)
+            f.xl = persist_xl(xlreq, t.xl_persist && !f.split && f.late_sym, f.twl, f.tickets);
+            return f;
         }
     }
     if (nrhs > 1 && half_form) {
-        for (int r = 0; r < nrhs; ++r)
-            FAM(pruned_zfused)(L, tn, data + (int64_t)r * dBatch, sym, tw, twl, g, st, 1, 0);
-        return;
+        f = FAM(pruned_zfused_form)(L, tn, g, have_twl, 1);
+        f.per_member = true;
+        return f;
     }
-#define LSFC_ZF(SP, PF) do { if (g.zm) { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, true>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, nrhs, dBatch))); } \
-                             else    { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, false>(data, sym, tw, tn.tw_lds ? twl : nullptr, g, st, nrhs, dBatch))); } } while (0)
-    // auto (-1): half-tile, split exchanges, symbol prefetch -- 6.95 -> 6.6 ms at 512^3 (profiles/r01_experiment_half_tile.log)
-    // with the z-even half symbol the full-tile form wins (6.05 ms, profiles/r01_experiment_even_z.log)
-#if LSFC_FAMILY == 2
-    const int zh = tn.z_half >= 0 ? tn.z_half : (g.zm ? 0 : 2);
-    if (L == 1024 && zh > 0 && g.dLine == 8 && ((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0) {
-        using C = Cfg1024;
-#define LSFC_ZH(SP, PF, W) do { if (g.zm) zfused_half_t<C, SP, PF, W, true>(data, sym, tw, g, st); \
-                                else zfused_half_t<C, SP, PF, W, false>(data, sym, tw, g, st); } while (0)
-        switch (zh) {
-        case 1: LSFC_ZH(false, true, 2); break;
-        case 2: LSFC_ZH(true, true, 2); break;
-        case 3: LSFC_ZH(true, false, 3); break;
-        default: LSFC_ZH(false, false, 2); break;
-        }
-#undef LSFC_ZH
-        LSFC_HIP(hipGetLastError());
-        return;
+    if (zh > 0) {
+        f.family = PassFamily::ZFUSED_HALF; f.lines = XB / 2;
+        f.split = zh == 2 || zh == 3; f.prefetch = zh == 1 || zh == 2;
+        f.wpe = L == 1024 ? (zh == 3 ? 3 : 2) : 1;
+        f.xl = (!f.split && t.xl_half) ? 1 : 0;
+        return f;
     }
-    // the 2048-point line in the 3D tiled layout: a whole 8-line tile does not fit the 160 KiB of LDS, half tiles do
-    if (L == 2048 && g.dLine == 8) {
-        LSFC_REQUIRE(((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
-        using C = Cfg2048;
+    if (half2048) {
         // LSFC_Z_QUARTER=1 (experiment, off): quarter tiles, two 256-thread workgroups per CU (74 KB of LDS each).  Measured on
         // the 2D tiled pass at n = 1024 (256 tiles): 35.4 against 34.2 us -- workgroups that start together run their phases
         // together, so two per CU overlap nothing in a one-tile kernel; the ticketed persistent form (2 half tiles per
         // workgroup) takes 54.8 us there (profiles/r02_2d_half_symbol.jsonl)
         const bool quarter = g.zm && env_flag_z_quarter();
-        if (quarter) zfused_half_t<C, false, false, 2, true, 2>(data, sym, tw, g, st);
-        else if (g.zm) zfused_half_t<C, false, false, 2, true>(data, sym, tw, g, st);
-        else zfused_half_t<C, false, false, 2, false>(data, sym, tw, g, st);
-        LSFC_HIP(hipGetLastError());
-        return;
+        f.family = PassFamily::ZFUSED_HALF; f.lines = quarter ? 2 : XB / 2; f.wpe = 2;
+        f.xl = (quarter ? t.xl_quarter : t.xl_half) ? 1 : 0;
+        return f;
     }
-#elif LSFC_FAMILY == 3
-    // the 1536-point line holds 24 elements per thread: in 8-line (512-thread) workgroups the fused pass is capped at
-    // 256 registers and spills.  Half tiles (4 lines, 256 threads, one wave per SIMD) lift the cap.
-    // z_half: 0 off, 1 (auto) whole-complex exchange + prefetch, 2 split + prefetch, 3 split, 4 whole-complex
-    // (768^3: fused pass 36.7 -> 29.7 ms, apply 64.7 -> 57.4 ms)
-    const int zh = tn.z_half >= 0 ? tn.z_half : 1;
-    if (L == 1536 && zh > 0 && g.dLine == 8 && ((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0) {
-        using C = Cfg1536;
-#define LSFC_ZH(SP, PF) do { if (g.zm) zfused_half_t<C, SP, PF, 1, true>(data, sym, tw, g, st); \
-                             else zfused_half_t<C, SP, PF, 1, false>(data, sym, tw, g, st); } while (0)
-        switch (zh) {
-        case 1: LSFC_ZH(false, true); break;
-        case 2: LSFC_ZH(true, true); break;
-        case 3: LSFC_ZH(true, false); break;
-        default: LSFC_ZH(false, false); break;
-        }
-#undef LSFC_ZH
-        LSFC_HIP(hipGetLastError());
-        return;
-    }
-#endif
     // auto (-1): measured on MI355X -- at L >= 1024 (16 elements/thread, 2 waves/SIMD either way) whole-complex
     // exchanges + symbol prefetch win (7.4 -> 6.7 ms at 512^3); below, split exchanges without prefetch (more waves)
     // mixed-radix lines (profiles/r01_experiment_mixed_radix_knobs.log): the symbol prefetch pays from L = 320 on
@@ -1016,16 +1066,86 @@ void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* s
 #else
     const bool e16 = L >= 320, full = false;
 #endif
-    bool sp = tn.split_z >= 0 ? tn.split_z != 0 : !full;
-    const bool pf = tn.sym_prefetch >= 0 ? tn.sym_prefetch != 0 : e16;
+    f.family = PassFamily::ZFUSED; f.lines = t.lines;
+    f.split = tn.split_z >= 0 ? tn.split_z != 0 : !full;
     // whole-complex exchange buffers of the longest lines exceed the 160 KiB of LDS: those run split
     // (sized by the workgroup zfused_t launches: Tune<C>::LINES lines -- the y passes alone use YLINES)
-    size_t full_lds = 0;
-    LSFC_DISPATCH_L(L, (full_lds = (size_t)LdsLayout<Tune<C>::LINES, 3, false>::line_elems(C::L) * Tune<C>::LINES * 16));
-    if (full_lds > (size_t)160 * 1024) sp = true;
-    if (sp) { if (pf) { LSFC_ZF(true, true); } else { LSFC_ZF(true, false); } }
-    else    { if (pf) { LSFC_ZF(false, true); } else { LSFC_ZF(false, false); } }
+    if (t.tile_lds[0] > LDS_BYTES) f.split = true;
+    // batch: one symbol load per tile for all right-hand sides, always up front (no PREFETCH flavour)
+    f.batch = nrhs > 1;
+    f.prefetch = !f.batch && (tn.sym_prefetch >= 0 ? tn.sym_prefetch != 0 : e16);
+    f.twl = tn.tw_lds && have_twl && t.tile_lds[f.split] + (size_t)t.twlen * sizeof(cplx) <= LDS_BYTES;   // the table must fit beside the exchange buffer
+    f.xl = (!f.split && t.xl_tile) ? 1 : 0;
+    return f;
+}
+
+void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom& g, hipStream_t st,
+                        int nrhs, int64_t dBatch) {
+    const PassForm f = FAM(pruned_zfused_form)(L, tn, g, twl != nullptr, nrhs);
+    if (f.per_member) {
+        for (int r = 0; r < nrhs; ++r)
+            FAM(pruned_zfused)(L, tn, data + (int64_t)r * dBatch, sym, tw, twl, g, st, 1, 0);
+        return;
+    }
+    switch (f.family) {
+    case PassFamily::ZFUSED_PERSIST_HALF:
+        LSFC_DISPATCH_L(L, (zfused_persist_half_t<C>(f, data, sym, twl, g, st)));
+        break;
+    case PassFamily::ZFUSED_PERSIST:
+        LSFC_REQUIRE(f.wpe == 1 && f.lines == XB, "internal: persistent whole tiles run %d lines, %d workgroups per CU", f.lines, f.wpe);
+        if (f.tickets)                     { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true, true>(f, data, sym, tw, twl, g, st))); }
+        else if (f.late_sym && !f.split)   { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true>(f, data, sym, tw, twl, g, st))); }
+        else if (f.late_sym)               { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true, true>(f, data, sym, tw, twl, g, st))); }
+        else if (f.split)                  { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true>(f, data, sym, tw, twl, g, st))); }
+        else                               { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false>(f, data, sym, tw, twl, g, st))); }
+        break;
+    case PassFamily::ZFUSED_HALF: {
+        // the instantiated flavours: (SPLIT, PREFETCH, WPE) of the description picks one, anything else is an internal error
+        const int flavour = (f.split ? 100 : 0) + (f.prefetch ? 10 : 0) + f.wpe;
+#define LSFC_ZH(C, SP, PF, W) do { if (f.ze) zfused_half_t<C, SP, PF, W, true>(f, data, sym, tw, g, st); \
+                                   else zfused_half_t<C, SP, PF, W, false>(f, data, sym, tw, g, st); } while (0)
+#if LSFC_FAMILY == 2
+        if (L == 1024) {
+            switch (flavour) {
+            case 112: LSFC_ZH(Cfg1024, true, true, 2); break;
+            case 103: LSFC_ZH(Cfg1024, true, false, 3); break;
+            case 12:  LSFC_ZH(Cfg1024, false, true, 2); break;
+            case 2:   LSFC_ZH(Cfg1024, false, false, 2); break;
+            default: fail(LSFC_EINVAL, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
+            }
+        } else {
+            LSFC_REQUIRE(L == 2048, "internal: half-tile fused pass at %d points", L);
+            LSFC_REQUIRE(((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
+            LSFC_REQUIRE(flavour == 2, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
+            if (f.lines == 2) zfused_half_t<Cfg2048, false, false, 2, true, 2>(f, data, sym, tw, g, st);
+            else LSFC_ZH(Cfg2048, false, false, 2);
+        }
+#elif LSFC_FAMILY == 3
+        LSFC_REQUIRE(L == 1536, "internal: half-tile fused pass at %d points", L);
+        switch (flavour) {
+        case 111: LSFC_ZH(Cfg1536, true, true, 1); break;
+        case 101: LSFC_ZH(Cfg1536, true, false, 1); break;
+        case 11:  LSFC_ZH(Cfg1536, false, true, 1); break;
+        case 1:   LSFC_ZH(Cfg1536, false, false, 1); break;
+        default: fail(LSFC_EINVAL, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
+        }
+#else
+        fail(LSFC_EINVAL, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
+#endif
+#undef LSFC_ZH
+        break;
+    }
+    case PassFamily::ZFUSED:
+        LSFC_REQUIRE(f.wpe == 1, "internal: one-tile fused kernels are bounded for one workgroup per CU, not %d", f.wpe);
+#define LSFC_ZF(SP, PF) do { if (f.ze) { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, true>(f, data, sym, tw, twl, g, st, nrhs, dBatch))); } \
+                             else      { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, false>(f, data, sym, tw, twl, g, st, nrhs, dBatch))); } } while (0)
+        if (f.split) { if (f.prefetch) { LSFC_ZF(true, true); } else { LSFC_ZF(true, false); } }
+        else         { if (f.prefetch) { LSFC_ZF(false, true); } else { LSFC_ZF(false, false); } }
 #undef LSFC_ZF
+        break;
+    default:
+        fail(LSFC_EINVAL, "internal: %s is not a form of the fused pass", pass_family_name(f.family));
+    }
     LSFC_HIP(hipGetLastError());
 }
 

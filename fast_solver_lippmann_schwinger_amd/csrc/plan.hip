@@ -8,6 +8,7 @@
 #include <thread>
 #include <functional>
 #include <mutex>
+#include <string>
 
 namespace lsfc {
 
@@ -427,10 +428,13 @@ static void pass_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, double alpha, 
 // The three geometries of the fused pass.  3D: A2 as tiles [x'/8][Ly][pitch2 >= 8*l] of 8 interleaved z lines, the symbol as
 // [x'/8][sym_rows][sym_hz][8]; `Wc` x' storage indices from the tile that `a2_off` / `sym_off` point to (a chunk of a
 // distributed plan; the whole range on one device).
-void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st) {
+static FusedGeom geom_3d(const lsfc_plan* p, int Wc) {
     const int Ly = p->pads[1];
-    const FusedGeom g{Wc, Ly, (int64_t)p->pitch2 * Ly, (int64_t)p->pitch2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8,
-                      p->ytab.p, p->zmirror.p, p->dims[2]};
+    return FusedGeom{Wc, Ly, (int64_t)p->pitch2 * Ly, (int64_t)p->pitch2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8,
+                     p->ytab.p, p->zmirror.p, p->dims[2]};
+}
+void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st) {
+    const FusedGeom g = geom_3d(p, Wc);
     pruned_zfused(p->pads[2], p->tuning, p->A2.p + a2_off, p->sym.p + sym_off, p->tw[2].p, p->twl[2].p, g, st, nrhs, p->a2_elems);
 }
 // 2D, natural rows: A1 as [m][pitch1 >= Lx], the lines along y; the symbol likewise, [rows][Lx]
@@ -440,6 +444,40 @@ static FusedGeom geom_2d_rows(const lsfc_plan* p) {
 // 2D, tiles: A1 as [Lx/8][tile2d >= 8*m] -- the 3D layout with one row per tile; the symbol as [Lx/8][sym_hz][8]
 static FusedGeom geom_2d_tiles(const lsfc_plan* p) {
     return FusedGeom{p->pads[0], 1, p->tile2d, 0, 8, (int64_t)8 * p->sym_hz, 0, 8, nullptr, p->zmirror.p, p->dims[1]};
+}
+// whether a batch of nrhs right-hand sides shares one launch per pass (lsfc_apply_batch)
+static bool batch_fused(const lsfc_plan* p, int nrhs) {
+    const bool fuse = p->tuning.batch_fuse > 0 ||
+                      (p->tuning.batch_fuse < 0 && (int64_t)p->pads[0] * p->pads[1] * p->pads[2] <= ((int64_t)1 << 24));
+    return !(nrhs == 1 || p->dist || p->multi || p->pipeline != lsfc_plan::PRUNED || !fuse);
+}
+// The kernels an apply of nrhs right-hand sides launches, one line per pass (lsfc_plan_describe_passes): the PassForm of each
+// pass from the very arguments pass_xfwd ... pass_xinv hand to the launchers
+static std::string describe_passes(const lsfc_plan* p, int nrhs) {
+    std::string out = std::string("pipeline=") + lsfc_plan_pipeline(p);
+    if (p->multi) return out + " multi-device\n";
+    if (p->dist) return out + " distributed\n";
+    out += "\n";
+    if (p->pipeline != lsfc_plan::PRUNED) return out;
+    const bool fused = batch_fused(p, nrhs);
+    const int per_launch = fused ? nrhs : 1;
+    char line[512];
+    auto add = [&](const PassForm& f) { pass_form_print(f, line, sizeof line); out += line; out += "\n"; };
+    const bool d3 = p->ndim == 3;
+    add(pruned_xfwd_form(p->pads[0], p->tuning, p->dims[0]));
+    if (d3) add(pruned_yfwd_form(p->pads[1], p->tuning, p->pads[0], p->dims[1], p->dims[2]));
+    const int fa = d3 ? 2 : 1;
+    add(pruned_zfused_form(p->pads[fa], p->tuning, d3 ? geom_3d(p, p->pads[0]) : (p->tile2d ? geom_2d_tiles(p) : geom_2d_rows(p)),
+                           p->twl[fa].p != nullptr, per_launch));
+    if (d3) add(pruned_yinv_form(p->pads[1], p->tuning, p->pads[0], p->dims[1], p->dims[2]));
+    add(pruned_xinv_form(p->pads[0], p->tuning, p->dims[0]));
+    // storage: ytab = 1 the y-even half of the symbol rows (each stored row serves a row and its mirror), zmirror = 1 the even half
+    // of every symbol line along the fused pass's axis; batch: how nrhs > 1 right-hand sides run through the passes
+    snprintf(line, sizeof line, "pitch1=%d pitch2=%d sym_rows=%d sym_hz=%d ytab=%d zmirror=%d tile2d=%lld batch=%s\n", p->pitch1, p->pitch2, p->sym_rows,
+             p->sym_hz, (int)(d3 && p->sym_rows != p->pads[1]), (int)(p->zmirror.p != nullptr), (long long)p->tile2d,
+             nrhs == 1 ? "none" : (fused ? "fused" : "per_member"));
+    out += line;
+    return out;
 }
 static void pass_fused(lsfc_plan* p, int nrhs, hipStream_t st) {
     if (p->ndim == 3) { plan_zfused_3d(p, p->pads[0], 0, 0, nrhs, st); return; }
@@ -478,9 +516,7 @@ void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double
 
 void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool use_nu, double alpha, double beta) {
     LSFC_REQUIRE(nrhs >= 1 && nrhs <= LSFC_MAX_BATCH, "batch of %d right-hand sides (1..%d per pass)", nrhs, LSFC_MAX_BATCH);
-    const bool fuse = p->tuning.batch_fuse > 0 ||
-                      (p->tuning.batch_fuse < 0 && (int64_t)p->pads[0] * p->pads[1] * p->pads[2] <= ((int64_t)1 << 24));
-    if (nrhs == 1 || p->dist || p->multi || p->pipeline != lsfc_plan::PRUNED || !fuse) {
+    if (!batch_fused(p, nrhs)) {
         for (int j = 0; j < nrhs; ++j) plan_convolve_dev(p, vb.x[j], vb.y[j], use_nu, alpha, beta);
         return;
     }
@@ -864,6 +900,19 @@ int lsfc_plan_get_symbol(const lsfc_plan* plan, double* out, int64_t capacity_co
         if (out) {
             LSFC_REQUIRE(capacity_complex >= (int64_t)plan->sym.n, "buffer too small");
             LSFC_HIP(hipMemcpy(out, plan->sym.p, plan->sym.bytes(), hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+int lsfc_plan_describe_passes(const lsfc_plan* plan, int nrhs, char* buf, int64_t capacity, int64_t* need) {
+    return guarded([&] {
+        LSFC_REQUIRE(plan && need, "NULL argument");
+        LSFC_REQUIRE(nrhs >= 1 && nrhs <= LSFC_MAX_BATCH, "nrhs must be 1..%d (the right-hand sides of one group of lsfc_apply_batch)", LSFC_MAX_BATCH);
+        const std::string text = describe_passes(plan, nrhs);
+        *need = (int64_t)text.size() + 1;
+        if (buf) {
+            LSFC_REQUIRE(capacity >= *need, "buffer too small");
+            memcpy(buf, text.c_str(), text.size() + 1);
         }
     });
 }

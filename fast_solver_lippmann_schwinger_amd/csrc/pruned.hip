@@ -14,6 +14,9 @@ namespace lsfc {
     void pruned_yfwd_f##F(int, const PrunedTuning&, const cplx*, cplx*, const cplx*, int, int, int, int, int, hipStream_t, int, int64_t, int64_t);     \
     void pruned_yinv_f##F(int, const PrunedTuning&, const cplx*, cplx*, const cplx*, int, int, int, int, int, hipStream_t, int, int64_t, int64_t);     \
     void pruned_zfused_f##F(int, const PrunedTuning&, cplx*, const cplx*, const cplx*, const cplx*, const FusedGeom&, hipStream_t, int, int64_t); \
+    PassForm pruned_xform_f##F(PassFamily, int, const PrunedTuning&, int);                                                \
+    PassForm pruned_yform_f##F(PassFamily, int, const PrunedTuning&, int, int, int);                                      \
+    PassForm pruned_zfused_form_f##F(int, const PrunedTuning&, const FusedGeom&, bool, int);                              \
     void pruned_perm_f##F(int, int*);                                                                                     \
     void pruned_warmup_f##F();                                                                                         \
     int pruned_twfull_len_f##F(int);                                                                                            \
@@ -89,6 +92,45 @@ void pruned_yinv(int L, const PrunedTuning& tn, const cplx* a2, cplx* a1, const 
 void pruned_zfused(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom& g, hipStream_t st, int nrhs, int64_t dBatch) {
     LSFC_ROUTE(L, pruned_zfused, L, tn, data, sym, tw, twl, g, st, nrhs, dBatch);
 }
+// the descriptions: pure host arithmetic, no launch (and no debug synchronisation)
+#define LSFC_ROUTE_FORM(L, NAME, ...)                                       \
+    switch (family(L)) {                                                    \
+    case 2: return NAME##_f2(__VA_ARGS__);                                  \
+    case 3: return NAME##_f3(__VA_ARGS__);                                  \
+    case 5: return NAME##_f5(__VA_ARGS__);                                  \
+    default: fail(LSFC_EINVAL, "pruned pipeline: unsupported padded length %d", (int)(L)); }
+PassForm pruned_xfwd_form(int L, const PrunedTuning& tn, int n) { LSFC_ROUTE_FORM(L, pruned_xform, PassFamily::XFWD, L, tn, n); }
+PassForm pruned_xinv_form(int L, const PrunedTuning& tn, int n) { LSFC_ROUTE_FORM(L, pruned_xform, PassFamily::XINV, L, tn, n); }
+PassForm pruned_yfwd_form(int L, const PrunedTuning& tn, int Lx, int m, int l) { LSFC_ROUTE_FORM(L, pruned_yform, PassFamily::YFWD, L, tn, Lx, m, l); }
+PassForm pruned_yinv_form(int L, const PrunedTuning& tn, int Lx, int m, int l) { LSFC_ROUTE_FORM(L, pruned_yform, PassFamily::YINV, L, tn, Lx, m, l); }
+PassForm pruned_zfused_form(int L, const PrunedTuning& tn, const FusedGeom& g, bool have_twl, int nrhs) {
+    LSFC_ROUTE_FORM(L, pruned_zfused_form, L, tn, g, have_twl, nrhs);
+}
+const char* pass_family_name(PassFamily fam) {
+    switch (fam) {
+    case PassFamily::XFWD: return "xfwd";
+    case PassFamily::XINV: return "xinv";
+    case PassFamily::YFWD: return "yfwd";
+    case PassFamily::YINV: return "yinv";
+    case PassFamily::ZFUSED: return "zfused";
+    case PassFamily::ZFUSED_HALF: return "zfused_half";
+    case PassFamily::ZFUSED_PERSIST: return "zfused_persist";
+    case PassFamily::ZFUSED_PERSIST_HALF: return "zfused_persist_half";
+    }
+    return "?";
+}
+int pass_form_print(const PassForm& f, char* buf, size_t cap) {
+    const bool xpass = f.family == PassFamily::XFWD || f.family == PassFamily::XINV;
+    const bool ypass = f.family == PassFamily::YFWD || f.family == PassFamily::YINV;
+    int k = snprintf(buf, cap, "%s L=%d SPLIT=%d FULL=%d", pass_family_name(f.family), f.L, (int)f.split, (int)f.full);
+    auto more = [&](const char* fmt, auto... a) { if (k >= 0 && (size_t)k < cap) k += snprintf(buf + k, cap - (size_t)k, fmt, a...); };
+    if (!xpass) more(" LINES=%d WPE=%d", f.lines, f.wpe);
+    if (ypass) more(" FORCED_SPLIT=%d TG=%d TZ=%d", (int)f.forced_split, f.tg, f.tz);
+    if (!xpass && !ypass) more(" PREFETCH=%d ZE=%d TWL=%d BATCH=%d LATE_SYM=%d TICKETS=%d XL=%d PER_MEMBER=%d", (int)f.prefetch, (int)f.ze, (int)f.twl,
+                                 (int)f.batch, (int)f.late_sym, (int)f.tickets, f.xl, (int)f.per_member);
+    return k;
+}
+
 void pruned_perm(int L, int* freq_of_storage) {
     switch (family(L)) {
     case 2: pruned_perm_f2(L, freq_of_storage); break;

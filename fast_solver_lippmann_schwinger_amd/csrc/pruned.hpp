@@ -74,6 +74,40 @@ struct FusedGeom {
     const int* zm;          // even symbol: partner storage index of every upper-half slot; NULL: full symbol lines
     int nin;                // valid entries per line (<= L/2)
 };
+// What a pass launches: the kernel family and the template flags of the instantiation.  Every pass has a pure host function
+// (no launch, no device access) from the inputs its dispatcher has to this description; the launchers switch on the description
+// and on nothing else, and lsfc_plan_describe_passes prints it, so that a test can see which kernel a tuning request selects.
+enum class PassFamily { XFWD, XINV, YFWD, YINV, ZFUSED, ZFUSED_HALF, ZFUSED_PERSIST, ZFUSED_PERSIST_HALF };
+// xfwd, xinv, yfwd, yinv, zfused, zfused_half, zfused_persist, zfused_persist_half
+const char* pass_family_name(PassFamily);
+struct PassForm {
+    PassFamily family = PassFamily::XFWD;
+    int L = 0;
+    bool split = false;            // SPLIT: re/im-split LDS exchanges
+    bool forced_split = false;     // y passes: split because whole-complex exchanges exceed the LDS, whatever split_s says
+    bool prefetch = false;         // PREFETCH: symbol loaded before the forward transform (one-tile fused kernels)
+    bool ze = false;               // ZE: z-even half symbol lines (mirror slots)
+    bool full = false;             // FULL: the grid fills the line (n == L/2), end-of-line predicates compiled away
+    bool twl = false;              // TWL: stage twiddles from the LDS-resident table
+    bool batch = false;            // BATCH: one launch for all right-hand sides, one symbol load per tile
+    bool late_sym = false;         // LATE_SYM: persistent forms, symbol loaded after the first forward stage
+    bool tickets = false;          // TICKETS: tiles handed out by per-XCD ticket counters
+    int xl = 0;                    // XL: lane exchanges between stages of equal radix (persistent forms: 0, 1, 3, 5; one-tile kernels: 0 / 1,
+                                   // not a choice there but the kernels' own constexpr, fft_kernels.hip xl_one_tile)
+    int lines = 0;                 // LINES: lines per workgroup (y and fused passes)
+    int wpe = 1;                   // WPE: workgroups per CU the kernel is bounded for (its __launch_bounds__)
+    int tg = 0, tz = 0;            // y passes: resolved block-order tile (x'-groups x z planes)
+    bool per_member = false;       // a batch that runs through this form member by member (one launch per right-hand side)
+};
+PassForm pruned_xfwd_form(int L, const PrunedTuning&, int n);
+PassForm pruned_xinv_form(int L, const PrunedTuning&, int n);
+PassForm pruned_yfwd_form(int L, const PrunedTuning&, int Lx, int m, int l);
+PassForm pruned_yinv_form(int L, const PrunedTuning&, int Lx, int m, int l);
+// have_twl: the caller holds the full stage-twiddle table of the line
+PassForm pruned_zfused_form(int L, const PrunedTuning&, const FusedGeom&, bool have_twl, int nrhs);
+// "family L=.. SPLIT=.. ..." (one line, no newline) into buf; returns the length written
+int pass_form_print(const PassForm&, char* buf, size_t cap);
+
 // twl: full stage-twiddle table or NULL; dBatch: distance between the batch members in `data`
 void pruned_zfused(int L, const PrunedTuning&, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom&, hipStream_t,
                    int nrhs = 1, int64_t dBatch = 0);

@@ -133,6 +133,15 @@ class _Operator:
         for key, value in knobs.items():
             L.check(L.load().lsfc_plan_set_tuning(self._plan, key.encode(), int(value)))
 
+    def describe_passes(self, nrhs=1):
+        """The kernels an apply of ``nrhs`` right-hand sides launches under the present tuning (lsfc_plan_describe_passes):
+        one line per pass -- family and template flags -- and the storage line (pitches, symbol layout)."""
+        need = C.c_int64(0)
+        L.check(L.load().lsfc_plan_describe_passes(self._plan, int(nrhs), None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        L.check(L.load().lsfc_plan_describe_passes(self._plan, int(nrhs), buf, need.value, C.byref(need)))
+        return buf.value.decode()
+
     def synchronize(self):
         L.check(L.load().lsfc_plan_synchronize(self._plan))
 

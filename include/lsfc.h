@@ -415,6 +415,26 @@ int lsfc_profile_apply(lsfc_plan* plan, const double* x_dev, double* y_dev, int 
  * (lsfc_apply_batch: 1 one fused pass per group of right-hand sides, 0 member by member, -1 by grid size).  Any other
  * key is LSFC_EINVAL.  Results never depend on them beyond rounding (the forms differ in how twiddles are obtained). */
 int lsfc_plan_set_tuning(lsfc_plan* plan, const char* key, int value);
+/* Which kernels an apply of nrhs right-hand sides (one group of lsfc_apply_batch, at most LSFC_MAX_BATCH in csrc/pruned.hpp) launches under the plan's present
+ * tuning, as text: "pipeline=<lsfc_plan_pipeline>", then for a single-device pruned plan one line per pass in launch order,
+ *   <family> L=<line length> SPLIT= FULL= [LINES= WPE=] [FORCED_SPLIT= TG= TZ=] [PREFETCH= ZE= TWL= BATCH= LATE_SYM= TICKETS= XL= PER_MEMBER=]
+ * (family: xfwd, yfwd, zfused | zfused_half | zfused_persist | zfused_persist_half, yinv, xinv; the flags are the template
+ * arguments of the instantiation, TG x TZ the resolved block-order tile of the y passes, PER_MEMBER=1 a batch that the fused pass
+ * runs one right-hand side at a time), and a last line
+ *   pitch1= pitch2= sym_rows= sym_hz= ytab=0|1 zmirror=0|1 tile2d= batch=none|fused|per_member
+ * (ytab / zmirror: the y-even half of the symbol rows / the even half of every symbol line is stored).  The rocFFT pipelines and
+ * distributed or multi-device plans report the pipeline line only.  Pure host arithmetic: nothing is launched.  Sizing as
+ * lsfc_plan_get_symbol: *need = bytes including the terminating NUL; buf may be NULL, else capacity >= *need.
+ * Requests the dispatcher does not run as asked: z_persist 5 needs >= 1024 points and a multiple of 16 tiles in row pairs, else it
+ * runs as 4; 6 needs such tiles too, else it runs as 3; 1-6 run split where whole-complex exchanges of 8 lines exceed the LDS;
+ * xlane 3 and 5 need tw_lds (without the table they run through LDS), 5 the ticketed form (else 1); lane exchanges exist
+ * in the persistent whole tiles of 128, 192, 256, 320, 384, 512, 640, 768 and 1024 points and in the ticketed half tiles of 1024,
+ * 1280, 1536 and 2048 points, XL = 0 elsewhere; tw_lds is dropped where the
+ * table does not fit beside the exchange buffer; z_half applies at 1024 and 1536 points with a multiple of 8 tiles only; in 3D
+ * the 2048-point line always runs whole-complex half tiles (split_z, sym_prefetch, tw_lds and z_persist 1-4, 6 do not apply), and
+ * the 1536-point line runs persistent whole tiles only with z_half = 0; whole-complex exchanges of the one-tile kernels and of
+ * the y passes run split from 1280 points on (they exceed the LDS). */
+int lsfc_plan_describe_passes(const lsfc_plan* plan, int nrhs, char* buf, int64_t capacity, int64_t* need);
 
 /* ---- device memory helpers for hosts without a HIP binding ---------------- */
 int lsfc_device_count(int* count);

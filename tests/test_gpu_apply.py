@@ -287,6 +287,10 @@ def test_fused_pass_forms_even_symbol_long_z_lines(lsfc, L, short):
         # 384, 640, and both 4.4 of 1280 = 20.4.4.4 in its half-tile form) through the lanes of the wavefront or through LDS
         for xl in (5, 3, 1, 0):
             M.set_tuning(z_persist=form, xlane=xl)
+            # the ticketed half tiles exist from 1024 points on; below, a request for them runs persistent whole tiles
+            # (every form and its substitutes: test_gpu_apply_forms.py)
+            if form == 5:
+                assert ("zfused_persist_half " in M.describe_passes()) == (L >= 1024)
             got[form] = M * b
             assert rel_err(got[form], want) < TOL, (form, xl)
     # twice in a row through the ticket counters (a fresh set per launch)
