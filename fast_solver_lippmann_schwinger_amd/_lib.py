@@ -18,6 +18,9 @@ LSFC_FLAG_DEFAULT, LSFC_FLAG_LITERAL_PAD, LSFC_FLAG_FORCE_ROCFFT, LSFC_FLAG_PATC
 LSFC_ORTH_MGS, LSFC_ORTH_CGS, LSFC_ORTH_DGKS = 0, 1, 2
 LSFC_EINVAL, LSFC_ENODEV, LSFC_ENOMEM, LSFC_ENOTCONV = -1, -2, -3, -5
 LSFC_UNIQUE_ID_BYTES = 128
+# how a member of lsfc_bicgstabl_batch ended (status[2 j]); 2..7: the scalar of a breakdown
+(LSFC_BICG_CONVERGED, LSFC_BICG_MAX_MV, LSFC_BICG_RHO, LSFC_BICG_SIGMA, LSFC_BICG_BETA, LSFC_BICG_ALPHA, LSFC_BICG_GAMMA,
+ LSFC_BICG_RESIDUAL) = range(8)
 
 PRECOND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 
@@ -70,6 +73,7 @@ SIGNATURES = {
     "lsfc_gmres": (_I, [_P, _P, _P, C.POINTER(GmresOpts), _P, _L, C.POINTER(GmresResult), _I]),
     "lsfc_gmres_batch": (_I, [_P, _P, _P, _L, C.POINTER(GmresOpts), _P, _L, C.POINTER(GmresResult), _I]),
     "lsfc_bicgstabl": (_I, [_P, _P, _P, C.POINTER(BicgstablOpts), _P, _L, C.POINTER(GmresResult), _I]),
+    "lsfc_bicgstabl_batch": (_I, [_P, _P, _P, _L, C.POINTER(BicgstablOpts), _P, _L, C.POINTER(GmresResult), _P, _I]),
     "lsfc_precond_create": (_I, [_PP, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_precond_destroy": (_I, [_P]),
     "lsfc_precond_set_stream": (_I, [_P, _P]),

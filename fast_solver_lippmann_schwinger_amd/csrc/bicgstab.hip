@@ -13,20 +13,33 @@
 // An update whose scalar is zero where it divides, or not finite, is skipped by every block (each block forms the scalar
 // from the same partials in the same order), the status word names it, and all later updates are skipped too: x and rs[0]
 // stay the last finite, mutually consistent pair.
+//
+// Lock step (lsfc_bicgstabl_batch): every kernel has a member dimension, blockIdx.y = position in the launch's member list
+// (struct Members, passed by value).  Member m owns its 2 l + 3 work vectors, a block of S_COUNT scalars, a block of
+// P_SLOTS * RED_BLOCKS partials and an entry of the tol^2 array; inside a member the block count, the grid-stride
+// mapping, the slots and the order of summation do not depend on the other members, so a member's bits are those of its
+// solve alone.  The host reads all scalar blocks in one copy per cycle and drops the members that have stopped from
+// the list of the next cycle.  lsfc_bicgstabl is the call with one member.
 #include "plan.hpp"
 #include "pointwise.hpp"
 #include "reduce.hpp"
+#include "blocktri.hpp"
+#include <algorithm>
 #include <cmath>
 #include <type_traits>
+#include <vector>
 
 namespace lsfc {
 namespace {
 
 constexpr int LMAX = 8, NVMAX = LMAX + 1;
+constexpr int NRHS_MAX = 64;                   // the bound of gmres_run_batch
 // device scalars (cplx each)
 enum { S_RHO = 0, S_SIGMA = 1, S_BETA = 2, S_ALPHA = 3, S_STATUS = 4 /* (code, cycle) */, S_RES = 5, S_GAMMA = 6 /* LMAX */,
        S_G = 16 /* NVMAX * NVMAX, row-major */, S_COUNT = 16 + NVMAX * NVMAX };
 enum { ST_OK = 0, ST_EXHAUSTED = 1, ST_RHO = 2, ST_SIGMA = 3, ST_BETA = 4, ST_ALPHA = 5, ST_GAMMA = 6, ST_RESIDUAL = 7 };
+static_assert(ST_RHO == LSFC_BICG_RHO && ST_SIGMA == LSFC_BICG_SIGMA && ST_BETA == LSFC_BICG_BETA && ST_ALPHA == LSFC_BICG_ALPHA &&
+              ST_GAMMA == LSFC_BICG_GAMMA && ST_RESIDUAL == LSFC_BICG_RESIDUAL, "the public codes are the status words");
 const char* const ST_NAME[] = { "", "", "rho is not finite", "sigma is zero or not finite", "beta = rho / sigma is not finite",
                                 "alpha = rho / sigma is not finite", "gamma (singular or non-finite Gram matrix)",
                                 "the residual norm is not finite" };
@@ -47,20 +60,65 @@ __device__ __forceinline__ cplx caddmul(cplx a, cplx c, cplx b) {
     return make_double2(a.x + fma(c.x, b.x, -c.y * b.y), a.y + fma(c.x, b.y, c.y * b.x));
 }
 
-// y = b - y  (initial residual from y = A x)
-__global__ void k_residual(cplx* __restrict__ y, const cplx* __restrict__ b, int64_t n) {
+// The members of one launch and where their data lives; by value in every kernel of the solve, member = m[blockIdx.y].
+// Member m: work vectors work + m wstride (rs[0..l], us[0..l], the shadow residual, n apart), x + m n,
+// scal + m S_COUNT, partial + m P_SLOTS RED_BLOCKS, tol2[m].
+struct Members {
+    cplx* work; cplx* x; cplx* scal; cplx* partial; const double* tol2;
+    int64_t wstride, n;
+    int m[NRHS_MAX];
+};
+__device__ __forceinline__ cplx* m_work(const Members& B, int m) { return B.work + (int64_t)m * B.wstride; }
+__device__ __forceinline__ cplx* m_scal(const Members& B, int m) { return B.scal + (int64_t)m * S_COUNT; }
+__device__ __forceinline__ cplx* m_partial(const Members& B, int m) { return B.partial + (int64_t)m * (P_SLOTS * RED_BLOCKS); }
+
+// rs[0] = b - rs[0]  (initial residual from rs[0] = A x)
+__global__ void k_residual(Members B, const cplx* __restrict__ ball) {
+    const int m = B.m[blockIdx.y];
+    const int64_t n = B.n;
+    cplx* __restrict__ y = m_work(B, m);
+    const cplx* __restrict__ b = ball + (int64_t)m * n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const cplx u = b[i], v = y[i]; y[i] = make_double2(u.x - v.x, u.y - v.y);
     }
 }
 
-// rho = sum(rpartial[0..nb)), beta = rho / sigma; us[i] = rs[i] - beta us[i] for i < NV (= j + 1); block 0 publishes rho, beta
+// partial slot `slot`: slices of sum_i conj(a[i]) b[i], a and b the work vectors at offsets aoff and boff (the kernel
+// of blas_dot_partial with a member dimension: the same slices, the same order)
+__global__ __launch_bounds__(RED_THREADS) void k_dot(Members B, int64_t aoff, int64_t boff, int slot) {
+    __shared__ cplx sh[RED_THREADS / 64];
+    const int m = B.m[blockIdx.y];
+    const int64_t n = B.n;
+    const cplx* __restrict__ a = m_work(B, m) + aoff;
+    const cplx* __restrict__ b = m_work(B, m) + boff;
+    cplx acc = make_double2(0.0, 0.0);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const cplx u = a[i], v = b[i];
+        acc.x = fma(u.x, v.x, fma(u.y, v.y, acc.x));
+        acc.y = fma(u.x, v.y, fma(-u.y, v.x, acc.y));
+    }
+    const cplx r = block_sum(acc, sh);
+    if (threadIdx.x == 0) m_partial(B, m)[(int64_t)slot * RED_BLOCKS + blockIdx.x] = r;
+}
+
+// scal[S_RES] = sqrt(sum of the P_NORM partials), whatever the status: the initial norm and the norm after a breakdown
+__global__ __launch_bounds__(64) void k_norm_finish(Members B, int nb) {
+    const int m = B.m[blockIdx.y];
+    const cplx s = finish_in_wave(m_partial(B, m) + (int64_t)P_NORM * RED_BLOCKS, nb);
+    if (threadIdx.x == 0) m_scal(B, m)[S_RES] = make_double2(sqrt(s.x), 0.0);
+}
+
+// rho = sum of the P_RHO partials, beta = rho / sigma; us[i] = rs[i] - beta us[i] for i < NV (= j + 1); block 0 publishes rho, beta
 template <int NV>
-__global__ __launch_bounds__(RED_THREADS) void k_bicg_u(cplx* __restrict__ us, const cplx* __restrict__ rs, int64_t ld, const cplx* __restrict__ rpartial,
-                                                         int nb, cplx* scal, int cycle, int64_t n) {
+__global__ __launch_bounds__(RED_THREADS) void k_bicg_u(Members B, int64_t uoff, int nb, int cycle) {
     __shared__ cplx bs; __shared__ int skip;
+    const int m = B.m[blockIdx.y];
+    const int64_t n = B.n, ld = B.n;
+    const cplx* __restrict__ rs = m_work(B, m);
+    cplx* __restrict__ us = m_work(B, m) + uoff;
+    cplx* scal = m_scal(B, m);
     if (threadIdx.x < 64) {
-        const cplx rho = finish_in_wave(rpartial, nb);
+        const cplx rho = finish_in_wave(m_partial(B, m) + (int64_t)P_RHO * RED_BLOCKS, nb);
         if (threadIdx.x == 0) {
             const cplx sg = scal[S_SIGMA]; const double st = scal[S_STATUS].x;
             const cplx beta = cdiv(rho, sg);
@@ -87,14 +145,19 @@ __global__ __launch_bounds__(RED_THREADS) void k_bicg_u(cplx* __restrict__ us, c
     }
 }
 
-// sigma = sum(spartial[0..nb)), alpha = rho / sigma; rs[i] -= alpha us[i+1] for i < NV (= j + 1), x += alpha us[0];
+// sigma = sum of the P_SIGMA partials, alpha = rho / sigma; rs[i] -= alpha us[i+1] for i < NV (= j + 1), x += alpha us[0];
 // block 0 publishes sigma, alpha
 template <int NV>
-__global__ __launch_bounds__(RED_THREADS) void k_bicg_rx(cplx* __restrict__ rs, const cplx* __restrict__ us, cplx* __restrict__ x, int64_t ld,
-                                                          const cplx* __restrict__ spartial, int nb, cplx* scal, int cycle, int64_t n) {
+__global__ __launch_bounds__(RED_THREADS) void k_bicg_rx(Members B, int64_t uoff, int nb, int cycle) {
     __shared__ cplx as; __shared__ int skip;
+    const int m = B.m[blockIdx.y];
+    const int64_t n = B.n, ld = B.n;
+    cplx* __restrict__ rs = m_work(B, m);
+    const cplx* __restrict__ us = m_work(B, m) + uoff;
+    cplx* __restrict__ x = B.x + (int64_t)m * n;
+    cplx* scal = m_scal(B, m);
     if (threadIdx.x < 64) {
-        const cplx sg = finish_in_wave(spartial, nb);
+        const cplx sg = finish_in_wave(m_partial(B, m) + (int64_t)P_SIGMA * RED_BLOCKS, nb);
         if (threadIdx.x == 0) {
             const cplx rho = scal[S_RHO]; const double st = scal[S_STATUS].x;
             const cplx alpha = cdiv(rho, sg);
@@ -125,8 +188,12 @@ __global__ __launch_bounds__(RED_THREADS) void k_bicg_rx(cplx* __restrict__ rs, 
 
 // partial[(P_GRAM + e) * RED_BLOCKS + block] = slice of <rs[a], rs[b]>, e = packed index of a <= b < NV (row after row)
 template <int NV>
-__global__ __launch_bounds__(RED_THREADS) void k_gram(const cplx* __restrict__ rs, int64_t ld, cplx* __restrict__ partial, int64_t n) {
+__global__ __launch_bounds__(RED_THREADS) void k_gram(Members B) {
     __shared__ cplx sh[RED_THREADS / 64];
+    const int m = B.m[blockIdx.y];
+    const int64_t n = B.n, ld = B.n;
+    const cplx* __restrict__ rs = m_work(B, m);
+    cplx* __restrict__ partial = m_partial(B, m);
     constexpr int NE = NV * (NV + 1) / 2;
     cplx acc[NE];
 #pragma unroll
@@ -155,12 +222,15 @@ __global__ __launch_bounds__(RED_THREADS) void k_gram(const cplx* __restrict__ r
     }
 }
 
-// One wave.  G from the partials (published in scal[S_G..], row-major NVMAX x NVMAX); G[0,0] <= tol^2: the Krylov space is
-// exhausted, status ST_EXHAUSTED and no solve of a singular G.  Otherwise gamma = G[1:,1:] \ G[1:,0] by LU with partial
-// pivoting (largest |.|^2 of the column, the lowest row on a tie) and sigma = -(sigma gamma_{l-1}): the factor of the MR
-// part and the sign flip that opens the next cycle.
-__global__ __launch_bounds__(64) void k_mr_solve(const cplx* __restrict__ partial, int nb, int nv, cplx* scal, double tol2, int cycle) {
+// One wave per member.  G from the partials (published in scal[S_G..], row-major NVMAX x NVMAX); G[0,0] <= tol^2: the
+// Krylov space is exhausted, status ST_EXHAUSTED and no solve of a singular G.  Otherwise gamma = G[1:,1:] \ G[1:,0] by LU
+// with partial pivoting (largest |.|^2 of the column, the lowest row on a tie) and sigma = -(sigma gamma_{l-1}): the
+// factor of the MR part and the sign flip that opens the next cycle.
+__global__ __launch_bounds__(64) void k_mr_solve(Members B, int nb, int nv, int cycle) {
     __shared__ cplx G[NVMAX][NVMAX];
+    const int m = B.m[blockIdx.y];
+    const cplx* __restrict__ partial = m_partial(B, m);
+    cplx* scal = m_scal(B, m);
     int e = 0;
     for (int a = 0; a < nv; ++a)
         for (int b = a; b < nv; ++b, ++e) {
@@ -171,7 +241,7 @@ __global__ __launch_bounds__(64) void k_mr_solve(const cplx* __restrict__ partia
     if (threadIdx.x != 0) return;
     for (int a = 0; a < nv; ++a) for (int b = 0; b < nv; ++b) scal[S_G + a * NVMAX + b] = G[a][b];
     if (scal[S_STATUS].x != 0.0) return;
-    if (G[0][0].x <= tol2) { scal[S_STATUS] = make_double2((double)ST_EXHAUSTED, (double)cycle); return; }
+    if (G[0][0].x <= B.tol2[m]) { scal[S_STATUS] = make_double2((double)ST_EXHAUSTED, (double)cycle); return; }
     const int l = nv - 1;
     cplx M[LMAX][LMAX], y[LMAX];
     for (int a = 0; a < l; ++a) { y[a] = G[a + 1][0]; for (int b = 0; b < l; ++b) M[a][b] = G[a + 1][b + 1]; }
@@ -203,10 +273,15 @@ __global__ __launch_bounds__(64) void k_mr_solve(const cplx* __restrict__ partia
 
 // us[0] -= sum gamma_i us[i+1]; x += sum gamma_i rs[i]; rs[0] -= sum gamma_i rs[i+1] (i < L); partial slot P_NORM: |rs[0]|^2
 template <int L>
-__global__ __launch_bounds__(RED_THREADS) void k_mr_update(cplx* __restrict__ us, cplx* __restrict__ rs, cplx* __restrict__ x, int64_t ld,
-                                                            const cplx* __restrict__ scal, cplx* __restrict__ partial, int64_t n) {
+__global__ __launch_bounds__(RED_THREADS) void k_mr_update(Members B, int64_t uoff) {
     __shared__ cplx sh[RED_THREADS / 64];
     __shared__ cplx gs[L];
+    const int m = B.m[blockIdx.y];
+    const int64_t n = B.n, ld = B.n;
+    cplx* __restrict__ rs = m_work(B, m);
+    cplx* __restrict__ us = m_work(B, m) + uoff;
+    cplx* __restrict__ x = B.x + (int64_t)m * n;
+    const cplx* __restrict__ scal = m_scal(B, m);
     if (scal[S_STATUS].x != 0.0) return;                 // (written by the kernels before this one only)
     if (threadIdx.x < L) gs[threadIdx.x] = scal[S_GAMMA + threadIdx.x];
     __syncthreads();
@@ -229,12 +304,14 @@ __global__ __launch_bounds__(RED_THREADS) void k_mr_update(cplx* __restrict__ us
         nrm.x = fma(r0.x, r0.x, fma(r0.y, r0.y, nrm.x));
     }
     const cplx s = block_sum(nrm, sh);
-    if (threadIdx.x == 0) partial[(int64_t)P_NORM * RED_BLOCKS + blockIdx.x] = s;
+    if (threadIdx.x == 0) m_partial(B, m)[(int64_t)P_NORM * RED_BLOCKS + blockIdx.x] = s;
 }
 
 // scal[S_RES] = sqrt(sum of the P_NORM partials), unless the cycle ended without an MR update
-__global__ __launch_bounds__(64) void k_res_finish(const cplx* __restrict__ partial, int nb, cplx* scal) {
-    const cplx s = finish_in_wave(partial + (int64_t)P_NORM * RED_BLOCKS, nb);
+__global__ __launch_bounds__(64) void k_res_finish(Members B, int nb) {
+    const int m = B.m[blockIdx.y];
+    cplx* scal = m_scal(B, m);
+    const cplx s = finish_in_wave(m_partial(B, m) + (int64_t)P_NORM * RED_BLOCKS, nb);
     if (threadIdx.x == 0 && scal[S_STATUS].x == 0.0) scal[S_RES] = make_double2(sqrt(s.x), 0.0);
 }
 
@@ -260,120 +337,208 @@ struct Event {
     ~Event() { if (e) (void)hipEventDestroy(e); }
 };
 
+// what the host keeps per member
+struct Solve {
+    double tol = 0.0, current = 0.0;
+    bool converged = false;
+    int bad = ST_OK, bad_cycle = 0;
+    int64_t cycles = 0, mvps = 0;
+};
+
 } // namespace
 
-// x (in/out) and b: device vectors; r_shadow (may be NULL): N complex on the device, or on the host (shadow_on_host).  Returns the breakdown code (ST_OK: none) and its cycle.
-static int bicgstabl_run(lsfc_plan* p, cplx* x, const cplx* b, const cplx* r_shadow, bool shadow_on_host, const lsfc_bicgstabl_opts& o, int l, int64_t maxmv,
-                         double reltol, double abstol, double* resnorm, int64_t cap, lsfc_gmres_result* res, int* bad_cycle) {
+// nrhs solves in lock step.  x (in/out) and b: nrhs device vectors back to back; r_shadow (may be NULL): nrhs vectors of N
+// complex on the device, or on the host (shadow_on_host); resnorm: nrhs rows of cap entries.  own_precond: the
+// preconditioner is the library's own object and takes all active members in group sweeps (precond_apply_batch_dev);
+// otherwise the callback gets one member at a time.  code[2 j], code[2 j + 1]: LSFC_BICG_* of member j and its cycle
+// (of the breakdown, else the last one).
+static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const cplx* r_shadow, bool shadow_on_host, bool own_precond,
+                          const lsfc_bicgstabl_opts& o, int l, int64_t maxmv, double reltol, double abstol, double* resnorm, int64_t cap,
+                          lsfc_gmres_result* res, int64_t* code) {
     const int64_t N = p->N;
     hipStream_t st = p->stream;
     const int nb = blas_red_blocks(N), nv = l + 1;
+    const int64_t wstride = (int64_t)(2 * l + 3) * N, uoff = (int64_t)nv * N, toff = 2 * (int64_t)nv * N;
     DevBuf<cplx> work, scal, partial;
-    work.alloc((size_t)(2 * l + 3) * (size_t)N);
-    scal.alloc(S_COUNT);
-    partial.alloc((size_t)P_SLOTS * RED_BLOCKS);
-    cplx* rs = work.p; cplx* us = rs + (size_t)nv * N; cplx* rt = us + (size_t)nv * N;
-    auto R = [&](int i) { return rs + (size_t)i * N; };
-    auto U = [&](int i) { return us + (size_t)i * N; };
-    auto slot = [&](int s) { return partial.p + (size_t)s * RED_BLOCKS; };
-    Pinned hs, vpin; hs.alloc(S_COUNT);
+    DevBuf<double> tol2;
+    work.alloc((size_t)nrhs * (size_t)wstride);
+    scal.alloc((size_t)nrhs * S_COUNT);
+    partial.alloc((size_t)nrhs * P_SLOTS * RED_BLOCKS);
+    tol2.alloc((size_t)nrhs);
+    auto R = [&](int m, int i) { return work.p + (size_t)m * (size_t)wstride + (size_t)i * N; };
+    auto U = [&](int m, int i) { return R(m, nv + i); };
+    Pinned hs, ht, vpin; hs.alloc((size_t)nrhs * S_COUNT); ht.alloc((size_t)(nrhs + 1) / 2);
     const bool host_cb = o.precond && !o.precond_on_device;
     if (host_cb) vpin.alloc((size_t)N);
     Event fetched; fetched.create();
+    Members base{};
+    base.work = work.p; base.x = x; base.scal = scal.p; base.partial = partial.p; base.tol2 = tol2.p; base.wstride = wstride; base.n = N;
+    auto members = [&](const std::vector<int>& list) { Members B = base; for (size_t a = 0; a < list.size(); ++a) B.m[a] = list[a]; return B; };
 
-    auto precondition = [&](cplx* v) {
+    // the operator on vector `in(m)` of every member of the list, in groups that share one pass of the pipeline
+    auto apply = [&](const std::vector<int>& list, auto&& in, auto&& out) {
+        for (size_t j0 = 0; j0 < list.size(); j0 += LSFC_MAX_BATCH) {
+            const int cnt = (int)std::min<size_t>(LSFC_MAX_BATCH, list.size() - j0);
+            VecBatch vb{};
+            for (int j = 0; j < cnt; ++j) { vb.x[j] = in(list[j0 + j]); vb.y[j] = out(list[j0 + j]); }
+            plan_convolve_batch_dev(p, cnt, vb, true, 1.0, p->omega * p->omega);
+        }
+    };
+    std::vector<cplx*> pv;
+    auto precondition = [&](const std::vector<int>& list, auto&& v) {
         if (!o.precond) return;
-        if (o.precond_on_device) {
-            const int rc = o.precond(o.precond_user, (double*)v, N);
-            if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+        if (own_precond) {
+            pv.clear();
+            for (int m : list) pv.push_back(v(m));
+            precond_apply_batch_dev((lsfc_precond*)o.precond_user, pv.data(), (int)pv.size(), st);
             return;
         }
-        LSFC_HIP(hipMemcpyAsync(vpin.p, v, (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        LSFC_HIP(hipStreamSynchronize(st));
-        const int rc = o.precond(o.precond_user, (double*)vpin.p, N);
-        if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-        LSFC_HIP(hipMemcpyAsync(v, vpin.p, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));
+        for (int m : list) {
+            if (o.precond_on_device) {
+                const int rc = o.precond(o.precond_user, (double*)v(m), N);
+                if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+                continue;
+            }
+            LSFC_HIP(hipMemcpyAsync(vpin.p, v(m), (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
+            LSFC_HIP(hipStreamSynchronize(st));
+            const int rc = o.precond(o.precond_user, (double*)vpin.p, N);
+            if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+            LSFC_HIP(hipMemcpyAsync(v(m), vpin.p, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));   // (the next copy into vpin is ordered after it on st)
+        }
     };
+    // all members' scalars in one copy
     auto fetch = [&]() {
-        LSFC_HIP(hipMemcpyAsync(hs.p, scal.p, (size_t)S_COUNT * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        LSFC_HIP(hipMemcpyAsync(hs.p, scal.p, (size_t)nrhs * S_COUNT * sizeof(cplx), hipMemcpyDeviceToHost, st));
         LSFC_HIP(hipEventRecord(fetched.e, st));
         LSFC_HIP(hipEventSynchronize(fetched.e));
     };
+    auto H = [&](int m) { return hs.p + (size_t)m * S_COUNT; };
+    // scal[S_RES] = ||rs[0]|| of the members of the list
+    auto norm0 = [&](const std::vector<int>& list) {
+        const Members B = members(list);
+        hipLaunchKernelGGL(k_dot, dim3(nb, (unsigned)list.size()), dim3(RED_THREADS), 0, st, B, (int64_t)0, (int64_t)0, (int)P_NORM);
+        hipLaunchKernelGGL(k_norm_finish, dim3(1, (unsigned)list.size()), dim3(64), 0, st, B, nb);
+    };
 
     // init: rs[0] = Pl \ (b - A x), us = 0, shadow residual, sigma = -1 (sigma = 1, negated by the first cycle)
-    int64_t mvps = 0;
-    if (o.initially_zero) LSFC_HIP(hipMemcpyAsync(R(0), b, (size_t)N * sizeof(cplx), hipMemcpyDeviceToDevice, st));
-    else {
-        plan_apply_dev(p, x, R(0));
-        hipLaunchKernelGGL(k_residual, dim3(ew_grid(N)), dim3(256), 0, st, R(0), b, N);
-        mvps = 1;
+    std::vector<Solve> S((size_t)nrhs);
+    std::vector<int> act((size_t)nrhs);
+    for (int m = 0; m < nrhs; ++m) act[(size_t)m] = m;
+    if (o.initially_zero) {
+        for (int m = 0; m < nrhs; ++m) LSFC_HIP(hipMemcpyAsync(R(m, 0), b + (size_t)m * N, (size_t)N * sizeof(cplx), hipMemcpyDeviceToDevice, st));
+    } else {
+        apply(act, [&](int m) { return (const cplx*)(x + (size_t)m * N); }, [&](int m) { return R(m, 0); });
+        hipLaunchKernelGGL(k_residual, dim3(ew_grid(N), (unsigned)nrhs), dim3(256), 0, st, members(act), b);
+        for (auto& s : S) s.mvps = 1;
     }
-    precondition(R(0));
-    LSFC_HIP(hipMemsetAsync(us, 0, (size_t)nv * (size_t)N * sizeof(cplx), st));
-    if (r_shadow && shadow_on_host) LSFC_HIP(hipMemcpyAsync(rt, r_shadow, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));
-    else LSFC_HIP(hipMemcpyAsync(rt, r_shadow ? r_shadow : R(0), (size_t)N * sizeof(cplx), hipMemcpyDeviceToDevice, st));
-    LSFC_HIP(hipMemsetAsync(scal.p, 0, (size_t)S_COUNT * sizeof(cplx), st));
-    static const cplx minus_one = { -1.0, 0.0 };
-    LSFC_HIP(hipMemcpyAsync(scal.p + S_SIGMA, &minus_one, sizeof(cplx), hipMemcpyHostToDevice, st));
-    blas_nrm2(R(0), slot(P_NORM), scal.p + S_RES, N, st);
+    precondition(act, [&](int m) { return R(m, 0); });
+    for (int m = 0; m < nrhs; ++m) {
+        LSFC_HIP(hipMemsetAsync(U(m, 0), 0, (size_t)nv * (size_t)N * sizeof(cplx), st));
+        const cplx* sh = r_shadow ? r_shadow + (size_t)m * N : R(m, 0);
+        LSFC_HIP(hipMemcpyAsync(R(m, 2 * nv), sh, (size_t)N * sizeof(cplx), r_shadow && shadow_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    }
+    for (size_t i = 0; i < (size_t)nrhs * S_COUNT; ++i) hs.p[i] = make_double2(0.0, 0.0);
+    for (int m = 0; m < nrhs; ++m) H(m)[S_SIGMA] = make_double2(-1.0, 0.0);
+    LSFC_HIP(hipMemcpyAsync(scal.p, hs.p, (size_t)nrhs * S_COUNT * sizeof(cplx), hipMemcpyHostToDevice, st));
+    norm0(act);
+    LSFC_HIP(hipGetLastError());
     fetch();
-    const double beta0 = hs.p[S_RES].x;
-    const double tol = std::max(reltol * beta0, abstol);
-    double current = beta0;
-    bool converged = beta0 <= tol;
-    int bad = std::isfinite(beta0) ? ST_OK : ST_RESIDUAL;
-    *bad_cycle = 0;
-    int64_t cycles = 0;
+    double* t2 = (double*)ht.p;
+    for (int m = 0; m < nrhs; ++m) {
+        Solve& s = S[(size_t)m];
+        const double beta0 = H(m)[S_RES].x;
+        s.tol = std::max(reltol * beta0, abstol);
+        s.current = beta0;
+        s.converged = beta0 <= s.tol;
+        s.bad = std::isfinite(beta0) ? ST_OK : ST_RESIDUAL;
+        t2[m] = s.tol * s.tol;
+    }
+    LSFC_HIP(hipMemcpyAsync(tol2.p, t2, (size_t)nrhs * sizeof(double), hipMemcpyHostToDevice, st));
+    auto running = [&](const Solve& s) { return !s.converged && s.bad == ST_OK && s.mvps < maxmv; };
+    auto still_active = [&]() { std::vector<int> a; for (int m = 0; m < nrhs; ++m) if (running(S[(size_t)m])) a.push_back(m); return a; };
+    act = still_active();
+    std::vector<int> broke;
 
-    while (!converged && bad == ST_OK && mvps < maxmv) {
+    // every member of the list is in the same cycle: all start at 0 and a member never rejoins
+    for (int64_t cycles = 0; !act.empty(); ++cycles) {
         const int cyc = (int)std::min<int64_t>(cycles + 1, 1 << 30);
+        const Members B = members(act);
+        const dim3 grid((unsigned)nb, (unsigned)act.size()), one(1, (unsigned)act.size());
         for (int j = 0; j < l; ++j) {                       // BiCG part
-            blas_dot_partial(rt, R(j), slot(P_RHO), N, st);
+            hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, st, B, toff, (int64_t)j * N, (int)P_RHO);
             dispatch<1, LMAX>(j + 1, [&](auto nvj) {
-                hipLaunchKernelGGL((k_bicg_u<decltype(nvj)::value>), dim3(nb), dim3(RED_THREADS), 0, st, us, (const cplx*)rs, N, (const cplx*)slot(P_RHO), nb, scal.p, cyc, N);
+                hipLaunchKernelGGL((k_bicg_u<decltype(nvj)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff, nb, cyc);
             });
-            plan_apply_dev(p, U(j), U(j + 1));
-            precondition(U(j + 1));
-            blas_dot_partial(rt, U(j + 1), slot(P_SIGMA), N, st);
+            apply(act, [&](int m) { return (const cplx*)U(m, j); }, [&](int m) { return U(m, j + 1); });
+            precondition(act, [&](int m) { return U(m, j + 1); });
+            hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, st, B, toff, uoff + (int64_t)(j + 1) * N, (int)P_SIGMA);
             dispatch<1, LMAX>(j + 1, [&](auto nvj) {
-                hipLaunchKernelGGL((k_bicg_rx<decltype(nvj)::value>), dim3(nb), dim3(RED_THREADS), 0, st, rs, (const cplx*)us, x, N, (const cplx*)slot(P_SIGMA), nb, scal.p, cyc, N);
+                hipLaunchKernelGGL((k_bicg_rx<decltype(nvj)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff, nb, cyc);
             });
-            plan_apply_dev(p, R(j), R(j + 1));
-            precondition(R(j + 1));
-            mvps += 2;
+            apply(act, [&](int m) { return (const cplx*)R(m, j); }, [&](int m) { return R(m, j + 1); });
+            precondition(act, [&](int m) { return R(m, j + 1); });
         }
         dispatch<2, NVMAX>(nv, [&](auto nvc) {              // MR part
-            hipLaunchKernelGGL((k_gram<decltype(nvc)::value>), dim3(nb), dim3(RED_THREADS), 0, st, (const cplx*)rs, N, partial.p, N);
+            hipLaunchKernelGGL((k_gram<decltype(nvc)::value>), grid, dim3(RED_THREADS), 0, st, B);
         });
-        hipLaunchKernelGGL(k_mr_solve, dim3(1), dim3(64), 0, st, (const cplx*)partial.p, nb, nv, scal.p, tol * tol, cyc);
+        hipLaunchKernelGGL(k_mr_solve, one, dim3(64), 0, st, B, nb, nv, cyc);
         dispatch<1, LMAX>(l, [&](auto lc) {
-            hipLaunchKernelGGL((k_mr_update<decltype(lc)::value>), dim3(nb), dim3(RED_THREADS), 0, st, us, rs, x, N, (const cplx*)scal.p, partial.p, N);
+            hipLaunchKernelGGL((k_mr_update<decltype(lc)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff);
         });
-        hipLaunchKernelGGL(k_res_finish, dim3(1), dim3(64), 0, st, (const cplx*)partial.p, nb, scal.p);
+        hipLaunchKernelGGL(k_res_finish, one, dim3(64), 0, st, B, nb);
         LSFC_HIP(hipGetLastError());
         fetch();
-        const int status = (int)hs.p[S_STATUS].x;
-        if (status == ST_OK) {
-            current = hs.p[S_RES].x;
-            if (!std::isfinite(current)) { bad = ST_RESIDUAL; *bad_cycle = cyc; }
-        } else if (status == ST_EXHAUSTED) {
-            current = std::sqrt(hs.p[S_G].x);
-            converged = true;
-        } else {
-            // breakdown: x and rs[0] are the last finite pair -- the residual of that iterate decides (a breakdown with
-            // the residual already below the tolerance is the exhausted Krylov space met one step early)
-            bad = status; *bad_cycle = (int)hs.p[S_STATUS].y;
-            blas_nrm2(R(0), slot(P_NORM), scal.p + S_RES, N, st);
-            fetch();
-            current = hs.p[S_RES].x;
+        broke.clear();
+        for (int m : act) {
+            Solve& s = S[(size_t)m];
+            s.mvps += 2 * l;
+            const int status = (int)H(m)[S_STATUS].x;
+            if (status == ST_OK) {
+                s.current = H(m)[S_RES].x;
+                if (!std::isfinite(s.current)) { s.bad = ST_RESIDUAL; s.bad_cycle = cyc; }
+            } else if (status == ST_EXHAUSTED) {
+                s.current = std::sqrt(H(m)[S_G].x);
+                s.converged = true;
+            } else {
+                // breakdown: x and rs[0] are the last finite pair -- the residual of that iterate decides (a breakdown with
+                // the residual already below the tolerance is the exhausted Krylov space met one step early)
+                s.bad = status; s.bad_cycle = (int)H(m)[S_STATUS].y;
+                broke.push_back(m);
+            }
         }
-        if (resnorm && cycles < cap) resnorm[cycles] = current;
-        ++cycles;
-        converged = converged || current <= tol;
+        if (!broke.empty()) {
+            norm0(broke);
+            LSFC_HIP(hipGetLastError());
+            fetch();
+            for (int m : broke) S[(size_t)m].current = H(m)[S_RES].x;
+        }
+        for (int m : act) {
+            Solve& s = S[(size_t)m];
+            if (resnorm && s.cycles < cap) resnorm[(size_t)m * (size_t)cap + (size_t)s.cycles] = s.current;
+            ++s.cycles;
+            s.converged = s.converged || s.current <= s.tol;
+        }
+        act = still_active();
     }
     LSFC_HIP(hipStreamSynchronize(st));
-    res->iters = cycles; res->mvps = mvps; res->converged = converged ? 1 : 0; res->final_resnorm = current;
-    return converged ? ST_OK : bad;
+    for (int m = 0; m < nrhs; ++m) {
+        const Solve& s = S[(size_t)m];
+        res[m].iters = s.cycles; res[m].mvps = s.mvps; res[m].converged = s.converged ? 1 : 0; res[m].final_resnorm = s.current;
+        code[2 * m] = s.converged ? LSFC_BICG_CONVERGED : (s.bad != ST_OK ? s.bad : LSFC_BICG_MAX_MV);
+        code[2 * m + 1] = (!s.converged && s.bad != ST_OK) ? s.bad_cycle : s.cycles;
+    }
+}
+
+// the argument checks of both entry points, before any device call
+static void check_args(const char* fn, lsfc_plan* plan, const double* x, const double* b, const lsfc_bicgstabl_opts* opts, const double* resnorm,
+                       int64_t resnorm_cap, const lsfc_gmres_result* result, int memspace) {
+    LSFC_REQUIRE(opts, "%s: NULL opts", fn);
+    LSFC_REQUIRE(opts->l >= 1 && opts->l <= LMAX, "%s: l = %d is outside 1..%d", fn, opts->l, LMAX);
+    for (int i = 0; i < 4; ++i) LSFC_REQUIRE(opts->reserved[i] == 0, "%s: reserved[%d] is not zero", fn, i);
+    LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "%s: unknown memspace %d", fn, memspace);
+    LSFC_REQUIRE(plan && x && b && result, "%s: NULL argument", fn);
+    LSFC_REQUIRE(resnorm || resnorm_cap <= 0, "%s: NULL resnorm with a capacity of %lld", fn, (long long)resnorm_cap);
+    LSFC_REQUIRE(!plan->multi && !plan->dist, "%s runs on a single-device plan (not a distributed or multi-device one)", fn);
 }
 
 } // namespace lsfc
@@ -382,16 +547,9 @@ using namespace lsfc;
 
 extern "C" int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts, double* resnorm,
                               int64_t resnorm_cap, lsfc_gmres_result* result, int memspace) {
-    int bad = ST_OK, bad_cycle = 0; bool notconv = false;
+    int64_t code[2] = { 0, 0 }; bool notconv = false;
     const int rc = guarded([&] {
-        // argument checks, before any device call
-        LSFC_REQUIRE(opts, "lsfc_bicgstabl: NULL opts");
-        LSFC_REQUIRE(opts->l >= 1 && opts->l <= LMAX, "lsfc_bicgstabl: l = %d is outside 1..%d", opts->l, LMAX);
-        for (int i = 0; i < 4; ++i) LSFC_REQUIRE(opts->reserved[i] == 0, "lsfc_bicgstabl: reserved[%d] is not zero", i);
-        LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "lsfc_bicgstabl: unknown memspace %d", memspace);
-        LSFC_REQUIRE(plan && x && b && result, "lsfc_bicgstabl: NULL argument");
-        LSFC_REQUIRE(resnorm || resnorm_cap <= 0, "lsfc_bicgstabl: NULL resnorm with a capacity of %lld", (long long)resnorm_cap);
-        LSFC_REQUIRE(!plan->multi && !plan->dist, "lsfc_bicgstabl runs on a single-device plan (not a distributed or multi-device one)");
+        check_args("lsfc_bicgstabl", plan, x, b, opts, resnorm, resnorm_cap, result, memspace);
         const int l = opts->l;
         const int64_t N = plan->N;
         const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
@@ -416,12 +574,66 @@ extern "C" int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const
             LSFC_HIP(hipMemcpy(plan->ys.p, b, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice));
             xd = plan->xs.p; bd = plan->ys.p;
         }
-        bad = bicgstabl_run(plan, (cplx*)xd, bd, sd, host, *opts, l, maxmv, reltol, abstol, resnorm, resnorm_cap > 0 ? resnorm_cap : 0, result, &bad_cycle);
+        // (the callback is called as given: one member has nobody to meet at the preconditioner)
+        bicgstabl_run(plan, 1, (cplx*)xd, bd, sd, host, false, *opts, l, maxmv, reltol, abstol, resnorm, resnorm_cap > 0 ? resnorm_cap : 0, result, code);
         if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost));
         notconv = !result->converged;
     });
     if (rc != LSFC_OK || !notconv) return rc;
-    if (bad != ST_OK) set_last_error("bicgstabl: breakdown in cycle %d: %s; x is the last finite iterate", bad_cycle, ST_NAME[bad]);
+    if (code[0] != LSFC_BICG_MAX_MV) set_last_error("bicgstabl: breakdown in cycle %d: %s; x is the last finite iterate", (int)code[1], ST_NAME[code[0]]);
     else set_last_error("bicgstabl: max_mv_products reached without convergence");
     return LSFC_ENOTCONV;
+}
+
+extern "C" int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts, double* resnorm,
+                                    int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* status, int memspace) {
+    std::vector<int64_t> code;
+    const int rc = guarded([&] {
+        LSFC_REQUIRE(nrhs >= 1 && nrhs <= NRHS_MAX, "lsfc_bicgstabl_batch: nrhs = %lld is outside 1..%d", (long long)nrhs, NRHS_MAX);
+        check_args("lsfc_bicgstabl_batch", plan, x, b, opts, resnorm, resnorm_cap, results, memspace);
+        const int l = opts->l, n = (int)nrhs;
+        const int64_t N = plan->N;
+        const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
+        const double reltol = opts->reltol >= 0 ? opts->reltol : std::sqrt(2.220446049250313e-16);
+        const double abstol = opts->abstol > 0 ? opts->abstol : 0.0;
+        const bool own_precond = opts->precond_on_device && opts->precond == &lsfc_precond_callback;
+        if (own_precond)
+            LSFC_REQUIRE(opts->precond_user && precond_size((lsfc_precond*)opts->precond_user) == N, "lsfc_bicgstabl_batch: preconditioner: size mismatch (%lld vs %lld)",
+                         (long long)N, opts->precond_user ? (long long)precond_size((lsfc_precond*)opts->precond_user) : -1LL);
+        LSFC_HIP(hipSetDevice(plan->device));
+        // memory rule: nrhs (2 l + 3) work vectors; host vectors: the staged x and b (2 nrhs vectors) on top
+        const bool host = memspace == LSFC_MEM_HOST;
+        const bool stage = host && plan->xs.n < (size_t)n * (size_t)N;
+        {
+            size_t free_b = 0, total_b = 0;
+            LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
+            const double per = ((double)(2 * l + 3) + (stage ? 2.0 : 0.0)) * (double)N * sizeof(cplx);
+            if ((double)n * per > (double)free_b)
+                fail(LSFC_ENOMEM, "lsfc_bicgstabl_batch: %d right-hand sides x (2 l + 3 = %d work vectors%s) of %lld complex need %.1f GB of device memory, "
+                     "%.1f GB are free -- %lld right-hand sides would fit; solve fewer per call or lower l", n, 2 * l + 3, stage ? " + staged x and b" : "",
+                     (long long)N, (double)n * per / 1e9, (double)free_b / 1e9, (long long)((double)free_b / per));
+        }
+        const cplx* xd = (const cplx*)x; const cplx* bd = (const cplx*)b; const cplx* sd = (const cplx*)opts->r_shadow;
+        const size_t bytes = (size_t)n * (size_t)N * sizeof(cplx);
+        if (host) {
+            if (stage) { plan->xs.alloc((size_t)n * (size_t)N); plan->ys.alloc((size_t)n * (size_t)N); }
+            LSFC_HIP(hipMemcpy(plan->xs.p, x, bytes, hipMemcpyHostToDevice));
+            LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
+            xd = plan->xs.p; bd = plan->ys.p;
+        }
+        code.assign((size_t)(2 * n), 0);
+        bicgstabl_run(plan, n, (cplx*)xd, bd, sd, host, own_precond, *opts, l, maxmv, reltol, abstol, resnorm, resnorm_cap > 0 ? resnorm_cap : 0, results, code.data());
+        if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, bytes, hipMemcpyDeviceToHost));
+        if (status) for (size_t i = 0; i < code.size(); ++i) status[i] = code[i];
+    });
+    if (rc != LSFC_OK) return rc;
+    // LSFC_OK whatever the members did (the rule of lsfc_gmres_batch); the message names the first that did not converge
+    for (int64_t j = 0; j < nrhs; ++j) {
+        const int64_t c = code[(size_t)(2 * j)], cyc = code[(size_t)(2 * j + 1)];
+        if (c == LSFC_BICG_CONVERGED) continue;
+        if (c == LSFC_BICG_MAX_MV) set_last_error("bicgstabl_batch: right-hand side %lld: max_mv_products reached without convergence in cycle %lld", (long long)j, (long long)cyc);
+        else set_last_error("bicgstabl_batch: right-hand side %lld: breakdown in cycle %lld: %s; its x is the last finite iterate", (long long)j, (long long)cyc, ST_NAME[c]);
+        break;
+    }
+    return LSFC_OK;
 }

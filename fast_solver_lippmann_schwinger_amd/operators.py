@@ -510,6 +510,83 @@ def bicgstabl_(x, A, b, l=2, Pl=None, max_mv_products=None, abstol=0.0, reltol=N
     return x
 
 
+_BICG_REASON = {L.LSFC_BICG_RHO: "rho is not finite", L.LSFC_BICG_SIGMA: "sigma is zero or not finite",
+                L.LSFC_BICG_BETA: "beta = rho / sigma is not finite", L.LSFC_BICG_ALPHA: "alpha = rho / sigma is not finite",
+                L.LSFC_BICG_GAMMA: "gamma (singular or non-finite Gram matrix)", L.LSFC_BICG_RESIDUAL: "the residual norm is not finite"}
+
+
+def bicgstabl_batch_(X, A, B, l=2, Pl=None, max_mv_products=None, abstol=0.0, reltol=None, log=False, Pl_on_device=False,
+                     r_shadow=None, initially_zero=False):
+    """``bicgstabl_`` for several right-hand sides in lock step (lsfc_bicgstabl_batch): rows of B, solutions in the rows of
+    X (contiguous, updated in place; numpy, or torch CUDA tensors).  Every step of a cycle is one launch over the rows
+    still running, the operator takes them in groups, and a ``SparsifyingPreconditioner`` takes them in group sweeps; any
+    other ``Pl`` is called for one row at a time (a host vector, or a torch CUDA tensor with ``Pl_on_device=True``).
+    Each row has its own tolerance and stopping test and its iterates are those of ``bicgstabl_`` on that row alone.
+    ``r_shadow``: None or one shadow residual per row, in the memory space of X.  nrhs <= 64; device memory
+    nrhs (2 l + 3) vectors.  Returns X or (X, [ConvergenceHistory per row]); ``.message`` of a row that did not converge
+    names the reason (max_mv_products, or the scalar of the breakdown) and the cycle."""
+    N = A.N
+    torch_in = _is_torch(X)
+    if torch_in:
+        if X.dim() != 2 or tuple(B.shape) != tuple(X.shape):
+            raise ValueError(f"DimensionMismatch: X and B must both be (nrhs, {N})")
+        nrhs = X.shape[0]
+        px, sx, keepx = _vec(X.reshape(-1), N, "X", count=nrhs, plan=A._plan)
+        pb, sb, keepb = _vec(B.reshape(-1), N, "B", count=nrhs)
+        if keepx.data_ptr() != X.data_ptr():
+            raise TypeError("X must be contiguous (it is updated in place)")
+    else:
+        if not (isinstance(X, np.ndarray) and X.dtype == np.complex128 and X.flags.c_contiguous and X.ndim == 2 and X.shape[1] == N):
+            raise TypeError(f"X must be a C-contiguous complex128 array of shape (nrhs, {N}) (it is updated in place)")
+        nrhs = X.shape[0]
+        Bc = np.ascontiguousarray(B, dtype=np.complex128)
+        if Bc.shape != X.shape:
+            raise ValueError("DimensionMismatch: B")
+        px, sx, pb, sb, keepb = X.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, Bc.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, Bc
+    if sx != sb:
+        raise TypeError("X and B must live in the same memory space")
+    opts = L.BicgstablOpts()
+    opts.l = int(l)
+    opts.max_mv_products = int(max_mv_products) if max_mv_products is not None else 0
+    opts.reltol = float(reltol) if reltol is not None else -1.0
+    opts.abstol = float(abstol)
+    opts.initially_zero = 1 if initially_zero else 0
+    keeps = None
+    if r_shadow is not None:
+        ps, ss, keeps = _vec(r_shadow.reshape(-1) if torch_in else np.asarray(r_shadow).reshape(-1), N, "r_shadow", count=nrhs)
+        if ss != sx:
+            raise TypeError("r_shadow and X must live in the same memory space")
+        opts.r_shadow = ps
+    err = []
+    cb = _precond_opts(opts, Pl, Pl_on_device, A, X, sx, err)
+    cap = (opts.max_mv_products if opts.max_mv_products > 0 else N) // (2 * max(opts.l, 1)) + 2
+    cap = max(1, min(cap, 1 << 20))
+    res = (L.GmresResult * max(nrhs, 1))()
+    resnorm = np.zeros((max(nrhs, 1), cap), dtype=np.float64)
+    status = np.zeros((max(nrhs, 1), 2), dtype=np.int64)
+    rc = L.load().lsfc_bicgstabl_batch(A._plan, px, pb, nrhs, C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, res,
+                                       status.ctypes.data_as(C.c_void_p), sx)
+    del cb, keeps, keepb
+    if err:
+        raise err[0]
+    L.check(rc)
+    if not log:
+        return X
+    hists = []
+    for j in range(nrhs):
+        h = ConvergenceHistory(resnorm[j, :min(res[j].iters, cap)].copy(), int(res[j].iters), int(res[j].mvps), bool(res[j].converged))
+        code, cyc = int(status[j, 0]), int(status[j, 1])
+        h.status = (code, cyc)
+        if code == L.LSFC_BICG_CONVERGED:
+            h.message = ""
+        elif code == L.LSFC_BICG_MAX_MV:
+            h.message = "bicgstabl: max_mv_products reached without convergence"
+        else:
+            h.message = f"bicgstabl: breakdown in cycle {cyc}: {_BICG_REASON.get(code, code)}; x is the last finite iterate"
+        hists.append(h)
+    return X, hists
+
+
 def apply_batch(M, B, mode=0):
     """Rows of B (nrhs, N) through the operator in batched passes (lsfc_apply_batch): mode 0 ``M * b``, 1 bare
     convolution, 2 convolution of nu .* b.  The multi-vector form of src/FastConvolution3D.jl:146-159."""

@@ -219,7 +219,7 @@ int lsfc_gmres_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, 
  * the cycle.  LSFC_ENOTCONV also when max_mv_products is reached (x still updated).
  * LSFC_EINVAL, before any device call: NULL opts, l outside 1..8, a non-zero reserved word, a bad memspace, NULL plan, x,
  * b or result, a distributed or multi-device plan.
- * Out of scope: multi-device / distributed plans, and a lock-step batch form like lsfc_gmres_batch. */
+ * Out of scope: multi-device / distributed plans. */
 typedef struct lsfc_bicgstabl_opts {
     int     l;               /* 1..8; IterativeSolvers' default is 2                                   */
     int64_t max_mv_products; /* <=0: N                                                                 */
@@ -234,6 +234,40 @@ typedef struct lsfc_bicgstabl_opts {
 
 int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts,
                    double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* result, int memspace);
+
+/* How a member of lsfc_bicgstabl_batch ended (status[2 j]); 2..7 name the scalar of a breakdown. */
+#define LSFC_BICG_CONVERGED 0   /* within its tolerance (an exhausted Krylov space included)          */
+#define LSFC_BICG_MAX_MV    1   /* max_mv_products reached                                            */
+#define LSFC_BICG_RHO       2   /* rho is not finite                                                  */
+#define LSFC_BICG_SIGMA     3   /* sigma is zero or not finite                                        */
+#define LSFC_BICG_BETA      4   /* beta = rho / sigma is not finite                                   */
+#define LSFC_BICG_ALPHA     5   /* alpha = rho / sigma is not finite                                  */
+#define LSFC_BICG_GAMMA     6   /* singular or non-finite Gram matrix of the minimal-residual step    */
+#define LSFC_BICG_RESIDUAL  7   /* the residual norm is not finite                                    */
+
+/* nrhs solves of lsfc_bicgstabl in lock step, the BiCGStab(l) form of lsfc_gmres_batch (x, b: nrhs vectors back to back;
+ * resnorm: nrhs rows of resnorm_cap entries; results[nrhs]; opts->r_shadow: NULL or nrhs vectors back to back in
+ * `memspace`; l, the tolerances, the cap, initially_zero and the preconditioner are shared).  The kernel sequence of a
+ * cycle does not depend on the data, so every step of a cycle is ONE launch over the members still running and the host
+ * reads the scalars of all of them in one copy per cycle: no host threads.  The operator is applied to the running
+ * members in groups (see lsfc_apply_batch); with precond = lsfc_precond_callback and precond_on_device = 1 the
+ * preconditioner takes them in lsfc_precond_apply_batch-style group sweeps on the plan's stream; any other callback
+ * (host, or the caller's own device callback) is called for one member at a time.
+ * Member j has its own tol = max(reltol * ||Pl^-1 r0_j||, abstol) and stopping test.  A member that has converged,
+ * broken down or reached max_mv_products leaves the group, its x final; a breakdown in one member does not touch the
+ * others.  Member j's iterates, history, iters, mvps and converged are those of lsfc_bicgstabl on that right-hand side
+ * alone: bit for bit wherever the batched operator and preconditioner applies are bitwise member-independent (the rocFFT
+ * pipelines, objects of lsfc_precond_create, block-tridiagonal objects); on the pruned pipeline with a fused batch pass
+ * to the rounding of lsfc_apply_batch.
+ * status (may be NULL): 2 * nrhs entries, (LSFC_BICG_* code, cycle) per member; the cycle of the breakdown, else the
+ * number of cycles run.
+ * Returns LSFC_OK even if some member did not converge (check results[j].converged); lsfc_last_error then names the first
+ * such member, its reason and its cycle.  LSFC_EINVAL, before any device call: the checks of lsfc_bicgstabl, nrhs outside
+ * 1..64, NULL results.  Device memory: nrhs * (2 l + 3) work vectors of N complex, with LSFC_MEM_HOST the staged x and b
+ * (2 nrhs vectors) on top, checked before anything is allocated: LSFC_ENOMEM with the figures and the largest nrhs that
+ * fits. */
+int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
+                         double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* status, int memspace);
 
 /* ---- device-resident SparsifyingPreconditioner apply ------------------------ */
 

@@ -374,4 +374,35 @@ function bicgstabl_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Comp
     log ? (x, resnorm[1:min(res[].iters, cap)]) : x
 end
 
+# bicgstabl_hip! for several right-hand sides in lock step, lsfc_bicgstabl_batch: columns of B, solutions in the columns of
+# X, r_shadow (optional) one shadow residual per column.  Every step of a cycle is one launch over the columns still
+# running; each column has its own tolerance and stopping test and leaves when it has converged, broken down or reached
+# max_mv_products.  A SparsifyingPreconditionerHIP takes the running columns in group sweeps; any other Pl gets one host
+# vector at a time.  Returns (X, histories, status): status[:, j] = (LSFC_BICG_* code, cycle) of column j (0 converged,
+# 1 max_mv_products, 2..7 the scalar of a breakdown: rho, sigma, beta, alpha, gamma, residual).  At most 64 columns.
+function bicgstabl_batch_hip!(X::Matrix{Complex{Float64}}, M::FastMHIP, B::Matrix{Complex{Float64}}, l::Int=2; Pl=nothing,
+                              max_mv_products=size(B, 1), abstol=0.0, reltol=sqrt(eps(Float64)), initially_zero=false, r_shadow=nothing)
+    size(X) == size(B) || throw(DimensionMismatch("X and B"))
+    nrhs = size(B, 2)
+    box = Ref{Any}(Pl)
+    if Pl isa SparsifyingPreconditionerHIP
+        cb = cglobal((:lsfc_precond_callback, liblsfc)); user = Pl.pc; ondev = Cint(1)
+    else
+        cb = Pl === nothing ? C_NULL : @cfunction(_precond_trampoline, Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64))
+        user = Pl === nothing ? C_NULL : pointer_from_objref(box); ondev = Cint(0)
+    end
+    shadow = r_shadow === nothing ? zeros(Complex{Float64}, 0, 0) : convert(Matrix{Complex{Float64}}, r_shadow)
+    r_shadow === nothing || size(shadow) == size(B) || throw(DimensionMismatch("r_shadow"))
+    cap = max(1, min(div(max_mv_products > 0 ? max_mv_products : size(B, 1), 2 * max(l, 1)) + 2, 1 << 20))
+    res = fill(GmresResult(0, 0, 0, 0.0), nrhs); resnorm = zeros(Float64, cap, nrhs); status = zeros(Int64, 2, nrhs)
+    GC.@preserve box shadow begin
+        opts = Ref(BicgstablOpts(l, max_mv_products, reltol, abstol, initially_zero ? 1 : 0, cb, user, ondev,
+                                 r_shadow === nothing ? C_NULL : Ptr{Cvoid}(pointer(shadow)), (Cint(0), Cint(0), Cint(0), Cint(0))))
+        check(ccall((:lsfc_bicgstabl_batch, liblsfc), Cint,
+                    (Ptr{Cvoid}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Int64, Ref{BicgstablOpts}, Ptr{Float64}, Int64, Ptr{GmresResult},
+                     Ptr{Int64}, Cint), M.plan, X, B, nrhs, opts, resnorm, cap, res, status, 0))
+    end
+    X, [resnorm[1:min(res[j].iters, cap), j] for j in 1:nrhs], status
+end
+
 end # module

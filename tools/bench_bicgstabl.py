@@ -8,10 +8,16 @@
                      neither fits.  GMRES has no check of its own for a single solve, so the tool applies its rule
                      ((restart + 2) vectors against the free memory) and does not call it otherwise: nothing is run into an
                      out-of-memory failure.
+  batch N [NRHS ...] plane waves of NRHS different directions (default 1 2 4 8) on the cube of N at l = 2, device tensors,
+                     reltol 1e-6: one bicgstabl_batch_ call against back-to-back bicgstabl_ calls on the same right-hand sides,
+                     alternated over three repetitions after a warm-up of both; without a preconditioner, and with
+                     SparsifyingPreconditioner.from_operator where its dense blocks fit (N <= 64).  Appended to
+                     profiles/bicgstabl_batch.jsonl: wall times, cycles and mvps per member, batch_info of the
+                     preconditioner, peak device memory
   kernels N L [L ...] three cycles of bicgstabl_ at each l on the cube of N, nothing recorded: the target of
                      `rocprofv3 --kernel-trace --stats -- python3 tools/bench_bicgstabl.py kernels 512 4 8`
                      (profiles/bicgstabl_kernel_stats.csv; the template argument in a kernel's name is its vector count)
-usage: python tools/bench_bicgstabl.py solve 256 512 | largest | kernels 512 4 8"""
+usage: python tools/bench_bicgstabl.py solve 256 512 | largest | batch 48 1 2 4 8 | kernels 512 4 8"""
 import json
 import os
 import sys
@@ -27,12 +33,13 @@ import fast_solver_lippmann_schwinger_amd as lsfc  # noqa: E402
 from tools.bench_configs import bump  # noqa: E402
 
 OUT = os.path.join(ROOT, "profiles", "bicgstabl.jsonl")
+OUT_BATCH = os.path.join(ROOT, "profiles", "bicgstabl_batch.jsonl")
 
 
-def emit(rec):
+def emit(rec, out=OUT):
     line = json.dumps(rec)
     print(line, flush=True)
-    with open(OUT, "a") as f:
+    with open(out, "a") as f:
         f.write(line + "\n")
 
 
@@ -145,6 +152,57 @@ def largest(sizes):
             break
 
 
+# incident directions of the batch measurement (unit vectors; tests/plasma_example.jl:160-176 uses two)
+DIRECTIONS = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1), (1, -1, 0)]
+
+
+def batch_problem(n, nrhs):
+    M, _ = problem(n)
+    k = float(n)
+    x = torch.from_numpy(-0.5 + np.arange(n) / n).cuda()
+    rhs = torch.empty((nrhs, n ** 3), dtype=torch.complex128, device="cuda")
+    for j in range(nrhs):
+        d = np.array(DIRECTIONS[j % len(DIRECTIONS)], dtype=float)
+        d /= np.linalg.norm(d) * (1 + j // len(DIRECTIONS))
+        ex, ey, ez = (torch.exp(1j * k * c * x) for c in d)                        # separable: exp(i k d . r), x fastest
+        u_inc = (ez[:, None, None] * ey[None, :, None] * ex[None, None, :]).reshape(-1)
+        rhs[j] = M * u_inc
+        rhs[j].sub_(u_inc).neg_()
+    return M, rhs
+
+
+def batch(n, counts, reltol=1e-6, reps=3):
+    for precond in (False, True):
+        if precond and n > 64:
+            emit({"mode": "batch", "n": n, "preconditioner": "blocktri", "error": f"not run: {n} dense blocks of {n * n}^2 complex do not fit"}, OUT_BATCH)
+            continue
+        for nrhs in counts:
+            M, rhs = batch_problem(n, nrhs)
+            P = lsfc.SparsifyingPreconditioner.from_operator(M) if precond else None
+            kw = dict(l=2, Pl=P, reltol=reltol, log=True)
+            one_by_one = lambda: [lsfc.bicgstabl_(torch.zeros_like(rhs[j]), M, rhs[j], **kw) for j in range(nrhs)]   # noqa: E731
+            together = lambda: lsfc.bicgstabl_batch_(torch.zeros_like(rhs), M, rhs, **kw)                            # noqa: E731
+            one_by_one(), together()                                                 # warm-up of every shape both use
+            t_single, t_batch, peak = [], [], 0.0
+            for _ in range(reps):                                                    # alternated
+                singles, t, _pm = timed(one_by_one)
+                t_single.append(t)
+                (X, hs), t, pm = timed(together)
+                t_batch.append(t)
+                peak = max(peak, pm.peak_used_GB)
+            diff = max(float(torch.linalg.norm(X[j] - singles[j][0]) / torch.linalg.norm(singles[j][0])) for j in range(nrhs))
+            emit({"mode": "batch", "n": n, "N": n ** 3, "nrhs": nrhs, "l": 2, "reltol": reltol, "preconditioner": "blocktri" if precond else None,
+                  "seconds_batch": t_batch, "seconds_one_by_one": t_single, "ratio_one_by_one_over_batch": min(t_single) / min(t_batch),
+                  "cycles": [h.iters for h in hs], "mvps": [h.mvps for h in hs], "converged": [h.isconverged for h in hs],
+                  "cycles_single": [h.iters for _, h in singles], "max_rel_diff_to_single": diff,
+                  "batch_info": P.batch_info() if precond else None, "peak_used_GB": peak}, OUT_BATCH)
+            if P is not None:
+                P.close()
+            M.close()
+            del M, rhs, X, singles
+            torch.cuda.empty_cache()
+
+
 def kernels(n, ls):
     M, rhs = problem(n)
     for l in ls:
@@ -161,6 +219,8 @@ if __name__ == "__main__":
             solve(n)
     elif mode == "largest":
         largest(sizes or [512, 640, 768, 1024])
+    elif mode == "batch" and sizes:
+        batch(sizes[0], sizes[1:] or [1, 2, 4, 8])
     elif mode == "kernels" and len(sizes) > 1:
         kernels(sizes[0], sizes[1:])
     else:
