@@ -376,15 +376,13 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
     auto members = [&](const std::vector<int>& list) { Members B = base; for (size_t a = 0; a < list.size(); ++a) B.m[a] = list[a]; return B; };
 
     // the operator on vector `in(m)` of every member of the list, in groups that share one pass of the pipeline
-    auto apply = [&](const std::vector<int>& list, auto&& in, auto&& out) {
-        for (size_t j0 = 0; j0 < list.size(); j0 += LSFC_MAX_BATCH) {
-            const int cnt = (int)std::min<size_t>(LSFC_MAX_BATCH, list.size() - j0);
-            VecBatch vb{};
-            for (int j = 0; j < cnt; ++j) { vb.x[j] = in(list[j0 + j]); vb.y[j] = out(list[j0 + j]); }
-            plan_convolve_batch_dev(p, cnt, vb, true, 1.0, p->omega * p->omega);
-        }
-    };
+    std::vector<const cplx*> av;
     std::vector<cplx*> pv;
+    auto apply = [&](const std::vector<int>& list, auto&& in, auto&& out) {
+        av.clear(); pv.clear();
+        for (int m : list) { av.push_back(in(m)); pv.push_back(out(m)); }
+        plan_apply_batch_dev(p, av.data(), pv.data(), list.size());
+    };
     auto precondition = [&](const std::vector<int>& list, auto&& v) {
         if (!o.precond) return;
         if (own_precond) {
@@ -393,18 +391,7 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
             precond_apply_batch_dev((lsfc_precond*)o.precond_user, pv.data(), (int)pv.size(), st);
             return;
         }
-        for (int m : list) {
-            if (o.precond_on_device) {
-                const int rc = o.precond(o.precond_user, (double*)v(m), N);
-                if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-                continue;
-            }
-            LSFC_HIP(hipMemcpyAsync(vpin.p, v(m), (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
-            LSFC_HIP(hipStreamSynchronize(st));
-            const int rc = o.precond(o.precond_user, (double*)vpin.p, N);
-            if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-            LSFC_HIP(hipMemcpyAsync(v(m), vpin.p, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));   // (the next copy into vpin is ordered after it on st)
-        }
+        for (int m : list) precond_call_dev(o.precond, o.precond_user, o.precond_on_device != 0, v(m), N, vpin.p, st);
     };
     // all members' scalars in one copy
     auto fetch = [&]() {
@@ -545,41 +532,18 @@ static void check_args(const char* fn, lsfc_plan* plan, const double* x, const d
 
 using namespace lsfc;
 
+// Both entry points (defined below them): the argument checks, the option defaults, the memory rule (nrhs (2 l + 3) work vectors; host vectors:
+// the staged x and b, 2 nrhs vectors, on top -- r_shadow is uploaded into its work vector), host staging through
+// plan->xs / plan->ys, and the solve.  batch: the texts of lsfc_bicgstabl_batch, and its members meet at the library's
+// own preconditioner; the single call has nobody to meet there and calls the callback as given.
+static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
+                            double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* code, int memspace);
+
 extern "C" int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts, double* resnorm,
                               int64_t resnorm_cap, lsfc_gmres_result* result, int memspace) {
-    int64_t code[2] = { 0, 0 }; bool notconv = false;
-    const int rc = guarded([&] {
-        check_args("lsfc_bicgstabl", plan, x, b, opts, resnorm, resnorm_cap, result, memspace);
-        const int l = opts->l;
-        const int64_t N = plan->N;
-        const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
-        const double reltol = opts->reltol >= 0 ? opts->reltol : std::sqrt(2.220446049250313e-16);
-        const double abstol = opts->abstol > 0 ? opts->abstol : 0.0;
-        LSFC_HIP(hipSetDevice(plan->device));
-        // memory rule: 2 l + 3 work vectors; host vectors: the staged x and b on top (r_shadow is uploaded into its work vector)
-        const bool host = memspace == LSFC_MEM_HOST;
-        const bool stage = host && plan->xs.n < (size_t)N;
-        {
-            size_t free_b = 0, total_b = 0;
-            LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
-            const double need = ((double)(2 * l + 3) + (stage ? 2.0 : 0.0)) * (double)N * sizeof(cplx);
-            if (need > (double)free_b)
-                fail(LSFC_ENOMEM, "lsfc_bicgstabl: (2 l + 3 = %d work vectors%s) of %lld complex need %.1f GB of device memory, %.1f GB are free "
-                     "-- lower l", 2 * l + 3, stage ? " + staged x and b" : "", (long long)N, need / 1e9, (double)free_b / 1e9);
-        }
-        const cplx* xd = (const cplx*)x; const cplx* bd = (const cplx*)b; const cplx* sd = (const cplx*)opts->r_shadow;
-        if (host) {
-            if (stage) { plan->xs.alloc((size_t)N); plan->ys.alloc((size_t)N); }
-            LSFC_HIP(hipMemcpy(plan->xs.p, x, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice));
-            LSFC_HIP(hipMemcpy(plan->ys.p, b, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice));
-            xd = plan->xs.p; bd = plan->ys.p;
-        }
-        // (the callback is called as given: one member has nobody to meet at the preconditioner)
-        bicgstabl_run(plan, 1, (cplx*)xd, bd, sd, host, false, *opts, l, maxmv, reltol, abstol, resnorm, resnorm_cap > 0 ? resnorm_cap : 0, result, code);
-        if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost));
-        notconv = !result->converged;
-    });
-    if (rc != LSFC_OK || !notconv) return rc;
+    int64_t code[2] = { 0, 0 };
+    const int rc = guarded([&] { bicgstabl_entry("lsfc_bicgstabl", false, plan, x, b, 1, opts, resnorm, resnorm_cap, result, code, memspace); });
+    if (rc != LSFC_OK || result->converged) return rc;
     if (code[0] != LSFC_BICG_MAX_MV) set_last_error("bicgstabl: breakdown in cycle %d: %s; x is the last finite iterate", (int)code[1], ST_NAME[code[0]]);
     else set_last_error("bicgstabl: max_mv_products reached without convergence");
     return LSFC_ENOTCONV;
@@ -587,44 +551,10 @@ extern "C" int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const
 
 extern "C" int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts, double* resnorm,
                                     int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* status, int memspace) {
-    std::vector<int64_t> code;
+    int64_t code[2 * NRHS_MAX] = { 0 };
     const int rc = guarded([&] {
-        LSFC_REQUIRE(nrhs >= 1 && nrhs <= NRHS_MAX, "lsfc_bicgstabl_batch: nrhs = %lld is outside 1..%d", (long long)nrhs, NRHS_MAX);
-        check_args("lsfc_bicgstabl_batch", plan, x, b, opts, resnorm, resnorm_cap, results, memspace);
-        const int l = opts->l, n = (int)nrhs;
-        const int64_t N = plan->N;
-        const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
-        const double reltol = opts->reltol >= 0 ? opts->reltol : std::sqrt(2.220446049250313e-16);
-        const double abstol = opts->abstol > 0 ? opts->abstol : 0.0;
-        const bool own_precond = opts->precond_on_device && opts->precond == &lsfc_precond_callback;
-        if (own_precond)
-            LSFC_REQUIRE(opts->precond_user && precond_size((lsfc_precond*)opts->precond_user) == N, "lsfc_bicgstabl_batch: preconditioner: size mismatch (%lld vs %lld)",
-                         (long long)N, opts->precond_user ? (long long)precond_size((lsfc_precond*)opts->precond_user) : -1LL);
-        LSFC_HIP(hipSetDevice(plan->device));
-        // memory rule: nrhs (2 l + 3) work vectors; host vectors: the staged x and b (2 nrhs vectors) on top
-        const bool host = memspace == LSFC_MEM_HOST;
-        const bool stage = host && plan->xs.n < (size_t)n * (size_t)N;
-        {
-            size_t free_b = 0, total_b = 0;
-            LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
-            const double per = ((double)(2 * l + 3) + (stage ? 2.0 : 0.0)) * (double)N * sizeof(cplx);
-            if ((double)n * per > (double)free_b)
-                fail(LSFC_ENOMEM, "lsfc_bicgstabl_batch: %d right-hand sides x (2 l + 3 = %d work vectors%s) of %lld complex need %.1f GB of device memory, "
-                     "%.1f GB are free -- %lld right-hand sides would fit; solve fewer per call or lower l", n, 2 * l + 3, stage ? " + staged x and b" : "",
-                     (long long)N, (double)n * per / 1e9, (double)free_b / 1e9, (long long)((double)free_b / per));
-        }
-        const cplx* xd = (const cplx*)x; const cplx* bd = (const cplx*)b; const cplx* sd = (const cplx*)opts->r_shadow;
-        const size_t bytes = (size_t)n * (size_t)N * sizeof(cplx);
-        if (host) {
-            if (stage) { plan->xs.alloc((size_t)n * (size_t)N); plan->ys.alloc((size_t)n * (size_t)N); }
-            LSFC_HIP(hipMemcpy(plan->xs.p, x, bytes, hipMemcpyHostToDevice));
-            LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
-            xd = plan->xs.p; bd = plan->ys.p;
-        }
-        code.assign((size_t)(2 * n), 0);
-        bicgstabl_run(plan, n, (cplx*)xd, bd, sd, host, own_precond, *opts, l, maxmv, reltol, abstol, resnorm, resnorm_cap > 0 ? resnorm_cap : 0, results, code.data());
-        if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, bytes, hipMemcpyDeviceToHost));
-        if (status) for (size_t i = 0; i < code.size(); ++i) status[i] = code[i];
+        bicgstabl_entry("lsfc_bicgstabl_batch", true, plan, x, b, nrhs, opts, resnorm, resnorm_cap, results, code, memspace);
+        if (status) for (int64_t i = 0; i < 2 * nrhs; ++i) status[i] = code[i];
     });
     if (rc != LSFC_OK) return rc;
     // LSFC_OK whatever the members did (the rule of lsfc_gmres_batch); the message names the first that did not converge
@@ -636,4 +566,46 @@ extern "C" int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b,
         break;
     }
     return LSFC_OK;
+}
+
+static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
+                            double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* code, int memspace) {
+    if (batch) LSFC_REQUIRE(nrhs >= 1 && nrhs <= NRHS_MAX, "%s: nrhs = %lld is outside 1..%d", fn, (long long)nrhs, NRHS_MAX);
+    check_args(fn, plan, x, b, opts, resnorm, resnorm_cap, results, memspace);
+    const int l = opts->l, n = (int)nrhs;
+    const int64_t N = plan->N;
+    const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
+    const double reltol = opts->reltol >= 0 ? opts->reltol : DEFAULT_RELTOL;
+    const double abstol = opts->abstol > 0 ? opts->abstol : 0.0;
+    const bool own_precond = batch && opts->precond_on_device && opts->precond == &lsfc_precond_callback;
+    if (own_precond)
+        LSFC_REQUIRE(opts->precond_user && precond_size((lsfc_precond*)opts->precond_user) == N, "%s: preconditioner: size mismatch (%lld vs %lld)", fn,
+                     (long long)N, opts->precond_user ? (long long)precond_size((lsfc_precond*)opts->precond_user) : -1LL);
+    LSFC_HIP(hipSetDevice(plan->device));
+    const bool host = memspace == LSFC_MEM_HOST;
+    const bool stage = host && plan->xs.n < (size_t)n * (size_t)N;
+    {
+        size_t free_b = 0, total_b = 0;
+        LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
+        const double per = ((double)(2 * l + 3) + (stage ? 2.0 : 0.0)) * (double)N * sizeof(cplx);
+        if ((double)n * per > (double)free_b) {
+            if (!batch)
+                fail(LSFC_ENOMEM, "lsfc_bicgstabl: (2 l + 3 = %d work vectors%s) of %lld complex need %.1f GB of device memory, %.1f GB are free "
+                     "-- lower l", 2 * l + 3, stage ? " + staged x and b" : "", (long long)N, per / 1e9, (double)free_b / 1e9);
+            fail(LSFC_ENOMEM, "lsfc_bicgstabl_batch: %d right-hand sides x (2 l + 3 = %d work vectors%s) of %lld complex need %.1f GB of device memory, "
+                 "%.1f GB are free -- %lld right-hand sides would fit; solve fewer per call or lower l", n, 2 * l + 3, stage ? " + staged x and b" : "",
+                 (long long)N, (double)n * per / 1e9, (double)free_b / 1e9, (long long)((double)free_b / per));
+        }
+    }
+    const cplx* xd = (const cplx*)x; const cplx* bd = (const cplx*)b;
+    const size_t bytes = (size_t)n * (size_t)N * sizeof(cplx);
+    if (host) {
+        if (stage) { plan->xs.alloc((size_t)n * (size_t)N); plan->ys.alloc((size_t)n * (size_t)N); }
+        LSFC_HIP(hipMemcpy(plan->xs.p, x, bytes, hipMemcpyHostToDevice));
+        LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
+        xd = plan->xs.p; bd = plan->ys.p;
+    }
+    bicgstabl_run(plan, n, (cplx*)xd, bd, (const cplx*)opts->r_shadow, host, own_precond, *opts, l, maxmv, reltol, abstol, resnorm,
+                  resnorm_cap > 0 ? resnorm_cap : 0, results, code);
+    if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, bytes, hipMemcpyDeviceToHost));
 }

@@ -10,11 +10,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <complex>
-#include <condition_variable>
-#include <exception>
-#include <functional>
-#include <mutex>
-#include <thread>
+#include <memory>
+#include <stdexcept>
 #include <vector>
 
 namespace lsfc {
@@ -27,22 +24,28 @@ GmresWorkspace::~GmresWorkspace() {
     for (auto& e : fetched) if (e) (void)hipEventDestroy(e);
 }
 
+// A workspace for vectors of N complex on the current device: the Krylov basis, A x, the scalars and their pinned mirror
+// (vectors), the pinned host vector of a host preconditioner callback (need_vpin)
+static std::unique_ptr<GmresWorkspace> new_workspace(int64_t N, int restart, bool need_vpin, bool vectors = true) {
+    std::unique_ptr<GmresWorkspace> w(new GmresWorkspace());
+    if (vectors) {
+        w->restart = restart;
+        w->V.alloc((size_t)(restart + 1) * (size_t)N);
+        w->hdev.alloc((size_t)restart + 2);
+        w->ydev.alloc((size_t)restart + 2);
+        w->partial.alloc((size_t)blas_partial_count());
+        w->ax.alloc((size_t)N);
+        LSFC_HIP(hipHostMalloc((void**)&w->hpin, 2 * ((size_t)restart + 2) * sizeof(cplx)));
+        for (auto& e : w->fetched) LSFC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (need_vpin) LSFC_HIP(hipHostMalloc((void**)&w->vpin, (size_t)N * sizeof(cplx)));
+    return w;
+}
+
+// The workspace a plan keeps across solves, grown on demand.
 // vectors = false: only the pinned host vector (the root of a multi-device plan, whose Krylov basis lives in its ranks)
 static GmresWorkspace* workspace(lsfc_plan* p, int restart, bool need_vpin, bool vectors = true) {
-    if (!p->gmres || (vectors && p->gmres->restart < restart)) {
-        p->gmres.reset(new GmresWorkspace());
-        GmresWorkspace* w = p->gmres.get();
-        if (vectors) {
-            w->restart = restart;
-            w->V.alloc((size_t)(restart + 1) * (size_t)p->N);
-            w->hdev.alloc((size_t)restart + 2);
-            w->ydev.alloc((size_t)restart + 2);
-            w->partial.alloc((size_t)blas_partial_count());
-            w->ax.alloc((size_t)p->N);
-            LSFC_HIP(hipHostMalloc((void**)&w->hpin, 2 * ((size_t)restart + 2) * sizeof(cplx)));
-            for (auto& e : w->fetched) LSFC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-    }
+    if (!p->gmres || (vectors && p->gmres->restart < restart)) p->gmres = new_workspace(p->N, restart, false, vectors);
     if (need_vpin && !p->gmres->vpin) LSFC_HIP(hipHostMalloc((void**)&p->gmres->vpin, (size_t)p->N * sizeof(cplx)));
     return p->gmres.get();
 }
@@ -90,96 +93,19 @@ static void solve_least_squares(const std::vector<zc>& H, int ldh, double beta, 
 // after the reduction and are read back from member 0.
 namespace {
 struct Member { lsfc_plan* p; GmresWorkspace* w; cplx* x; const cplx* b; };
-
-// lsfc_gmres_batch: every right-hand side runs the ordinary solver on its own host thread; the threads meet here
-// whenever they need the operator, and the last one to arrive applies it to all of them in ONE batched pass of the
-// pipeline (plan_convolve_batch_dev).  A solve that has converged leaves the group.
-struct ApplyBatcher {
-    lsfc_plan* p; int active;
-    std::mutex mu, cb_mu;                // cb_mu serialises the user's preconditioner callback
-    std::condition_variable cv;
-    int waiting = 0; uint64_t gen = 0;
-    std::vector<const cplx*> in; std::vector<cplx*> out;
-    std::exception_ptr err;
-    void run_locked() {
-        try {
-            LSFC_HIP(hipSetDevice(p->device));
-            for (size_t j0 = 0; j0 < in.size(); j0 += LSFC_MAX_BATCH) {
-                const int cnt = (int)std::min<size_t>(LSFC_MAX_BATCH, in.size() - j0);
-                VecBatch vb{};
-                for (int j = 0; j < cnt; ++j) { vb.x[j] = in[j0 + j]; vb.y[j] = out[j0 + j]; }
-                plan_convolve_batch_dev(p, cnt, vb, true, 1.0, p->omega * p->omega);
-            }
-        } catch (...) { err = std::current_exception(); }
-        in.clear(); out.clear(); waiting = 0; ++gen;
-        cv.notify_all();
-    }
-    void apply(const cplx* x, cplx* y) {
-        std::unique_lock<std::mutex> lk(mu);
-        in.push_back(x); out.push_back(y); ++waiting;
-        if (waiting == active) run_locked();
-        else { const uint64_t g = gen; cv.wait(lk, [&] { return gen != g; }); }
-        if (err) std::rethrow_exception(err);
-    }
-    void leave() {
-        std::unique_lock<std::mutex> lk(mu);
-        --active;
-        if (active > 0 && waiting == active) run_locked();
-    }
-};
-
-// The second meeting point of lsfc_gmres_batch, for the library's own device preconditioner (lsfc_precond_callback): the
-// last member to arrive applies it to the Krylov columns of all waiting members in group sweeps (precond_apply_batch_dev),
-// on the plan's stream.  Every member applies the operator and the preconditioner in the same alternation, so the two
-// meeting points never wait for each other.
-struct PrecondBatcher {
-    lsfc_plan* p; lsfc_precond* pc; int active;
-    std::mutex mu;
-    std::condition_variable cv;
-    int waiting = 0; uint64_t gen = 0;
-    std::vector<cplx*> v;
-    std::exception_ptr err;
-    void run_locked() {
-        try {
-            LSFC_HIP(hipSetDevice(p->device));
-            precond_apply_batch_dev(pc, v.data(), (int)v.size(), p->stream);
-        } catch (...) { err = std::current_exception(); }
-        v.clear(); waiting = 0; ++gen;
-        cv.notify_all();
-    }
-    void apply(cplx* x) {
-        std::unique_lock<std::mutex> lk(mu);
-        v.push_back(x); ++waiting;
-        if (waiting == active) run_locked();
-        else { const uint64_t g = gen; cv.wait(lk, [&] { return gen != g; }); }
-        if (err) std::rethrow_exception(err);
-    }
-    void leave() {
-        std::unique_lock<std::mutex> lk(mu);
-        --active;
-        if (active > 0 && waiting == active) run_locked();
-    }
-};
+struct Request;
 
 struct Team {
     lsfc_plan* root;
     std::vector<Member> mem;
     bool reduce = false;                // local inner products are partial sums
     GmresWorkspace* rootw = nullptr;    // pinned host vector of the preconditioner callback
-    ApplyBatcher* batcher = nullptr;    // lsfc_gmres_batch: operator applications go through the rendezvous
-    PrecondBatcher* pbatcher = nullptr; // ... and so do applications of the library's own device preconditioner
 
     static void dev(const Member& m) { LSFC_HIP(hipSetDevice(m.p->device)); }
     static cplx* V(const Member& m, int j) { return m.w->V.p + (size_t)j * (size_t)m.p->N; }
     template <class F> void each(F&& f) { for (auto& m : mem) { dev(m); f(m); } }
 
-    void apply(const std::function<const cplx*(const Member&)>& in, const std::function<cplx*(const Member&)>& out) {
-        if (batcher) { batcher->apply(in(mem[0]), out(mem[0])); return; }
-        if (!root->multi) { dev(mem[0]); plan_apply_dev(root, in(mem[0]), out(mem[0])); return; }
-        std::vector<const cplx*> xi; std::vector<cplx*> yo;
-        for (auto& m : mem) { xi.push_back(in(m)); yo.push_back(out(m)); }
-        multi_convolve_dev(root, xi.data(), yo.data(), true, 1.0, root->omega * root->omega);
-    }
+    void apply(const Request& q);
     void allreduce(int off, int count) {
         if (!reduce) return;
         if (!root->multi) { dev(mem[0]); dist_allreduce_sum(root, mem[0].w->hdev.p + off, count); return; }
@@ -201,61 +127,102 @@ struct Team {
         LSFC_HIP(hipEventRecord(m.w->fetched[slot], m.p->stream));
     }
     void fetch_wait(int slot) { dev(mem[0]); LSFC_HIP(hipEventSynchronize(mem[0].w->fetched[slot])); }
-    void fetch_h(int count, int slot = 0) { fetch_post(count, slot); fetch_wait(slot); }
     cplx* hpin(int slot = 0) { return mem[0].w->hpin + (size_t)slot * ((size_t)mem[0].w->restart + 2); }
     void sync() { each([](Member& m) { LSFC_HIP(hipStreamSynchronize(m.p->stream)); }); }
 };
 
-void solve(Team& T, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap, lsfc_gmres_result* res, int restart,
-           int64_t maxiter, double reltol, double abstol, const lsfc_gmres_opts& o) {
-    const int64_t Ntot = T.root->N;
+// What a solve wants next: the operator on one vector of every member, then the preconditioner on Krylov column `col`.
+//   init    the initial residual of a cycle, V[:,0] = Pl \ (b - A x); apply == false (initially_zero at the first start): V[:,0] = Pl \ b
+//   else    expand column col: V[:,col] = Pl \ (A V[:,col-1])
+struct Request {
+    bool init, apply; int col;
+    const cplx* in(const Member& m) const { return init ? m.x : Team::V(m, col - 1); }
+    cplx* out(const Member& m) const { return init ? m.w->ax.p : Team::V(m, col); }
+    bool same_kind(const Request& q) const { return init == q.init && apply == q.apply && col == q.col; }
+};
 
-    auto precondition = [&](int col) {
-        if (!o.precond) return;
-        if (T.pbatcher) { T.pbatcher->apply(Team::V(T.mem[0], col)); return; }
-        std::unique_lock<std::mutex> cb_lock;
-        if (T.batcher) cb_lock = std::unique_lock<std::mutex>(T.batcher->cb_mu);
-        if (o.precond_on_device) {
-            LSFC_REQUIRE(T.mem.size() == 1, "a device-resident preconditioner callback needs a single-device plan");
-            const int rc = o.precond(o.precond_user, (double*)Team::V(T.mem[0], col), T.mem[0].p->N);
-            if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-            return;
-        }
-        // host callback, in place on the whole vector (the two-argument ldiv!): gather the slabs, call, scatter
-        cplx* vpin = T.rootw->vpin;
-        int64_t off = 0;
-        T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(vpin + off, Team::V(m, col), (size_t)m.p->N * sizeof(cplx), hipMemcpyDeviceToHost, m.p->stream)); off += m.p->N; });
-        T.sync();
-        const int rc = o.precond(o.precond_user, (double*)vpin, T.mem.size() == 1 ? T.mem[0].p->N : Ntot);
-        if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-        off = 0;
-        T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(Team::V(m, col), vpin + off, (size_t)m.p->N * sizeof(cplx), hipMemcpyHostToDevice, m.p->stream)); off += m.p->N; });
-    };
+void Team::apply(const Request& q) {
+    if (!root->multi) { dev(mem[0]); plan_apply_dev(root, q.in(mem[0]), q.out(mem[0])); return; }
+    std::vector<const cplx*> xi; std::vector<cplx*> yo;
+    for (auto& m : mem) { xi.push_back(q.in(m)); yo.push_back(q.out(m)); }
+    multi_convolve_dev(root, xi.data(), yo.data(), true, 1.0, root->omega * root->omega);
+}
 
-    // init!: V1 = Pl \ (b - A x) normalised, returns beta
-    auto init = [&](bool skip_mv) -> double {
-        if (skip_mv) T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(Team::V(m, 0), m.b, (size_t)m.p->N * sizeof(cplx), hipMemcpyDeviceToDevice, m.p->stream)); });
-        else {
-            T.apply([](const Member& m) { return (const cplx*)m.x; }, [](const Member& m) { return m.w->ax.p; });
-            T.each([&](Member& m) { blas_sub(Team::V(m, 0), m.b, m.w->ax.p, m.p->N, m.p->stream); });
-        }
-        precondition(0);
-        T.each([&](Member& m) { blas_nrm2(Team::V(m, 0), m.w->partial.p, m.w->hdev.p, m.p->N, m.p->stream, T.reduce); });
-        T.finish_nrm(0);
-        T.each([&](Member& m) { blas_scale_inv_dev(Team::V(m, 0), m.w->hdev.p, m.p->N, m.p->stream); });
-        T.fetch_h(1);
-        return T.hpin()[0].x;
-    };
+struct Resolved { lsfc_gmres_opts o; int restart; int64_t maxiter; double reltol, abstol; };
+Resolved resolve(const lsfc_gmres_opts* opts_in, int64_t N) {
+    Resolved r;
+    if (opts_in) r.o = *opts_in;
+    else { r.o.restart = 0; r.o.maxiter = 0; r.o.reltol = -1; r.o.abstol = 0; r.o.orth = LSFC_ORTH_MGS; r.o.initially_zero = 0; r.o.precond = nullptr; r.o.precond_user = nullptr; r.o.precond_on_device = 0; }
+    r.restart = (int)(r.o.restart > 0 ? r.o.restart : std::min<int64_t>(20, N));
+    r.maxiter = r.o.maxiter > 0 ? r.o.maxiter : N;
+    r.reltol = r.o.reltol >= 0 ? r.o.reltol : DEFAULT_RELTOL;
+    r.abstol = r.o.abstol > 0 ? r.o.abstol : 0.0;
+    LSFC_REQUIRE(r.o.orth == LSFC_ORTH_MGS || r.o.orth == LSFC_ORTH_CGS || r.o.orth == LSFC_ORTH_DGKS, "unknown orthogonalisation %d", r.o.orth);
+    LSFC_REQUIRE(r.restart >= 1, "restart must be >= 1");
+    return r;
+}
+
+// One solve, cut at the operator: request() names what is to be applied and preconditioned next, applied() and post()
+// enqueue the solve's own kernels behind it, consume() reads the scalars back and advances the iteration.  The driver
+// does the applying and the preconditioning -- gmres_run / gmres_run_multi for one solve, gmres_run_batch for all
+// running members of a batch at once.
+struct Solve {
+    Team& T;
+    const Resolved& r; const lsfc_gmres_opts& o;
+    double* resnorm; int64_t cap; lsfc_gmres_result* res;
+    const int restart, ldh; const int64_t Ntot;
+    bool fused, mgs_blocked, lookahead;
+    std::vector<zc> H, nullvec, y;
+    double beta = 0.0, current = 0.0, accumulator = 1.0, tol = 0.0;
+    int k = 1;
+    int posted = -1;                    // columns of this cycle whose kernels are in the stream (>= k - 1); -1: not even the initial residual
+    int64_t iteration = 0, mvps;
+    bool need_init = true, started = false;
+
+    Solve(Team& team, const Resolved& rr, double* resnorm_, int64_t cap_, lsfc_gmres_result* res_, bool batch)
+        : T(team), r(rr), o(rr.o), resnorm(resnorm_), cap(cap_), res(res_), restart(rr.restart), ldh(rr.restart + 1), Ntot(T.root->N),
+          H((size_t)(rr.restart + 1) * rr.restart, zc(0)), nullvec((size_t)rr.restart + 1, zc(1)), mvps(rr.o.initially_zero ? 1 : 0) {
+        // one device, no all-reduce between a reduction and its consumer: the fused kernels (pointwise.hip) sum block partials
+        // inside the consuming kernel -- same summation order, bit-identical scalars, roughly half the launches
+        fused = !T.reduce && T.mem.size() == 1;
+        // modified Gram-Schmidt in blocks (pointwise.hip: k_mgs_block) where the sweep is bound by HBM traffic: vectors of >= 2^22
+        // entries (LSFC_MGS_BLOCK=0 / 1 forces the strict one-vector-at-a-time sweep / the blocked one)
+        const char* mb_env = getenv("LSFC_MGS_BLOCK");
+        mgs_blocked = mb_env ? atoi(mb_env) != 0 : Ntot >= ((int64_t)1 << 22);
+        // One step ahead: on one device nothing the host computes feeds back into the kernels of a step (the fused kernels read
+        // their scalars from device memory), so the host may post step k + 1 before it has seen the scalars of step k and the
+        // device never idles through the read-back, the Hessenberg update and the next launches.  The step posted past
+        // convergence is surplus (its column is not used); none is posted past maxiter or past the restart length.  Worth it
+        // where a step is short (small grids); off for DGKS (the host decides about the second sweep), for callbacks of
+        // the caller (they would see one call more than the reference makes) -- the library's own device preconditioner
+        // (lsfc_precond_callback: stream-ordered, no side effects) is fine -- and in a batch (the members post together).
+        const char* lag_env = getenv("LSFC_GMRES_LOOKAHEAD");
+        const bool own_precond = o.precond_on_device && o.precond == &lsfc_precond_callback;
+        lookahead = fused && !batch && o.orth != LSFC_ORTH_DGKS && (!o.precond || own_precond) &&
+                    (lag_env ? atoi(lag_env) != 0 : Ntot <= ((int64_t)1 << 22));
+    }
+
+    bool running() const { return need_init || !(iteration >= r.maxiter || current <= tol); }
+
+    // steps in flight: the one the host is about to read and, with lookahead, the one after it
+    bool request(Request& q) const {
+        if (posted < 0) { q = { true, !(o.initially_zero && !started), 0 }; return true; }
+        const int want = k + (lookahead ? 1 : 0);
+        if (need_init || !(posted < want && posted < restart && iteration + (posted - (k - 1)) < r.maxiter)) return false;
+        q = { false, true, posted + 1 };
+        return true;
+    }
+
+    // init!: V1 = b - A x (the preconditioner comes next)
+    void applied(const Request& q) {
+        if (!q.init) return;
+        if (q.apply) T.each([&](Member& m) { blas_sub(Team::V(m, 0), m.b, m.w->ax.p, m.p->N, m.p->stream); });
+        else T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(Team::V(m, 0), m.b, (size_t)m.p->N * sizeof(cplx), hipMemcpyDeviceToDevice, m.p->stream)); });
+    }
+
+    cplx* slot(int s2) { return T.mem[0].w->partial.p + (size_t)s2 * (size_t)blas_partial_slot(); }
     // h[j0..j0+k) = V[:, 0..k)' w  and  w -= V h   (classical Gram-Schmidt sweep over the first k columns), then ||w||
-    // one device, no all-reduce between a reduction and its consumer: the fused kernels (pointwise.hip) sum block partials
-    // inside the consuming kernel -- same summation order, bit-identical scalars, roughly half the launches
-    const bool fused = !T.reduce && T.mem.size() == 1;
-    // modified Gram-Schmidt in blocks (pointwise.hip: k_mgs_block) where the sweep is bound by HBM traffic: vectors of >= 2^22
-    // entries (LSFC_MGS_BLOCK=0 / 1 forces the strict one-vector-at-a-time sweep / the blocked one)
-    const char* mb_env = getenv("LSFC_MGS_BLOCK");
-    const bool mgs_blocked = mb_env ? atoi(mb_env) != 0 : Ntot >= ((int64_t)1 << 22);
-    auto slot = [&](int s2) { return T.mem[0].w->partial.p + (size_t)s2 * (size_t)blas_partial_slot(); };
-    auto cgs_sweep = [&](int k, bool scale_now, int hslot = 0, bool wait = true) {
+    void cgs_sweep(int k, bool scale_now, int hslot = 0, bool wait = true) {
         if (fused && k <= 64) {
             Member& m = T.mem[0];
             Team::dev(m);
@@ -285,35 +252,21 @@ void solve(Team& T, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap
         if (scale_now) T.each([&](Member& m) { blas_scale_inv_dev(Team::V(m, k), m.w->hdev.p + k, m.p->N, m.p->stream); });
         T.fetch_post(k + 1, hslot);
         if (wait) T.fetch_wait(hslot);
-    };
+    }
 
-    std::vector<zc> H((size_t)(restart + 1) * restart, zc(0));
-    const int ldh = restart + 1;
-    std::vector<zc> nullvec((size_t)restart + 1, zc(1));
-    int64_t mvps = o.initially_zero ? 1 : 0;
-    double beta = init(o.initially_zero != 0);
-    double current = beta, accumulator = 1.0;
-    nullvec[0] = 1.0;
-    const double tol = std::max(reltol * current, abstol);
-    int k = 1; int64_t iteration = 0;
-    std::vector<zc> y;
-
-    // One step ahead: on one device nothing the host computes feeds back into the kernels of a step (the fused kernels read
-    // their scalars from device memory), so the host may post step k + 1 before it has seen the scalars of step k and the
-    // device never idles through the read-back, the Hessenberg update and the next launches.  The step posted past
-    // convergence is surplus (its column is not used); none is posted past maxiter or past the restart length.  Worth it
-    // where a step is short (small grids); off for DGKS (the host decides about the second sweep) and for callbacks of
-    // the caller (they would see one call more than the reference makes) -- the library's own device preconditioner
-    // (lsfc_precond_callback: stream-ordered, no side effects) is fine.
-    const char* lag_env = getenv("LSFC_GMRES_LOOKAHEAD");
-    const bool own_precond = o.precond_on_device && o.precond == &lsfc_precond_callback;
-    const bool lookahead = fused && !T.batcher && o.orth != LSFC_ORTH_DGKS && (!o.precond || own_precond) &&
-                           (lag_env ? atoi(lag_env) != 0 : Ntot <= ((int64_t)1 << 22));
-    // expand!: V[:,kk+1] = A V[:,kk], ldiv!(Pl, V[:,kk+1]), orthogonalise; the scalars travel to pinned slot kk & 1
-    auto post_step = [&](int kk) {
-        const int hs = kk & 1;
-        T.apply([kk](const Member& m) { return (const cplx*)Team::V(m, kk - 1); }, [kk](const Member& m) { return Team::V(m, kk); });
-        precondition(kk);
+    // the solve's kernels behind the preconditioned column, and the fetch of their scalars
+    void post(const Request& q) {
+        posted = q.col;
+        if (q.init) {
+            // init!: normalise V1; beta travels to pinned slot 0
+            T.each([&](Member& m) { blas_nrm2(Team::V(m, 0), m.w->partial.p, m.w->hdev.p, m.p->N, m.p->stream, T.reduce); });
+            T.finish_nrm(0);
+            T.each([&](Member& m) { blas_scale_inv_dev(Team::V(m, 0), m.w->hdev.p, m.p->N, m.p->stream); });
+            T.fetch_post(1, 0);
+            return;
+        }
+        // expand!: orthogonalise V[:,kk] against the columns before it; the scalars travel to pinned slot kk & 1
+        const int kk = q.col, hs = kk & 1;
         if (o.orth == LSFC_ORTH_MGS && fused && mgs_blocked) {
             // blocks of MB basis vectors: one pass takes the inner products with a whole block (and of its vectors with each
             // other), the next one recovers the MGS coefficients, updates w with the block and takes the next block's products
@@ -354,13 +307,20 @@ void solve(Team& T, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap
         } else {
             cgs_sweep(kk, o.orth == LSFC_ORTH_CGS, hs, false);
         }
-    };
+    }
 
-    int posted = 0;                                         // columns of this cycle whose kernels are in the stream (>= k - 1)
-    while (!(iteration >= maxiter || current <= tol)) {
-        // steps in flight: the one the host is about to read and, with lookahead, the one after it
-        const int want = k + (lookahead ? 1 : 0);
-        while (posted < want && posted < restart && iteration + (posted - (k - 1)) < maxiter) { ++posted; post_step(posted); }
+    // the oldest fetch in flight: beta of a (re)start, or step k
+    void consume() {
+        if (need_init) {
+            T.fetch_wait(0);
+            beta = T.hpin()[0].x;
+            accumulator = 1.0;
+            nullvec[0] = 1.0;
+            if (started) ++mvps;
+            else { current = beta; tol = std::max(r.reltol * current, r.abstol); started = true; }
+            need_init = false;
+            return;
+        }
         ++mvps;
         double nrm;
         cplx* hp = T.hpin(k & 1);
@@ -417,34 +377,52 @@ void solve(Team& T, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap
                 }
             });
             T.sync();
-            k = 1; posted = 0;
-            if (!(current <= tol)) {
-                beta = init(false);
-                accumulator = 1.0;
-                nullvec[0] = 1.0;
-                ++mvps;
-            }
+            // a cycle that ended above the tolerance starts the next one, whatever maxiter says: the reference's order
+            need_init = !(current <= tol);
+            k = 1; posted = need_init ? -1 : 0;
         }
         if (resnorm && iteration < cap) resnorm[iteration] = current;
         ++iteration;
     }
+
+    void finish() { res->iters = iteration; res->mvps = mvps; res->converged = current <= tol ? 1 : 0; res->final_resnorm = current; }
+};
+
+// the preconditioner on Krylov column `col` of one solve
+void precondition(Team& T, const lsfc_gmres_opts& o, int col) {
+    if (!o.precond) return;
+    if (o.precond_on_device) LSFC_REQUIRE(T.mem.size() == 1, "a device-resident preconditioner callback needs a single-device plan");
+    if (T.mem.size() == 1) {
+        Member& m = T.mem[0];
+        Team::dev(m);
+        precond_call_dev(o.precond, o.precond_user, o.precond_on_device != 0, Team::V(m, col), m.p->N, T.rootw->vpin, m.p->stream);
+        return;
+    }
+    // host callback, in place on the whole vector (the two-argument ldiv!): gather the slabs, call, scatter
+    cplx* vpin = T.rootw->vpin;
+    int64_t off = 0;
+    T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(vpin + off, Team::V(m, col), (size_t)m.p->N * sizeof(cplx), hipMemcpyDeviceToHost, m.p->stream)); off += m.p->N; });
     T.sync();
-    res->iters = iteration; res->mvps = mvps; res->converged = current <= tol ? 1 : 0; res->final_resnorm = current;
-    (void)opts_in;
+    const int rc = o.precond(o.precond_user, (double*)vpin, T.root->N);
+    if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+    off = 0;
+    T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(Team::V(m, col), vpin + off, (size_t)m.p->N * sizeof(cplx), hipMemcpyHostToDevice, m.p->stream)); off += m.p->N; });
 }
 
-struct Resolved { lsfc_gmres_opts o; int restart; int64_t maxiter; double reltol, abstol; };
-Resolved resolve(const lsfc_gmres_opts* opts_in, int64_t N) {
-    Resolved r;
-    if (opts_in) r.o = *opts_in;
-    else { r.o.restart = 0; r.o.maxiter = 0; r.o.reltol = -1; r.o.abstol = 0; r.o.orth = LSFC_ORTH_MGS; r.o.initially_zero = 0; r.o.precond = nullptr; r.o.precond_user = nullptr; r.o.precond_on_device = 0; }
-    r.restart = (int)(r.o.restart > 0 ? r.o.restart : std::min<int64_t>(20, N));
-    r.maxiter = r.o.maxiter > 0 ? r.o.maxiter : N;
-    r.reltol = r.o.reltol >= 0 ? r.o.reltol : std::sqrt(2.220446049250313e-16);
-    r.abstol = r.o.abstol > 0 ? r.o.abstol : 0.0;
-    LSFC_REQUIRE(r.o.orth == LSFC_ORTH_MGS || r.o.orth == LSFC_ORTH_CGS || r.o.orth == LSFC_ORTH_DGKS, "unknown orthogonalisation %d", r.o.orth);
-    LSFC_REQUIRE(r.restart >= 1, "restart must be >= 1");
-    return r;
+// one solve over a team
+void solve(Team& T, const Resolved& r, double* resnorm, int64_t cap, lsfc_gmres_result* res) {
+    Solve S(T, r, resnorm, cap, res, false);
+    while (S.running()) {
+        for (Request q; S.request(q);) {
+            if (q.apply) T.apply(q);
+            S.applied(q);
+            precondition(T, r.o, q.col);
+            S.post(q);
+        }
+        S.consume();
+    }
+    T.sync();
+    S.finish();
 }
 } // namespace
 
@@ -456,63 +434,72 @@ void gmres_run(lsfc_plan* p, cplx* x, const cplx* b, const lsfc_gmres_opts* opts
     T.rootw = w;
     // slab-distributed plan (one process per GPU): every inner product / squared norm is completed by an all-reduce over the ranks
     T.reduce = p->dist && !p->dist->sim && !p->dist->member && (p->dist->nranks > 1 || p->dist->force_comm);
-    solve(T, opts_in, resnorm, cap, res, r.restart, r.maxiter, r.reltol, r.abstol, r.o);
+    solve(T, r, resnorm, cap, res);
 }
 
+// Lock step, on the calling thread.  All running members are always in the same phase -- they start together, the restart
+// comes at the same k for every member and costs each of them one operator application, DGKS applies none, and a member
+// only ever leaves -- so a round is: one request per member (all of one kind), the operator on all of them in groups that
+// share a pass of the pipeline, the preconditioner (the library's own object: all columns at once; any other callback:
+// member by member, in member order), every member's kernels, and only then the scalars of each.
 void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap,
                      lsfc_gmres_result* res) {
     const Resolved r = resolve(opts_in, p->N);
-    const bool need_vpin = r.o.precond != nullptr && !r.o.precond_on_device;
+    const bool host_cb = r.o.precond != nullptr && !r.o.precond_on_device;
+    const bool own_precond = r.o.precond_on_device && r.o.precond == &lsfc_precond_callback;
+    lsfc_precond* pc = (lsfc_precond*)r.o.precond_user;
     // one workspace (Krylov basis, scalars, pinned buffers) per right-hand side: nrhs * (restart + 2) vectors of N complex.
     // Checked against the free device memory up front (a failed hipMalloc half way through leaves a half-built batch), and
     // released again when the call returns -- the single-solve workspace of the plan is the one that is kept across calls.
     {
         size_t free_b = 0, total_b = 0;
         LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
-        size_t have = 0;
-        for (auto& w : p->gmres_batch) if (w && w->restart >= r.restart) have += w->V.bytes() + w->ax.bytes();
         const double need = (double)nrhs * ((double)r.restart + 2.0) * (double)p->N * sizeof(cplx);
-        if (need > (double)free_b + (double)have)
+        if (need > (double)free_b)
             fail(LSFC_ENOMEM, "lsfc_gmres_batch: %d right-hand sides x (restart %d + 2) vectors of %lld complex need %.1f GB of device memory, %.1f GB are free "
-                 "-- solve fewer right-hand sides per call or lower the restart length", nrhs, r.restart, (long long)p->N, need / 1e9, ((double)free_b + (double)have) / 1e9);
+                 "-- solve fewer right-hand sides per call or lower the restart length", nrhs, r.restart, (long long)p->N, need / 1e9, (double)free_b / 1e9);
     }
-    struct Release { lsfc_plan* p; ~Release() { p->gmres_batch.clear(); } } release_on_return{p};
-    if ((int)p->gmres_batch.size() < nrhs) p->gmres_batch.resize((size_t)nrhs);
-    for (int j = 0; j < nrhs; ++j) {
-        std::unique_ptr<GmresWorkspace> keep = std::move(p->gmres);
-        p->gmres = std::move(p->gmres_batch[(size_t)j]);
-        workspace(p, r.restart, need_vpin);
-        p->gmres_batch[(size_t)j] = std::move(p->gmres);
-        p->gmres = std::move(keep);
-    }
+    std::vector<std::unique_ptr<GmresWorkspace>> ws;
+    for (int j = 0; j < nrhs; ++j) ws.push_back(new_workspace(p->N, r.restart, host_cb && j == 0));      // (one pinned vector serves every member's callback)
     LSFC_HIP(hipStreamSynchronize(p->stream));
-    ApplyBatcher batcher; batcher.p = p; batcher.active = nrhs;
-    // the library's own device preconditioner is applied to all members at once; any other callback one member at a time
-    const bool own_precond = r.o.precond_on_device && r.o.precond == &lsfc_precond_callback;
-    PrecondBatcher pbatcher; pbatcher.p = p; pbatcher.pc = (lsfc_precond*)r.o.precond_user; pbatcher.active = nrhs;
     if (own_precond)
-        LSFC_REQUIRE(pbatcher.pc && precond_size(pbatcher.pc) == p->N, "preconditioner: size mismatch (%lld vs %lld)",
-                     (long long)p->N, pbatcher.pc ? (long long)precond_size(pbatcher.pc) : -1LL);
-    std::vector<std::exception_ptr> errs((size_t)nrhs);
-    std::vector<std::thread> th;
-    for (int j = 0; j < nrhs; ++j)
-        th.emplace_back([&, j] {
-            try {
-                LSFC_HIP(hipSetDevice(p->device));
-                Team T; T.root = p; T.batcher = &batcher;
-                if (own_precond) T.pbatcher = &pbatcher;
-                GmresWorkspace* w = p->gmres_batch[(size_t)j].get();
-                T.mem.push_back({p, w, x + (int64_t)j * p->N, b + (int64_t)j * p->N});
-                T.rootw = w;
-                solve(T, opts_in, resnorm ? resnorm + (int64_t)j * cap : nullptr, cap, res + j, r.restart, r.maxiter, r.reltol, r.abstol, r.o);
-            } catch (...) { errs[(size_t)j] = std::current_exception(); }
-            batcher.leave();
-            pbatcher.leave();
-        });
-    for (auto& t : th) t.join();
-    LSFC_HIP(hipSetDevice(p->device));
+        LSFC_REQUIRE(pc && precond_size(pc) == p->N, "preconditioner: size mismatch (%lld vs %lld)", (long long)p->N, pc ? (long long)precond_size(pc) : -1LL);
+    std::vector<Team> teams((size_t)nrhs);
+    std::vector<Solve> S;
+    S.reserve((size_t)nrhs);
+    std::vector<Solve*> act;
+    for (int j = 0; j < nrhs; ++j) {
+        Team& T = teams[(size_t)j];
+        T.root = p;
+        T.mem.push_back({p, ws[(size_t)j].get(), x + (int64_t)j * p->N, b + (int64_t)j * p->N});
+        S.emplace_back(T, r, resnorm ? resnorm + (int64_t)j * cap : nullptr, cap, res + j, true);
+        act.push_back(&S.back());
+    }
+    try {
+        std::vector<Request> q;
+        std::vector<const cplx*> in; std::vector<cplx*> out, col;
+        while (!act.empty()) {
+            q.resize(act.size()); in.clear(); out.clear(); col.clear();
+            for (size_t a = 0; a < act.size(); ++a) {
+                const Member& m = act[a]->T.mem[0];
+                if (!act[a]->request(q[a]) || !q[a].same_kind(q[0])) throw std::logic_error("lsfc_gmres_batch: the members of a round are not in the same phase");
+                in.push_back(q[a].in(m)); out.push_back(q[a].out(m)); col.push_back(Team::V(m, q[a].col));
+            }
+            if (q[0].apply) plan_apply_batch_dev(p, in.data(), out.data(), in.size());
+            for (size_t a = 0; a < act.size(); ++a) act[a]->applied(q[a]);
+            if (own_precond) precond_apply_batch_dev(pc, col.data(), (int)col.size(), p->stream);
+            else if (r.o.precond) for (cplx* v : col) precond_call_dev(r.o.precond, r.o.precond_user, r.o.precond_on_device != 0, v, p->N, ws[0]->vpin, p->stream);
+            for (size_t a = 0; a < act.size(); ++a) act[a]->post(q[a]);
+            size_t kept = 0;
+            for (Solve* s : act) { s->consume(); if (s->running()) act[kept++] = s; }
+            act.resize(kept);
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(p->stream);              // the workspaces are about to go
+        throw;
+    }
     LSFC_HIP(hipStreamSynchronize(p->stream));
-    for (auto& e : errs) if (e) std::rethrow_exception(e);
+    for (auto& s : S) s.finish();
 }
 
 void gmres_run_multi(lsfc_plan* root, cplx* x_host, const cplx* b_host, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap,
@@ -534,7 +521,7 @@ void gmres_run_multi(lsfc_plan* root, cplx* x_host, const cplx* b_host, const ls
         T.mem.push_back({p, w, p->xs.p, p->ys.p});
         off += p->N;
     }
-    solve(T, opts_in, resnorm, cap, res, r.restart, r.maxiter, r.reltol, r.abstol, r.o);
+    solve(T, r, resnorm, cap, res);
     off = 0;
     for (auto& m : T.mem) {
         Team::dev(m);

@@ -530,6 +530,26 @@ void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool us
     pruned_convolve(p, nrhs, vb, use_nu, alpha, beta);
 }
 
+void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out, size_t cnt) {
+    for (size_t j0 = 0; j0 < cnt; j0 += LSFC_MAX_BATCH) {
+        const int n = (int)std::min<size_t>(LSFC_MAX_BATCH, cnt - j0);
+        VecBatch vb{};
+        for (int j = 0; j < n; ++j) { vb.x[j] = in[j0 + j]; vb.y[j] = out[j0 + j]; }
+        plan_convolve_batch_dev(p, n, vb, true, 1.0, p->omega * p->omega);
+    }
+}
+
+void precond_call_dev(lsfc_precond_fn precond, void* user, bool on_device, cplx* v, int64_t N, cplx* pinned, hipStream_t st) {
+    if (!on_device) {
+        LSFC_HIP(hipMemcpyAsync(pinned, v, (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        LSFC_HIP(hipStreamSynchronize(st));
+    }
+    const int rc = precond(user, (double*)(on_device ? v : pinned), N);
+    if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+    // (whatever next goes into the pinned vector is ordered after this copy on st)
+    if (!on_device) LSFC_HIP(hipMemcpyAsync(v, pinned, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));
+}
+
 static void ensure_staging(lsfc_plan* p, int64_t count) {
     if (p->xs.n < (size_t)count) { p->xs.alloc((size_t)count); p->ys.alloc((size_t)count); }
 }

@@ -139,7 +139,6 @@ struct lsfc_plan {
     std::unique_ptr<lsfc::HostPipe> hostpipe;
 
     std::unique_ptr<lsfc::GmresWorkspace> gmres;
-    std::vector<std::unique_ptr<lsfc::GmresWorkspace>> gmres_batch;    // one workspace per right-hand side of lsfc_gmres_batch
     std::unique_ptr<lsfc::DistState> dist;
     std::unique_ptr<lsfc::MultiState> multi;
 
@@ -156,6 +155,13 @@ void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double
 void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool use_nu, double alpha, double beta);
 // the operator M = I + omega^2 G nu
 inline void plan_apply_dev(lsfc_plan* p, const cplx* x, cplx* y) { plan_convolve_dev(p, x, y, true, 1.0, p->omega * p->omega); }
+// ... on cnt (in, out) pairs, in groups of LSFC_MAX_BATCH that share one pass of the pipeline (the batched solvers)
+void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out, size_t cnt);
+
+// The solvers' defaults and their call of the caller's preconditioner on one device vector of N complex: the device
+// callback as given; the host callback on the pinned vector, with the copies and the synchronisation of `st` around it
+constexpr double DEFAULT_RELTOL = 0x1p-26;      // sqrt(eps)
+void precond_call_dev(lsfc_precond_fn precond, void* user, bool on_device, cplx* v, int64_t N, cplx* pinned, hipStream_t st);
 
 // The fused z pass of the 3D tiled layout on `Wc` x' storage indices, starting at the tile that the offsets into A2 and
 // the symbol point to (the whole range on one device; dist.hip: one chunk of the owned range)
@@ -196,8 +202,8 @@ void plan_kernel0(lsfc_plan* p);
 // GMRES (gmres.hip)
 void gmres_run(lsfc_plan* p, cplx* x_dev, const cplx* b_dev, const lsfc_gmres_opts* opts, double* resnorm, int64_t cap,
                lsfc_gmres_result* res);
-// nrhs independent solves in lock step (device vectors back to back, nrhs <= 64): every Arnoldi step applies the operator
-// to all unconverged right-hand sides in one batch
+// nrhs independent solves in lock step on the calling thread (device vectors back to back, nrhs <= 64): every Arnoldi step
+// applies the operator to all unconverged right-hand sides in one batch; the workspaces live for the call
 void gmres_run_batch(lsfc_plan* p, cplx* x_dev, const cplx* b_dev, int nrhs, const lsfc_gmres_opts* opts, double* resnorm, int64_t cap,
                      lsfc_gmres_result* res);
 // multi-device plan: x (in/out) and b are HOST vectors of the full size; the Krylov basis is spread over the devices

@@ -611,7 +611,8 @@ def gmres_batch_(X, A, B, Pl=None, abstol=0.0, reltol=None, restart=None, maxite
     solves of tests/plasma_example.jl:160-176 (two incident directions, one after the other in the reference) run in
     lock step, one batched operator application per Arnoldi step.  Each row's iterates are those of ``gmres_`` on that
     row alone.  ``Pl``: a SparsifyingPreconditioner is applied on the device to all unconverged rows at once (one group
-    sweep per step for a block-tridiagonal object); any other callable ``v -> None`` gets one host vector at a time.
+    sweep per step for a block-tridiagonal object); any other callable ``v -> None`` gets one host vector at a time, row
+    after row, on the calling thread.  The library starts no threads, and the groups of rows are the same in every run.
     Returns X or (X, [ConvergenceHistory per row])."""
     torch_in = _is_torch(X)
     if torch_in:

@@ -191,8 +191,10 @@ int lsfc_gmres(lsfc_plan* plan, double* x, const double* b, const lsfc_gmres_opt
  * operator to all unconverged right-hand sides in one batched pass (see lsfc_apply_batch).  With precond =
  * lsfc_precond_callback and precond_on_device = 1 the right-hand sides meet at the preconditioner as well: one
  * lsfc_precond_apply_batch-style group sweep over the Krylov vectors of all unconverged right-hand sides per step.  Any
- * other callback (host, or the caller's own device callback) is invoked for one right-hand side at a time.  Returns LSFC_OK even if some right-hand side hit maxiter: check
- * results[j].converged.  Device memory: nrhs * (restart + 2) vectors of N complex for the duration of the call (checked
+ * other callback (host, or the caller's own device callback) is invoked for one right-hand side at a time, in the order of
+ * the right-hand sides.  No host threads: everything, the callback included, runs on the calling thread, and the groups of
+ * the batched passes are formed in the order of the right-hand sides, the same in every run.  Returns LSFC_OK even if some
+ * right-hand side hit maxiter: check results[j].converged.  Device memory: nrhs * (restart + 2) vectors of N complex for the duration of the call (checked
  * against the free memory up front: LSFC_ENOMEM with the figures; released on return). */
 int lsfc_gmres_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_gmres_opts* opts,
                      double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int memspace);
