@@ -23,7 +23,6 @@
 #include "plan.hpp"
 #include "pointwise.hpp"
 #include "reduce.hpp"
-#include "blocktri.hpp"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -348,11 +347,10 @@ struct Solve {
 } // namespace
 
 // nrhs solves in lock step.  x (in/out) and b: nrhs device vectors back to back; r_shadow (may be NULL): nrhs vectors of N
-// complex on the device, or on the host (shadow_on_host); resnorm: nrhs rows of cap entries.  own_precond: the
-// preconditioner is the library's own object and takes all active members in group sweeps (precond_apply_batch_dev);
-// otherwise the callback gets one member at a time.  code[2 j], code[2 j + 1]: LSFC_BICG_* of member j and its cycle
-// (of the breakdown, else the last one).
-static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const cplx* r_shadow, bool shadow_on_host, bool own_precond,
+// complex on the device, or on the host (shadow_on_host); resnorm: nrhs rows of cap entries.  pc takes the active members
+// of every round (Precond::apply).  code[2 j], code[2 j + 1]: LSFC_BICG_* of member j and its cycle (of the breakdown,
+// else the last one).
+static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
                           const lsfc_bicgstabl_opts& o, int l, int64_t maxmv, double reltol, double abstol, double* resnorm, int64_t cap,
                           lsfc_gmres_result* res, int64_t* code) {
     const int64_t N = p->N;
@@ -368,8 +366,7 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
     auto R = [&](int m, int i) { return work.p + (size_t)m * (size_t)wstride + (size_t)i * N; };
     auto U = [&](int m, int i) { return R(m, nv + i); };
     Pinned hs, ht, vpin; hs.alloc((size_t)nrhs * S_COUNT); ht.alloc((size_t)(nrhs + 1) / 2);
-    const bool host_cb = o.precond && !o.precond_on_device;
-    if (host_cb) vpin.alloc((size_t)N);
+    if (pc.fn && !pc.on_device) vpin.alloc((size_t)N);
     Event fetched; fetched.create();
     Members base{};
     base.work = work.p; base.x = x; base.scal = scal.p; base.partial = partial.p; base.tol2 = tol2.p; base.wstride = wstride; base.n = N;
@@ -384,14 +381,9 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
         plan_apply_batch_dev(p, av.data(), pv.data(), list.size());
     };
     auto precondition = [&](const std::vector<int>& list, auto&& v) {
-        if (!o.precond) return;
-        if (own_precond) {
-            pv.clear();
-            for (int m : list) pv.push_back(v(m));
-            precond_apply_batch_dev((lsfc_precond*)o.precond_user, pv.data(), (int)pv.size(), st);
-            return;
-        }
-        for (int m : list) precond_call_dev(o.precond, o.precond_user, o.precond_on_device != 0, v(m), N, vpin.p, st);
+        pv.clear();
+        for (int m : list) pv.push_back(v(m));
+        pc.apply(pv.data(), pv.size(), vpin.p, st);
     };
     // all members' scalars in one copy
     auto fetch = [&]() {
@@ -577,10 +569,7 @@ static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double*
     const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
     const double reltol = opts->reltol >= 0 ? opts->reltol : DEFAULT_RELTOL;
     const double abstol = opts->abstol > 0 ? opts->abstol : 0.0;
-    const bool own_precond = batch && opts->precond_on_device && opts->precond == &lsfc_precond_callback;
-    if (own_precond)
-        LSFC_REQUIRE(opts->precond_user && precond_size((lsfc_precond*)opts->precond_user) == N, "%s: preconditioner: size mismatch (%lld vs %lld)", fn,
-                     (long long)N, opts->precond_user ? (long long)precond_size((lsfc_precond*)opts->precond_user) : -1LL);
+    const Precond pc(opts->precond, opts->precond_user, opts->precond_on_device != 0, batch, N, fn);
     LSFC_HIP(hipSetDevice(plan->device));
     const bool host = memspace == LSFC_MEM_HOST;
     const bool stage = host && plan->xs.n < (size_t)n * (size_t)N;
@@ -605,7 +594,7 @@ static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double*
         LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
         xd = plan->xs.p; bd = plan->ys.p;
     }
-    bicgstabl_run(plan, n, (cplx*)xd, bd, (const cplx*)opts->r_shadow, host, own_precond, *opts, l, maxmv, reltol, abstol, resnorm,
+    bicgstabl_run(plan, n, (cplx*)xd, bd, (const cplx*)opts->r_shadow, host, pc, *opts, l, maxmv, reltol, abstol, resnorm,
                   resnorm_cap > 0 ? resnorm_cap : 0, results, code);
     if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, bytes, hipMemcpyDeviceToHost));
 }

@@ -6,7 +6,6 @@
 // only O(restart) scalars per step cross to the host.
 #include "plan.hpp"
 #include "pointwise.hpp"
-#include "blocktri.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <complex>
@@ -389,13 +388,14 @@ struct Solve {
 };
 
 // the preconditioner on Krylov column `col` of one solve
-void precondition(Team& T, const lsfc_gmres_opts& o, int col) {
-    if (!o.precond) return;
-    if (o.precond_on_device) LSFC_REQUIRE(T.mem.size() == 1, "a device-resident preconditioner callback needs a single-device plan");
+void precondition(Team& T, const Precond& pc, int col) {
+    if (!pc.fn) return;
+    if (pc.on_device) LSFC_REQUIRE(T.mem.size() == 1, "a device-resident preconditioner callback needs a single-device plan");
     if (T.mem.size() == 1) {
         Member& m = T.mem[0];
         Team::dev(m);
-        precond_call_dev(o.precond, o.precond_user, o.precond_on_device != 0, Team::V(m, col), m.p->N, T.rootw->vpin, m.p->stream);
+        cplx* const v = Team::V(m, col);
+        pc.apply(&v, 1, T.rootw->vpin, m.p->stream);
         return;
     }
     // host callback, in place on the whole vector (the two-argument ldiv!): gather the slabs, call, scatter
@@ -403,7 +403,7 @@ void precondition(Team& T, const lsfc_gmres_opts& o, int col) {
     int64_t off = 0;
     T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(vpin + off, Team::V(m, col), (size_t)m.p->N * sizeof(cplx), hipMemcpyDeviceToHost, m.p->stream)); off += m.p->N; });
     T.sync();
-    const int rc = o.precond(o.precond_user, (double*)vpin, T.root->N);
+    const int rc = pc.fn(pc.user, (double*)vpin, T.root->N);
     if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
     off = 0;
     T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(Team::V(m, col), vpin + off, (size_t)m.p->N * sizeof(cplx), hipMemcpyHostToDevice, m.p->stream)); off += m.p->N; });
@@ -412,11 +412,12 @@ void precondition(Team& T, const lsfc_gmres_opts& o, int col) {
 // one solve over a team
 void solve(Team& T, const Resolved& r, double* resnorm, int64_t cap, lsfc_gmres_result* res) {
     Solve S(T, r, resnorm, cap, res, false);
+    const Precond pc(r.o.precond, r.o.precond_user, r.o.precond_on_device != 0, false, T.root->N, nullptr);   // (a single solve meets nobody)
     while (S.running()) {
         for (Request q; S.request(q);) {
             if (q.apply) T.apply(q);
             S.applied(q);
-            precondition(T, r.o, q.col);
+            precondition(T, pc, q.col);
             S.post(q);
         }
         S.consume();
@@ -440,14 +441,11 @@ void gmres_run(lsfc_plan* p, cplx* x, const cplx* b, const lsfc_gmres_opts* opts
 // Lock step, on the calling thread.  All running members are always in the same phase -- they start together, the restart
 // comes at the same k for every member and costs each of them one operator application, DGKS applies none, and a member
 // only ever leaves -- so a round is: one request per member (all of one kind), the operator on all of them in groups that
-// share a pass of the pipeline, the preconditioner (the library's own object: all columns at once; any other callback:
-// member by member, in member order), every member's kernels, and only then the scalars of each.
+// share a pass of the pipeline, the preconditioner (Precond::apply), every member's kernels, and only then the scalars of each.
 void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap,
                      lsfc_gmres_result* res) {
     const Resolved r = resolve(opts_in, p->N);
-    const bool host_cb = r.o.precond != nullptr && !r.o.precond_on_device;
-    const bool own_precond = r.o.precond_on_device && r.o.precond == &lsfc_precond_callback;
-    lsfc_precond* pc = (lsfc_precond*)r.o.precond_user;
+    const Precond pc(r.o.precond, r.o.precond_user, r.o.precond_on_device != 0, true, p->N, nullptr);
     // one workspace (Krylov basis, scalars, pinned buffers) per right-hand side: nrhs * (restart + 2) vectors of N complex.
     // Checked against the free device memory up front (a failed hipMalloc half way through leaves a half-built batch), and
     // released again when the call returns -- the single-solve workspace of the plan is the one that is kept across calls.
@@ -460,10 +458,8 @@ void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_
                  "-- solve fewer right-hand sides per call or lower the restart length", nrhs, r.restart, (long long)p->N, need / 1e9, (double)free_b / 1e9);
     }
     std::vector<std::unique_ptr<GmresWorkspace>> ws;
-    for (int j = 0; j < nrhs; ++j) ws.push_back(new_workspace(p->N, r.restart, host_cb && j == 0));      // (one pinned vector serves every member's callback)
+    for (int j = 0; j < nrhs; ++j) ws.push_back(new_workspace(p->N, r.restart, pc.fn && !pc.on_device && j == 0));      // (one pinned vector serves every member's callback)
     LSFC_HIP(hipStreamSynchronize(p->stream));
-    if (own_precond)
-        LSFC_REQUIRE(pc && precond_size(pc) == p->N, "preconditioner: size mismatch (%lld vs %lld)", (long long)p->N, pc ? (long long)precond_size(pc) : -1LL);
     std::vector<Team> teams((size_t)nrhs);
     std::vector<Solve> S;
     S.reserve((size_t)nrhs);
@@ -487,8 +483,7 @@ void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_
             }
             if (q[0].apply) plan_apply_batch_dev(p, in.data(), out.data(), in.size());
             for (size_t a = 0; a < act.size(); ++a) act[a]->applied(q[a]);
-            if (own_precond) precond_apply_batch_dev(pc, col.data(), (int)col.size(), p->stream);
-            else if (r.o.precond) for (cplx* v : col) precond_call_dev(r.o.precond, r.o.precond_user, r.o.precond_on_device != 0, v, p->N, ws[0]->vpin, p->stream);
+            pc.apply(col.data(), col.size(), ws[0]->vpin, p->stream);
             for (size_t a = 0; a < act.size(); ++a) act[a]->post(q[a]);
             size_t kept = 0;
             for (Solve* s : act) { s->consume(); if (s->running()) act[kept++] = s; }

@@ -1,6 +1,7 @@
 // lsfc C ABI: plan construction, the operator apply, timing helpers (gfx950).
 #include "plan.hpp"
 #include "pointwise.hpp"
+#include "blocktri.hpp"
 #include <cmath>
 #include <cstring>
 #include <condition_variable>
@@ -539,15 +540,25 @@ void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out,
     }
 }
 
-void precond_call_dev(lsfc_precond_fn precond, void* user, bool on_device, cplx* v, int64_t N, cplx* pinned, hipStream_t st) {
-    if (!on_device) {
-        LSFC_HIP(hipMemcpyAsync(pinned, v, (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        LSFC_HIP(hipStreamSynchronize(st));
+Precond::Precond(lsfc_precond_fn f, void* u, bool dev, bool meet, int64_t n, const char* who)
+    : fn(f), user(u), on_device(dev), own(meet && dev && f == &lsfc_precond_callback), N(n) {
+    const int64_t have = own && user ? precond_size((lsfc_precond*)user) : -1;
+    if (own) LSFC_REQUIRE(have == N, "%s%spreconditioner: size mismatch (%lld vs %lld)", who ? who : "", who ? ": " : "", (long long)N, (long long)have);
+}
+
+void Precond::apply(cplx* const* v, size_t cnt, cplx* pinned, hipStream_t st) const {
+    if (!fn) return;
+    if (own) { precond_apply_batch_dev((lsfc_precond*)user, v, (int)cnt, st); return; }
+    for (size_t j = 0; j < cnt; ++j) {
+        if (!on_device) {
+            LSFC_HIP(hipMemcpyAsync(pinned, v[j], (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
+            LSFC_HIP(hipStreamSynchronize(st));
+        }
+        const int rc = fn(user, (double*)(on_device ? v[j] : pinned), N);
+        if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+        // (whatever next goes into the pinned vector is ordered after this copy on st)
+        if (!on_device) LSFC_HIP(hipMemcpyAsync(v[j], pinned, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));
     }
-    const int rc = precond(user, (double*)(on_device ? v : pinned), N);
-    if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-    // (whatever next goes into the pinned vector is ordered after this copy on st)
-    if (!on_device) LSFC_HIP(hipMemcpyAsync(v, pinned, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));
 }
 
 static void ensure_staging(lsfc_plan* p, int64_t count) {

@@ -158,10 +158,15 @@ inline void plan_apply_dev(lsfc_plan* p, const cplx* x, cplx* y) { plan_convolve
 // ... on cnt (in, out) pairs, in groups of LSFC_MAX_BATCH that share one pass of the pipeline (the batched solvers)
 void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out, size_t cnt);
 
-// The solvers' defaults and their call of the caller's preconditioner on one device vector of N complex: the device
-// callback as given; the host callback on the pinned vector, with the copies and the synchronisation of `st` around it
+// The solvers' defaults, and the caller's preconditioner of a solve on vectors of N complex, resolved once.  own: the library's own
+// object on the device, where the members of a batch meet (`meet`): apply() hands it all cnt vectors for its group sweeps; any other
+// callback gets them one by one, in order, a host callback through `pinned`.  The size of an own object is checked here, under `who`.
 constexpr double DEFAULT_RELTOL = 0x1p-26;      // sqrt(eps)
-void precond_call_dev(lsfc_precond_fn precond, void* user, bool on_device, cplx* v, int64_t N, cplx* pinned, hipStream_t st);
+struct Precond {
+    lsfc_precond_fn fn; void* user; bool on_device, own; int64_t N;
+    Precond(lsfc_precond_fn fn, void* user, bool on_device, bool meet, int64_t N, const char* who);
+    void apply(cplx* const* v, size_t cnt, cplx* pinned, hipStream_t st) const;
+};
 
 // The fused z pass of the 3D tiled layout on `Wc` x' storage indices, starting at the tile that the offsets into A2 and
 // the symbol point to (the whole range on one device; dist.hip: one chunk of the owned range)

@@ -357,77 +357,45 @@ def _device_view(ptr, n):
 _ORTH = {"ModifiedGramSchmidt": L.LSFC_ORTH_MGS, "ClassicalGramSchmidt": L.LSFC_ORTH_CGS, "DGKS": L.LSFC_ORTH_DGKS}
 
 
-def gmres_(x, A, b, Pl=None, abstol=0.0, reltol=None, restart=None, maxiter=None, log=False,
-           initially_zero=False, orth_meth="ModifiedGramSchmidt", Pl_on_device=False):
-    """gmres!(x, A, b; Pl, abstol, reltol, restart, maxiter, log, initially_zero, orth_meth).
-
-    ``Pl`` is a callable ``v -> None`` that overwrites the host numpy vector v with Pl \\ v -- the
-    two-argument in-place ``ldiv!(Pl, v)`` of src/preconditioner.jl:147-170.  x is updated in place.
-    ``Pl_on_device=True``: Pl instead receives a torch CUDA tensor aliasing the Krylov vector on the device (no PCIe
-    round trip) and must work on torch's current stream."""
-    N = A.N
-    px, sx, keepx = _vec(x, N, "x", plan=A._plan)
-    pb, sb, keepb = _vec(b, N, "b")
+def _solve_vecs(x, b, A):
+    """(x, b) of a single solve -> (px, pb, memspace, keepalive of b); x is updated in place, so it goes in as it is"""
+    px, sx, keepx = _vec(x, A.N, "x", plan=A._plan)
+    pb, sb, keepb = _vec(b, A.N, "b")
     if sx != sb:
         raise TypeError("x and b must live in the same memory space")
     if not _is_torch(x) and keepx is not x:
         raise TypeError("x must be a contiguous complex128 array (it is updated in place)")
-    opts = L.GmresOpts()
-    opts.restart = int(restart) if restart is not None else 0
-    opts.maxiter = int(maxiter) if maxiter is not None else 0
-    opts.reltol = float(reltol) if reltol is not None else -1.0
-    opts.abstol = float(abstol)
-    opts.orth = _ORTH[orth_meth]
-    opts.initially_zero = 1 if initially_zero else 0
-    err = []
-    native_pc = getattr(Pl, "_pc", None) if Pl is not None else None
-    if native_pc is not None:
-        # device-resident SparsifyingPreconditioner: the library calls it directly, no Python in the loop; the Krylov
-        # basis lives on the device wherever x and b live, so the preconditioner sees device vectors either way
-        if sx == L.LSFC_MEM_DEVICE:
-            import torch
-            Pl.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
-        else:
-            L.check(L.load().lsfc_plan_set_stream(A._plan, None))
-            Pl.set_stream(0)
-        lib = L.load()
-        opts.precond = C.cast(lib.lsfc_precond_callback, L.PRECOND_FN)
-        opts.precond_user = native_pc
-        opts.precond_on_device = 1
-    elif Pl is not None:
-        def _cb(user, v, n):
-            try:
-                if Pl_on_device:
-                    Pl(_device_view(C.cast(v, C.c_void_p).value, n))
-                    return 0
-                arr = np.ctypeslib.as_array(C.cast(v, C.POINTER(C.c_double)), shape=(2 * n,)).view(np.complex128)
-                Pl(arr)
-                return 0
-            except Exception as e:      # never let a Python exception cross the C boundary
-                err.append(e)
-                return 1
-        cb = L.PRECOND_FN(_cb)
-        opts.precond = cb
-        opts.precond_on_device = 1 if Pl_on_device else 0
-    cap = int(maxiter) if maxiter is not None else N
-    cap = max(1, min(cap, 1 << 20))
-    res = L.GmresResult()
-    resnorm = np.zeros(cap, dtype=np.float64)
-    rc = L.load().lsfc_gmres(A._plan, px, pb, C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, C.byref(res), sx)
-    if err:
-        raise err[0]
-    if rc not in (0, L.LSFC_ENOTCONV):
-        L.check(rc)
-    if log:
-        return x, ConvergenceHistory(resnorm[:min(res.iters, cap)].copy(), int(res.iters), int(res.mvps), bool(res.converged))
-    return x
+    return px, pb, sx, keepb
+
+
+def _batch_vecs(X, B, A):
+    """(X, B) of a batched solve, one right-hand side per row -> (nrhs, (px, pb, memspace, keepalive of B)); X is
+    updated in place, so it goes in as it is"""
+    N = A.N
+    if _is_torch(X):
+        nrhs = X.shape[0]
+        px, sx, keepx = _vec(X.reshape(-1), N, "X", count=nrhs, plan=A._plan)
+        pb, sb, keepb = _vec(B.reshape(-1), N, "B", count=nrhs)
+        if keepx.data_ptr() != X.data_ptr():
+            raise TypeError("X must be contiguous (it is updated in place)")
+        if sx != sb:
+            raise TypeError("X and B must live in the same memory space")
+        return nrhs, (px, pb, sx, keepb)
+    if not (isinstance(X, np.ndarray) and X.dtype == np.complex128 and X.flags.c_contiguous and X.ndim == 2 and X.shape[1] == N):
+        raise TypeError(f"X must be a C-contiguous complex128 array of shape (nrhs, {N}) (it is updated in place)")
+    Bc = np.ascontiguousarray(B, dtype=np.complex128)
+    if Bc.shape != X.shape:
+        raise ValueError("DimensionMismatch: B")
+    return X.shape[0], (X.ctypes.data_as(C.c_void_p), Bc.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, Bc)
 
 
 def _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err):
     """fill precond / precond_user / precond_on_device of a solver's option struct (gmres_ documents the three routes);
-    returns what must stay alive for the duration of the call"""
+    returns what must stay alive for the duration of the call; an exception of Pl ends up in err"""
     native_pc = getattr(Pl, "_pc", None) if Pl is not None else None
     if native_pc is not None:
+        # device-resident SparsifyingPreconditioner: the library calls it directly, no Python in the loop; the Krylov
+        # basis lives on the device wherever x and b live, so the preconditioner sees device vectors either way
         if sx == L.LSFC_MEM_DEVICE:
             import torch
             Pl.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
@@ -457,6 +425,91 @@ def _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err):
     return cb
 
 
+def _solve(entry, A, x, vecs, nrhs, opts, Pl, Pl_on_device, cap, ok=(0,), status=None):
+    """One call of the library's solver `entry` (nrhs None: the single form) -> (rc, results, resnorm rows).  In this order:
+    the stream moves of _precond_opts, the call, the exception of the caller's Pl (the library only saw its callback fail),
+    the return code.  The copy of b in vecs, r_shadow (the caller holds it) and the ctypes callback live until this returns."""
+    px, pb, sx, keepb = vecs
+    err = []
+    cb = _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err)
+    rows = 1 if nrhs is None else max(nrhs, 1)
+    res = (L.GmresResult * rows)()
+    resnorm = np.zeros((rows, cap), dtype=np.float64)
+    args = [A._plan, px, pb]
+    if nrhs is not None:
+        args.append(nrhs)
+    args += [C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, res]
+    if status is not None:
+        args.append(status.ctypes.data_as(C.c_void_p))
+    rc = getattr(L.load(), entry)(*args, sx)
+    if err:
+        raise err[0]
+    if rc not in ok:
+        L.check(rc)
+    return rc, res, resnorm
+
+
+def _history(res, resnorm, cap):
+    """ConvergenceHistory of one solve from its result struct and its row of resnorm"""
+    return ConvergenceHistory(resnorm[:min(res.iters, cap)].copy(), int(res.iters), int(res.mvps), bool(res.converged))
+
+
+def _gmres_opts(abstol, reltol, restart, maxiter, initially_zero, orth_meth):
+    opts = L.GmresOpts()
+    opts.restart = int(restart) if restart is not None else 0
+    opts.maxiter = int(maxiter) if maxiter is not None else 0
+    opts.reltol = float(reltol) if reltol is not None else -1.0
+    opts.abstol = float(abstol)
+    opts.orth = _ORTH[orth_meth]
+    opts.initially_zero = 1 if initially_zero else 0
+    return opts
+
+
+def _gmres_cap(maxiter, N):
+    """length of a resnorm row: one entry per iteration"""
+    return max(1, min(int(maxiter) if maxiter is not None else N, 1 << 20))
+
+
+def gmres_(x, A, b, Pl=None, abstol=0.0, reltol=None, restart=None, maxiter=None, log=False,
+           initially_zero=False, orth_meth="ModifiedGramSchmidt", Pl_on_device=False):
+    """gmres!(x, A, b; Pl, abstol, reltol, restart, maxiter, log, initially_zero, orth_meth).
+
+    ``Pl`` is a callable ``v -> None`` that overwrites the host numpy vector v with Pl \\ v -- the
+    two-argument in-place ``ldiv!(Pl, v)`` of src/preconditioner.jl:147-170.  x is updated in place.
+    ``Pl_on_device=True``: Pl instead receives a torch CUDA tensor aliasing the Krylov vector on the device (no PCIe
+    round trip) and must work on torch's current stream."""
+    vecs = _solve_vecs(x, b, A)
+    opts = _gmres_opts(abstol, reltol, restart, maxiter, initially_zero, orth_meth)
+    cap = _gmres_cap(maxiter, A.N)
+    rc, res, resnorm = _solve("lsfc_gmres", A, x, vecs, None, opts, Pl, Pl_on_device, cap, ok=(0, L.LSFC_ENOTCONV))
+    if log:
+        return x, _history(res[0], resnorm[0], cap)
+    return x
+
+
+def _bicgstabl_opts(l, max_mv_products, abstol, reltol, initially_zero, r_shadow, N, count, sx, xname):
+    """-> (opts, keepalive of r_shadow); r_shadow: None or count vectors, flat, in the memory space of x"""
+    opts = L.BicgstablOpts()
+    opts.l = int(l)
+    opts.max_mv_products = int(max_mv_products) if max_mv_products is not None else 0
+    opts.reltol = float(reltol) if reltol is not None else -1.0
+    opts.abstol = float(abstol)
+    opts.initially_zero = 1 if initially_zero else 0
+    if r_shadow is None:
+        return opts, None
+    ps, ss, keeps = _vec(r_shadow, N, "r_shadow", count=count)
+    if ss != sx:
+        raise TypeError(f"r_shadow and {xname} must live in the same memory space")
+    opts.r_shadow = ps
+    return opts, keeps
+
+
+def _bicgstabl_cap(opts, N):
+    """length of a resnorm row: one entry per cycle of 2 l operator applications (capped like gmres_)"""
+    cap = (opts.max_mv_products if opts.max_mv_products > 0 else N) // (2 * max(opts.l, 1)) + 2
+    return max(1, min(cap, 1 << 20))
+
+
 def bicgstabl_(x, A, b, l=2, Pl=None, max_mv_products=None, abstol=0.0, reltol=None, log=False, Pl_on_device=False,
                r_shadow=None, initially_zero=False):
     """bicgstabl!(x, A, b, l; Pl, max_mv_products, abstol, reltol, log): left-preconditioned BiCGStab(l) on the device
@@ -471,40 +524,12 @@ def bicgstabl_(x, A, b, l=2, Pl=None, max_mv_products=None, abstol=0.0, reltol=N
     A breakdown (rho, sigma or gamma zero where it divides, or not finite) ends the solve with x the last finite iterate;
     the history then reports ``isconverged == False`` unless that iterate is within the tolerance already.  x is
     updated in place."""
-    N = A.N
-    px, sx, keepx = _vec(x, N, "x", plan=A._plan)
-    pb, sb, keepb = _vec(b, N, "b")
-    if sx != sb:
-        raise TypeError("x and b must live in the same memory space")
-    if not _is_torch(x) and keepx is not x:
-        raise TypeError("x must be a contiguous complex128 array (it is updated in place)")
-    opts = L.BicgstablOpts()
-    opts.l = int(l)
-    opts.max_mv_products = int(max_mv_products) if max_mv_products is not None else 0
-    opts.reltol = float(reltol) if reltol is not None else -1.0
-    opts.abstol = float(abstol)
-    opts.initially_zero = 1 if initially_zero else 0
-    keeps = None
-    if r_shadow is not None:
-        ps, ss, keeps = _vec(r_shadow, N, "r_shadow")
-        if ss != sx:
-            raise TypeError("r_shadow and x must live in the same memory space")
-        opts.r_shadow = ps
-    err = []
-    cb = _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err)
-    # one history entry per cycle of 2 l operator applications (capped like gmres_)
-    cap = (opts.max_mv_products if opts.max_mv_products > 0 else N) // (2 * max(opts.l, 1)) + 2
-    cap = max(1, min(cap, 1 << 20))
-    res = L.GmresResult()
-    resnorm = np.zeros(cap, dtype=np.float64)
-    rc = L.load().lsfc_bicgstabl(A._plan, px, pb, C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, C.byref(res), sx)
-    del cb, keeps, keepb
-    if err:
-        raise err[0]
-    if rc not in (0, L.LSFC_ENOTCONV):
-        L.check(rc)
+    vecs = _solve_vecs(x, b, A)
+    opts, keeps = _bicgstabl_opts(l, max_mv_products, abstol, reltol, initially_zero, r_shadow, A.N, 1, vecs[2], "x")
+    cap = _bicgstabl_cap(opts, A.N)
+    rc, res, resnorm = _solve("lsfc_bicgstabl", A, x, vecs, None, opts, Pl, Pl_on_device, cap, ok=(0, L.LSFC_ENOTCONV))
     if log:
-        hist = ConvergenceHistory(resnorm[:min(res.iters, cap)].copy(), int(res.iters), int(res.mvps), bool(res.converged))
+        hist = _history(res[0], resnorm[0], cap)
         hist.message = L.load().lsfc_last_error().decode(errors="replace") if rc == L.LSFC_ENOTCONV else ""
         return x, hist
     return x
@@ -525,56 +550,21 @@ def bicgstabl_batch_(X, A, B, l=2, Pl=None, max_mv_products=None, abstol=0.0, re
     ``r_shadow``: None or one shadow residual per row, in the memory space of X.  nrhs <= 64; device memory
     nrhs (2 l + 3) vectors.  Returns X or (X, [ConvergenceHistory per row]); ``.message`` of a row that did not converge
     names the reason (max_mv_products, or the scalar of the breakdown) and the cycle."""
-    N = A.N
     torch_in = _is_torch(X)
-    if torch_in:
-        if X.dim() != 2 or tuple(B.shape) != tuple(X.shape):
-            raise ValueError(f"DimensionMismatch: X and B must both be (nrhs, {N})")
-        nrhs = X.shape[0]
-        px, sx, keepx = _vec(X.reshape(-1), N, "X", count=nrhs, plan=A._plan)
-        pb, sb, keepb = _vec(B.reshape(-1), N, "B", count=nrhs)
-        if keepx.data_ptr() != X.data_ptr():
-            raise TypeError("X must be contiguous (it is updated in place)")
-    else:
-        if not (isinstance(X, np.ndarray) and X.dtype == np.complex128 and X.flags.c_contiguous and X.ndim == 2 and X.shape[1] == N):
-            raise TypeError(f"X must be a C-contiguous complex128 array of shape (nrhs, {N}) (it is updated in place)")
-        nrhs = X.shape[0]
-        Bc = np.ascontiguousarray(B, dtype=np.complex128)
-        if Bc.shape != X.shape:
-            raise ValueError("DimensionMismatch: B")
-        px, sx, pb, sb, keepb = X.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, Bc.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, Bc
-    if sx != sb:
-        raise TypeError("X and B must live in the same memory space")
-    opts = L.BicgstablOpts()
-    opts.l = int(l)
-    opts.max_mv_products = int(max_mv_products) if max_mv_products is not None else 0
-    opts.reltol = float(reltol) if reltol is not None else -1.0
-    opts.abstol = float(abstol)
-    opts.initially_zero = 1 if initially_zero else 0
-    keeps = None
+    if torch_in and (X.dim() != 2 or tuple(B.shape) != tuple(X.shape)):
+        raise ValueError(f"DimensionMismatch: X and B must both be (nrhs, {A.N})")
+    nrhs, vecs = _batch_vecs(X, B, A)
     if r_shadow is not None:
-        ps, ss, keeps = _vec(r_shadow.reshape(-1) if torch_in else np.asarray(r_shadow).reshape(-1), N, "r_shadow", count=nrhs)
-        if ss != sx:
-            raise TypeError("r_shadow and X must live in the same memory space")
-        opts.r_shadow = ps
-    err = []
-    cb = _precond_opts(opts, Pl, Pl_on_device, A, X, sx, err)
-    cap = (opts.max_mv_products if opts.max_mv_products > 0 else N) // (2 * max(opts.l, 1)) + 2
-    cap = max(1, min(cap, 1 << 20))
-    res = (L.GmresResult * max(nrhs, 1))()
-    resnorm = np.zeros((max(nrhs, 1), cap), dtype=np.float64)
+        r_shadow = r_shadow.reshape(-1) if torch_in else np.asarray(r_shadow).reshape(-1)
+    opts, keeps = _bicgstabl_opts(l, max_mv_products, abstol, reltol, initially_zero, r_shadow, A.N, nrhs, vecs[2], "X")
+    cap = _bicgstabl_cap(opts, A.N)
     status = np.zeros((max(nrhs, 1), 2), dtype=np.int64)
-    rc = L.load().lsfc_bicgstabl_batch(A._plan, px, pb, nrhs, C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, res,
-                                       status.ctypes.data_as(C.c_void_p), sx)
-    del cb, keeps, keepb
-    if err:
-        raise err[0]
-    L.check(rc)
+    _, res, resnorm = _solve("lsfc_bicgstabl_batch", A, X, vecs, nrhs, opts, Pl, Pl_on_device, cap, status=status)
     if not log:
         return X
     hists = []
     for j in range(nrhs):
-        h = ConvergenceHistory(resnorm[j, :min(res[j].iters, cap)].copy(), int(res[j].iters), int(res[j].mvps), bool(res[j].converged))
+        h = _history(res[j], resnorm[j], cap)
         code, cyc = int(status[j, 0]), int(status[j, 1])
         h.status = (code, cyc)
         if code == L.LSFC_BICG_CONVERGED:
@@ -614,64 +604,14 @@ def gmres_batch_(X, A, B, Pl=None, abstol=0.0, reltol=None, restart=None, maxite
     sweep per step for a block-tridiagonal object); any other callable ``v -> None`` gets one host vector at a time, row
     after row, on the calling thread.  The library starts no threads, and the groups of rows are the same in every run.
     Returns X or (X, [ConvergenceHistory per row])."""
-    torch_in = _is_torch(X)
-    if torch_in:
-        nrhs = X.shape[0]
-        px, sx, keepx = _vec(X.reshape(-1), A.N, "X", count=nrhs, plan=A._plan)
-        pb, sb, keepb = _vec(B.reshape(-1), A.N, "B", count=nrhs)
-        if keepx.data_ptr() != X.data_ptr():
-            raise TypeError("X must be contiguous (it is updated in place)")
-    else:
-        if not (isinstance(X, np.ndarray) and X.dtype == np.complex128 and X.flags.c_contiguous and X.ndim == 2 and X.shape[1] == A.N):
-            raise TypeError(f"X must be a C-contiguous complex128 array of shape (nrhs, {A.N}) (it is updated in place)")
-        nrhs = X.shape[0]
-        Bc = np.ascontiguousarray(B, dtype=np.complex128)
-        if Bc.shape != X.shape:
-            raise ValueError("DimensionMismatch: B")
-        px, sx, pb, sb, keepb = X.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, Bc.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, Bc
-    if sx != sb:
-        raise TypeError("X and B must live in the same memory space")
-    opts = L.GmresOpts()
-    opts.restart = int(restart) if restart is not None else 0
-    opts.maxiter = int(maxiter) if maxiter is not None else 0
-    opts.reltol = float(reltol) if reltol is not None else -1.0
-    opts.abstol = float(abstol)
-    opts.orth = _ORTH[orth_meth]
-    opts.initially_zero = 1 if initially_zero else 0
-    err = []
-    native_pc = getattr(Pl, "_pc", None) if Pl is not None else None
-    if native_pc is not None:
-        # device-resident SparsifyingPreconditioner, as in gmres_: called by the library on the device vectors; the
-        # right-hand sides meet at it and a block-tridiagonal object takes their Krylov vectors in one group sweep
-        if sx == L.LSFC_MEM_DEVICE:
-            import torch
-            Pl.set_stream(torch.cuda.current_stream(X.device).cuda_stream)
-        else:
-            L.check(L.load().lsfc_plan_set_stream(A._plan, None))
-            Pl.set_stream(0)
-        opts.precond = C.cast(L.load().lsfc_precond_callback, L.PRECOND_FN)
-        opts.precond_user = native_pc
-        opts.precond_on_device = 1
-    elif Pl is not None:
-        def _cb(user, v, n):
-            try:
-                Pl(np.ctypeslib.as_array(C.cast(v, C.POINTER(C.c_double)), shape=(2 * n,)).view(np.complex128))
-                return 0
-            except Exception as e:
-                err.append(e)
-                return 1
-        cb = L.PRECOND_FN(_cb)
-        opts.precond = cb
-    cap = max(1, min(int(maxiter) if maxiter is not None else A.N, 1 << 20))
-    res = (L.GmresResult * nrhs)()
-    resnorm = np.zeros((nrhs, cap), dtype=np.float64)
-    rc = L.load().lsfc_gmres_batch(A._plan, px, pb, nrhs, C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, res, sx)
-    if err:
-        raise err[0]
-    L.check(rc)
+    nrhs, vecs = _batch_vecs(X, B, A)
+    opts = _gmres_opts(abstol, reltol, restart, maxiter, initially_zero, orth_meth)
+    cap = _gmres_cap(maxiter, A.N)
+    # a device-resident SparsifyingPreconditioner is called by the library on the device vectors, as in gmres_; the
+    # right-hand sides meet at it and a block-tridiagonal object takes their Krylov vectors in one group sweep
+    _, res, resnorm = _solve("lsfc_gmres_batch", A, X, vecs, nrhs, opts, Pl, False, cap)
     if log:
-        return X, [ConvergenceHistory(resnorm[j, :min(res[j].iters, cap)].copy(), int(res[j].iters), int(res[j].mvps), bool(res[j].converged))
-                   for j in range(nrhs)]
+        return X, [_history(res[j], resnorm[j], cap) for j in range(nrhs)]
     return X
 
 

@@ -7,57 +7,19 @@ the reductions see the order of summation.  Criteria of that suite: history with
 1e-10, iters / mvps / converged equal (one cycle apart only where the reference stops within 1e-8 of the tolerance).
 The real-operator tests run the 3D 16^3 golden problem and the preconditioned systems of tests/test_gpu_sparsify.py."""
 import ctypes as C
-import types
+import functools
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 from oracle import lsfc_oracle as o
 import bicgstabl_ref as br
 import cases
 from conftest import rel_err
+import krylov_common as kc
+from krylov_common import _diag_precond, plan  # noqa: F401  (plan: the cached identity plans)
 
 pytestmark = pytest.mark.gpu
-
-
-def _shape(N):
-    """(n, m) with n m = N, both <= 8192, as square as possible"""
-    best = None
-    for n in range(1, 8193):
-        if N % n == 0 and N // n <= 8192 and (best is None or abs(n - N // n) < abs(best[0] - best[1])):
-            best = (n, N // n)
-    assert best is not None, N
-    return best
-
-
-_PLANS = {}
-
-
-@pytest.fixture(scope="module")
-def plan(lsfc):
-    """plan(N) -> a cached 2D plan with a ones symbol and nu == 0 whose apply is the identity, bitwise"""
-    def get(N):
-        if N not in _PLANS:
-            n, m = _shape(N)
-            M = lsfc.FastM(np.ones((2 * n, 2 * m), complex), np.zeros(N), 2 * n, 2 * m, n, m, 1.0,
-                           quadRule="Greengard_Vico", flags=lsfc._lib.LSFC_FLAG_FORCE_ROCFFT)
-            x = br.random_rhs(N, seed=N)
-            assert np.array_equal((M * x).view(np.float64), x.view(np.float64)), f"M * x != x at N = {N}"
-            _PLANS[N] = M
-        return _PLANS[N]
-    yield get
-    for M in _PLANS.values():
-        M.close()
-    _PLANS.clear()
-
-
-def _diag_precond(lsfc, lam):
-    """SparsifyingPreconditioner(Msp = I, As = diag(lam)) with identity factors: ldiv!(P, v) = lam .* v on the device"""
-    N = lam.size
-    eye = sp.identity(N, dtype=complex, format="csr")
-    lu = types.SimpleNamespace(perm_r=np.arange(N), perm_c=np.arange(N), L=eye, U=eye)
-    return lsfc.SparsifyingPreconditioner(eye, sp.diags(lam, format="csr"), lu=lu)
 
 
 _CASES = br.gpu_cases()
@@ -71,22 +33,7 @@ def _ref(label):
     return _REFS[label]
 
 
-def _check(label, x, hist, ref, gmap=None, rtol=1e-10):
-    r = np.asarray(hist["resnorm"])
-    assert np.all(np.isfinite(r)) and np.all(np.isfinite(x)), f"{label}: non-finite output"
-    same = (hist.iters, hist.mvps, hist.isconverged) == (ref["iters"], ref["mvps"], ref["converged"])
-    if not same:
-        last = ref["resnorm"][-1] if ref["resnorm"].size else ref["beta0"]
-        near = abs(last - ref["tol"]) <= 1e-8 * ref["tol"]
-        assert near and abs(hist.iters - ref["iters"]) <= 1, \
-            f"{label}: iters/mvps/converged {hist.iters}/{hist.mvps}/{hist.isconverged} vs reference " \
-            f"{ref['iters']}/{ref['mvps']}/{ref['converged']} ({getattr(hist, 'message', '')})"
-    ex, i = br.history_excess(r, ref, rtol=rtol)
-    print(f"{label}: {hist.iters} cycles, {hist.mvps} mvps, history excess {ex:.3f}")
-    assert ex < 1.0, f"{label}: history entry {i}: {r[i]!r} vs reference {ref['resnorm'][i]!r} ({ex:.2f}x the allowance)"
-    xr = ref["x"] if gmap is None else ref["x"][gmap]
-    err = float(np.sqrt(np.sum(np.abs(x - xr) ** 2) / np.sum(np.abs(xr) ** 2)))
-    assert err < max(1e-10, rtol), f"{label}: x differs from the reference iterate by {err:.2e}"
+_check = functools.partial(kc._check, history_excess=br.history_excess)
 
 
 def _run(lsfc, M, label, P, gmap=None, **over):

@@ -4,6 +4,7 @@ preconditioner, where the batched applies are bitwise member-independent -- and 
 tests/test_bicgstabl_batch_cases_cpu.py has checked the input condition.  "Bitwise" is np.array_equal on x, on the history
 and on (iters, mvps, converged)."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -13,9 +14,12 @@ import bicgstabl_ref as br
 import bicgstabl_batch_cases as bc
 import cases
 from conftest import rel_err
-from test_gpu_bicgstabl import _check, _diag_precond, plan  # noqa: F401  (plan: the cached identity plans)
+import krylov_common as kc
+from krylov_common import _bitwise, _diag_precond, plan  # noqa: F401  (plan: the cached identity plans)
 
 pytestmark = pytest.mark.gpu
+
+_check = functools.partial(kc._check, history_excess=br.history_excess)
 
 
 def _batch(lsfc, M, P, members, **over):
@@ -35,12 +39,6 @@ def _single(lsfc, M, P, kw):
                            abstol=kw.get("abstol", 0.0), log=True,
                            r_shadow=None if kw.get("r_shadow") is None else np.array(kw["r_shadow"], dtype=complex),
                            initially_zero=bool(kw.get("initially_zero", False)))
-
-
-def _bitwise(tag, X, hs, j, x1, h1):
-    assert np.array_equal(X[j].view(np.float64), x1.view(np.float64)), f"{tag}: x of member {j} is not its single solve"
-    assert np.array_equal(hs[j]["resnorm"], h1["resnorm"]), f"{tag}: history of member {j}: {hs[j]['resnorm']} vs {h1['resnorm']}"
-    assert (hs[j].iters, hs[j].mvps, hs[j].isconverged) == (h1.iters, h1.mvps, h1.isconverged), (tag, j)
 
 
 def _batch_is_the_single_solves(lsfc, M, P, members, tag):

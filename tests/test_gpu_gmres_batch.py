@@ -11,8 +11,7 @@ import pytest
 
 import cases
 import gmres_ref as gr
-from test_gpu_bicgstabl import _diag_precond, plan  # noqa: F401  (plan: the cached identity plans)
-from test_gpu_bicgstabl_batch import _bitwise
+from krylov_common import _bitwise, _diag_precond, plan  # noqa: F401  (plan: the cached identity plans)
 
 pytestmark = pytest.mark.gpu
 

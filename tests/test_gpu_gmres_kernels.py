@@ -6,13 +6,14 @@ diag(lambda) -- the device SparsifyingPreconditioner with Msp = I, As = diag(lam
 splu), or a host / torch callback.  GMRES then iterates on exactly diag(lambda), and equal entries stay bitwise equal on
 the device: only the reductions see the order of summation.  Histories must match the reference to 1e-10 relative (plus
 the restart allowance of gmres_ref.history_excess) while it is above 1e-9 beta, x to 1e-10."""
-import types
+import functools
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 import gmres_ref as gr
+import krylov_common as kc
+from krylov_common import _diag_precond, plan  # noqa: F401  (plan: the cached identity plans)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,45 +21,6 @@ ORTH = {"MGS": "ModifiedGramSchmidt", "CGS": "ClassicalGramSchmidt", "DGKS": "DG
 # (orth, LSFC_MGS_BLOCK) of the device paths: strict / blocked MGS, fused or chunked CGS, DGKS
 PATHS = [("MGS", "0"), ("MGS", "1"), ("CGS", None), ("DGKS", None)]
 LARGE = [1 << 20, (1 << 20) + 3, (1 << 22) - 1, 1 << 22, (1 << 22) + 1]   # 2^20 + 1 = 17 * 61681 has no plan shape
-
-
-def _shape(N):
-    """(n, m) with n m = N, both <= 8192, as square as possible"""
-    best = None
-    for n in range(1, 8193):
-        if N % n == 0 and N // n <= 8192 and (best is None or abs(n - N // n) < abs(best[0] - best[1])):
-            best = (n, N // n)
-    assert best is not None, N
-    return best
-
-
-_PLANS = {}
-
-
-@pytest.fixture(scope="module")
-def plan(lsfc):
-    """plan(N) -> a cached 2D plan with a ones symbol and nu == 0 whose apply is the identity, bitwise"""
-    def get(N):
-        if N not in _PLANS:
-            n, m = _shape(N)
-            M = lsfc.FastM(np.ones((2 * n, 2 * m), complex), np.zeros(N), 2 * n, 2 * m, n, m, 1.0,
-                           quadRule="Greengard_Vico", flags=lsfc._lib.LSFC_FLAG_FORCE_ROCFFT)
-            x = gr.random_rhs(N, seed=N)
-            assert np.array_equal((M * x).view(np.float64), x.view(np.float64)), f"M * x != x at N = {N}"
-            _PLANS[N] = M
-        return _PLANS[N]
-    yield get
-    for M in _PLANS.values():
-        M.close()
-    _PLANS.clear()
-
-
-def _diag_precond(lsfc, lam):
-    """SparsifyingPreconditioner(Msp = I, As = diag(lam)) with identity factors: ldiv!(P, v) = lam .* v on the device"""
-    N = lam.size
-    eye = sp.identity(N, dtype=complex, format="csr")
-    lu = types.SimpleNamespace(perm_r=np.arange(N), perm_c=np.arange(N), L=eye, U=eye)
-    return lsfc.SparsifyingPreconditioner(eye, sp.diags(lam, format="csr"), lu=lu)
 
 
 _REFS = {}
@@ -70,23 +32,7 @@ def _ref(key, b, lam, counts=None, **kw):
     return _REFS[key]
 
 
-def _check(label, x, hist, ref, gmap=None):
-    """device result (x on the full vector, ConvergenceHistory) against the reference (x per group)"""
-    r = np.asarray(hist["resnorm"])
-    assert np.all(np.isfinite(r)) and np.all(np.isfinite(x)), f"{label}: non-finite output"
-    same = (hist.iters, hist.mvps, hist.isconverged) == (ref["iters"], ref["mvps"], ref["converged"])
-    if not same:
-        # one iteration apart only where the reference stops within 1e-8 (relative) of the tolerance
-        last = ref["resnorm"][-1] if ref["resnorm"].size else ref["beta0"]
-        near = abs(last - ref["tol"]) <= 1e-8 * ref["tol"]
-        assert near and abs(hist.iters - ref["iters"]) <= 1, \
-            f"{label}: iters/mvps/converged {hist.iters}/{hist.mvps}/{hist.isconverged} vs reference " \
-            f"{ref['iters']}/{ref['mvps']}/{ref['converged']}"
-    ex, i = gr.history_excess(r, ref)
-    assert ex < 1.0, f"{label}: history entry {i}: {r[i]!r} vs reference {ref['resnorm'][i]!r} ({ex:.2f}x the allowance)"
-    xr = ref["x"] if gmap is None else ref["x"][gmap]
-    err = float(np.sqrt(np.sum(np.abs(x - xr) ** 2) / np.sum(np.abs(xr) ** 2)))
-    assert err < 1e-10, f"{label}: x differs from the reference iterate by {err:.2e}"
+_check = functools.partial(kc._check, history_excess=gr.history_excess)
 
 
 def _solve(lsfc, M, P, b, monkeypatch, orth, mgs_block=None, lookahead=None, **kw):
