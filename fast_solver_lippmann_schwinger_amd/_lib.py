@@ -18,6 +18,7 @@ LSFC_FLAG_DEFAULT, LSFC_FLAG_LITERAL_PAD, LSFC_FLAG_FORCE_ROCFFT, LSFC_FLAG_PATC
 LSFC_ORTH_MGS, LSFC_ORTH_CGS, LSFC_ORTH_DGKS = 0, 1, 2
 LSFC_EINVAL, LSFC_ENODEV, LSFC_ENOMEM, LSFC_ENOTCONV = -1, -2, -3, -5
 LSFC_UNIQUE_ID_BYTES = 128
+LSFC_OP_N, LSFC_OP_T, LSFC_OP_H = 0, 1, 2
 # how a member of lsfc_bicgstabl_batch ended (status[2 j]); 2..7: the scalar of a breakdown
 (LSFC_BICG_CONVERGED, LSFC_BICG_MAX_MV, LSFC_BICG_RHO, LSFC_BICG_SIGMA, LSFC_BICG_BETA, LSFC_BICG_ALPHA, LSFC_BICG_GAMMA,
  LSFC_BICG_RESIDUAL) = range(8)
@@ -66,6 +67,9 @@ SIGNATURES = {
     "lsfc_plan_pipeline": (C.c_char_p, [_P]),
     "lsfc_plan_set_nu": (_I, [_P, _P, _I]),
     "lsfc_plan_get_symbol": (_I, [_P, _P, _L, C.POINTER(_L)]),
+    "lsfc_plan_set_op": (_I, [_P, _I]),
+    "lsfc_plan_get_op": (_I, [_P, C.POINTER(_I)]),
+    "lsfc_plan_symmetry_defect": (_I, [_P, C.POINTER(_D)]),
     "lsfc_apply": (_I, [_P, _P, _P, _I]),
     "lsfc_convolve": (_I, [_P, _P, _P, _I, _I]),
     "lsfc_apply_batch": (_I, [_P, _P, _P, _L, _I, _I]),

@@ -45,7 +45,7 @@ static constexpr int XB = 8;           // x' lines per strided workgroup: 8 * 16
 template <class C, int LPW, bool SPLIT, bool EXACT>
 __global__ __launch_bounds__(C::T * LPW)
 void k_xfwd(const VecBatch vb, int64_t obatch, const double* __restrict__ nu, cplx* __restrict__ out,
-            const cplx* __restrict__ tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride) {
+            const cplx* __restrict__ tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, int cj) {
     // blockIdx.y = right-hand side of the batch
     const cplx* __restrict__ x = vb.x[blockIdx.y];
     out += (int64_t)blockIdx.y * obatch;
@@ -64,6 +64,11 @@ void k_xfwd(const VecBatch vb, int64_t obatch, const double* __restrict__ nu, cp
         const double* nin = nu + lc * n;
 #pragma unroll
         for (int e = 0; e < E / 2; ++e) { const double s = (EXACT || t + T * e < n) ? nin[t + T * e] : 0.0; v[e].x *= s; v[e].y *= s; }
+    }
+    // cj (a kernel argument, like nu: one scalar branch per wave): the transform of conj(x), for the adjoint operator
+    if (cj) {
+#pragma unroll
+        for (int e = 0; e < E / 2; ++e) v[e].y = -v[e].y;
     }
 #pragma unroll
     for (int e = E / 2; e < E; ++e) v[e] = make_double2(0.0, 0.0);
@@ -84,7 +89,8 @@ void k_xfwd(const VecBatch vb, int64_t obatch, const double* __restrict__ nu, cp
 template <class C, int LPW, bool SPLIT, bool EXACT>
 __global__ __launch_bounds__(C::T * LPW)
 void k_xinv(const cplx* __restrict__ in, const VecBatch vb, int64_t ibatch, double alpha, double beta,
-            const cplx* __restrict__ tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride) {
+            const cplx* __restrict__ tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride,
+            const double* nu, int cj) {
     const cplx* xorig = vb.x[blockIdx.y];
     cplx* y = vb.y[blockIdx.y];
     in += (int64_t)blockIdx.y * ibatch;
@@ -103,12 +109,20 @@ void k_xinv(const cplx* __restrict__ in, const VecBatch vb, int64_t ibatch, doub
         v[e] = in[(int64_t)c * bstride + lc * Wp + (s - c * W)];
     }
     fft_inverse<C, LL, true>(v, t, tw, smem, ll * LL::line_elems(C::L), 0);
+    // y = alpha*x + beta * nu .* (conj) v: nu (the transposed operator; NOT __restrict__, like x it is read at the very index this
+    // thread then stores to) and cj are kernel arguments, as alpha is -- scalar branches, and with neither the arithmetic below
+    // is what it was (beta * v)
+    if (cj) {
+#pragma unroll
+        for (int e = 0; e < E / 2; ++e) v[e].y = -v[e].y;
+    }
     if (valid) {
 #pragma unroll
         for (int e = 0; e < E / 2; ++e) {
             if (EXACT || t + T * e < n) {
                 const int64_t idx = line * n + t + T * e;
-                cplx r = make_double2(beta * v[e].x, beta * v[e].y);
+                const double bs = nu ? beta * nu[idx] : beta;
+                cplx r = make_double2(bs * v[e].x, bs * v[e].y);
                 if (alpha != 0.0) { const cplx xo = xorig[idx]; r.x = fma(alpha, xo.x, r.x); r.y = fma(alpha, xo.y, r.y); }
                 y[idx] = r;
             }
@@ -633,21 +647,21 @@ template <class C> struct Tune {
 #endif
 };
 
-template <class C, bool SPLIT> static void xfwd_t(const PassForm& f, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st) {
+template <class C, bool SPLIT> static void xfwd_t(const PassForm& f, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, bool cj) {
     constexpr int LPW = Tune<C>::LPW;
     using LL = LdsLayout<1, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
     auto k = f.full ? k_xfwd<C, LPW, SPLIT, true> : k_xfwd<C, LPW, SPLIT, false>;
     allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, vb, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride);
+    hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, vb, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, (int)cj);
 }
-template <class C, bool SPLIT> static void xinv_t(const PassForm& f, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st) {
+template <class C, bool SPLIT> static void xinv_t(const PassForm& f, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, const double* nu, bool cj) {
     constexpr int LPW = Tune<C>::LPW;
     using LL = LdsLayout<1, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
     auto k = f.full ? k_xinv<C, LPW, SPLIT, true> : k_xinv<C, LPW, SPLIT, false>;
     allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride);
+    hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, nu, (int)cj);
 }
 static void ytile(const PrunedTuning& tn, int L, int ngrp, int l, int& TG, int& TZ) {
     // auto (0): all groups x 1 plane, except at L >= 1024 where 32 groups x 8 planes keeps the 128-B chunks that the
@@ -925,20 +939,20 @@ static int chunk_magic(int L, int W) {
     LSFC_REQUIRE(W >= 8 && W <= L && L % W == 0 && L <= 2048, "chunk width %d does not divide the line length %d", W, L);
     return (1 << 22) / W + 1;
 }
-void FAM(pruned_xfwd)(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride) {
+void FAM(pruned_xfwd)(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, bool cj) {
     const int wmagic = chunk_magic(L, W);
     if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
     const PassForm f = FAM(pruned_xform)(PassFamily::XFWD, L, tn, n);
-    if (f.split) { LSFC_DISPATCH_L(L, (xfwd_t<C, true>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
-    else         { LSFC_DISPATCH_L(L, (xfwd_t<C, false>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
+    if (f.split) { LSFC_DISPATCH_L(L, (xfwd_t<C, true>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
+    else         { LSFC_DISPATCH_L(L, (xfwd_t<C, false>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
     LSFC_HIP(hipGetLastError());
 }
-void FAM(pruned_xinv)(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride) {
+void FAM(pruned_xinv)(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, const double* nu, bool cj) {
     const int wmagic = chunk_magic(L, W);
     if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
     const PassForm f = FAM(pruned_xform)(PassFamily::XINV, L, tn, n);
-    if (f.split) { LSFC_DISPATCH_L(L, (xinv_t<C, true>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
-    else         { LSFC_DISPATCH_L(L, (xinv_t<C, false>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st))); }
+    if (f.split) { LSFC_DISPATCH_L(L, (xinv_t<C, true>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, cj))); }
+    else         { LSFC_DISPATCH_L(L, (xinv_t<C, false>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, cj))); }
     LSFC_HIP(hipGetLastError());
 }
 void FAM(pruned_yfwd)(int L, const PrunedTuning& tn, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {

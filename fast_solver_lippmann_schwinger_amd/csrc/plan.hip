@@ -402,13 +402,17 @@ static VecBatch slab_vectors(const lsfc_plan* p, const VecBatch& vb, int nrhs, S
 static cplx* slab_a1(const lsfc_plan* p, Slab s) { return p->A1.p + (int64_t)s.z0 * p->dims[1] * p->pitch1; }
 static cplx* slab_a2(const lsfc_plan* p, Slab s) { return p->A2.p + (int64_t)8 * s.z0; }
 
-static void pass_xfwd(lsfc_plan* p, const VecBatch& vb, int nrhs, const double* nu, Slab s, hipStream_t st) {
+// nu at the first plane of a slab, if the pass on side `side` of the convolution is the one that multiplies by it
+static const double* slab_nu(const lsfc_plan* p, const ConvOp& op, NuSide side, Slab s) {
+    return op.nu == side ? p->nu.p + (int64_t)s.z0 * p->dims[0] * p->dims[1] : nullptr;
+}
+static void pass_xfwd(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Slab s, hipStream_t st) {
     const int Lx = p->pads[0], n = p->dims[0];
     const int64_t nlines = (int64_t)p->dims[1] * s.nz;
     const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    if (nu) nu += (int64_t)s.z0 * n * p->dims[1];
-    if (p->tile2d) pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d);
-    else pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, slab_a1(p, s), p->tw[0].p, nlines, Lx, p->pitch1, n, st);
+    const double* nu = slab_nu(p, op, NuSide::INPUT, s);
+    if (p->tile2d) pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, op.conj);
+    else pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, slab_a1(p, s), p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, op.conj);
 }
 static void pass_yfwd(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {         // 3D only
     pruned_yfwd(p->pads[1], p->tuning, slab_a1(p, s), slab_a2(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
@@ -418,12 +422,13 @@ static void pass_yinv(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {         
     pruned_yinv(p->pads[1], p->tuning, slab_a2(p, s), slab_a1(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
                 nrhs, p->a1_elems, p->a2_elems);
 }
-static void pass_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, double alpha, double beta, Slab s, hipStream_t st) {
+static void pass_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Slab s, hipStream_t st) {
     const int Lx = p->pads[0], n = p->dims[0];
     const int64_t nlines = (int64_t)p->dims[1] * s.nz;
     const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, v, nrhs, p->a1_elems, alpha, beta, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d);
-    else pruned_xinv(Lx, p->tuning, slab_a1(p, s), v, nrhs, p->a1_elems, alpha, beta, p->tw[0].p, nlines, Lx, p->pitch1, n, st);
+    const double* nu = slab_nu(p, op, NuSide::OUTPUT, s);
+    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, nu, op.conj);
+    else pruned_xinv(Lx, p->tuning, slab_a1(p, s), v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, nu, op.conj);
 }
 
 // The three geometries of the fused pass.  3D: A2 as tiles [x'/8][Ly][pitch2 >= 8*l] of 8 interleaved z lines, the symbol as
@@ -486,39 +491,45 @@ static void pass_fused(lsfc_plan* p, int nrhs, hipStream_t st) {
 }
 
 // nrhs <= batch_cap right-hand sides through the pruned pipeline on the plan's stream
-static void pruned_convolve(lsfc_plan* p, int nrhs, const VecBatch& vb, bool use_nu, double alpha, double beta) {
+static void pruned_convolve(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op) {
     // (round 3, measured slower and removed again -- profiles/r03_experiment_a1_window.log: the x and y passes chunk by chunk over
     // groups of z planes through one chunk-sized window of A1, hoping the Infinity Cache would absorb the 2 x 4.3 GB of A1 traffic)
     hipStream_t st = p->stream;
     const Slab all = whole_grid(p);
-    pass_xfwd(p, vb, nrhs, use_nu ? p->nu.p : nullptr, all, st);
+    pass_xfwd(p, vb, nrhs, op, all, st);
     if (p->ndim == 3) pass_yfwd(p, nrhs, all, st);
     pass_fused(p, nrhs, st);
     if (p->ndim == 3) pass_yinv(p, nrhs, all, st);
-    pass_xinv(p, vb, nrhs, alpha, beta, all, st);
+    pass_xinv(p, vb, nrhs, op, all, st);
 }
 
-void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double alpha, double beta) {
-    if (p->dist) { dist_convolve_dev(p, x, y, use_nu, alpha, beta); return; }
+// (distributed and multi-device plans know M and the bare convolutions only: lsfc_plan_set_op refuses them)
+static bool forward_only(const ConvOp& op) { return op.nu != NuSide::OUTPUT && !op.conj; }
+
+void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op) {
+    if (p->dist) {
+        LSFC_REQUIRE(forward_only(op), "the transposed and the adjoint operator are not available on a distributed plan");
+        dist_convolve_dev(p, x, y, op.nu == NuSide::INPUT, op.alpha, op.beta);
+        return;
+    }
     if (p->pipeline == lsfc_plan::PRUNED) {
         VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
-        pruned_convolve(p, 1, vb, use_nu, alpha, beta);
+        pruned_convolve(p, 1, vb, op);
     } else {
-        const double* nu = use_nu ? p->nu.p : nullptr;
         hipStream_t st = p->stream;
         const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
-        pw_embed(x, nu, p->W.p, p->dims, p->pads, st);
+        pw_embed(x, op.nu == NuSide::INPUT ? p->nu.p : nullptr, p->W.p, p->dims, p->pads, st, op.conj);
         p->fwd->exec(p->W.p, st);
         pw_mul_inplace(p->W.p, p->sym.p, total, st);
         p->inv->exec(p->W.p, st);
-        pw_crop_axpy(p->W.p, x, y, alpha, beta, p->dims, p->pads, p->crop, st);
+        pw_crop_axpy(p->W.p, x, y, op.alpha, op.beta, p->dims, p->pads, p->crop, st, op.nu == NuSide::OUTPUT ? p->nu.p : nullptr, op.conj);
     }
 }
 
-void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool use_nu, double alpha, double beta) {
+void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op) {
     LSFC_REQUIRE(nrhs >= 1 && nrhs <= LSFC_MAX_BATCH, "batch of %d right-hand sides (1..%d per pass)", nrhs, LSFC_MAX_BATCH);
     if (!batch_fused(p, nrhs)) {
-        for (int j = 0; j < nrhs; ++j) plan_convolve_dev(p, vb.x[j], vb.y[j], use_nu, alpha, beta);
+        for (int j = 0; j < nrhs; ++j) plan_convolve_dev(p, vb.x[j], vb.y[j], op);
         return;
     }
     if (nrhs > p->batch_cap) {
@@ -528,7 +539,7 @@ void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool us
         if (p->ndim == 3) p->A2.alloc((size_t)(p->a2_elems * nrhs));
         p->batch_cap = nrhs;
     }
-    pruned_convolve(p, nrhs, vb, use_nu, alpha, beta);
+    pruned_convolve(p, nrhs, vb, op);
 }
 
 void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out, size_t cnt) {
@@ -536,8 +547,14 @@ void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out,
         const int n = (int)std::min<size_t>(LSFC_MAX_BATCH, cnt - j0);
         VecBatch vb{};
         for (int j = 0; j < n; ++j) { vb.x[j] = in[j0 + j]; vb.y[j] = out[j0 + j]; }
-        plan_convolve_batch_dev(p, n, vb, true, 1.0, p->omega * p->omega);
+        plan_convolve_batch_dev(p, n, vb, plan_operator(p));
     }
+}
+
+void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, const char* who) {
+    LSFC_REQUIRE(p->op == LSFC_OP_N || fn != &lsfc_precond_callback,
+                 "%s%sthe library's preconditioner object approximates inv(M), not its transpose or adjoint: not available under lsfc_plan_set_op(T | H)",
+                 who ? who : "", who ? ": " : "");
 }
 
 Precond::Precond(lsfc_precond_fn f, void* u, bool dev, bool meet, int64_t n, const char* who)
@@ -597,7 +614,7 @@ static int host_pipeline_chunks(const lsfc_plan* p) {
 // nrhs right-hand sides through the pipeline with TWO staging slots: while right-hand side j is transformed back and its chunks leave
 // for the host, the chunks of right-hand side j + 1 arrive -- across right-hand sides the two PCIe directions do overlap (512^3: 53-55
 // ms per right-hand side against 83-87 for one alone).
-static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_t nrhs, bool use_nu, double alpha, double beta, int K) {
+static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_t nrhs, const ConvOp& op, int K) {
     if (!p->hostpipe) {
         std::unique_ptr<HostPipe> hp(new HostPipe());
         LSFC_HIP(hipStreamCreateWithFlags(&hp->up, hipStreamNonBlocking));
@@ -614,7 +631,6 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
     }
     const int slots = nrhs > 1 ? 2 : 1;
     if (p->xs.n < (size_t)(slots * p->N)) { LSFC_HIP(hipStreamSynchronize(p->stream)); p->xs.alloc((size_t)(slots * p->N)); p->ys.alloc((size_t)(slots * p->N)); }
-    const double* nu = use_nu ? p->nu.p : nullptr;
     hipStream_t st = p->stream;
     const int lz = p->dims[2] / K;
     const int64_t chunk = (int64_t)p->dims[0] * p->dims[1] * lz;
@@ -669,7 +685,7 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
             LSFC_HIP(hipMemcpyAsync(xs + off, xj + off, (size_t)chunk * sizeof(cplx), hipMemcpyHostToDevice, hp->up));
             LSFC_HIP(hipEventRecord(ev, hp->up));
             LSFC_HIP(hipStreamWaitEvent(st, ev, 0));
-            pass_xfwd(p, sv, 1, nu, Slab{c * lz, lz}, st);
+            pass_xfwd(p, sv, 1, op, Slab{c * lz, lz}, st);
             pass_yfwd(p, 1, Slab{c * lz, lz}, st);
         }
         pass_fused(p, 1, st);
@@ -677,7 +693,7 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
             const int64_t off = c * chunk;
             hipEvent_t ev = hp->ev_down[(size_t)(sl * K + c)];
             pass_yinv(p, 1, Slab{c * lz, lz}, st);
-            pass_xinv(p, sv, 1, alpha, beta, Slab{c * lz, lz}, st);
+            pass_xinv(p, sv, 1, op, Slab{c * lz, lz}, st);
             LSFC_HIP(hipEventRecord(ev, st));
             if (helper) {
                 { std::lock_guard<std::mutex> lk(dmu); dq.push_back(Down{ev, yj + off, ys + off, sl, c == K - 1, j}); }
@@ -700,13 +716,14 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
     LSFC_HIP(hipStreamSynchronize(st));
 }
 
-static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs, bool use_nu, double alpha, double beta, int memspace) {
+static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs, const ConvOp& op, int memspace) {
     LSFC_REQUIRE(p && x && y, "NULL argument");
     LSFC_REQUIRE(nrhs >= 1, "nrhs must be >= 1");
     if (p->multi) {
         // one host process, several devices: the vector is scattered over the ranks' z-slabs, applied, gathered
         LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "a multi-device plan takes host vectors here; per-device slabs go through lsfc_multi_apply_dev");
-        for (int64_t j = 0; j < nrhs; ++j) multi_convolve_host(p, (const cplx*)x + j * p->N, (cplx*)y + j * p->N, use_nu, alpha, beta);
+        LSFC_REQUIRE(forward_only(op), "the transposed and the adjoint operator are not available on a multi-device plan");
+        for (int64_t j = 0; j < nrhs; ++j) multi_convolve_host(p, (const cplx*)x + j * p->N, (cplx*)y + j * p->N, op.nu == NuSide::INPUT, op.alpha, op.beta);
         return;
     }
     LSFC_HIP(hipSetDevice(p->device));
@@ -716,7 +733,7 @@ static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs,
             const int cnt = (int)std::min<int64_t>(LSFC_MAX_BATCH, nrhs - j0);
             VecBatch vb{};
             for (int j = 0; j < cnt; ++j) { vb.x[j] = (const cplx*)x + (j0 + j) * p->N; vb.y[j] = (cplx*)y + (j0 + j) * p->N; }
-            plan_convolve_batch_dev(p, cnt, vb, use_nu, alpha, beta);
+            plan_convolve_batch_dev(p, cnt, vb, op);
         }
         return;
     }
@@ -727,7 +744,7 @@ static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs,
     if (K <= 1) ensure_staging(p, p->N * group);
     if (K > 1) {
         // (y aliasing x: right-hand side j + 1 is uploaded while j is downloaded into the same memory -- distinct vectors, no hazard)
-        host_pipelined_convolve(p, (const cplx*)x, (cplx*)y, nrhs, use_nu, alpha, beta, K);
+        host_pipelined_convolve(p, (const cplx*)x, (cplx*)y, nrhs, op, K);
         return;
     }
     // LSFC_HOST_COPY=sync (developer switch, diagnostics of the round-2 first-apply fault): the round-2 workaround, a
@@ -742,7 +759,7 @@ static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs,
         } else LSFC_HIP(hipMemcpyAsync(p->xs.p, (const cplx*)x + j0 * p->N, bytes, hipMemcpyHostToDevice, p->stream));
         VecBatch vb{};
         for (int j = 0; j < cnt; ++j) { vb.x[j] = p->xs.p + (int64_t)j * p->N; vb.y[j] = p->ys.p + (int64_t)j * p->N; }
-        plan_convolve_batch_dev(p, cnt, vb, use_nu, alpha, beta);
+        plan_convolve_batch_dev(p, cnt, vb, op);
         LSFC_HIP(hipMemcpyAsync((cplx*)y + j0 * p->N, p->ys.p, bytes, hipMemcpyDeviceToHost, p->stream));
         LSFC_HIP(hipStreamSynchronize(p->stream));
     }
@@ -757,7 +774,7 @@ void plan_kernel0(lsfc_plan* p) {
     LSFC_HIP(hipMemsetAsync(e.p, 0, (size_t)N * sizeof(cplx), p->stream));
     const cplx one = make_double2(1.0, 0.0);
     LSFC_HIP(hipMemcpyAsync(e.p, &one, sizeof one, hipMemcpyHostToDevice, p->stream));
-    plan_convolve_dev(p, e.p, p->kernel0.p, false, 0.0, 1.0);
+    plan_convolve_dev(p, e.p, p->kernel0.p, conv_plain(false, 0.0, 1.0));
     LSFC_HIP(hipStreamSynchronize(p->stream));
 }
 } // namespace lsfc
@@ -949,17 +966,74 @@ int lsfc_plan_describe_passes(const lsfc_plan* plan, int nrhs, char* buf, int64_
 }
 
 int lsfc_apply(lsfc_plan* plan, const double* x, double* y, int memspace) {
-    return guarded([&] { LSFC_REQUIRE(plan, "NULL plan"); convolve_any(plan, x, y, 1, true, 1.0, plan->omega * plan->omega, memspace); });
+    return guarded([&] { LSFC_REQUIRE(plan, "NULL plan"); convolve_any(plan, x, y, 1, plan_operator(plan), memspace); });
 }
 int lsfc_convolve(lsfc_plan* plan, const double* x, double* y, int apply_nu, int memspace) {
-    return guarded([&] { convolve_any(plan, x, y, 1, apply_nu != 0, 0.0, 1.0, memspace); });
+    return guarded([&] { convolve_any(plan, x, y, 1, conv_plain(apply_nu != 0, 0.0, 1.0), memspace); });
 }
 int lsfc_apply_batch(lsfc_plan* plan, const double* x, double* y, int64_t nrhs, int mode, int memspace) {
     return guarded([&] {
         LSFC_REQUIRE(plan, "NULL plan");
         LSFC_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (apply), 1 (convolve) or 2 (convolve with nu)");
-        if (mode == 0) convolve_any(plan, x, y, nrhs, true, 1.0, plan->omega * plan->omega, memspace);
-        else convolve_any(plan, x, y, nrhs, mode == 2, 0.0, 1.0, memspace);
+        if (mode == 0) convolve_any(plan, x, y, nrhs, plan_operator(plan), memspace);
+        else convolve_any(plan, x, y, nrhs, conv_plain(mode == 2, 0.0, 1.0), memspace);
+    });
+}
+
+// The symmetry defect of G as this plan convolves with it (lsfc.h), measured once per plan: two bare convolutions of the probe
+// vectors and four reductions on the fixed-order tree.  NaN (an unpatched singular symbol) is kept as NaN and never passes.
+static double symmetry_defect(lsfc_plan* p) {
+    if (p->sym_defect >= 0.0 || p->sym_defect != p->sym_defect) return p->sym_defect;
+    LSFC_HIP(hipSetDevice(p->device));
+    const int64_t N = p->N;
+    hipStream_t st = p->stream;
+    DevBuf<cplx> x, xbar, y, ybar, gx, gy, partial, out;
+    for (DevBuf<cplx>* b : { &x, &xbar, &y, &ybar, &gx, &gy }) b->alloc((size_t)N);
+    partial.alloc((size_t)blas_partial_count()); out.alloc(4);
+    pw_probe(x.p, xbar.p, N, 0, st);
+    pw_probe(y.p, ybar.p, N, 1, st);
+    const ConvOp bare = conv_plain(false, 0.0, 1.0);
+    plan_convolve_dev(p, x.p, gx.p, bare);
+    plan_convolve_dev(p, y.p, gy.p, bare);
+    blas_dot(ybar.p, gx.p, partial.p, out.p + 0, N, st);          // sum y .* (G x): blas_dot conjugates its first argument
+    blas_dot(xbar.p, gy.p, partial.p, out.p + 1, N, st);          // sum x .* (G y)
+    blas_nrm2(gx.p, partial.p, out.p + 2, N, st);
+    blas_nrm2(y.p, partial.p, out.p + 3, N, st);
+    cplx h[4];
+    LSFC_HIP(hipMemcpyAsync(h, out.p, sizeof h, hipMemcpyDeviceToHost, st));
+    LSFC_HIP(hipStreamSynchronize(st));
+    const double den = h[2].x * h[3].x;
+    const double num = hypot(h[0].x - h[1].x, h[0].y - h[1].y);
+    p->sym_defect = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : NAN);
+    return p->sym_defect;
+}
+static void require_single_device(const lsfc_plan* plan) {
+    LSFC_REQUIRE(!plan->multi, "the transposed and the adjoint operator are not available on a multi-device plan");
+    LSFC_REQUIRE(!plan->dist, "the transposed and the adjoint operator are not available on a distributed (or simulated-rank) plan");
+}
+
+int lsfc_plan_set_op(lsfc_plan* plan, int op) {
+    return guarded([&] {
+        LSFC_REQUIRE(op == LSFC_OP_N || op == LSFC_OP_T || op == LSFC_OP_H, "op must be LSFC_OP_N, LSFC_OP_T or LSFC_OP_H (got %d)", op);
+        LSFC_REQUIRE(plan, "NULL plan");
+        if (op != LSFC_OP_N) {
+            require_single_device(plan);
+            const double d = symmetry_defect(plan);
+            // (the op stays what it was: N, since nothing but N gets past this line on such a plan)
+            if (!(d <= 1e-10)) fail(LSFC_EINVAL, "the Green's matrix of this plan is not symmetric (symmetry defect %.3e > 1e-10): "
+                                                 "I + w^2 diag(nu) G is not its transpose", d);
+        }
+        plan->op = op;
+    });
+}
+int lsfc_plan_get_op(const lsfc_plan* plan, int* op) {
+    return guarded([&] { LSFC_REQUIRE(plan && op, "NULL argument"); *op = plan->op; });
+}
+int lsfc_plan_symmetry_defect(lsfc_plan* plan, double* defect) {
+    return guarded([&] {
+        LSFC_REQUIRE(plan && defect, "NULL argument");
+        require_single_device(plan);
+        *defect = symmetry_defect(plan);
     });
 }
 
@@ -1106,7 +1180,9 @@ int lsfc_profile_apply(lsfc_plan* plan, const double* x_dev, double* y_dev, int 
         auto stages_add_fn = [](std::vector<Stage>& v) {
             return [&v](const char* name, double bytes, std::function<void()> run) { v.push_back({name, bytes, std::move(run)}); };
         };
-        const double om2 = p->omega * p->omega;
+        // the operator lsfc_plan_set_op selected; nub = the 8 B per point of nu, in the pass that multiplies by it
+        const ConvOp op = plan_operator(p);
+        const double nu_in = op.nu == NuSide::INPUT ? 8 * N : 0.0, nu_out = op.nu == NuSide::OUTPUT ? 8 * N : 0.0;
         if (p->dist) {
             dist_profile_stages(p, x, y, stages_add_fn(stages));
         } else if (p->pipeline == lsfc_plan::PRUNED) {
@@ -1114,19 +1190,20 @@ int lsfc_profile_apply(lsfc_plan* plan, const double* x_dev, double* y_dev, int 
             VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
             const Slab all = whole_grid(p);
             const bool d3 = p->ndim == 3;
-            stages.push_back({"xfwd", N * (C + 8) + 2 * N * C, [=] { pass_xfwd(p, vb, 1, p->nu.p, all, st); }});
+            stages.push_back({"xfwd", N * C + nu_in + 2 * N * C, [=] { pass_xfwd(p, vb, 1, op, all, st); }});
             if (d3) stages.push_back({"yfwd", (2 + 4) * N * C, [=] { pass_yfwd(p, 1, all, st); }});
             stages.push_back({d3 ? "zfused" : "yfused", d3 ? (4 + 8 + 4) * N * C : (2 + 4 + 2) * N * C, [=] { pass_fused(p, 1, st); }});
             if (d3) stages.push_back({"yinv", (4 + 2) * N * C, [=] { pass_yinv(p, 1, all, st); }});
-            stages.push_back({"xinv", (2 + 1 + 1) * N * C, [=] { pass_xinv(p, vb, 1, 1.0, om2, all, st); }});
+            stages.push_back({"xinv", (2 + 1 + 1) * N * C + nu_out, [=] { pass_xinv(p, vb, 1, op, all, st); }});
         } else {
             const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
             const double P = (double)total;
-            stages.push_back({"embed", N * (C + 8) + P * C, [=] { pw_embed(x, p->nu.p, p->W.p, p->dims, p->pads, st); }});
+            const double* nui = op.nu == NuSide::INPUT ? p->nu.p : nullptr; const double* nuo = op.nu == NuSide::OUTPUT ? p->nu.p : nullptr;
+            stages.push_back({"embed", N * C + nu_in + P * C, [=] { pw_embed(x, nui, p->W.p, p->dims, p->pads, st, op.conj); }});
             stages.push_back({"rocfft_fwd", 2 * P * C, [=] { p->fwd->exec(p->W.p, st); }});
             stages.push_back({"symbol_mul", 3 * P * C, [=] { pw_mul_inplace(p->W.p, p->sym.p, total, st); }});
             stages.push_back({"rocfft_inv", 2 * P * C, [=] { p->inv->exec(p->W.p, st); }});
-            stages.push_back({"crop_axpy", 3 * N * C, [=] { pw_crop_axpy(p->W.p, x, y, 1.0, om2, p->dims, p->pads, p->crop, st); }});
+            stages.push_back({"crop_axpy", 3 * N * C + nu_out, [=] { pw_crop_axpy(p->W.p, x, y, op.alpha, op.beta, p->dims, p->pads, p->crop, st, nuo, op.conj); }});
         }
         LSFC_REQUIRE((int)stages.size() <= max_stages, "max_stages too small (need %d)", (int)stages.size());
         *nstages = (int)stages.size();

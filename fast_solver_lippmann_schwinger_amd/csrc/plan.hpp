@@ -103,6 +103,8 @@ struct lsfc_plan {
     double omega = 0.0;
     int quad_rule = LSFC_QUAD_GREENGARD_VICO;
     unsigned flags = 0;
+    int op = LSFC_OP_N;              // which of M, its transpose, its adjoint "the operator" means (lsfc_plan_set_op)
+    double sym_defect = -1.0;        // symmetry defect of G through the plan's own convolution; < 0: not measured yet
     enum Pipeline { PRUNED = 0, ROCFFT_REDUCED = 1, ROCFFT_LITERAL = 2 } pipeline = PRUNED;
 
     lsfc::DevBuf<double> nu;
@@ -148,13 +150,25 @@ struct lsfc_plan {
 
 namespace lsfc {
 
-// y = alpha*x + beta*conv((use_nu ? nu : 1) .* x); device pointers, stream-ordered.
-void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double alpha, double beta);
+// What one pass of the pipeline computes around the bare convolution G:
+//   y = alpha*x + beta * [nu .*] c( G ( [nu .*] c(x) ) ),   c = conj or the identity,
+// nu on the input (M, lsfc_convolve with apply_nu), on the output (the transpose I + w^2 diag(nu) G) or nowhere.  The adjoint
+// conj(T conj(.)) is the transpose with c = conj: conj(alpha*conj(x)) = alpha*x for the real alpha, beta used here.
+enum class NuSide { NONE, INPUT, OUTPUT };
+struct ConvOp { NuSide nu; bool conj; double alpha, beta; };
+inline ConvOp conv_plain(bool use_nu, double alpha, double beta) { return ConvOp{use_nu ? NuSide::INPUT : NuSide::NONE, false, alpha, beta}; }
+// "the operator" of the plan: M, or what lsfc_plan_set_op selected
+inline ConvOp plan_operator(const lsfc_plan* p) {
+    const double w2 = p->omega * p->omega;
+    return p->op == LSFC_OP_N ? ConvOp{NuSide::INPUT, false, 1.0, w2} : ConvOp{NuSide::OUTPUT, p->op == LSFC_OP_H, 1.0, w2};
+}
+// device pointers, stream-ordered.
+void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op);
 // nrhs <= LSFC_MAX_BATCH right-hand sides in one pass of the pipeline: y_j = alpha*x_j + beta*conv(...x_j); the symbol is read
 // once per batch in the fused pass (pruned pipeline; the other pipelines run the members one after the other)
-void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, bool use_nu, double alpha, double beta);
-// the operator M = I + omega^2 G nu
-inline void plan_apply_dev(lsfc_plan* p, const cplx* x, cplx* y) { plan_convolve_dev(p, x, y, true, 1.0, p->omega * p->omega); }
+void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op);
+// the operator M = I + omega^2 G nu, or its transpose / adjoint (lsfc_plan_set_op)
+inline void plan_apply_dev(lsfc_plan* p, const cplx* x, cplx* y) { plan_convolve_dev(p, x, y, plan_operator(p)); }
 // ... on cnt (in, out) pairs, in groups of LSFC_MAX_BATCH that share one pass of the pipeline (the batched solvers)
 void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out, size_t cnt);
 
@@ -162,6 +176,8 @@ void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out,
 // object on the device, where the members of a batch meet (`meet`): apply() hands it all cnt vectors for its group sweeps; any other
 // callback gets them one by one, in order, a host callback through `pinned`.  The size of an own object is checked here, under `who`.
 constexpr double DEFAULT_RELTOL = 0x1p-26;      // sqrt(eps)
+// The library's own preconditioner object approximates inv(M), not its transpose: refused under lsfc_plan_set_op(T | H)
+void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, const char* who);
 struct Precond {
     lsfc_precond_fn fn; void* user; bool on_device, own; int64_t N;
     Precond(lsfc_precond_fn fn, void* user, bool on_device, bool meet, int64_t N, const char* who);

@@ -19,9 +19,9 @@ static inline unsigned grid_for(int64_t count, int block = 256, int cap = 256 * 
 
 // ---- rocFFT pipelines: embed and crop ---------------------------------------
 
-// W[p0][p1][p2] (x fastest) = (i<n && j<m && k<l) ? (nu?nu:1)*x : 0
+// W[p0][p1][p2] (x fastest) = (i<n && j<m && k<l) ? (nu?nu:1)*(cj ? conj(x) : x) : 0
 __global__ void k_embed(const cplx* __restrict__ x, const double* __restrict__ nu, cplx* __restrict__ W,
-                        int n, int m, int l, int p0, int p1, int p2) {
+                        int n, int m, int l, int p0, int p1, int p2, int cj) {
     const int64_t total = (int64_t)p0 * p1 * p2;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         const int i = (int)(idx % p0); const int64_t r = idx / p0; const int j = (int)(r % p1); const int k = (int)(r / p1);
@@ -30,6 +30,7 @@ __global__ void k_embed(const cplx* __restrict__ x, const double* __restrict__ n
             const int64_t s = i + (int64_t)n * (j + (int64_t)m * k);
             v = x[s];
             if (nu) { const double c = nu[s]; v.x *= c; v.y *= c; }
+            if (cj) v.y = -v.y;
         }
         W[idx] = v;
     }
@@ -42,22 +43,23 @@ __global__ void k_mul_inplace(cplx* __restrict__ W, const cplx* __restrict__ S, 
     }
 }
 
-// y = alpha*x + beta*W[o0+i][o1+j][o2+k]
+// y = alpha*x + beta*(nu?nu:1)*(cj ? conj(w) : w), w = W[o0+i][o1+j][o2+k]
 __global__ void k_crop_axpy(const cplx* __restrict__ W, const cplx* x, cplx* y, double alpha, double beta,
-                            int n, int m, int l, int p0, int p1, int o0, int o1, int o2) {
+                            int n, int m, int l, int p0, int p1, int o0, int o1, int o2, const double* __restrict__ nu, int cj) {
     const int64_t total = (int64_t)n * m * l;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         const int i = (int)(idx % n); const int64_t r = idx / n; const int j = (int)(r % m); const int k = (int)(r / m);
         const cplx w = W[(o0 + i) + (int64_t)p0 * ((o1 + j) + (int64_t)p1 * (o2 + k))];
-        cplx v = make_double2(beta * w.x, beta * w.y);
+        const double bs = nu ? beta * nu[idx] : beta;
+        cplx v = make_double2(bs * w.x, bs * (cj ? -w.y : w.y));
         if (alpha != 0.0) { const cplx xo = x[idx]; v.x = fma(alpha, xo.x, v.x); v.y = fma(alpha, xo.y, v.y); }
         y[idx] = v;
     }
 }
 
-void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t st) {
+void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t st, bool conj) {
     const int64_t total = (int64_t)pads[0] * pads[1] * pads[2];
-    hipLaunchKernelGGL(k_embed, dim3(grid_for(total)), dim3(256), 0, st, x, nu, W, dims[0], dims[1], dims[2], pads[0], pads[1], pads[2]);
+    hipLaunchKernelGGL(k_embed, dim3(grid_for(total)), dim3(256), 0, st, x, nu, W, dims[0], dims[1], dims[2], pads[0], pads[1], pads[2], (int)conj);
     LSFC_HIP(hipGetLastError());
 }
 void pw_mul_inplace(cplx* W, const cplx* S, int64_t total, hipStream_t st) {
@@ -65,10 +67,27 @@ void pw_mul_inplace(cplx* W, const cplx* S, int64_t total, hipStream_t st) {
     LSFC_HIP(hipGetLastError());
 }
 void pw_crop_axpy(const cplx* W, const cplx* x, cplx* y, double alpha, double beta, const int dims[3], const int pads[3],
-                  const int off[3], hipStream_t st) {
+                  const int off[3], hipStream_t st, const double* nu, bool conj) {
     const int64_t total = (int64_t)dims[0] * dims[1] * dims[2];
     hipLaunchKernelGGL(k_crop_axpy, dim3(grid_for(total)), dim3(256), 0, st, W, x, y, alpha, beta, dims[0], dims[1], dims[2],
-                       pads[0], pads[1], off[0], off[1], off[2]);
+                       pads[0], pads[1], off[0], off[1], off[2], nu, (int)conj);
+    LSFC_HIP(hipGetLastError());
+}
+
+// Probe vectors of the symmetry check (lsfc_plan_symmetry_defect): v[i] = exp(2 pi i u), u a 53-bit hash of (i, which) -- unit modulus,
+// a function of the index only (the same in every run, on every device) -- and vbar = conj(v), so that the BILINEAR form
+// sum a .* b is blas_dot(abar, b) on the fixed-order tree.
+__global__ void k_probe(cplx* __restrict__ v, cplx* __restrict__ vbar, int64_t n, unsigned long long which) {
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        unsigned long long h = ((unsigned long long)idx + 1ull) * 0x9E3779B97F4A7C15ull + which * 0xD1B54A32D192ED03ull;
+        h ^= h >> 30; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 27; h *= 0x94D049BB133111EBull; h ^= h >> 31;
+        const double u = (double)(h >> 11) * 0x1p-53;
+        double sn, cs; sincospi(2.0 * u, &sn, &cs);
+        v[idx] = make_double2(cs, sn); vbar[idx] = make_double2(cs, -sn);
+    }
+}
+void pw_probe(cplx* v, cplx* vbar, int64_t n, int which, hipStream_t st) {
+    hipLaunchKernelGGL(k_probe, dim3(grid_for(n)), dim3(256), 0, st, v, vbar, n, (unsigned long long)which);
     LSFC_HIP(hipGetLastError());
 }
 

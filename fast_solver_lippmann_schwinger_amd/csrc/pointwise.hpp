@@ -4,11 +4,13 @@
 
 namespace lsfc {
 
-// rocFFT pipelines
-void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t);
+// rocFFT pipelines: W = pad((nu ? nu : 1) .* (conj ? conj(x) : x)) ...
+void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t, bool conj = false);
 void pw_mul_inplace(cplx* W, const cplx* S, int64_t total, hipStream_t);
 void pw_crop_axpy(const cplx* W, const cplx* x, cplx* y, double alpha, double beta, const int dims[3], const int pads[3],
-                  const int off[3], hipStream_t);
+                  const int off[3], hipStream_t, const double* nu = nullptr, bool conj = false);   // ... y = alpha*x + beta * nu .* (conj) crop(W)
+// unit-modulus probe vector number `which` and its conjugate, a function of the index only (the symmetry check of a plan)
+void pw_probe(cplx* v, cplx* vbar, int64_t n, int which, hipStream_t);
 // symbol preparation
 void pw_roll_scale(const cplx* src, cplx* dst, const int p[3], const int s[3], double scale, hipStream_t);
 void pw_resample_kernel(const cplx* src, cplx* dst, const int p[3], const int q[3], const int origin[3], const int nmax[3], double scale, hipStream_t);

@@ -13,6 +13,7 @@ Names, argument meaning and error behaviour follow the Julia reference
   sampleGConv / sampleG3D             src/FastConvolution.jl:278-306, src/FastConvolution3D.jl:136-160
   gmres_ (= gmres!)                   IterativeSolvers.jl, call sites examples/example.jl:85,91
   bicgstabl_ (= bicgstabl!)           IterativeSolvers.jl (the short-recurrence alternative; same Pl hook)
+  M.T, M.H, M.rmatvec                 transpose(M), M' of LinearMaps / rmatvec of scipy's LinearOperator (lsfc_plan_set_op)
 
 Vectors are flat complex128 arrays in column-major (x fastest) order: numpy
 arrays (host memory, copied through PCIe inside the call) or torch CUDA tensors
@@ -21,6 +22,7 @@ computes on the CPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -49,6 +51,39 @@ def _vec(a, N, name, count=1, plan=None):
 
 
 _QUAD = {"trapezoidal": L.LSFC_QUAD_TRAPEZOIDAL, "Greengard_Vico": L.LSFC_QUAD_GREENGARD_VICO}
+
+
+@contextlib.contextmanager
+def _op_of(M):
+    """The plan of M means M.T or M.H while a call through such a view runs, and M again afterwards (also when it raises)"""
+    op = getattr(M, "_op", L.LSFC_OP_N)
+    if op == L.LSFC_OP_N:
+        yield
+        return
+    lib = L.load()
+    L.check(lib.lsfc_plan_set_op(M._plan, op))
+    try:
+        yield
+    finally:
+        lib.lsfc_plan_set_op(M._plan, L.LSFC_OP_N)
+
+
+def _mul_into(M, Y, b):
+    """mul!(Y, M, b) for an operator or a view of one"""
+    px, sx, kx = _vec(b, M.N, "b", plan=M._plan)
+    if _is_torch(Y):
+        py, sy, _ = _vec(Y, M.N, "Y")
+        if sy != sx:
+            raise TypeError("Y and b must live in the same memory space")
+    else:
+        if not (isinstance(Y, np.ndarray) and Y.dtype == np.complex128 and Y.flags.c_contiguous and Y.size == M.N):
+            raise TypeError("Y: need a contiguous complex128 array of the operator size")
+        if sx != L.LSFC_MEM_HOST:
+            raise TypeError("Y and b must live in the same memory space")
+        py = Y.ctypes.data_as(C.c_void_p)
+    with _op_of(M):
+        L.check(L.load().lsfc_apply(M._plan, px, py, sx))
+    return Y
 
 
 class _Operator:
@@ -99,19 +134,36 @@ class _Operator:
 
     def mul_(self, Y, b):
         """LinearAlgebra.mul!(Y, M, b): Y[:] = M*b  (src/FastConvolution.jl:50-54)."""
-        px, sx, kx = _vec(b, self.N, "b", plan=self._plan)
-        if _is_torch(Y):
-            py, sy, _ = _vec(Y, self.N, "Y")
-            if sy != sx:
-                raise TypeError("Y and b must live in the same memory space")
-            L.check(L.load().lsfc_apply(self._plan, px, py, sx))
-            return Y
-        if not (isinstance(Y, np.ndarray) and Y.dtype == np.complex128 and Y.flags.c_contiguous and Y.size == self.N):
-            raise TypeError("Y: need a contiguous complex128 array of the operator size")
-        if sx != L.LSFC_MEM_HOST:
-            raise TypeError("Y and b must live in the same memory space")
-        L.check(L.load().lsfc_apply(self._plan, px, Y.ctypes.data_as(C.c_void_p), sx))
-        return Y
+        return _mul_into(self, Y, b)
+
+    # -- transpose and adjoint (lsfc_plan_set_op): light views, no second plan ---
+    def transpose(self):
+        """I + omega^2 diag(nu) G: the transpose of M for the symmetric Green's matrix (checked by the library at the first call)"""
+        return OperatorView(self, L.LSFC_OP_T)
+
+    def adjoint(self):
+        """conj(M.T conj(.)), the adjoint of M (nu and omega are real)"""
+        return OperatorView(self, L.LSFC_OP_H)
+
+    T = property(transpose)
+    H = property(adjoint)
+
+    def rmatvec(self, b):
+        return self.H * b
+
+    def symmetry_defect(self):
+        """|sum y.*(G x) - sum x.*(G y)| / (||G x|| ||y||) of two fixed probe vectors through the plan's own convolution
+        (lsfc_plan_symmetry_defect); the views exist where it is <= 1e-10"""
+        d = C.c_double(0)
+        L.check(L.load().lsfc_plan_symmetry_defect(self._plan, C.byref(d)))
+        return d.value
+
+    def aslinearoperator(self):
+        """scipy.sparse.linalg.LinearOperator with matvec and rmatvec (LSQR, BiCG, QMR) on host vectors"""
+        from scipy.sparse.linalg import LinearOperator
+        H = self.H
+        return LinearOperator(self.shape, matvec=lambda v: self * np.asarray(v).reshape(-1),
+                              rmatvec=lambda v: H * np.asarray(v).reshape(-1), dtype=np.complex128)
 
     def set_nu(self, nu):
         nu = np.ascontiguousarray(nu, dtype=np.float64)
@@ -155,6 +207,61 @@ class _Operator:
             self.close()
         except Exception:
             pass
+
+
+class OperatorView:
+    """M.T or M.H: the parent operator plus an op, no second plan.  Accepted wherever an operator is (fastconvolution, mul_,
+    apply_batch mode 0, the four solvers, time_apply, profile_apply): a call through a view sets the op of the parent's
+    plan, calls, and restores M.  conj(M) is not offered, so M.T.H and M.H.T raise."""
+
+    dtype = np.complex128
+
+    def __init__(self, parent, op):
+        self.parent, self._op = parent, op
+
+    @property
+    def _plan(self):
+        return self.parent._plan
+
+    @property
+    def N(self):
+        return self.parent.N
+
+    @property
+    def shape(self):
+        return self.parent.shape
+
+    def size(self, dim=None):
+        return self.parent.size(dim)
+
+    def eltype(self):
+        return np.complex128
+
+    def _out_like(self, b, count=1):
+        return self.parent._out_like(b, count)
+
+    def _other(self, op, name):
+        if op == self._op:
+            return self.parent
+        raise NotImplementedError(f"{name}: conj(M) is not offered (only M, M.T and M.H)")
+
+    def transpose(self):
+        return self._other(L.LSFC_OP_T, "M.H.T")
+
+    def adjoint(self):
+        return self._other(L.LSFC_OP_H, "M.T.H")
+
+    T = property(transpose)
+    H = property(adjoint)
+
+    def __mul__(self, b):
+        return fastconvolution(self, b)
+
+    __matmul__ = __mul__
+    matvec = __mul__
+
+    def mul_(self, Y, b):
+        return _mul_into(self, Y, b)
 
 
 class FastM(_Operator):
@@ -226,7 +333,8 @@ def fastconvolution(M, b):
     px, sx, keep = _vec(b, M.N, "b", plan=M._plan)
     y = M._out_like(keep)
     py, _, _ = _vec(y, M.N, "y")
-    L.check(L.load().lsfc_apply(M._plan, px, py, sx))
+    with _op_of(M):
+        L.check(L.load().lsfc_apply(M._plan, px, py, sx))
     return y
 
 
@@ -431,6 +539,8 @@ def _solve(entry, A, x, vecs, nrhs, opts, Pl, Pl_on_device, cap, ok=(0,), status
     the return code.  The copy of b in vecs, r_shadow (the caller holds it) and the ctypes callback live until this returns."""
     px, pb, sx, keepb = vecs
     err = []
+    if getattr(A, "_op", L.LSFC_OP_N) != L.LSFC_OP_N and getattr(Pl, "_pc", None) is not None:
+        raise ValueError("a SparsifyingPreconditioner approximates inv(M), not its transpose or adjoint: not available with M.T / M.H")
     cb = _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err)
     rows = 1 if nrhs is None else max(nrhs, 1)
     res = (L.GmresResult * rows)()
@@ -441,7 +551,8 @@ def _solve(entry, A, x, vecs, nrhs, opts, Pl, Pl_on_device, cap, ok=(0,), status
     args += [C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, res]
     if status is not None:
         args.append(status.ctypes.data_as(C.c_void_p))
-    rc = getattr(L.load(), entry)(*args, sx)
+    with _op_of(A):
+        rc = getattr(L.load(), entry)(*args, sx)
     if err:
         raise err[0]
     if rc not in ok:
@@ -579,19 +690,24 @@ def bicgstabl_batch_(X, A, B, l=2, Pl=None, max_mv_products=None, abstol=0.0, re
 
 def apply_batch(M, B, mode=0):
     """Rows of B (nrhs, N) through the operator in batched passes (lsfc_apply_batch): mode 0 ``M * b``, 1 bare
-    convolution, 2 convolution of nu .* b.  The multi-vector form of src/FastConvolution3D.jl:146-159."""
+    convolution, 2 convolution of nu .* b.  The multi-vector form of src/FastConvolution3D.jl:146-159.
+    A view (M.T, M.H) is an operator, not a convolution: mode 0 only."""
+    if mode != 0 and getattr(M, "_op", L.LSFC_OP_N) != L.LSFC_OP_N:
+        raise ValueError("apply_batch: modes 1 and 2 describe G, which M.T and M.H do not change; pass M")
     if _is_torch(B):
         nrhs = B.shape[0]
         pb, sb, keep = _vec(B.reshape(-1), M.N, "B", count=nrhs, plan=M._plan)
         import torch
         Y = torch.empty_like(keep)
-        L.check(L.load().lsfc_apply_batch(M._plan, pb, C.c_void_p(Y.data_ptr()), nrhs, mode, sb))
+        with _op_of(M):
+            L.check(L.load().lsfc_apply_batch(M._plan, pb, C.c_void_p(Y.data_ptr()), nrhs, mode, sb))
         return Y.reshape(nrhs, M.N)
     B = np.ascontiguousarray(B, dtype=np.complex128)
     if B.ndim != 2 or B.shape[1] != M.N:
         raise ValueError(f"DimensionMismatch: B must be (nrhs, {M.N})")
     Y = np.empty_like(B)
-    L.check(L.load().lsfc_apply_batch(M._plan, B.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p), B.shape[0], mode, L.LSFC_MEM_HOST))
+    with _op_of(M):
+        L.check(L.load().lsfc_apply_batch(M._plan, B.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p), B.shape[0], mode, L.LSFC_MEM_HOST))
     return Y
 
 
@@ -624,7 +740,8 @@ def time_apply(M, x_dev, y_dev, reps):
     if sx != L.LSFC_MEM_DEVICE or sy != L.LSFC_MEM_DEVICE:
         raise TypeError("time_apply needs device tensors")
     ms = C.c_double(0)
-    L.check(L.load().lsfc_time_apply(M._plan, px, py, int(reps), C.byref(ms)))
+    with _op_of(M):
+        L.check(L.load().lsfc_time_apply(M._plan, px, py, int(reps), C.byref(ms)))
     return ms.value
 
 
@@ -635,5 +752,6 @@ def profile_apply(M, x_dev, y_dev, reps=3):
     py = _vec(y_dev, M.N, "y")[0] if y_dev is not None else None
     names = (C.c_char_p * 16)()
     ms, nb, ns = (C.c_double * 16)(), (C.c_double * 16)(), C.c_int(0)
-    L.check(L.load().lsfc_profile_apply(M._plan, px, py, int(reps), 16, names, ms, nb, C.byref(ns)))
+    with _op_of(M):
+        L.check(L.load().lsfc_profile_apply(M._plan, px, py, int(reps), 16, names, ms, nb, C.byref(ns)))
     return [(names[i].decode(), ms[i], nb[i]) for i in range(ns.value)]

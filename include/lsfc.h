@@ -148,6 +148,38 @@ int lsfc_apply_batch(lsfc_plan* plan, const double* x, double* y, int64_t nrhs, 
  * by this entry; use lsfc_apply_batch for that quirk.) */
 int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, double* out, int memspace);
 
+/* ---- the transposed and the adjoint operator ------------------------------ */
+
+/* nu and omega are real and the Green's matrix G of every builder is complex symmetric, so
+ *     M^T = I + omega^2 diag(nu) G        and        M^H y = conj(M^T conj(y)).
+ * In the pipeline only the nu multiply moves, from the loads of the first x pass to the stores of the last one; M^H adds
+ * two conjugations there.  The y passes, the fused pass and the HBM traffic per point are those of M.
+ *
+ * The op is plan state (default LSFC_OP_N).  It is READ by everything that means "the operator": lsfc_apply,
+ * lsfc_apply_batch mode 0, lsfc_time_apply, lsfc_profile_apply and every operator application inside lsfc_gmres,
+ * lsfc_gmres_batch, lsfc_bicgstabl and lsfc_bicgstabl_batch.  It is NOT read by lsfc_convolve, lsfc_apply_batch modes 1
+ * and 2, lsfc_sample_sources, lsfc_sparsify_build and lsfc_precond_create_from_plan: those keep describing G and M.
+ *
+ * I + omega^2 diag(nu) G is the transpose only when G is symmetric, and lsfc_plan_create_2d/3d take any symbol.  So the first
+ * lsfc_plan_set_op(T | H) or lsfc_plan_symmetry_defect of a plan measures, through the plan's own convolution,
+ *     defect = |sum y.*(G x) - sum x.*(G y)| / (||G x|| ||y||)
+ * for two fixed unit-modulus probe vectors generated on the device from the grid index (the same in every run), and keeps
+ * the figure.  defect > 1e-10: lsfc_plan_set_op returns LSFC_EINVAL, the message names the defect, and the op stays N
+ * (symmetric operators measure ~1e-16, non-symmetric ones ~1e-2 and more).
+ *
+ * LSFC_EINVAL, before any device call: NULL plan; op outside 0..2; a distributed, simulated-rank or multi-device plan.
+ * A solve under op != N whose preconditioner is the library's own object (precond == lsfc_precond_callback) returns
+ * LSFC_EINVAL: that object approximates inv(M), not its transpose.  Caller callbacks pass through unchanged.
+ *
+ * Out of scope: complex nu; the transposed preconditioner As^T Msp^-T; distributed and multi-device plans; non-symmetric
+ * kernels (they would need the reflected symbol). */
+#define LSFC_OP_N 0   /* M           (default)                         */
+#define LSFC_OP_T 1   /* transpose   I + w^2 diag(nu) G                */
+#define LSFC_OP_H 2   /* adjoint     conj(T conj(.))                   */
+int lsfc_plan_set_op(lsfc_plan* plan, int op);
+int lsfc_plan_get_op(const lsfc_plan* plan, int* op);
+int lsfc_plan_symmetry_defect(lsfc_plan* plan, double* defect);
+
 /* ---- GMRES ---------------------------------------------------------------- */
 
 /* In-place left preconditioner, mirrors the two-argument ldiv!(Pl, v)

@@ -405,4 +405,53 @@ function bicgstabl_batch_hip!(X::Matrix{Complex{Float64}}, M::FastMHIP, B::Matri
     X, [resnorm[1:min(res[j].iters, cap), j] for j in 1:nrhs], status
 end
 
+# transpose(M) and M' -- lsfc_plan_set_op (include/lsfc.h).  nu and omega are real and the Green's matrix is complex symmetric, so
+# transpose(M) = I + omega^2 diag(nu) G and M' y = conj(transpose(M) conj(y)): the same pipeline with the nu multiply moved from
+# the first x pass to the last, plus two conjugations for M'.  The wrappers hold the parent and an op, no second plan; a call
+# through one sets the op of the parent's plan, calls, and restores M (also when the call throws).  The library measures the
+# symmetry of G through the plan's own convolution at the first such call and refuses (rc -1) a plan whose symbol is not
+# symmetric; distributed and multi-device plans are refused too.  A SparsifyingPreconditionerHIP approximates inv(M), not its
+# transpose: the solvers refuse it with a wrapper.  conj(M) is not offered: transpose(M') and (transpose(M))' throw.
+const OP_N = Cint(0); const OP_T = Cint(1); const OP_H = Cint(2)
+struct TransposeFastMHIP; parent::FastMHIP; end
+struct AdjointFastMHIP; parent::FastMHIP; end
+const FastMHIPView = Union{TransposeFastMHIP, AdjointFastMHIP}
+_op(::TransposeFastMHIP) = OP_T
+_op(::AdjointFastMHIP) = OP_H
+LinearAlgebra.transpose(M::FastMHIP) = TransposeFastMHIP(M)
+LinearAlgebra.adjoint(M::FastMHIP) = AdjointFastMHIP(M)
+LinearAlgebra.transpose(V::TransposeFastMHIP) = V.parent
+LinearAlgebra.adjoint(V::AdjointFastMHIP) = V.parent
+LinearAlgebra.transpose(::AdjointFastMHIP) = error("conj(M) is not offered (only M, transpose(M) and M')")
+LinearAlgebra.adjoint(::TransposeFastMHIP) = error("conj(M) is not offered (only M, transpose(M) and M')")
+Base.size(V::FastMHIPView, dim) = size(V.parent, dim)
+Base.size(V::FastMHIPView) = size(V.parent)
+Base.eltype(::FastMHIPView) = Complex{Float64}
+function _with_op(f, V::FastMHIPView)
+    check(ccall((:lsfc_plan_set_op, liblsfc), Cint, (Ptr{Cvoid}, Cint), V.parent.plan, _op(V)))
+    try
+        return f(V.parent)
+    finally
+        ccall((:lsfc_plan_set_op, liblsfc), Cint, (Ptr{Cvoid}, Cint), V.parent.plan, OP_N)
+    end
+end
+*(V::FastMHIPView, b::AbstractArray{Complex{Float64},1}) = _with_op(M -> fastconvolution(M, b), V)
+LinearAlgebra.mul!(Y::AbstractArray{Complex{Float64},1}, V::FastMHIPView, b::AbstractArray{Complex{Float64},1}) = (Y[:] = V * b)
+LinearAlgebra.mul!(Y::Vector{Complex{Float64}}, V::FastMHIPView, b::Vector{Complex{Float64}}) = _with_op(M -> mul!(Y, M, b), V)
+function symmetry_defect(M::FastMHIP)
+    d = Ref{Float64}(0.0)
+    check(ccall((:lsfc_plan_symmetry_defect, liblsfc), Cint, (Ptr{Cvoid}, Ref{Float64}), M.plan, d))
+    d[]
+end
+_no_own_precond(Pl) = Pl isa SparsifyingPreconditionerHIP &&
+    throw(ArgumentError("a SparsifyingPreconditionerHIP approximates inv(M), not its transpose or adjoint"))
+function gmres_hip!(x::Vector{Complex{Float64}}, V::FastMHIPView, b::Vector{Complex{Float64}}; Pl=nothing, kw...)
+    _no_own_precond(Pl)
+    _with_op(M -> gmres_hip!(x, M, b; Pl=Pl, kw...), V)
+end
+function bicgstabl_hip!(x::Vector{Complex{Float64}}, V::FastMHIPView, b::Vector{Complex{Float64}}, l::Int=2; Pl=nothing, kw...)
+    _no_own_precond(Pl)
+    _with_op(M -> bicgstabl_hip!(x, M, b, l; Pl=Pl, kw...), V)
+end
+
 end # module
