@@ -314,12 +314,6 @@ __global__ __launch_bounds__(64) void k_res_finish(Members B, int nb) {
     if (threadIdx.x == 0 && scal[S_STATUS].x == 0.0) scal[S_RES] = make_double2(sqrt(s.x), 0.0);
 }
 
-template <int LO, int HI, class F> void dispatch(int v, F&& f) {
-    if constexpr (LO > HI) fail(LSFC_EINVAL, "bicgstabl: no kernel for %d vectors", v);
-    else if (v == LO) f(std::integral_constant<int, LO>{});
-    else dispatch<LO + 1, HI>(v, f);
-}
-
 inline unsigned ew_grid(int64_t n) {
     const int64_t g = (n + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -445,23 +439,23 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
         const dim3 grid((unsigned)nb, (unsigned)act.size()), one(1, (unsigned)act.size());
         for (int j = 0; j < l; ++j) {                       // BiCG part
             hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, st, B, toff, (int64_t)j * N, (int)P_RHO);
-            dispatch<1, LMAX>(j + 1, [&](auto nvj) {
+            dispatch<1, LMAX>(j + 1, "bicgstabl", [&](auto nvj) {
                 hipLaunchKernelGGL((k_bicg_u<decltype(nvj)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff, nb, cyc);
             });
             apply(act, [&](int m) { return (const cplx*)U(m, j); }, [&](int m) { return U(m, j + 1); });
             precondition(act, [&](int m) { return U(m, j + 1); });
             hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, st, B, toff, uoff + (int64_t)(j + 1) * N, (int)P_SIGMA);
-            dispatch<1, LMAX>(j + 1, [&](auto nvj) {
+            dispatch<1, LMAX>(j + 1, "bicgstabl", [&](auto nvj) {
                 hipLaunchKernelGGL((k_bicg_rx<decltype(nvj)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff, nb, cyc);
             });
             apply(act, [&](int m) { return (const cplx*)R(m, j); }, [&](int m) { return R(m, j + 1); });
             precondition(act, [&](int m) { return R(m, j + 1); });
         }
-        dispatch<2, NVMAX>(nv, [&](auto nvc) {              // MR part
+        dispatch<2, NVMAX>(nv, "bicgstabl", [&](auto nvc) {              // MR part
             hipLaunchKernelGGL((k_gram<decltype(nvc)::value>), grid, dim3(RED_THREADS), 0, st, B);
         });
         hipLaunchKernelGGL(k_mr_solve, one, dim3(64), 0, st, B, nb, nv, cyc);
-        dispatch<1, LMAX>(l, [&](auto lc) {
+        dispatch<1, LMAX>(l, "bicgstabl", [&](auto lc) {
             hipLaunchKernelGGL((k_mr_update<decltype(lc)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff);
         });
         hipLaunchKernelGGL(k_res_finish, one, dim3(64), 0, st, B, nb);

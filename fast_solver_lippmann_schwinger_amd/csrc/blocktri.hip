@@ -12,7 +12,11 @@
 // Storage of the inverses: complex double, or (LSFC_PRECOND_INV_F32) interleaved float pairs, K b^2 8 B.  The elimination
 // is the same fp64 arithmetic either way: at float storage block k is inverted in one of two fp64 work blocks (the Schur
 // update of block k + 1 reads it there), then rounded once to nearest-even into the float array.  The sweeps widen every
-// stored entry to fp64 on load and sum in fp64 in the order of the fp64 object; they are templates over the stored type.
+// stored entry to fp64 on load and sum in fp64 in the order of the fp64 object.  There is one sweep kernel per shape, a
+// template over the stored type T (k_bt_walk<T>, k_bt_step<FWD, T>, k_btb_product<R, T>), and the enqueue functions pick
+// T once (with_storage).  The storages differ in the load alone: a lane's 16 B load is one row of complex double, or
+// rows i and i + 1 of float pairs (BT_LANE_ROWS<T>; bt_accum / bt_accum2 in the step, the column loop in the product),
+// so a workgroup covers twice the rows at float storage.  Staging, chunk loop, accumulators, LDS fold and store are shared.
 //
 // Set-up, per block:  Schur update as two sparse gathers (W = L_k S_{k-1}^{-1}; S_k = D_k - W U_{k-1}, U by columns),
 // then a blocked in-place Gauss-Jordan inversion without pivoting, panels of 32 columns:
@@ -29,13 +33,15 @@
 // nothing after the inversion knows of the pivoting.
 //
 // Apply: one kernel per step of the two sweeps; a workgroup forms the stencil product (L_k z_{k-1} or U_k x_{k+1}) in
-// LDS and multiplies 16 rows of S_k^{-1} with it (16 B loads, 32 column slots folded through LDS in a fixed order).
-// Planes of at most 96 rows are walked inside one launch by a single workgroup.
+// LDS and multiplies 16 lanes of rows of S_k^{-1} with it (16 B loads: 16 rows of complex double, 32 of float pairs; 32
+// column slots folded through LDS in a fixed order, one row of a lane after the other).
+// Planes of at most 96 rows are walked inside one launch by a single workgroup, one row per lane at either storage.
 //
 // Apply to a GROUP of up to 8 right-hand sides (blocktri_enqueue_batch): three launches per step.  A small kernel forms the
 // stencil product once for all members (b x R), the product kernel reads S_k^{-1} once and applies every loaded entry to
-// all R members (tiles of 64 rows x a range of columns, so that one step fills the device), a third kernel folds the
-// column ranges in a fixed order.  What is summed for one member, and in which order, is fixed by b alone.
+// all R members (tiles of 64 lanes of rows -- 64 rows of complex double, 128 of float pairs -- x a range of columns, so
+// that one step fills the device), a third kernel folds the column ranges in a fixed order.  What is summed for one
+// member, and in which order, is fixed by b alone.
 #include "blocktri.hpp"
 #include <algorithm>
 #include <chrono>
@@ -485,51 +491,39 @@ __device__ __forceinline__ cplx bt_fold(cplx acc, cplx* red) {
     return s;
 }
 
-// one step of a sweep over many workgroups, 16 rows each: forward writes z_k, backward updates it in place to x_k
-// (a workgroup writes rows of block k only and reads block k -+ 1 only)
-template <bool FWD>
-__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step(BtApply a, const cplx* __restrict__ S, int k, const cplx* __restrict__ w, cplx* x) {
-    __shared__ cplx t[AP_CHUNK], red[AP_ROWS * AP_SLOTS];
-    const int r = threadIdx.x & (AP_ROWS - 1), slot = threadIdx.x / AP_ROWS;
-    const int64_t i = (int64_t)blockIdx.x * AP_ROWS + r;
-    const cplx* Sk = S + (int64_t)k * a.b * a.b;
-    cplx acc = make_double2(0.0, 0.0);
-    for (int64_t jc = 0; jc < a.b; jc += AP_CHUNK) {
-        const int n = (int)(a.b - jc < AP_CHUNK ? a.b - jc : AP_CHUNK);
-        bt_stage<FWD>(a, k, jc, n, w, x, t);
-        __syncthreads();
-        bt_accum(Sk, a.b, i, jc, n, slot, t, acc);
-        __syncthreads();
-    }
-    const cplx s = bt_fold(acc, red);
-    if (slot == 0 && i < a.b) {
-        cplx& o = x[(int64_t)k * a.b + i];
-        if (FWD) o = s; else { o.x -= s.x; o.y -= s.y; }
-    }
-}
+// rows of S_k^{-1} that a lane of the step and product kernels takes with one 16 B load: one row of complex double, or
+// rows i and i + 1 of float pairs.  The load is all that the two storages do differently.
+template <typename T> constexpr int BT_LANE_ROWS = (int)(sizeof(cplx) / sizeof(T));
 
-// the same step at float storage: 32 rows per workgroup, a thread takes rows i, i + 1 of its columns with one 16 B load
-// (a quarter wave reads 256 B of a column, as above); a row's sum runs over the same columns and slots in the same order
-template <bool FWD>
-__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step32(BtApply a, const cplx32* __restrict__ S, int k, const cplx* __restrict__ w, cplx* x) {
+// one step of a sweep over many workgroups, 16 lanes of rows each (a quarter wave reads 256 B of a column): forward writes
+// z_k, backward updates it in place to x_k (a workgroup writes rows of block k only and reads block k -+ 1 only)
+template <bool FWD, typename T>
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step(BtApply a, const T* __restrict__ S, int k, const cplx* __restrict__ w, cplx* x) {
+    constexpr int LR = BT_LANE_ROWS<T>;
     __shared__ cplx t[AP_CHUNK], red[AP_ROWS * AP_SLOTS];
     const int r = threadIdx.x & (AP_ROWS - 1), slot = threadIdx.x / AP_ROWS;
-    const int64_t i = (int64_t)blockIdx.x * (2 * AP_ROWS) + 2 * r;
-    const cplx32* Sk = S + (int64_t)k * a.b * a.b;
-    cplx acc0 = make_double2(0.0, 0.0), acc1 = make_double2(0.0, 0.0);
+    const int64_t i = ((int64_t)blockIdx.x * AP_ROWS + r) * LR;
+    const T* Sk = S + (int64_t)k * a.b * a.b;
+    cplx acc[LR];
+#pragma unroll
+    for (int h = 0; h < LR; ++h) acc[h] = make_double2(0.0, 0.0);
     for (int64_t jc = 0; jc < a.b; jc += AP_CHUNK) {
         const int n = (int)(a.b - jc < AP_CHUNK ? a.b - jc : AP_CHUNK);
         bt_stage<FWD>(a, k, jc, n, w, x, t);
         __syncthreads();
-        if (i + 1 < a.b) bt_accum2(Sk, a.b, i, jc, n, slot, t, acc0, acc1);
-        else bt_accum(Sk, a.b, i, jc, n, slot, t, acc0);                    // the last row of an odd plane, or none
+        if constexpr (LR == 2) {
+            if (i + 1 < a.b) bt_accum2(Sk, a.b, i, jc, n, slot, t, acc[0], acc[1]);
+            else bt_accum(Sk, a.b, i, jc, n, slot, t, acc[0]);              // the last row of an odd plane, or none
+        } else bt_accum(Sk, a.b, i, jc, n, slot, t, acc[0]);
         __syncthreads();
     }
-    const cplx s0 = bt_fold(acc0, red), s1 = bt_fold(acc1, red);
-    if (slot == 0) {
-        cplx* o = x + (int64_t)k * a.b + i;
-        if (i < a.b) { if (FWD) o[0] = s0; else { o[0].x -= s0.x; o[0].y -= s0.y; } }
-        if (i + 1 < a.b) { if (FWD) o[1] = s1; else { o[1].x -= s1.x; o[1].y -= s1.y; } }
+#pragma unroll
+    for (int h = 0; h < LR; ++h) {
+        const cplx s = bt_fold(acc[h], red);
+        if (slot == 0 && i + h < a.b) {
+            cplx& o = x[(int64_t)k * a.b + i + h];
+            if (FWD) o = s; else { o.x -= s.x; o.y -= s.y; }
+        }
     }
 }
 
@@ -600,81 +594,51 @@ __global__ __launch_bounds__(256) void k_btb_stage(BtApply a, int k, int R, int6
 
 // part[c, r, i] = sum over the columns j of range c of S_k^{-1}[i, j] t[j, r].  Workgroup (row tile, column range): the
 // range's rows of t go to LDS, wave `slot` takes the columns slot, slot + 4, ... of the range, lane = row: a wave reads
-// 64 consecutive rows of one column (16 B per lane) and applies the entry to the R members (R accumulators, the R values
-// of t read from LDS at one address for the whole wave).  The four slots are folded through LDS in slot order.
-template <int R>
-__global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product(const cplx* __restrict__ Sk, int64_t b, int cols, const cplx* __restrict__ t,
+// 64 lanes of consecutive rows of one column (16 B per lane, 1 KiB per wave: 64 rows of complex double, or 128 rows of
+// float pairs with rows i, i + 1 on a lane) and applies every entry to the R members (R accumulators per row, the R values
+// of t read from LDS at one address for the whole wave).  The four slots are folded through LDS in slot order, one row
+// of a lane after the other.  A row's sum runs over the same columns, slots and ranges in the same order at either
+// storage, and the tiling is a function of b alone, so a member's bits do not depend on its companions.
+template <int R, typename T>
+__global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product(const T* __restrict__ Sk, int64_t b, int cols, const cplx* __restrict__ t,
                                                                     cplx* __restrict__ part) {
+    constexpr int LR = BT_LANE_ROWS<T>;
     __shared__ cplx ts[BB_COLS_MAX * R], red[(BB_SLOTS - 1) * R * BB_ROWS];
     const int lane = threadIdx.x & (BB_ROWS - 1), slot = threadIdx.x / BB_ROWS;
-    const int64_t i = (int64_t)blockIdx.x * BB_ROWS + lane, jc = (int64_t)blockIdx.y * cols;
+    const int64_t i = ((int64_t)blockIdx.x * BB_ROWS + lane) * LR, jc = (int64_t)blockIdx.y * cols;
     const int n = (int)(b - jc < cols ? b - jc : cols);
     for (int e = threadIdx.x; e < n * R; e += BB_ROWS * BB_SLOTS) ts[e] = t[jc * R + e];
     __syncthreads();
-    cplx acc[R];
+    cplx acc[LR][R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = make_double2(0.0, 0.0);
-    if (i < b) {
-        const cplx* p = Sk + i + (jc + slot) * b;
+    for (int h = 0; h < LR; ++h)
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[h][r] = make_double2(0.0, 0.0);
+    bool paired = false;
+    if constexpr (LR == 2) {
+        if (i + 1 < b) {
+            paired = true;
+            const T* p = Sk + i + (jc + slot) * b;
+#pragma unroll 4
+            for (int jj = slot; jj < n; jj += BB_SLOTS, p += (int64_t)BB_SLOTS * b) {
+                const f4u v = *(const f4u*)p;
+                const cplx s0 = make_double2((double)v.x, (double)v.y), s1 = make_double2((double)v.z, (double)v.w);
+#pragma unroll
+                for (int r = 0; r < R; ++r) { const cplx tj = ts[jj * R + r]; cfma_x(acc[0][r], s0, tj); cfma_x(acc[1][r], s1, tj); }
+            }
+        }
+    }
+    if (!paired && i < b) {                                                   // one row: complex double, or the last row of an odd plane
+        const T* p = Sk + i + (jc + slot) * b;
 #pragma unroll 4
         for (int jj = slot; jj < n; jj += BB_SLOTS, p += (int64_t)BB_SLOTS * b) {
-            const cplx s = *p;
+            const cplx s = bt_ld(p);
 #pragma unroll
-            for (int r = 0; r < R; ++r) cfma_x(acc[r], s, ts[jj * R + r]);
-        }
-    }
-    if (slot > 0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) red[((slot - 1) * R + r) * BB_ROWS + lane] = acc[r];
-    }
-    __syncthreads();
-    if (slot == 0 && i < b) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            cplx s = acc[r];
-            for (int q = 0; q < BB_SLOTS - 1; ++q) { const cplx v = red[(q * R + r) * BB_ROWS + lane]; s.x += v.x; s.y += v.y; }
-            part[((int64_t)blockIdx.y * R + r) * b + i] = s;
-        }
-    }
-}
-
-// The product at float storage.  Workgroup (tile of 128 rows, column range): a lane takes rows i, i + 1 of a column
-// with one 16 B load, so a wave still reads 1 KiB of a column per instruction.  Both rows have their own R accumulators;
-// a row's sum runs over the columns, slots and ranges of the fp64 form in the same order, and the tiling is a function
-// of b alone, so a member's bits do not depend on its companions here either.  The slots are folded row half by row
-// half through the LDS of the fp64 form.
-template <int R>
-__global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product32(const cplx32* __restrict__ Sk, int64_t b, int cols, const cplx* __restrict__ t,
-                                                                      cplx* __restrict__ part) {
-    __shared__ cplx ts[BB_COLS_MAX * R], red[(BB_SLOTS - 1) * R * BB_ROWS];
-    const int lane = threadIdx.x & (BB_ROWS - 1), slot = threadIdx.x / BB_ROWS;
-    const int64_t i = (int64_t)blockIdx.x * (2 * BB_ROWS) + 2 * lane, jc = (int64_t)blockIdx.y * cols;
-    const int n = (int)(b - jc < cols ? b - jc : cols);
-    for (int e = threadIdx.x; e < n * R; e += BB_ROWS * BB_SLOTS) ts[e] = t[jc * R + e];
-    __syncthreads();
-    cplx acc[2][R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[0][r] = acc[1][r] = make_double2(0.0, 0.0);
-    if (i + 1 < b) {
-        const cplx32* p = Sk + i + (jc + slot) * b;
-#pragma unroll 4
-        for (int jj = slot; jj < n; jj += BB_SLOTS, p += (int64_t)BB_SLOTS * b) {
-            const f4u v = *(const f4u*)p;
-            const cplx s0 = make_double2((double)v.x, (double)v.y), s1 = make_double2((double)v.z, (double)v.w);
-#pragma unroll
-            for (int r = 0; r < R; ++r) { const cplx tj = ts[jj * R + r]; cfma_x(acc[0][r], s0, tj); cfma_x(acc[1][r], s1, tj); }
-        }
-    } else if (i < b) {                                                       // the last row of an odd plane
-        const cplx32* p = Sk + i + (jc + slot) * b;
-#pragma unroll 4
-        for (int jj = slot; jj < n; jj += BB_SLOTS, p += (int64_t)BB_SLOTS * b) {
-            const cplx s0 = bt_ld(p);
-#pragma unroll
-            for (int r = 0; r < R; ++r) cfma_x(acc[0][r], s0, ts[jj * R + r]);
+            for (int r = 0; r < R; ++r) cfma_x(acc[0][r], s, ts[jj * R + r]);
         }
     }
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < LR; ++h) {
         if (slot > 0) {
 #pragma unroll
             for (int r = 0; r < R; ++r) red[((slot - 1) * R + r) * BB_ROWS + lane] = acc[h][r];
@@ -688,7 +652,7 @@ __global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product32(const cplx
                 part[((int64_t)blockIdx.y * R + r) * b + i + h] = s;
             }
         }
-        __syncthreads();
+        if (h + 1 < LR) __syncthreads();                                      // red is free for the lane's next row
     }
 }
 
@@ -857,22 +821,21 @@ void blocktri_destroy(BlockTri* bt) { delete bt; }
 const int* blocktri_col32(const BlockTri* bt) { return bt->col.p; }
 int64_t blocktri_nnz(const BlockTri* bt) { return bt->nnz; }
 
+// the stored inverses under their own type: f(S) with S the float pairs or the complex doubles
+template <class F> static void with_storage(const BlockTri* bt, F&& f) {
+    if (bt->prec == BLOCKTRI_INV_F32) f((const cplx32*)bt->S32.p); else f((const cplx*)bt->S.p);
+}
+
 void blocktri_enqueue(const BlockTri* bt, const cplx* w, cplx* x, hipStream_t st) {
     const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p};
     const dim3 wg(AP_ROWS * AP_SLOTS);
-    if (bt->prec == BLOCKTRI_INV_F32) {
-        const cplx32* S = bt->S32.p;
-        if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk<cplx32>, dim3(1), wg, 0, st, a, S, w, x); return; }
-        const unsigned g = nblk(bt->b, 2 * AP_ROWS);
-        for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(k_bt_step32<true>, dim3(g), wg, 0, st, a, S, k, w, x);
-        for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(k_bt_step32<false>, dim3(g), wg, 0, st, a, S, k, w, x);
-        return;
-    }
-    const cplx* S = bt->S.p;
-    if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk<cplx>, dim3(1), wg, 0, st, a, S, w, x); return; }
-    const unsigned g = nblk(bt->b, AP_ROWS);
-    for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(k_bt_step<true>, dim3(g), wg, 0, st, a, S, k, w, x);
-    for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(k_bt_step<false>, dim3(g), wg, 0, st, a, S, k, w, x);
+    with_storage(bt, [&](auto S) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(S)>>;
+        if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk<T>, dim3(1), wg, 0, st, a, S, w, x); return; }
+        const dim3 g(nblk(bt->b, AP_ROWS * BT_LANE_ROWS<T>));
+        for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bt_step<true, T>), g, wg, 0, st, a, S, k, w, x);
+        for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bt_step<false, T>), g, wg, 0, st, a, S, k, w, x);
+    });
 }
 
 int64_t blocktri_batch_reserve(BlockTri* bt, int R) {
@@ -884,17 +847,6 @@ int64_t blocktri_batch_reserve(BlockTri* bt, int R) {
     return (int64_t)(bt->bt_t.bytes() + bt->bt_part.bytes());
 }
 
-template <int R>
-static void launch_product(const BlockTri* bt, int k, int cols, const cplx* t, cplx* part, hipStream_t st) {
-    const int64_t b = bt->b;
-    if (bt->prec == BLOCKTRI_INV_F32)
-        hipLaunchKernelGGL(k_btb_product32<R>, dim3(nblk(b, 2 * BB_ROWS), nblk(b, cols)), dim3(BB_ROWS * BB_SLOTS), 0, st,
-                           (const cplx32*)(bt->S32.p + (int64_t)k * b * b), b, cols, t, part);
-    else
-        hipLaunchKernelGGL(k_btb_product<R>, dim3(nblk(b, BB_ROWS), nblk(b, cols)), dim3(BB_ROWS * BB_SLOTS), 0, st,
-                           (const cplx*)(bt->S.p + (int64_t)k * b * b), b, cols, t, part);
-}
-
 void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, hipStream_t st) {
     LSFC_REQUIRE(R >= 1 && R <= 8 && R <= bt->batch_cap, "internal: group of %d right-hand sides, work space for %d", R, bt->batch_cap);
     const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p};
@@ -902,28 +854,19 @@ void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, h
     const int cols = bb_cols(b), nranges = (int)nblk(b, cols);
     const unsigned g = nblk(b * R, 256);
     cplx* t = bt->bt_t.p; cplx* part = bt->bt_part.p;
-    auto product = [&](int k) {
-        switch (R) {
-            case 1: launch_product<1>(bt, k, cols, t, part, st); break;
-            case 2: launch_product<2>(bt, k, cols, t, part, st); break;
-            case 3: launch_product<3>(bt, k, cols, t, part, st); break;
-            case 4: launch_product<4>(bt, k, cols, t, part, st); break;
-            case 5: launch_product<5>(bt, k, cols, t, part, st); break;
-            case 6: launch_product<6>(bt, k, cols, t, part, st); break;
-            case 7: launch_product<7>(bt, k, cols, t, part, st); break;
-            default: launch_product<8>(bt, k, cols, t, part, st); break;
-        }
-    };
-    for (int k = 0; k < (int)bt->K; ++k) {
-        hipLaunchKernelGGL(k_btb_stage<true>, dim3(g), dim3(256), 0, st, a, k, R, N, w, (const cplx*)x, t);
-        product(k);
-        hipLaunchKernelGGL(k_btb_fold<true>, dim3(g), dim3(256), 0, st, b, k, R, nranges, N, (const cplx*)part, x);
-    }
-    for (int k = (int)bt->K - 2; k >= 0; --k) {
-        hipLaunchKernelGGL(k_btb_stage<false>, dim3(g), dim3(256), 0, st, a, k, R, N, w, (const cplx*)x, t);
-        product(k);
-        hipLaunchKernelGGL(k_btb_fold<false>, dim3(g), dim3(256), 0, st, b, k, R, nranges, N, (const cplx*)part, x);
-    }
+    with_storage(bt, [&](auto S) { dispatch<1, 8>(R, "block-tridiagonal group apply", [&](auto rc) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(S)>>;
+        const dim3 pg(nblk(b, BB_ROWS * BT_LANE_ROWS<T>), (unsigned)nranges);
+        auto step = [&](int k, auto fwd) {
+            constexpr bool FWD = decltype(fwd)::value;
+            hipLaunchKernelGGL(k_btb_stage<FWD>, dim3(g), dim3(256), 0, st, a, k, R, N, w, (const cplx*)x, t);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_btb_product<decltype(rc)::value, T>), pg, dim3(BB_ROWS * BB_SLOTS), 0, st, S + (int64_t)k * b * b, b, cols,
+                               (const cplx*)t, part);
+            hipLaunchKernelGGL(k_btb_fold<FWD>, dim3(g), dim3(256), 0, st, b, k, R, nranges, N, (const cplx*)part, x);
+        };
+        for (int k = 0; k < (int)bt->K; ++k) step(k, std::true_type{});
+        for (int k = (int)bt->K - 2; k >= 0; --k) step(k, std::false_type{});
+    }); });
 }
 
 BlockTriInfo blocktri_info(const BlockTri* bt) {

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <string>
 #include <stdexcept>
+#include <type_traits>
 
 #include "../../include/lsfc.h"
 
@@ -56,6 +57,13 @@ struct PhaseTimer {
         t0 = t1;
     }
 };
+
+// run-time count -> template argument: f(std::integral_constant<int, v>) for v in [LO, HI], an error under `who` outside it
+template <int LO, int HI, class F> void dispatch(int v, const char* who, F&& f) {
+    if constexpr (LO > HI) fail(LSFC_EINVAL, "%s: no kernel for %d vectors", who, v);
+    else if (v == LO) f(std::integral_constant<int, LO>{});
+    else dispatch<LO + 1, HI>(v, who, f);
+}
 
 inline bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 

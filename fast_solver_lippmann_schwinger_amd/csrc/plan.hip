@@ -86,11 +86,14 @@ static int env_switch(const char* name) { const char* e = getenv(name); return e
 static bool sym_even_y_enabled() { return env_switch("LSFC_SYM_EVEN_Y") != '0'; }
 static bool sym_even_z_enabled() { return env_switch("LSFC_SYM_EVEN_Z") != '0'; }
 
-static void select_device(int device) {
+void select_device(int device, const char* what, bool say_why) {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0) fail(LSFC_ENODEV, "no HIP device available (%s): the lsfc operator has no CPU fallback",
-                                            e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+    if (e != hipSuccess || count <= 0) {
+        const char* why = e == hipSuccess ? "device count is 0" : hipGetErrorString(e);
+        if (say_why) fail(LSFC_ENODEV, "no HIP device available (%s): the %s has no CPU fallback", why, what);
+        fail(LSFC_ENODEV, "no HIP device available: the %s has no CPU fallback", what);
+    }
     LSFC_REQUIRE(device >= 0 && device < count, "device %d out of range (have %d)", device, count);
     LSFC_HIP(hipSetDevice(device));
 }
@@ -101,7 +104,7 @@ void plan_common_init(lsfc_plan* p, int ndim, int64_t n, int64_t m, int64_t l, c
     LSFC_REQUIRE(quad_rule == LSFC_QUAD_TRAPEZOIDAL || quad_rule == LSFC_QUAD_GREENGARD_VICO,
                  "unknown quadRule %d (the reference leaves B undefined, src/FastConvolution.jl:106)", quad_rule);
     LSFC_REQUIRE(nu_host != nullptr, "nu is NULL");
-    select_device(device);
+    select_device(device, "lsfc operator", true);
     pruned_warmup(device);
     p->device = device; p->ndim = ndim;
     p->dims[0] = (int)n; p->dims[1] = (int)m; p->dims[2] = (int)l;
@@ -1225,7 +1228,7 @@ int lsfc_device_count(int* count) {
     return guarded([&] { LSFC_REQUIRE(count, "NULL argument"); int c = 0; hipError_t e = hipGetDeviceCount(&c); *count = (e == hipSuccess) ? c : 0; });
 }
 int lsfc_malloc(void** dptr, size_t bytes, int device) {
-    return guarded([&] { LSFC_REQUIRE(dptr, "NULL argument"); select_device(device); LSFC_HIP(hipMalloc(dptr, bytes)); });
+    return guarded([&] { LSFC_REQUIRE(dptr, "NULL argument"); select_device(device, "lsfc operator", true); LSFC_HIP(hipMalloc(dptr, bytes)); });
 }
 int lsfc_free(void* dptr) { return guarded([&] { if (dptr) LSFC_HIP(hipFree(dptr)); }); }
 int lsfc_memcpy_h2d(void* dst, const void* src, size_t bytes) { return guarded([&] { LSFC_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); }); }

@@ -188,6 +188,10 @@ struct Precond {
 // the symbol point to (the whole range on one device; dist.hip: one chunk of the owned range)
 void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st);
 
+// makes `device` current.  Without any device: LSFC_ENODEV, "no HIP device available: the <what> has no CPU fallback", with HIP's
+// reason in brackets after "available" if say_why.  The caller warms up (pruned_warmup) where work follows.
+void select_device(int device, const char* what, bool say_why = false);
+
 void plan_common_init(lsfc_plan* p, int ndim, int64_t n, int64_t m, int64_t l, const double* nu_host, double omega,
                       int quad_rule, unsigned flags, int device);
 

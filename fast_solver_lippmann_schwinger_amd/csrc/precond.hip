@@ -515,6 +515,43 @@ static void launch_factor(const TriFactor& F, const cplx* b, cplx* x, hipStream_
     }
 }
 
+// LSFC_PRECOND_GRAPH=0 (developer switch): plain stream launches instead of the captured graphs
+static bool graphs_enabled() {
+    static const bool v = !(getenv("LSFC_PRECOND_GRAPH") && getenv("LSFC_PRECOND_GRAPH")[0] == '0');
+    return v;
+}
+
+// A fixed sequence of launches on internal buffers only, captured once in a hipGraph and replayed from then on.
+struct CapturedSeq {
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    CapturedSeq() = default;
+    CapturedSeq(const CapturedSeq&) = delete; CapturedSeq& operator=(const CapturedSeq&) = delete;
+    ~CapturedSeq() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+    // what enqueue(stream) queues, on `st`; `group`: the group size that the sequence is for, 0 for the single apply
+    template <class F> void replay(hipStream_t st, int group, F&& enqueue) {
+        if (!graphs_enabled()) { enqueue(st); LSFC_HIP(hipGetLastError()); return; }
+        if (!exec) {
+            hipStream_t cs; LSFC_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+            hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+            if (e == hipSuccess) {
+                enqueue(cs);
+                e = hipStreamEndCapture(cs, &graph);
+            }
+            if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            (void)hipStreamDestroy(cs);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                if (group) fail(LSFC_EHIP, "preconditioner: graph capture of a group of %d failed: %s", group, hipGetErrorString(e));
+                fail(LSFC_EHIP, "preconditioner: graph capture failed: %s", hipGetErrorString(e));
+            }
+        }
+        LSFC_HIP(hipGraphLaunch(exec, st));
+    }
+};
+
 } // namespace lsfc
 
 struct lsfc_precond {
@@ -525,26 +562,18 @@ struct lsfc_precond {
     lsfc::DevBuf<int> rgather, cscatter; lsfc::DevBuf<double> rscale;
     lsfc::TriFactor L, U;
     lsfc::BlockTri* bt = nullptr;      // block-tridiagonal factorisation (blocktri.hip) instead of L, U
-    lsfc::DevBuf<lsfc::cplx> vin, y0, z, w, vout, hstage;
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; hipStream_t captured_on = nullptr;
+    lsfc::DevBuf<lsfc::cplx> vin, y0, z, w, vout;
+    lsfc::DevBuf<lsfc::cplx> hstage;   // host vectors of lsfc_precond_apply and _apply_batch pass through here, grown on demand
+    lsfc::CapturedSeq seq;             // SpMV and solves of one apply
     int launches = 0;
     // groups of right-hand sides (block-tridiagonal objects): member-major work buffers for bcap members, one graph per group size
-    lsfc::DevBuf<lsfc::cplx> bvin, by0, bvout, bhstage;
+    lsfc::DevBuf<lsfc::cplx> bvin, by0, bvout;
     int bcap = 0;
-    hipGraph_t bgraph[lsfc::LSFC_MAX_BATCH + 1] = {}; hipGraphExec_t bexec[lsfc::LSFC_MAX_BATCH + 1] = {};
+    std::unique_ptr<lsfc::CapturedSeq[]> bseq;      // indexed by group size
     int64_t bsweeps = 0, bvectors = 0, blargest = 0, bwork_bytes = 0;
-    void drop_group_graphs() {
-        for (int r = 0; r <= lsfc::LSFC_MAX_BATCH; ++r) {
-            if (bexec[r]) { (void)hipGraphExecDestroy(bexec[r]); bexec[r] = nullptr; }
-            if (bgraph[r]) { (void)hipGraphDestroy(bgraph[r]); bgraph[r] = nullptr; }
-        }
-    }
-    ~lsfc_precond() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        drop_group_graphs();
-        lsfc::blocktri_destroy(bt);
-    }
+    void drop_group_graphs() { bseq.reset(new lsfc::CapturedSeq[lsfc::LSFC_MAX_BATCH + 1]); }
+    lsfc_precond() { drop_group_graphs(); }
+    ~lsfc_precond() { lsfc::blocktri_destroy(bt); }
 };
 
 namespace lsfc {
@@ -563,27 +592,7 @@ static void enqueue_all(lsfc_precond* pc, hipStream_t st) {
 static void precond_apply_dev(lsfc_precond* pc, cplx* v, hipStream_t st) {
     const size_t bytes = (size_t)pc->N * sizeof(cplx);
     LSFC_HIP(hipMemcpyAsync(pc->vin.p, v, bytes, hipMemcpyDeviceToDevice, st));
-    // LSFC_PRECOND_GRAPH=0 (developer switch): plain stream launches instead of the captured graph
-    static const bool no_graph = getenv("LSFC_PRECOND_GRAPH") && getenv("LSFC_PRECOND_GRAPH")[0] == '0';
-    if (no_graph) {
-        enqueue_all(pc, st);
-        LSFC_HIP(hipGetLastError());
-        LSFC_HIP(hipMemcpyAsync(v, pc->vout.p, bytes, hipMemcpyDeviceToDevice, st));
-        return;
-    }
-    if (!pc->exec) {
-        // capture the fixed sequence once (internal buffers only), then replay it
-        hipStream_t cs; LSFC_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-        hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            enqueue_all(pc, cs);
-            e = hipStreamEndCapture(cs, &pc->graph);
-        }
-        if (e == hipSuccess) e = hipGraphInstantiate(&pc->exec, pc->graph, nullptr, nullptr, 0);
-        (void)hipStreamDestroy(cs);
-        if (e != hipSuccess) { (void)hipGetLastError(); fail(LSFC_EHIP, "preconditioner: graph capture failed: %s", hipGetErrorString(e)); }
-    }
-    LSFC_HIP(hipGraphLaunch(pc->exec, st));
+    pc->seq.replay(st, 0, [&](hipStream_t s) { enqueue_all(pc, s); });
     LSFC_HIP(hipMemcpyAsync(v, pc->vout.p, bytes, hipMemcpyDeviceToDevice, st));
 }
 
@@ -591,12 +600,9 @@ static void precond_apply_dev(lsfc_precond* pc, cplx* v, hipStream_t st) {
 static void enqueue_group(lsfc_precond* pc, int R, hipStream_t st) {
     const int N = (int)pc->N;
     const dim3 grid((unsigned)(((int64_t)N * 8 + 255) / 256)), block(256);
-#define LSFC_SPMV(RR) hipLaunchKernelGGL(k_spmv_batch<RR>, grid, block, 0, st, pc->a_rowptr.p, pc->a_col.p, pc->a_val.p, (const cplx*)pc->bvin.p, pc->by0.p, N)
-    switch (R) {
-        case 1: LSFC_SPMV(1); break; case 2: LSFC_SPMV(2); break; case 3: LSFC_SPMV(3); break; case 4: LSFC_SPMV(4); break;
-        case 5: LSFC_SPMV(5); break; case 6: LSFC_SPMV(6); break; case 7: LSFC_SPMV(7); break; default: LSFC_SPMV(8); break;
-    }
-#undef LSFC_SPMV
+    dispatch<1, LSFC_MAX_BATCH>(R, "preconditioner group apply", [&](auto rc) {
+        hipLaunchKernelGGL(k_spmv_batch<decltype(rc)::value>, grid, block, 0, st, pc->a_rowptr.p, pc->a_col.p, pc->a_val.p, (const cplx*)pc->bvin.p, pc->by0.p, N);
+    });
     blocktri_enqueue_batch(pc->bt, R, pc->by0.p, pc->bvout.p, st);
 }
 
@@ -615,22 +621,7 @@ static void precond_apply_group(lsfc_precond* pc, cplx* const* v, int R, hipStre
     for (int r = 0; r < R; ++r) g.v[r] = v[r];
     const dim3 cgrid((unsigned)((pc->N + 255) / 256), (unsigned)R);
     hipLaunchKernelGGL(k_group_copy<true>, cgrid, dim3(256), 0, st, g, pc->bvin.p, pc->N);
-    static const bool no_graph = getenv("LSFC_PRECOND_GRAPH") && getenv("LSFC_PRECOND_GRAPH")[0] == '0';
-    if (no_graph) enqueue_group(pc, R, st);
-    else {
-        if (!pc->bexec[R]) {
-            hipStream_t cs; LSFC_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                enqueue_group(pc, R, cs);
-                e = hipStreamEndCapture(cs, &pc->bgraph[R]);
-            }
-            if (e == hipSuccess) e = hipGraphInstantiate(&pc->bexec[R], pc->bgraph[R], nullptr, nullptr, 0);
-            (void)hipStreamDestroy(cs);
-            if (e != hipSuccess) { (void)hipGetLastError(); fail(LSFC_EHIP, "preconditioner: graph capture of a group of %d failed: %s", R, hipGetErrorString(e)); }
-        }
-        LSFC_HIP(hipGraphLaunch(pc->bexec[R], st));
-    }
+    pc->bseq[R].replay(st, R, [&](hipStream_t s) { enqueue_group(pc, R, s); });
     hipLaunchKernelGGL(k_group_copy<false>, cgrid, dim3(256), 0, st, g, pc->bvout.p, pc->N);
     LSFC_HIP(hipGetLastError());
     ++pc->bsweeps; pc->bvectors += R; pc->blargest = std::max<int64_t>(pc->blargest, R);
@@ -651,6 +642,21 @@ void warmup_precond() {
     LSFC_HIP(hipGetLastError());
 }
 
+// nrhs HOST vectors back to back, a group at a time through the staging buffer: copy up, apply(staged vectors, how many),
+// copy down; synchronised on return
+template <class F> static void apply_staged(lsfc_precond* pc, cplx* v, int64_t nrhs, F&& apply) {
+    const int64_t N = pc->N, grp = std::min<int64_t>(nrhs, LSFC_MAX_BATCH);
+    if (pc->hstage.n < (size_t)(grp * N)) pc->hstage.alloc((size_t)(grp * N));
+    for (int64_t j0 = 0; j0 < nrhs; j0 += grp) {
+        const int cnt = (int)std::min<int64_t>(grp, nrhs - j0);
+        const size_t bytes = (size_t)cnt * (size_t)N * sizeof(cplx);
+        LSFC_HIP(hipMemcpyAsync(pc->hstage.p, v + j0 * N, bytes, hipMemcpyHostToDevice, pc->stream));
+        apply(pc->hstage.p, cnt);
+        LSFC_HIP(hipMemcpyAsync(v + j0 * N, pc->hstage.p, bytes, hipMemcpyDeviceToHost, pc->stream));
+    }
+    LSFC_HIP(hipStreamSynchronize(pc->stream));
+}
+
 } // namespace lsfc
 
 using namespace lsfc;
@@ -666,10 +672,7 @@ int lsfc_precond_create(lsfc_precond** out, int64_t N,
         LSFC_REQUIRE(out, "NULL argument"); *out = nullptr;
         LSFC_REQUIRE(N >= 1 && N < ((int64_t)1 << 31), "preconditioner: N out of range");
         LSFC_REQUIRE(As_rowptr && As_col && As_val && L_rowptr && L_col && L_val && U_rowptr && U_col && U_val, "NULL argument");
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) fail(LSFC_ENODEV, "no HIP device available: the preconditioner apply has no CPU fallback");
-        LSFC_REQUIRE(device >= 0 && device < count, "device %d out of range (have %d)", device, count);
-        LSFC_HIP(hipSetDevice(device));
+        select_device(device, "preconditioner apply");
         pruned_warmup(device);                             // every code object of the library resident before any work of this process is queued
         std::unique_ptr<lsfc_precond> pc(new lsfc_precond());
         pc->device = device; pc->N = N;
@@ -724,12 +727,7 @@ int lsfc_precond_apply(lsfc_precond* pc, double* v, int memspace) {
         LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "bad memspace %d", memspace);
         LSFC_HIP(hipSetDevice(pc->device));
         if (memspace == LSFC_MEM_DEVICE) { precond_apply_dev(pc, (cplx*)v, pc->stream); return; }
-        if (pc->hstage.n < (size_t)pc->N) pc->hstage.alloc((size_t)pc->N);
-        const size_t bytes = (size_t)pc->N * sizeof(cplx);
-        LSFC_HIP(hipMemcpyAsync(pc->hstage.p, v, bytes, hipMemcpyHostToDevice, pc->stream));
-        precond_apply_dev(pc, pc->hstage.p, pc->stream);
-        LSFC_HIP(hipMemcpyAsync(v, pc->hstage.p, bytes, hipMemcpyDeviceToHost, pc->stream));
-        LSFC_HIP(hipStreamSynchronize(pc->stream));
+        apply_staged(pc, (cplx*)v, 1, [&](cplx* staged, int) { precond_apply_dev(pc, staged, pc->stream); });
     });
 }
 
@@ -739,25 +737,12 @@ int lsfc_precond_apply_batch(lsfc_precond* pc, double* v, int64_t nrhs, int mems
         LSFC_REQUIRE(nrhs >= 1 && nrhs < ((int64_t)1 << 31), "nrhs = %lld: need at least one right-hand side", (long long)nrhs);
         LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "bad memspace %d", memspace);
         LSFC_HIP(hipSetDevice(pc->device));
-        const int64_t N = pc->N;
         std::vector<cplx*> ptr((size_t)nrhs);
-        if (memspace == LSFC_MEM_DEVICE) {
-            for (int64_t j = 0; j < nrhs; ++j) ptr[(size_t)j] = (cplx*)v + j * N;
-            precond_apply_batch_dev(pc, ptr.data(), (int)nrhs, pc->stream);
-            return;
-        }
-        // host vectors: staged through device memory a group at a time
-        const int64_t grp = std::min<int64_t>(nrhs, LSFC_MAX_BATCH);
-        if (pc->bhstage.n < (size_t)(grp * N)) pc->bhstage.alloc((size_t)(grp * N));
-        for (int64_t j0 = 0; j0 < nrhs; j0 += grp) {
-            const int cnt = (int)std::min<int64_t>(grp, nrhs - j0);
-            const size_t bytes = (size_t)cnt * (size_t)N * sizeof(cplx);
-            LSFC_HIP(hipMemcpyAsync(pc->bhstage.p, (cplx*)v + j0 * N, bytes, hipMemcpyHostToDevice, pc->stream));
-            for (int j = 0; j < cnt; ++j) ptr[(size_t)j] = pc->bhstage.p + (int64_t)j * N;
+        auto apply = [&](cplx* dev, int cnt) {              // cnt device vectors back to back
+            for (int j = 0; j < cnt; ++j) ptr[(size_t)j] = dev + (int64_t)j * pc->N;
             precond_apply_batch_dev(pc, ptr.data(), cnt, pc->stream);
-            LSFC_HIP(hipMemcpyAsync((cplx*)v + j0 * N, pc->bhstage.p, bytes, hipMemcpyDeviceToHost, pc->stream));
-        }
-        LSFC_HIP(hipStreamSynchronize(pc->stream));
+        };
+        if (memspace == LSFC_MEM_DEVICE) apply((cplx*)v, (int)nrhs); else apply_staged(pc, (cplx*)v, nrhs, apply);
     });
 }
 
@@ -818,14 +803,6 @@ static lsfc_precond* create_blocktri_dev(int64_t N, int64_t K, const int64_t* ro
     return pc.release();
 }
 
-static void select_device(int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) fail(LSFC_ENODEV, "no HIP device available: the preconditioner has no CPU fallback");
-    LSFC_REQUIRE(device >= 0 && device < count, "device %d out of range (have %d)", device, count);
-    LSFC_HIP(hipSetDevice(device));
-    pruned_warmup(device);
-}
-
 // the options of the two _opts constructors, checked before any device call; NULL: fp64 storage, no pivoting
 struct BtOpts { int prec, pivoting; };
 static BtOpts checked_opts(const lsfc_blocktri_opts* o) {
@@ -868,7 +845,8 @@ int lsfc_precond_create_blocktri_opts(lsfc_precond** out, int64_t N, int64_t nbl
         LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "bad memspace %d", memspace);
         LSFC_REQUIRE(N >= 1 && N < ((int64_t)1 << 31), "preconditioner: N out of range");
         LSFC_REQUIRE(nblocks >= 1 && N % nblocks == 0, "block-tridiagonal preconditioner: N = %lld is not divisible by nblocks = %lld", (long long)N, (long long)nblocks);
-        select_device(device);
+        select_device(device, "preconditioner");
+        pruned_warmup(device);
         blocktri_require_memory(N, nblocks, 0.0, "lsfc_precond_create_blocktri", prec, piv);   // from the dimensions and options alone, before any array is read
         if (memspace == LSFC_MEM_DEVICE) { *out = create_blocktri_dev(N, nblocks, rowptr, col, (const cplx*)As_val, (const cplx*)Msp_val, device, prec, piv); return; }
         const int64_t nnz = rowptr[N];
@@ -903,7 +881,8 @@ int lsfc_precond_create_from_plan_opts(lsfc_precond** out, lsfc_plan* plan, cons
         const int64_t N = n * m * l, K = plan->ndim == 2 ? m : l;
         int64_t nnz = 0;
         if (int rc = lsfc_sparsify_pattern(n, m, l, &nnz, nullptr, nullptr, nullptr)) fail(rc, "%s", lsfc_last_error());
-        select_device(plan->device);
+        select_device(plan->device, "preconditioner");
+        pruned_warmup(plan->device);
         blocktri_require_memory(N, K, (double)nnz * 40.0, "lsfc_precond_create_from_plan", prec, piv);
         DevBuf<int64_t> drp, dcol; DevBuf<cplx> das, dmsp;
         drp.alloc((size_t)N + 1); dcol.alloc((size_t)nnz); das.alloc((size_t)nnz); dmsp.alloc((size_t)nnz);
