@@ -81,6 +81,8 @@ SIGNATURES = {
     "lsfc_precond_create": (_I, [_PP, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_precond_destroy": (_I, [_P]),
     "lsfc_precond_set_stream": (_I, [_P, _P]),
+    "lsfc_precond_set_op": (_I, [_P, _I]),
+    "lsfc_precond_get_op": (_I, [_P, C.POINTER(_I), C.POINTER(_L)]),
     "lsfc_precond_apply": (_I, [_P, _P, _I]),
     "lsfc_precond_apply_batch": (_I, [_P, _P, _L, _I]),
     "lsfc_precond_batch_info": (_I, [_P, C.POINTER(_L)]),

@@ -563,7 +563,7 @@ static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double*
     const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
     const double reltol = opts->reltol >= 0 ? opts->reltol : DEFAULT_RELTOL;
     const double abstol = opts->abstol > 0 ? opts->abstol : 0.0;
-    plan_check_precond_op(plan, opts->precond, fn);
+    plan_check_precond_op(plan, opts->precond, opts->precond_user, fn);
     const Precond pc(opts->precond, opts->precond_user, opts->precond_on_device != 0, batch, N, fn);
     LSFC_HIP(hipSetDevice(plan->device));
     const bool host = memspace == LSFC_MEM_HOST;

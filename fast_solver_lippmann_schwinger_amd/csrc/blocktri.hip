@@ -118,6 +118,32 @@ __global__ void k_bt_usort(int64_t N, const int64_t* __restrict__ ucolptr, int* 
     for (int64_t i = s; i < e; ++i) uval[i] = val[uidx[i]];
 }
 
+// The transposed tables (blocktri_transpose_tables) are one more transposition by the same two kernels -- k_bt_ufill from
+// rowptr[r] instead of rhi[r] takes the whole row, k_bt_usort sorts every row of the transpose by its column -- with the
+// count of all entries per column before it and the split of the transposed rows after it.
+__global__ void k_bt_tcount(int64_t nnz, const int* __restrict__ col32, int* __restrict__ cnt) {
+    const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (q < nnz) atomicAdd(&cnt[col32[q]], 1);
+}
+
+// row c of the transpose: where its diagonal block and its upper coupling begin (as k_bt_check splits a row of Msp), and the
+// values of As^T on the transposed pattern
+__global__ void k_bt_tsplit(int64_t N, int64_t b, const int64_t* __restrict__ tptr, const int* __restrict__ tcol, const int64_t* __restrict__ tidx,
+                            const cplx* __restrict__ as_val, int64_t* __restrict__ rlo, int64_t* __restrict__ rhi, cplx* __restrict__ tas) {
+    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const int64_t s = tptr[c], e = tptr[c + 1], k = c / b;
+    int64_t lo = e, hi = e;
+    for (int64_t q = s; q < e; ++q) {
+        const int64_t cb = tcol[q] / b;
+        if (cb >= k && lo == e) lo = q;
+        if (cb > k && hi == e) hi = q;
+        tas[q] = as_val[tidx[q]];
+    }
+    if (lo > hi) lo = hi;
+    rlo[c] = lo; rhi[c] = hi;
+}
+
 // ---- set-up: Schur update ------------------------------------------------------------------------------------------
 
 // W = L_k S_{k-1}^{-1}: W[i, r] = sum over the lower coupling of row i
@@ -553,6 +579,182 @@ __global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_walk(BtApply a, const
     }
 }
 
+// ---- the transposed apply: x <- Msp^{-T} w -----------------------------------------------------------------------------
+//
+//     forward   z_k = S_k^{-T} (w_k - U_{k-1}^T z_{k-1})        backward   x_k = z_k - S_k^{-T} (L_{k+1}^T x_{k+1})
+//
+// on the same stored S_k^{-1}.  BtApply then holds the CSR of Msp^T (its "lower" part is U_{k-1}^T, its "upper" part
+// L_{k+1}^T), so bt_stage and k_btb_stage are the ones above.  The dense product y[j] = sum_i S_k^{-1}[i + j b] t[i] sums
+// along the contiguous axis: a wave walks down columns, 16 B per lane and column (one row of complex double, or rows
+// i, i + 1 of float pairs, both for the same output), several columns in flight so that one LDS read of t feeds them all,
+// and the per-lane partial sums are folded across the wave at the end.
+
+// Sums over the 64 lanes of a wave of P doubles per lane (P a power of two, at most 64), by the butterfly 1, 2, 4, ..., 32 in
+// which the partners split the values between them while there are several: P - 1 + (6 - log2 P) cross-lane moves instead
+// of 6 P, and the steps with the most values to move are the ones inside a quad, which are DPP moves on the VALU and not
+// trips through the LDS crossbar.  Every sum is the one the plain butterfly of that order gives, whatever P.  Afterwards
+// v[0] of lane L is the sum of value bt_scatter_index<P>(L) (lanes that agree in their low log2 P bits hold the same one).
+template <int O>
+__device__ __forceinline__ double bt_xor_lane(double x) {                         // x of lane ^ O
+    if constexpr (O == 1 || O == 2) {
+        constexpr int quad_perm = O == 1 ? 0xB1 : 0x4E;                           // [1, 0, 3, 2] and [2, 3, 0, 1]
+        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), quad_perm, 0xF, 0xF, false);
+        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), quad_perm, 0xF, 0xF, false);
+        return __hiloint2double(hi, lo);
+    } else return __shfl_xor(x, O, 64);
+}
+template <int H, int O, int P>
+__device__ __forceinline__ void bt_wave_sums_step(double (&v)[P], int lane) {      // the step with partner lane ^ O, H values kept
+    if constexpr (O <= 32) {
+        if constexpr (H >= 1) {
+            const bool up = (lane & O) != 0;
+#pragma unroll
+            for (int m = 0; m < H; ++m) {
+                const double send = up ? v[m] : v[m + H], keep = up ? v[m + H] : v[m];
+                v[m] = keep + bt_xor_lane<O>(send);
+            }
+        } else v[0] += bt_xor_lane<O>(v[0]);
+        bt_wave_sums_step<H / 2, O * 2>(v, lane);
+    }
+}
+template <int P>
+__device__ __forceinline__ void bt_wave_sums(double (&v)[P]) {
+    static_assert(P >= 1 && P <= 64 && (P & (P - 1)) == 0, "a power of two up to the wave size");
+    bt_wave_sums_step<P / 2, 1>(v, threadIdx.x & 63);
+}
+template <int P>
+__device__ __forceinline__ int bt_scatter_index(int lane) {
+    int idx = 0;
+#pragma unroll
+    for (int h = P / 2, o = 1; h >= 1; h >>= 1, o <<= 1) idx += (lane & o) ? h : 0;
+    return idx;
+}
+template <int P> constexpr int BT_HOLDER_MASK = 63 & ~(P - 1);                    // lanes with these bits clear (lane < P) write the sums
+constexpr int bt_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+
+static constexpr int ST_WAVES = AP_ROWS * AP_SLOTS / 64;   // the waves of a workgroup share its columns and split the rows
+static constexpr int ST_COLS = 16;        // columns of S_k^{-1} per workgroup, all in flight on every wave
+static constexpr int WT_COLS = 4;         // walk kernel: columns in flight per wave
+
+// this wave's share of sum_i S_k^{-1}[ic + i, j0 + c] t[i], i < n, for the ncol columns of the workgroup: chunks of
+// 64 lane loads (64 or 128 rows), chunk q on wave q mod 8, a lane's chunks in ascending order
+// FULL: all 16 columns exist -- the 16 loads of a lane are issued together, ahead of the first multiply-add.  The last
+// workgroup of a plane whose size is no multiple of 16 takes its columns one by one.
+template <bool FULL, typename T>
+__device__ __forceinline__ void bt_accum_t(const T* __restrict__ Sk, int64_t b, int64_t j0, int ncol, int64_t ic, int n, const cplx* t,
+                                           cplx (&acc)[ST_COLS]) {
+    constexpr int LR = BT_LANE_ROWS<T>;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int ii = (wave * 64 + lane) * LR; ii < n; ii += ST_WAVES * 64 * LR) {
+        const T* p = Sk + ic + ii + j0 * b;
+        const cplx t0 = t[ii];
+        if constexpr (LR == 2) {
+            if (ii + 1 < n) {                                              // (n is even unless the plane ends here)
+                const cplx t1 = t[ii + 1];
+                if constexpr (FULL) {
+                    f4u v[ST_COLS];
+#pragma unroll
+                    for (int c = 0; c < ST_COLS; ++c) v[c] = *(const f4u*)(p + (int64_t)c * b);
+#pragma unroll
+                    for (int c = 0; c < ST_COLS; ++c) {
+                        cfma(acc[c], make_double2((double)v[c].x, (double)v[c].y), t0);
+                        cfma(acc[c], make_double2((double)v[c].z, (double)v[c].w), t1);
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < ST_COLS; ++c) if (c < ncol) {
+                        const f4u v = *(const f4u*)(p + (int64_t)c * b);
+                        cfma(acc[c], make_double2((double)v.x, (double)v.y), t0);
+                        cfma(acc[c], make_double2((double)v.z, (double)v.w), t1);
+                    }
+                }
+                continue;
+            }
+        }
+        if constexpr (FULL) {
+            cplx v[ST_COLS];
+#pragma unroll
+            for (int c = 0; c < ST_COLS; ++c) v[c] = bt_ld(p + (int64_t)c * b);
+#pragma unroll
+            for (int c = 0; c < ST_COLS; ++c) cfma(acc[c], v[c], t0);
+        } else {
+#pragma unroll
+            for (int c = 0; c < ST_COLS; ++c) if (c < ncol) cfma(acc[c], bt_ld(p + (int64_t)c * b), t0);
+        }
+    }
+}
+
+// one step of a transposed sweep over many workgroups: 16 columns each, the 8 waves take the row chunks in turn.  The lanes
+// of a wave are folded by bt_wave_sums, the waves through LDS in wave order.
+template <bool FWD, typename T>
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_step_t(BtApply a, const T* __restrict__ S, int k, const cplx* __restrict__ w, cplx* x) {
+    __shared__ cplx t[AP_CHUNK];
+    __shared__ double red[ST_WAVES][2 * ST_COLS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t j0 = (int64_t)blockIdx.x * ST_COLS;
+    const int ncol = (int)(a.b - j0 < ST_COLS ? a.b - j0 : ST_COLS);
+    const T* Sk = S + (int64_t)k * a.b * a.b;
+    cplx acc[ST_COLS];
+#pragma unroll
+    for (int c = 0; c < ST_COLS; ++c) acc[c] = make_double2(0.0, 0.0);
+    for (int64_t ic = 0; ic < a.b; ic += AP_CHUNK) {
+        const int n = (int)(a.b - ic < AP_CHUNK ? a.b - ic : AP_CHUNK);
+        bt_stage<FWD>(a, k, ic, n, w, x, t);
+        __syncthreads();
+        if (ncol == ST_COLS) bt_accum_t<true>(Sk, a.b, j0, ncol, ic, n, t, acc); else bt_accum_t<false>(Sk, a.b, j0, ncol, ic, n, t, acc);
+        __syncthreads();
+    }
+    double v[2 * ST_COLS];
+#pragma unroll
+    for (int c = 0; c < ST_COLS; ++c) { v[2 * c] = acc[c].x; v[2 * c + 1] = acc[c].y; }
+    bt_wave_sums(v);
+    if ((lane & BT_HOLDER_MASK<2 * ST_COLS>) == 0) red[wave][bt_scatter_index<2 * ST_COLS>(lane)] = v[0];
+    __syncthreads();
+    if ((int)threadIdx.x < ncol) {
+        cplx s = make_double2(0.0, 0.0);
+        for (int q = 0; q < ST_WAVES; ++q) { s.x += red[q][2 * threadIdx.x]; s.y += red[q][2 * threadIdx.x + 1]; }
+        cplx& o = x[(int64_t)k * a.b + j0 + threadIdx.x];
+        if (FWD) o = s; else { o.x -= s.x; o.y -= s.y; }
+    }
+}
+
+// small planes (b <= WALK_B): both transposed sweeps by ONE workgroup.  Wave q takes the columns 4 q .. 4 q + 3, then
+// 32 columns on; one row per lane and load at either storage, as in k_bt_walk.
+template <typename T>
+__global__ __launch_bounds__(AP_ROWS * AP_SLOTS) void k_bt_walk_t(BtApply a, const T* __restrict__ S, const cplx* __restrict__ w, cplx* x) {
+    __shared__ cplx t[WALK_B];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = (int)a.b;
+    for (int step = 0; step < 2 * a.K - 1; ++step) {
+        const bool fwd = step < a.K;
+        const int k = fwd ? step : 2 * a.K - 2 - step;
+        if (fwd) bt_stage<true>(a, k, 0, b, w, x, t); else bt_stage<false>(a, k, 0, b, w, x, t);
+        __syncthreads();
+        const T* Sk = S + (int64_t)k * b * b;
+        for (int j0 = wave * WT_COLS; j0 < b; j0 += ST_WAVES * WT_COLS) {          // (uniform over the wave)
+            double v[2 * WT_COLS];
+#pragma unroll
+            for (int c = 0; c < 2 * WT_COLS; ++c) v[c] = 0.0;
+            for (int i = lane; i < b; i += 64) {
+                const cplx ti = t[i];
+#pragma unroll
+                for (int c = 0; c < WT_COLS; ++c) if (j0 + c < b) {
+                    cplx s = make_double2(v[2 * c], v[2 * c + 1]);
+                    cfma(s, bt_ld(Sk + i + (int64_t)(j0 + c) * b), ti);
+                    v[2 * c] = s.x; v[2 * c + 1] = s.y;
+                }
+            }
+            bt_wave_sums(v);
+            const int idx = bt_scatter_index<2 * WT_COLS>(lane), j = j0 + idx / 2;
+            if ((lane & BT_HOLDER_MASK<2 * WT_COLS>) == 0 && j < b) {
+                double* o = (double*)&x[(int64_t)k * b + j] + (idx & 1);
+                if (fwd) *o = v[0]; else *o -= v[0];
+            }
+        }
+        __syncthreads();                          // this step's rows are visible to the next step (same workgroup)
+    }
+}
+
 // ---- the apply for a group of right-hand sides -------------------------------------------------------------------------
 //
 // Vectors of a group are member-major (member r at offset r N); the stencil product t is b x R with the R values of a row
@@ -656,6 +858,99 @@ __global__ __launch_bounds__(BB_ROWS * BB_SLOTS) void k_btb_product(const T* __r
     }
 }
 
+// The transposed group product: part[c, r, j] = sum over the rows i of range c of S_k^{-1}[i, j] t[i, r].  Workgroup
+// (column tile, row range): the range's rows of t go to LDS member by member (a wave reads the 64 or 128 values of one
+// member at consecutive addresses), each of the four waves takes `wcols` columns of the tile, two at a time: a lane loads
+// its 16 B of each column for the whole range first, then applies every entry to the R members.  At float storage a range
+// is half as many lane loads, so a wave takes four columns at a time there: 8 loads of 16 B per lane in flight and 2 R or
+// 4 R accumulators at either storage.  The lanes are folded by
+// bt_wave_sums and the sums go straight to `part`: no wave shares a column with another.  Ranges are folded by k_btb_fold.
+// Tile and range come from b alone and the multiply-adds are spelled out, so a member's bits do not depend on its companions.
+static constexpr int BT_WAVES = 4;        // waves per workgroup, each with its own columns
+static constexpr int BT_CJ = 2;           // columns in flight per wave at complex double (2 R accumulators), twice as many of float pairs
+static constexpr int BT_RANGE_MAX = 256;  // rows of S_k^{-1} per workgroup at most (R = 8: 32 KiB of t in LDS)
+
+// tile and range from b alone: b / 32 x b / 128 workgroups below 2048 rows (256 of them at b = 1024), b / 64 x b / 256 from there on
+static int bt_range_t(int64_t b) { return b < 2048 ? 128 : BT_RANGE_MAX; }        // rows per workgroup
+static int bt_wcols_t(int64_t b) { return b < 2048 ? 8 : 16; }                    // columns per wave, four waves per tile
+
+// a lane's 16 B of one column of the range, rows ii (and ii + 1): zero beyond the n rows of the range
+__device__ __forceinline__ cplx bt_ld_rows(const cplx* p, int ii, int n) { return ii < n ? *p : make_double2(0.0, 0.0); }
+__device__ __forceinline__ f4u bt_ld_rows(const cplx32* p, int ii, int n) {
+    f4u v = {0.f, 0.f, 0.f, 0.f};
+    if (ii + 1 < n) v = *(const f4u*)p;
+    else if (ii < n) { const cplx32 e = *p; v.x = e.x; v.y = e.y; }          // the last row of an odd plane
+    return v;
+}
+
+template <int R, typename T>
+__global__ __launch_bounds__(64 * BT_WAVES) void k_btb_product_t(const T* __restrict__ Sk, int64_t b, int wcols, int range, const cplx* __restrict__ t,
+                                                                 cplx* __restrict__ part) {
+    constexpr int LR = BT_LANE_ROWS<T>;
+    constexpr int NCH = BT_RANGE_MAX / (64 * LR);                             // lane loads per column and range at most: 4, or 2 of float pairs
+    constexpr int CJ = BT_CJ * LR;                                            // columns in flight: 2, or 4 of float pairs (8 loads either way)
+    constexpr int P = bt_pow2(2 * CJ * R);
+    using V = decltype(bt_ld_rows((const T*)nullptr, 0, 0));
+    __shared__ cplx ts[BT_RANGE_MAX * R];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i0 = (int64_t)blockIdx.y * range;
+    const int n = (int)(b - i0 < range ? b - i0 : range);
+    // t of the range, member by member, zero beyond its n rows: the loop below multiplies whole lane loads
+    for (int e = threadIdx.x; e < BT_RANGE_MAX * R; e += 64 * BT_WAVES)
+        ts[(e % R) * BT_RANGE_MAX + e / R] = e < n * R ? t[i0 * R + e] : make_double2(0.0, 0.0);
+    __syncthreads();
+    const int64_t jw = ((int64_t)blockIdx.x * BT_WAVES + wave) * wcols;
+    for (int cg = 0; cg < wcols && jw + cg < b; cg += CJ) {                   // (uniform over the wave; no barrier below)
+        const int64_t j = jw + cg;
+        const int ncj = (int)(b - j < CJ ? b - j : CJ);
+        // every load of the pass first: NCH x CJ = 8 of 16 B per lane in flight.  A column past the plane repeats column j, unused.
+        V sv[NCH][CJ];
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+            for (int c = 0; c < CJ; ++c) {
+                const int ii = (ch * 64 + lane) * LR;
+                sv[ch][c] = bt_ld_rows(Sk + i0 + ii + (j + (c < ncj ? c : 0)) * b, ii, n);
+            }
+        cplx acc[CJ][R];
+#pragma unroll
+        for (int c = 0; c < CJ; ++c)
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[c][r] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+            if (ch * 64 * LR >= n) break;                                     // (uniform)
+            const int ii = (ch * 64 + lane) * LR;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const cplx t0 = ts[r * BT_RANGE_MAX + ii];
+                if constexpr (LR == 2) {
+                    const cplx t1 = ts[r * BT_RANGE_MAX + ii + 1];
+#pragma unroll
+                    for (int c = 0; c < CJ; ++c) {
+                        cfma_x(acc[c][r], make_double2((double)sv[ch][c].x, (double)sv[ch][c].y), t0);
+                        cfma_x(acc[c][r], make_double2((double)sv[ch][c].z, (double)sv[ch][c].w), t1);
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < CJ; ++c) cfma_x(acc[c][r], sv[ch][c], t0);
+                }
+            }
+        }
+        double v[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) v[q] = 0.0;
+#pragma unroll
+        for (int c = 0; c < CJ; ++c)
+#pragma unroll
+            for (int r = 0; r < R; ++r) { v[2 * (c * R + r)] = acc[c][r].x; v[2 * (c * R + r) + 1] = acc[c][r].y; }
+        bt_wave_sums(v);
+        const int idx = bt_scatter_index<P>(lane), c = idx / (2 * R), r = (idx / 2) % R;
+        if ((lane & BT_HOLDER_MASK<P>) == 0 && c < ncj)
+            ((double*)&part[((int64_t)blockIdx.y * R + r) * b + j + c])[idx & 1] = v[0];
+    }
+}
+
 // the column ranges in range order: forward writes (z_r)_k, backward updates it in place to (x_r)_k
 template <bool FWD>
 __global__ __launch_bounds__(256) void k_btb_fold(int64_t b, int k, int R, int nranges, int64_t N, const cplx* __restrict__ part, cplx* __restrict__ x) {
@@ -679,6 +974,13 @@ struct BlockTri {
     int64_t factor_us = 0; double min_ratio = 0.0;
     bool pivoted = false; DevBuf<int> perm;                                  // partial pivoting: perm[k b + i] = row of S_k that became pivot row i
     DevBuf<cplx> bt_t, bt_part; int batch_cap = 0;                           // group apply: stencil products (b x R), partial sums (ranges x R x b)
+    // the transposed apply (blocktri_transpose_tables, on first use): CSR of Msp^T split at the block boundaries as the one
+    // above is, and the values of As^T on the same pattern
+    DevBuf<int64_t> t_rowptr, t_rlo, t_rhi; DevBuf<int> t_col; DevBuf<cplx> t_val, t_as; bool has_t = false;
+    BtApply tables(bool transposed) const {
+        if (transposed) return BtApply{b, (int)K, t_rowptr.p, t_rlo.p, t_rhi.p, t_col.p, t_val.p};
+        return BtApply{b, (int)K, rowptr.p, rlo.p, rhi.p, col.p, val.p};
+    }
     int launches() const { return b <= WALK_B ? 1 : (int)(2 * K - 1); }
 };
 
@@ -817,6 +1119,42 @@ BlockTri* blocktri_factor(int64_t N, int64_t K, const int64_t* rowptr, const int
     return factor_once(N, K, rowptr, col, msp, prec, true, nullptr);          // the whole factorisation again, pivoting in every block
 }
 
+// The tables of the transposed apply, built once: every entry (r, c) of the private CSR goes to row c of the transpose.
+// Slots are handed out by integer counters and every transposed row is then sorted by its column, so two objects of one
+// input hold the same tables.  Synchronous; allocates.
+BlockTriT blocktri_transpose_tables(BlockTri* bt, const cplx* as_val) {
+    if (!bt->has_t) {
+        const int64_t N = bt->N, nnz = bt->nnz;
+        hipStream_t st = nullptr;
+        DevBuf<int> cnt; cnt.alloc((size_t)N);
+        LSFC_HIP(hipMemsetAsync(cnt.p, 0, cnt.bytes(), st));
+        hipLaunchKernelGGL(k_bt_tcount, dim3(nblk(nnz, 256)), dim3(256), 0, st, nnz, (const int*)bt->col.p, cnt.p);
+        LSFC_HIP(hipGetLastError());
+        std::vector<int> hcnt((size_t)N);
+        LSFC_HIP(hipMemcpyAsync(hcnt.data(), cnt.p, cnt.bytes(), hipMemcpyDeviceToHost, st));
+        LSFC_HIP(hipStreamSynchronize(st));
+        std::vector<int64_t> hptr((size_t)N + 1, 0);
+        for (int64_t c = 0; c < N; ++c) hptr[(size_t)c + 1] = hptr[(size_t)c] + hcnt[(size_t)c];
+        LSFC_REQUIRE(hptr[(size_t)N] == nnz, "internal: the transpose of %lld entries has %lld", (long long)nnz, (long long)hptr[(size_t)N]);
+        DevBuf<int64_t> tidx; tidx.alloc((size_t)nnz);
+        bt->t_rowptr.alloc((size_t)N + 1); bt->t_rlo.alloc((size_t)N); bt->t_rhi.alloc((size_t)N);
+        bt->t_col.alloc((size_t)nnz); bt->t_val.alloc((size_t)nnz); bt->t_as.alloc((size_t)nnz);
+        LSFC_HIP(hipMemcpyAsync(bt->t_rowptr.p, hptr.data(), hptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        LSFC_HIP(hipMemsetAsync(cnt.p, 0, cnt.bytes(), st));
+        // (k_bt_ufill from rowptr[r] on: the whole row)
+        hipLaunchKernelGGL(k_bt_ufill, dim3(nblk(N, 256)), dim3(256), 0, st, N, (const int64_t*)bt->rowptr.p, (const int64_t*)bt->rowptr.p, (const int*)bt->col.p,
+                           (const int64_t*)bt->t_rowptr.p, cnt.p, bt->t_col.p, tidx.p);
+        hipLaunchKernelGGL(k_bt_usort, dim3(nblk(N, 256)), dim3(256), 0, st, N, (const int64_t*)bt->t_rowptr.p, bt->t_col.p, tidx.p, (const cplx*)bt->val.p, bt->t_val.p);
+        hipLaunchKernelGGL(k_bt_tsplit, dim3(nblk(N, 256)), dim3(256), 0, st, N, bt->b, (const int64_t*)bt->t_rowptr.p, (const int*)bt->t_col.p,
+                           (const int64_t*)tidx.p, as_val, bt->t_rlo.p, bt->t_rhi.p, bt->t_as.p);
+        LSFC_HIP(hipGetLastError());
+        LSFC_HIP(hipStreamSynchronize(st));
+        bt->has_t = true;
+    }
+    const int64_t bytes = (int64_t)(bt->t_rowptr.bytes() + bt->t_rlo.bytes() + bt->t_rhi.bytes() + bt->t_col.bytes() + bt->t_val.bytes() + bt->t_as.bytes());
+    return BlockTriT{bt->t_rowptr.p, bt->t_col.p, bt->t_as.p, bytes};
+}
+
 void blocktri_destroy(BlockTri* bt) { delete bt; }
 const int* blocktri_col32(const BlockTri* bt) { return bt->col.p; }
 int64_t blocktri_nnz(const BlockTri* bt) { return bt->nnz; }
@@ -826,11 +1164,19 @@ template <class F> static void with_storage(const BlockTri* bt, F&& f) {
     if (bt->prec == BLOCKTRI_INV_F32) f((const cplx32*)bt->S32.p); else f((const cplx*)bt->S.p);
 }
 
-void blocktri_enqueue(const BlockTri* bt, const cplx* w, cplx* x, hipStream_t st) {
-    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p};
+void blocktri_enqueue(const BlockTri* bt, const cplx* w, cplx* x, hipStream_t st, bool transposed) {
+    LSFC_REQUIRE(!transposed || bt->has_t, "internal: transposed sweep without its tables");
+    const BtApply a = bt->tables(transposed);
     const dim3 wg(AP_ROWS * AP_SLOTS);
     with_storage(bt, [&](auto S) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(S)>>;
+        if (transposed) {
+            if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk_t<T>, dim3(1), wg, 0, st, a, S, w, x); return; }
+            const dim3 g(nblk(bt->b, ST_COLS));
+            for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bt_step_t<true, T>), g, wg, 0, st, a, S, k, w, x);
+            for (int k = (int)bt->K - 2; k >= 0; --k) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bt_step_t<false, T>), g, wg, 0, st, a, S, k, w, x);
+            return;
+        }
         if (bt->b <= WALK_B) { hipLaunchKernelGGL(k_bt_walk<T>, dim3(1), wg, 0, st, a, S, w, x); return; }
         const dim3 g(nblk(bt->b, AP_ROWS * BT_LANE_ROWS<T>));
         for (int k = 0; k < (int)bt->K; ++k) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bt_step<true, T>), g, wg, 0, st, a, S, k, w, x);
@@ -840,28 +1186,33 @@ void blocktri_enqueue(const BlockTri* bt, const cplx* w, cplx* x, hipStream_t st
 
 int64_t blocktri_batch_reserve(BlockTri* bt, int R) {
     if (R > bt->batch_cap) {
-        const int64_t nranges = (bt->b + bb_cols(bt->b) - 1) / bb_cols(bt->b);
+        const int64_t nranges = std::max<int64_t>(nblk(bt->b, bb_cols(bt->b)), nblk(bt->b, bt_range_t(bt->b)));   // either sweep
         bt->bt_t.alloc((size_t)(bt->b * R)); bt->bt_part.alloc((size_t)(nranges * R * bt->b));
         bt->batch_cap = R;
     }
     return (int64_t)(bt->bt_t.bytes() + bt->bt_part.bytes());
 }
 
-void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, hipStream_t st) {
+void blocktri_enqueue_batch(const BlockTri* bt, int R, const cplx* w, cplx* x, hipStream_t st, bool transposed) {
     LSFC_REQUIRE(R >= 1 && R <= 8 && R <= bt->batch_cap, "internal: group of %d right-hand sides, work space for %d", R, bt->batch_cap);
-    const BtApply a{bt->b, (int)bt->K, bt->rowptr.p, bt->rlo.p, bt->rhi.p, bt->col.p, bt->val.p};
+    LSFC_REQUIRE(!transposed || bt->has_t, "internal: transposed sweep without its tables");
+    const BtApply a = bt->tables(transposed);
     const int64_t b = bt->b, N = bt->N;
-    const int cols = bb_cols(b), nranges = (int)nblk(b, cols);
+    const int cols = bb_cols(b), range = bt_range_t(b), wcols = bt_wcols_t(b), nranges = (int)nblk(b, transposed ? range : cols);
     const unsigned g = nblk(b * R, 256);
     cplx* t = bt->bt_t.p; cplx* part = bt->bt_part.p;
     with_storage(bt, [&](auto S) { dispatch<1, 8>(R, "block-tridiagonal group apply", [&](auto rc) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(S)>>;
-        const dim3 pg(nblk(b, BB_ROWS * BT_LANE_ROWS<T>), (unsigned)nranges);
+        const dim3 pg(nblk(b, BB_ROWS * BT_LANE_ROWS<T>), (unsigned)nranges), pgt(nblk(b, BT_WAVES * wcols), (unsigned)nranges);
         auto step = [&](int k, auto fwd) {
             constexpr bool FWD = decltype(fwd)::value;
             hipLaunchKernelGGL(k_btb_stage<FWD>, dim3(g), dim3(256), 0, st, a, k, R, N, w, (const cplx*)x, t);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_btb_product<decltype(rc)::value, T>), pg, dim3(BB_ROWS * BB_SLOTS), 0, st, S + (int64_t)k * b * b, b, cols,
-                               (const cplx*)t, part);
+            if (transposed)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_btb_product_t<decltype(rc)::value, T>), pgt, dim3(64 * BT_WAVES), 0, st, S + (int64_t)k * b * b, b, wcols,
+                                   range, (const cplx*)t, part);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_btb_product<decltype(rc)::value, T>), pg, dim3(BB_ROWS * BB_SLOTS), 0, st, S + (int64_t)k * b * b, b, cols,
+                                   (const cplx*)t, part);
             hipLaunchKernelGGL(k_btb_fold<FWD>, dim3(g), dim3(256), 0, st, b, k, R, nranges, N, (const cplx*)part, x);
         };
         for (int k = 0; k < (int)bt->K; ++k) step(k, std::true_type{});

@@ -35,13 +35,19 @@ int blocktri_precision(const BlockTri*);
 void blocktri_destroy(BlockTri*);
 const int* blocktri_col32(const BlockTri*);          // the columns as 32-bit integers (device), nnz of them
 int64_t blocktri_nnz(const BlockTri*);
-// x <- Msp^{-1} w (device vectors of N, w != x), enqueued on st as a single chain of launches
-void blocktri_enqueue(const BlockTri*, const cplx* w, cplx* x, hipStream_t st);
+// The tables of the transposed apply: the CSR of Msp^T split at the block boundaries (kept inside), and for the caller's
+// SpMV its row pointers and columns with the values of As^T on that pattern (as_val: As on the pattern of Msp, device).
+// Built on the first call (synchronous, allocates: not inside a stream capture), returned as they are from then on.
+struct BlockTriT { const int64_t* rowptr; const int* col; const cplx* as_val; int64_t bytes; };
+BlockTriT blocktri_transpose_tables(BlockTri*, const cplx* as_val);
+// x <- Msp^{-1} w (device vectors of N, w != x), enqueued on st as a single chain of launches; `transposed`: x <- Msp^{-T} w
+// from the same inverses (after blocktri_transpose_tables)
+void blocktri_enqueue(const BlockTri*, const cplx* w, cplx* x, hipStream_t st, bool transposed = false);
 // The same for a group of R <= 8 right-hand sides, member r at w + r N and x + r N: every S_k^{-1} is read once per group.
 // The bits of a member's result do not depend on R or on r.  blocktri_batch_reserve(bt, R) first (it allocates: not
 // inside a stream capture); it returns the bytes of the group work space.
 int64_t blocktri_batch_reserve(BlockTri*, int R);
-void blocktri_enqueue_batch(const BlockTri*, int R, const cplx* w, cplx* x, hipStream_t st);
+void blocktri_enqueue_batch(const BlockTri*, int R, const cplx* w, cplx* x, hipStream_t st, bool transposed = false);
 BlockTriInfo blocktri_info(const BlockTri*);
 void blocktri_get_block(const BlockTri*, int64_t k, cplx* host_out);  // the stored block, widened to double at float storage
 // perm[i] = row of S_k that became pivot row i, b entries to the host (the identity on an object factorised without pivoting)
@@ -53,5 +59,6 @@ void warmup_blocktri();
 // lsfc_precond_create member by member through the single-vector path.
 void precond_apply_batch_dev(lsfc_precond* pc, cplx* const* v, int cnt, hipStream_t st);
 int64_t precond_size(const lsfc_precond* pc);
+int precond_op(const lsfc_precond* pc);                // LSFC_OP_N | _T | _H: what the applies of pc compute (lsfc_precond_set_op)
 
 } // namespace lsfc

@@ -411,7 +411,7 @@ void precondition(Team& T, const Precond& pc, int col) {
 
 // one solve over a team
 void solve(Team& T, const Resolved& r, double* resnorm, int64_t cap, lsfc_gmres_result* res) {
-    plan_check_precond_op(T.root, r.o.precond, nullptr);
+    plan_check_precond_op(T.root, r.o.precond, r.o.precond_user, nullptr);
     Solve S(T, r, resnorm, cap, res, false);
     const Precond pc(r.o.precond, r.o.precond_user, r.o.precond_on_device != 0, false, T.root->N, nullptr);   // (a single solve meets nobody)
     while (S.running()) {
@@ -446,7 +446,7 @@ void gmres_run(lsfc_plan* p, cplx* x, const cplx* b, const lsfc_gmres_opts* opts
 void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap,
                      lsfc_gmres_result* res) {
     const Resolved r = resolve(opts_in, p->N);
-    plan_check_precond_op(p, r.o.precond, nullptr);
+    plan_check_precond_op(p, r.o.precond, r.o.precond_user, nullptr);
     const Precond pc(r.o.precond, r.o.precond_user, r.o.precond_on_device != 0, true, p->N, nullptr);
     // one workspace (Krylov basis, scalars, pinned buffers) per right-hand side: nrhs * (restart + 2) vectors of N complex.
     // Checked against the free device memory up front (a failed hipMalloc half way through leaves a half-built batch), and

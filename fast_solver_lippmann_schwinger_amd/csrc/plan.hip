@@ -554,10 +554,12 @@ void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out,
     }
 }
 
-void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, const char* who) {
-    LSFC_REQUIRE(p->op == LSFC_OP_N || fn != &lsfc_precond_callback,
-                 "%s%sthe library's preconditioner object approximates inv(M), not its transpose or adjoint: not available under lsfc_plan_set_op(T | H)",
-                 who ? who : "", who ? ": " : "");
+void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, void* precond_user, const char* who) {
+    if (fn != &lsfc_precond_callback) return;
+    static const char* const names[] = {"LSFC_OP_N", "LSFC_OP_T", "LSFC_OP_H"};
+    const int pop = precond_user ? precond_op((const lsfc_precond*)precond_user) : LSFC_OP_N;
+    LSFC_REQUIRE(pop == p->op, "%s%sthe library's preconditioner object is set to %s and approximates the inverse of that form of M, the plan is set to %s: "
+                 "lsfc_precond_set_op and lsfc_plan_set_op must agree", who ? who : "", who ? ": " : "", names[pop], names[p->op]);
 }
 
 Precond::Precond(lsfc_precond_fn f, void* u, bool dev, bool meet, int64_t n, const char* who)

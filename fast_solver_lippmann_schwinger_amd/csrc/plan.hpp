@@ -176,8 +176,9 @@ void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out,
 // object on the device, where the members of a batch meet (`meet`): apply() hands it all cnt vectors for its group sweeps; any other
 // callback gets them one by one, in order, a host callback through `pinned`.  The size of an own object is checked here, under `who`.
 constexpr double DEFAULT_RELTOL = 0x1p-26;      // sqrt(eps)
-// The library's own preconditioner object approximates inv(M), not its transpose: refused under lsfc_plan_set_op(T | H)
-void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, const char* who);
+// The library's own preconditioner object (fn == lsfc_precond_callback) approximates the inverse of M, M^T or M^H as its own
+// op says (lsfc_precond_set_op): refused unless that is the plan's op.  A caller's callback passes.
+void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, void* precond_user, const char* who);
 struct Precond {
     lsfc_precond_fn fn; void* user; bool on_device, own; int64_t N;
     Precond(lsfc_precond_fn fn, void* user, bool on_device, bool meet, int64_t N, const char* who);

@@ -23,6 +23,8 @@
 // of this file): its apply is the same SpMV followed by the block-tridiagonal sweeps, captured and replayed the same way.
 // Such an object also takes GROUPS of up to 8 vectors (precond_apply_batch_dev, lsfc_precond_apply_batch): one SpMV launch
 // and one sweep per group, As and every S_k^{-1} read once per group; one captured graph per group size.
+// Under lsfc_precond_set_op(T | H) it applies the transpose As^T Msp^{-T} (the transposed sweeps of blocktri.hip first, then
+// the SpMV with As^T) or the adjoint (the same between two conjugating copies), single and in groups, from graphs of their own.
 #include "common.hpp"
 #include "pruned.hpp"
 #include "plan.hpp"
@@ -86,13 +88,16 @@ __global__ void k_spmv_batch(const int64_t* __restrict__ rowptr, const int* __re
 }
 
 // the vectors of a group, wherever they live, into / out of the member-major work buffer (TO_WORK: work <- v, else v <- work)
+// CONJ: the copy conjugates (the adjoint apply is conj . transposed apply . conj, with both conjugations in these copies)
 struct GroupPtrs { cplx* v[LSFC_MAX_BATCH]; };
-template <bool TO_WORK>
+template <bool TO_WORK, bool CONJ = false>
 __global__ void k_group_copy(GroupPtrs g, cplx* __restrict__ work, int64_t n) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     cplx* v = g.v[blockIdx.y];
-    if (TO_WORK) work[(int64_t)blockIdx.y * n + i] = v[i]; else v[i] = work[(int64_t)blockIdx.y * n + i];
+    cplx s = TO_WORK ? v[i] : work[(int64_t)blockIdx.y * n + i];
+    if (CONJ) s.y = -s.y;
+    if (TO_WORK) work[(int64_t)blockIdx.y * n + i] = s; else v[i] = s;
 }
 
 // one row of a triangular solve, LANES lanes: x[row] = (b[row] - sum_{j != row} a_j x[col_j]) * inv_diag
@@ -571,7 +576,17 @@ struct lsfc_precond {
     int bcap = 0;
     std::unique_ptr<lsfc::CapturedSeq[]> bseq;      // indexed by group size
     int64_t bsweeps = 0, bvectors = 0, blargest = 0, bwork_bytes = 0;
-    void drop_group_graphs() { bseq.reset(new lsfc::CapturedSeq[lsfc::LSFC_MAX_BATCH + 1]); }
+    // what the applies compute (lsfc_precond_set_op): Msp^{-1} As, its transpose As^T Msp^{-T}, or its adjoint.  The
+    // transposed sequence (sweeps first, then the SpMV with As^T) has graphs of its own; T and H share them, the
+    // conjugations of H sit in the copies around the graph.
+    int op = LSFC_OP_N;
+    lsfc::BlockTriT tt{};              // the tables of the transposed apply, built by the first set_op(T | H)
+    lsfc::CapturedSeq seq_t;
+    std::unique_ptr<lsfc::CapturedSeq[]> bseq_t;
+    void drop_group_graphs() {
+        bseq.reset(new lsfc::CapturedSeq[lsfc::LSFC_MAX_BATCH + 1]);
+        bseq_t.reset(new lsfc::CapturedSeq[lsfc::LSFC_MAX_BATCH + 1]);
+    }
     lsfc_precond() { drop_group_graphs(); }
     ~lsfc_precond() { lsfc::blocktri_destroy(bt); }
 };
@@ -588,9 +603,29 @@ static void enqueue_all(lsfc_precond* pc, hipStream_t st) {
     hipLaunchKernelGGL(k_scatter, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, pc->w.p, pc->cscatter.p, pc->vout.p, N);
 }
 
-// v (device, N complex) <- Msp^{-1} (As v), stream-ordered on `st`
+// the transposed sequence of a block-tridiagonal object: vout <- As^T (Msp^{-T} vin), the sweeps first
+static void enqueue_all_t(lsfc_precond* pc, hipStream_t st) {
+    const int N = (int)pc->N;
+    blocktri_enqueue(pc->bt, pc->vin.p, pc->y0.p, st, true);
+    hipLaunchKernelGGL(k_spmv_gather<8>, dim3((unsigned)(((int64_t)N * 8 + 255) / 256)), dim3(256), 0, st, pc->tt.rowptr, pc->tt.col, pc->tt.as_val,
+                       (const int*)nullptr, (const double*)nullptr, (const cplx*)pc->y0.p, pc->vout.p, N);
+}
+
+// v (device, N complex) <- Msp^{-1} (As v), or what pc->op makes of it, stream-ordered on `st`
 static void precond_apply_dev(lsfc_precond* pc, cplx* v, hipStream_t st) {
     const size_t bytes = (size_t)pc->N * sizeof(cplx);
+    if (pc->op != LSFC_OP_N) {
+        const bool conj = pc->op == LSFC_OP_H;
+        GroupPtrs g{}; g.v[0] = v;
+        const dim3 cgrid((unsigned)((pc->N + 255) / 256), 1u);
+        if (conj) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_group_copy<true, true>), cgrid, dim3(256), 0, st, g, pc->vin.p, pc->N);
+        else LSFC_HIP(hipMemcpyAsync(pc->vin.p, v, bytes, hipMemcpyDeviceToDevice, st));
+        pc->seq_t.replay(st, 0, [&](hipStream_t s) { enqueue_all_t(pc, s); });
+        if (conj) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_group_copy<false, true>), cgrid, dim3(256), 0, st, g, pc->vout.p, pc->N);
+        else LSFC_HIP(hipMemcpyAsync(v, pc->vout.p, bytes, hipMemcpyDeviceToDevice, st));
+        LSFC_HIP(hipGetLastError());
+        return;
+    }
     LSFC_HIP(hipMemcpyAsync(pc->vin.p, v, bytes, hipMemcpyDeviceToDevice, st));
     pc->seq.replay(st, 0, [&](hipStream_t s) { enqueue_all(pc, s); });
     LSFC_HIP(hipMemcpyAsync(v, pc->vout.p, bytes, hipMemcpyDeviceToDevice, st));
@@ -604,6 +639,16 @@ static void enqueue_group(lsfc_precond* pc, int R, hipStream_t st) {
         hipLaunchKernelGGL(k_spmv_batch<decltype(rc)::value>, grid, block, 0, st, pc->a_rowptr.p, pc->a_col.p, pc->a_val.p, (const cplx*)pc->bvin.p, pc->by0.p, N);
     });
     blocktri_enqueue_batch(pc->bt, R, pc->by0.p, pc->bvout.p, st);
+}
+
+// the same for the transposed apply: the group sweep first, then the SpMV with As^T for R members
+static void enqueue_group_t(lsfc_precond* pc, int R, hipStream_t st) {
+    const int N = (int)pc->N;
+    const dim3 grid((unsigned)(((int64_t)N * 8 + 255) / 256)), block(256);
+    blocktri_enqueue_batch(pc->bt, R, pc->bvin.p, pc->by0.p, st, true);
+    dispatch<1, LSFC_MAX_BATCH>(R, "preconditioner group apply", [&](auto rc) {
+        hipLaunchKernelGGL(k_spmv_batch<decltype(rc)::value>, grid, block, 0, st, pc->tt.rowptr, pc->tt.col, pc->tt.as_val, (const cplx*)pc->by0.p, pc->bvout.p, N);
+    });
 }
 
 // one group of R <= LSFC_MAX_BATCH vectors of a block-tridiagonal object
@@ -620,9 +665,13 @@ static void precond_apply_group(lsfc_precond* pc, cplx* const* v, int R, hipStre
     GroupPtrs g{};
     for (int r = 0; r < R; ++r) g.v[r] = v[r];
     const dim3 cgrid((unsigned)((pc->N + 255) / 256), (unsigned)R);
-    hipLaunchKernelGGL(k_group_copy<true>, cgrid, dim3(256), 0, st, g, pc->bvin.p, pc->N);
-    pc->bseq[R].replay(st, R, [&](hipStream_t s) { enqueue_group(pc, R, s); });
-    hipLaunchKernelGGL(k_group_copy<false>, cgrid, dim3(256), 0, st, g, pc->bvout.p, pc->N);
+    const bool conj = pc->op == LSFC_OP_H;
+    if (conj) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_group_copy<true, true>), cgrid, dim3(256), 0, st, g, pc->bvin.p, pc->N);
+    else hipLaunchKernelGGL(k_group_copy<true>, cgrid, dim3(256), 0, st, g, pc->bvin.p, pc->N);
+    if (pc->op == LSFC_OP_N) pc->bseq[R].replay(st, R, [&](hipStream_t s) { enqueue_group(pc, R, s); });
+    else pc->bseq_t[R].replay(st, R, [&](hipStream_t s) { enqueue_group_t(pc, R, s); });
+    if (conj) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_group_copy<false, true>), cgrid, dim3(256), 0, st, g, pc->bvout.p, pc->N);
+    else hipLaunchKernelGGL(k_group_copy<false>, cgrid, dim3(256), 0, st, g, pc->bvout.p, pc->N);
     LSFC_HIP(hipGetLastError());
     ++pc->bsweeps; pc->bvectors += R; pc->blargest = std::max<int64_t>(pc->blargest, R);
 }
@@ -633,6 +682,7 @@ void precond_apply_batch_dev(lsfc_precond* pc, cplx* const* v, int cnt, hipStrea
 }
 
 int64_t precond_size(const lsfc_precond* pc) { return pc->N; }
+int precond_op(const lsfc_precond* pc) { return pc->op; }
 
 // loads this translation unit's code object on the current device (pruned.hip: pruned_warmup -- every code object of the library is
 // resident before the first transfer or pass of a process exists; DESIGN 3, "The round-2 first-apply GPU fault")
@@ -719,6 +769,28 @@ int lsfc_precond_destroy(lsfc_precond* pc) {
 
 int lsfc_precond_set_stream(lsfc_precond* pc, void* stream) {
     return guarded([&] { LSFC_REQUIRE(pc, "NULL preconditioner"); pc->stream = (hipStream_t)stream; });
+}
+
+int lsfc_precond_set_op(lsfc_precond* pc, int op) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc, "NULL preconditioner");
+        LSFC_REQUIRE(op == LSFC_OP_N || op == LSFC_OP_T || op == LSFC_OP_H, "bad op %d (LSFC_OP_N, LSFC_OP_T or LSFC_OP_H)", op);
+        LSFC_REQUIRE(op == LSFC_OP_N || pc->bt, "the transposed and the adjoint apply need a block-tridiagonal object (lsfc_precond_create_blocktri / "
+                     "_from_plan); this one holds the host's LU factors (lsfc_precond_create), whose transposed level-scheduled solves are not offered");
+        if (op != LSFC_OP_N && !pc->tt.rowptr) {
+            LSFC_HIP(hipSetDevice(pc->device));
+            pc->tt = blocktri_transpose_tables(pc->bt, pc->a_val.p);
+        }
+        pc->op = op;
+    });
+}
+
+int lsfc_precond_get_op(const lsfc_precond* pc, int* op, int64_t* table_bytes) {
+    return guarded([&] {
+        LSFC_REQUIRE(pc && op, "NULL argument");
+        *op = pc->op;
+        if (table_bytes) *table_bytes = pc->tt.bytes;
+    });
 }
 
 int lsfc_precond_apply(lsfc_precond* pc, double* v, int memspace) {

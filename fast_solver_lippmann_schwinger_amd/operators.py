@@ -28,6 +28,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .preconditioner import _op_of as _precond_op_of
 
 
 def _is_torch(a):
@@ -539,8 +540,14 @@ def _solve(entry, A, x, vecs, nrhs, opts, Pl, Pl_on_device, cap, ok=(0,), status
     the return code.  The copy of b in vecs, r_shadow (the caller holds it) and the ctypes callback live until this returns."""
     px, pb, sx, keepb = vecs
     err = []
-    if getattr(A, "_op", L.LSFC_OP_N) != L.LSFC_OP_N and getattr(Pl, "_pc", None) is not None:
-        raise ValueError("a SparsifyingPreconditioner approximates inv(M), not its transpose or adjoint: not available with M.T / M.H")
+    native = getattr(Pl, "_pc", None) is not None
+    a_op, p_op = getattr(A, "_op", L.LSFC_OP_N), getattr(Pl, "_op", L.LSFC_OP_N)
+    if native and p_op != a_op:
+        if p_op == L.LSFC_OP_N:
+            raise ValueError("a SparsifyingPreconditioner approximates inv(M), not its transpose or adjoint: not available with M.T / M.H "
+                             "(P.T and P.H of a block-tridiagonal one are)")
+        names = ("", ".T", ".H")
+        raise ValueError(f"Pl = P{names[p_op]} approximates inv(M{names[p_op]}), not inv(M{names[a_op]}): the ops of operator and preconditioner must agree")
     cb = _precond_opts(opts, Pl, Pl_on_device, A, x, sx, err)
     rows = 1 if nrhs is None else max(nrhs, 1)
     res = (L.GmresResult * rows)()
@@ -551,7 +558,7 @@ def _solve(entry, A, x, vecs, nrhs, opts, Pl, Pl_on_device, cap, ok=(0,), status
     args += [C.byref(opts), resnorm.ctypes.data_as(C.c_void_p), cap, res]
     if status is not None:
         args.append(status.ctypes.data_as(C.c_void_p))
-    with _op_of(A):
+    with _op_of(A), (_precond_op_of(Pl) if native else contextlib.nullcontext()):    # both ops held for the call, restored after
         rc = getattr(L.load(), entry)(*args, sx)
     if err:
         raise err[0]
@@ -588,7 +595,10 @@ def gmres_(x, A, b, Pl=None, abstol=0.0, reltol=None, restart=None, maxiter=None
     ``Pl`` is a callable ``v -> None`` that overwrites the host numpy vector v with Pl \\ v -- the
     two-argument in-place ``ldiv!(Pl, v)`` of src/preconditioner.jl:147-170.  x is updated in place.
     ``Pl_on_device=True``: Pl instead receives a torch CUDA tensor aliasing the Krylov vector on the device (no PCIe
-    round trip) and must work on torch's current stream."""
+    round trip) and must work on torch's current stream.
+    A ``SparsifyingPreconditioner`` is applied by the library itself on the device.  It goes with the operator of its own
+    op: ``Pl=P`` with M, ``Pl=P.T`` with M.T, ``Pl=P.H`` with M.H (block-tridiagonal objects); any other pairing raises
+    ValueError.  The same holds for bicgstabl_ and the two batch solvers."""
     vecs = _solve_vecs(x, b, A)
     opts = _gmres_opts(abstol, reltol, restart, maxiter, initially_zero, orth_meth)
     cap = _gmres_cap(maxiter, A.N)

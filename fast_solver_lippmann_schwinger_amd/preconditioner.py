@@ -19,6 +19,7 @@ inverts every Schur block with partial row pivoting (``"auto"``: only after the 
 stored blocks are the inverses themselves either way, so the applies do not change."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -177,6 +178,18 @@ class SparsifyingPreconditioner:
         L.check(L.load().lsfc_precond_blocktri_get_pivots(self._pc, int(k), out.ctypes.data_as(C.c_void_p), b))
         return out
 
+    # -- P.T / P.H: the preconditioner of M.T / M.H ----------------------------------------------------------------------
+    def transpose(self):
+        """As^T Msp^-T, which approximates inv(M.T) (block-tridiagonal objects; lsfc_precond_set_op)"""
+        return PreconditionerView(self, L.LSFC_OP_T)
+
+    def adjoint(self):
+        """conj(P.T conj(.)), which approximates inv(M.H)"""
+        return PreconditionerView(self, L.LSFC_OP_H)
+
+    T = property(transpose)
+    H = property(adjoint)
+
     # -- ldiv!(P, b) / P \\ b -- src/preconditioner.jl:132-170 ---------------------------------------------------------
     def ldiv_(self, v):
         """in place: v <- Msp^{-1} (As v).  numpy vector (copied over PCIe) or torch CUDA tensor (stays on the device,
@@ -266,3 +279,76 @@ class SparsifyingPreconditioner:
             self.close()
         except Exception:
             pass
+
+
+@contextlib.contextmanager
+def _op_of(P):
+    """The object behind P means P.T or P.H while a call through such a view runs, and P again afterwards (also when it
+    raises).  The first use of a view builds the transposed tables on the device (not inside a stream capture)."""
+    op = getattr(P, "_op", L.LSFC_OP_N)
+    if op == L.LSFC_OP_N:
+        yield
+        return
+    lib = L.load()
+    L.check(lib.lsfc_precond_set_op(P._pc, op))
+    try:
+        yield
+    finally:
+        lib.lsfc_precond_set_op(P._pc, L.LSFC_OP_N)
+
+
+class PreconditionerView:
+    """P.T or P.H: the parent preconditioner plus an op, no second object and no second copy of the inverses.  Accepted as
+    ``Pl`` of the four solvers with the operator view of the same op (M.T with P.T, M.H with P.H).  A call through a view
+    sets the op of the parent's object, calls, and restores P.  conj(P) is not offered, so P.T.H and P.H.T raise.  Only a
+    block-tridiagonal parent has views: the host-LU route has no transposed solves."""
+
+    def __init__(self, parent, op):
+        if getattr(parent, "factor", None) != "blocktri":
+            raise ValueError("P.T / P.H need a block-tridiagonal preconditioner (factor='blocktri' or from_operator): the host-LU "
+                             "route has no transposed triangular solves")
+        self.parent, self._op = parent, op
+
+    @property
+    def _pc(self):
+        return self.parent._pc
+
+    @property
+    def N(self):
+        return self.parent.N
+
+    def _other(self, op, name):
+        if op == self._op:
+            return self.parent
+        raise NotImplementedError(f"{name}: conj(P) is not offered (only P, P.T and P.H)")
+
+    def transpose(self):
+        return self._other(L.LSFC_OP_T, "P.H.T")
+
+    def adjoint(self):
+        return self._other(L.LSFC_OP_H, "P.T.H")
+
+    T = property(transpose)
+    H = property(adjoint)
+
+    def ldiv_(self, v):
+        with _op_of(self):
+            return self.parent.ldiv_(v)
+
+    def __call__(self, v):
+        self.ldiv_(v)
+
+    def solve(self, b):
+        with _op_of(self):
+            return self.parent.solve(b)
+
+    def ldiv_batch_(self, V):
+        with _op_of(self):
+            return self.parent.ldiv_batch_(V)
+
+    def solve_batch(self, B):
+        with _op_of(self):
+            return self.parent.solve_batch(B)
+
+    def set_stream(self, stream):
+        self.parent.set_stream(stream)

@@ -168,11 +168,13 @@ int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, d
  * (symmetric operators measure ~1e-16, non-symmetric ones ~1e-2 and more).
  *
  * LSFC_EINVAL, before any device call: NULL plan; op outside 0..2; a distributed, simulated-rank or multi-device plan.
- * A solve under op != N whose preconditioner is the library's own object (precond == lsfc_precond_callback) returns
- * LSFC_EINVAL: that object approximates inv(M), not its transpose.  Caller callbacks pass through unchanged.
+ * A solve whose preconditioner is the library's own object (precond == lsfc_precond_callback) is accepted if and only if
+ * the object's op (lsfc_precond_set_op below, default N) equals the plan's; otherwise it returns LSFC_EINVAL and the
+ * message names both ops.  Caller callbacks pass through unchanged.
  *
- * Out of scope: complex nu; the transposed preconditioner As^T Msp^-T; distributed and multi-device plans; non-symmetric
- * kernels (they would need the reflected symbol). */
+ * The transposed and the adjoint preconditioner As^T Msp^-T exist for block-tridiagonal objects (lsfc_precond_set_op).
+ * Out of scope: complex nu; the transposed apply of an object of lsfc_precond_create (host LU factors); right
+ * preconditioning; distributed and multi-device plans; non-symmetric kernels (they would need the reflected symbol). */
 #define LSFC_OP_N 0   /* M           (default)                         */
 #define LSFC_OP_T 1   /* transpose   I + w^2 diag(nu) G                */
 #define LSFC_OP_H 2   /* adjoint     conj(T conj(.))                   */
@@ -429,6 +431,26 @@ int lsfc_precond_blocktri_get_block(const lsfc_precond* pc, int64_t k, double* o
 /* On such an object, at either storage, lsfc_precond_apply / _apply_batch / _batch_info / _callback / _set_stream /
  * _destroy work as on any other, and lsfc_gmres_batch groups its members' applies as before; lsfc_precond_stats
  * returns nblocks, nblocks and the launch count; lsfc_precond_schedule returns LSFC_EINVAL (there are no levels). */
+
+/* The transposed and the adjoint preconditioner of a block-tridiagonal object.  P = Msp^-1 As approximates inv(M), so
+ *     P^T = As^T Msp^-T  approximates inv(M^T)      and      P^H v = conj(P^T conj(v))  approximates inv(M^H).
+ * Msp^-T is applied from the SAME stored inverses S_k^-1 (no second copy, no second factorisation) by
+ *     forward    z_k = S_k^-T (w_k - U_{k-1}^T z_{k-1})                  k = 0 .. K-1
+ *     backward   x_{K-1} = z_{K-1},  x_k = z_k - S_k^-T (L_{k+1}^T x_{k+1})   k = K-2 .. 0
+ * and As^T follows the sweeps (under N the SpMV comes first).  An apply reads the bytes the N apply reads.
+ *
+ * The op is state of the object (default LSFC_OP_N), as it is of a plan.  It is READ by lsfc_precond_apply,
+ * lsfc_precond_apply_batch, lsfc_precond_callback and by the group sweeps inside lsfc_gmres_batch and
+ * lsfc_bicgstabl_batch.  Everything else keeps describing the N object: lsfc_precond_stats, _blocktri_info, _get_block,
+ * _get_pivots, _batch_info and _inverse_precision.
+ * The first lsfc_precond_set_op(T | H) builds the CSR of Msp^T and As^T on the device (deterministic: two objects of one
+ * input apply bitwise alike); it synchronises and allocates, so it must not run inside a stream capture.  *table_bytes
+ * (may be NULL) is the size of those tables, 0 on an object that never left N; such an object allocates nothing more and
+ * launches exactly what it launched before this call existed.
+ * LSFC_EINVAL, before any device call: NULL pc; op outside 0..2; T | H on an object of lsfc_precond_create (the transposed
+ * apply needs a block-tridiagonal object; the transposed level-scheduled solves are not offered). */
+int lsfc_precond_set_op(lsfc_precond* pc, int op);     /* LSFC_OP_N (default) | LSFC_OP_T | LSFC_OP_H */
+int lsfc_precond_get_op(const lsfc_precond* pc, int* op, int64_t* table_bytes /* may be NULL */);
 
 /* ---- assembly of the sparsifying matrices (As, As*G, Msp) ------------------- */
 

@@ -292,8 +292,12 @@ function _precond_trampoline(user::Ptr{Cvoid}, v::Ptr{Float64}, n::Int64)::Cint
     ldiv!(Pl, unsafe_wrap(Array, Ptr{Complex{Float64}}(v), n))
     return Cint(0)
 end
+# on M itself a wrapper transpose(P) / P' (defined with the operator wrappers below) is a mismatch of ops
+_own_on_m(Pl) = Pl isa PrecondHIPView &&
+    throw(ArgumentError("transpose(P) and P' approximate the inverses of transpose(M) and M': pass them with the operator wrapper of the same kind"))
 function gmres_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Complex{Float64}}; Pl=nothing, restart=min(20, length(b)),
                     maxiter=length(b), reltol=sqrt(eps(Float64)), abstol=0.0, initially_zero=false)
+    _own_on_m(Pl)
     box = Ref{Any}(Pl)
     if Pl isa SparsifyingPreconditionerHIP        # applied on the device by the library itself: no PCIe, no Julia in the loop
         cb = cglobal((:lsfc_precond_callback, liblsfc)); user = Pl.pc; ondev = Cint(1)
@@ -319,6 +323,7 @@ function gmres_batch_hip!(X::Matrix{Complex{Float64}}, M::FastMHIP, B::Matrix{Co
                           maxiter=size(B, 1), reltol=sqrt(eps(Float64)), abstol=0.0, initially_zero=false)
     size(X) == size(B) || throw(DimensionMismatch("X and B"))
     nrhs = size(B, 2)
+    _own_on_m(Pl)
     box = Ref{Any}(Pl)
     if Pl isa SparsifyingPreconditionerHIP
         cb = cglobal((:lsfc_precond_callback, liblsfc)); user = Pl.pc; ondev = Cint(1)
@@ -351,6 +356,7 @@ struct BicgstablOpts
 end
 function bicgstabl_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Complex{Float64}}, l::Int=2; Pl=nothing,
                         max_mv_products=length(b), abstol=0.0, reltol=sqrt(eps(Float64)), log::Bool=true, initially_zero=false, r_shadow=nothing)
+    _own_on_m(Pl)
     box = Ref{Any}(Pl)
     if Pl isa SparsifyingPreconditionerHIP        # applied on the device by the library itself: no host code inside the BiCG part
         cb = cglobal((:lsfc_precond_callback, liblsfc)); user = Pl.pc; ondev = Cint(1)
@@ -384,6 +390,7 @@ function bicgstabl_batch_hip!(X::Matrix{Complex{Float64}}, M::FastMHIP, B::Matri
                               max_mv_products=size(B, 1), abstol=0.0, reltol=sqrt(eps(Float64)), initially_zero=false, r_shadow=nothing)
     size(X) == size(B) || throw(DimensionMismatch("X and B"))
     nrhs = size(B, 2)
+    _own_on_m(Pl)
     box = Ref{Any}(Pl)
     if Pl isa SparsifyingPreconditionerHIP
         cb = cglobal((:lsfc_precond_callback, liblsfc)); user = Pl.pc; ondev = Cint(1)
@@ -411,7 +418,8 @@ end
 # through one sets the op of the parent's plan, calls, and restores M (also when the call throws).  The library measures the
 # symmetry of G through the plan's own convolution at the first such call and refuses (rc -1) a plan whose symbol is not
 # symmetric; distributed and multi-device plans are refused too.  A SparsifyingPreconditionerHIP approximates inv(M), not its
-# transpose: the solvers refuse it with a wrapper.  conj(M) is not offered: transpose(M') and (transpose(M))' throw.
+# transpose: with an operator wrapper the solvers take transpose(P) / P' of it (below) and refuse P itself.  conj(M) is not
+# offered: transpose(M') and (transpose(M))' throw.
 const OP_N = Cint(0); const OP_T = Cint(1); const OP_H = Cint(2)
 struct TransposeFastMHIP; parent::FastMHIP; end
 struct AdjointFastMHIP; parent::FastMHIP; end
@@ -443,15 +451,58 @@ function symmetry_defect(M::FastMHIP)
     check(ccall((:lsfc_plan_symmetry_defect, liblsfc), Cint, (Ptr{Cvoid}, Ref{Float64}), M.plan, d))
     d[]
 end
-_no_own_precond(Pl) = Pl isa SparsifyingPreconditionerHIP &&
-    throw(ArgumentError("a SparsifyingPreconditionerHIP approximates inv(M), not its transpose or adjoint"))
+
+# transpose(P) and P' of a block-tridiagonal SparsifyingPreconditionerHIP -- lsfc_precond_set_op (include/lsfc.h): As^T Msp^-T from
+# the same stored inverses, which approximates inv(transpose(M)), and its conjugated form for M'.  Small wrappers, parent plus op, no
+# second object: ldiv! through one sets the op of the parent's object, applies, and restores P (also when the call throws).  The
+# library refuses (rc -1) an object of the host-LU route.  The solvers take a wrapper as Pl with the operator wrapper of the same
+# op (transpose(M) with transpose(P), M' with P') and throw otherwise.  conj(P) is not offered.
+# NOTE: like the rest of this binding the wrappers are written against include/lsfc.h and have not been executed (no Julia
+# toolchain where the library is built and tested).
+struct TransposePrecondHIP; parent::SparsifyingPreconditionerHIP; end
+struct AdjointPrecondHIP; parent::SparsifyingPreconditionerHIP; end
+const PrecondHIPView = Union{TransposePrecondHIP, AdjointPrecondHIP}
+_op(::TransposePrecondHIP) = OP_T
+_op(::AdjointPrecondHIP) = OP_H
+_op(::Any) = OP_N
+LinearAlgebra.transpose(P::SparsifyingPreconditionerHIP) = TransposePrecondHIP(P)
+LinearAlgebra.adjoint(P::SparsifyingPreconditionerHIP) = AdjointPrecondHIP(P)
+LinearAlgebra.transpose(V::TransposePrecondHIP) = V.parent
+LinearAlgebra.adjoint(V::AdjointPrecondHIP) = V.parent
+LinearAlgebra.transpose(::AdjointPrecondHIP) = error("conj(P) is not offered (only P, transpose(P) and P')")
+LinearAlgebra.adjoint(::TransposePrecondHIP) = error("conj(P) is not offered (only P, transpose(P) and P')")
+function _with_op(f, V::PrecondHIPView)
+    check(ccall((:lsfc_precond_set_op, liblsfc), Cint, (Ptr{Cvoid}, Cint), V.parent.pc, _op(V)))
+    try
+        return f(V.parent)
+    finally
+        ccall((:lsfc_precond_set_op, liblsfc), Cint, (Ptr{Cvoid}, Cint), V.parent.pc, OP_N)
+    end
+end
+LinearAlgebra.ldiv!(V::PrecondHIPView, b::Vector{Complex{Float64}}) = _with_op(P -> ldiv!(P, b), V)
+Base.:\(V::PrecondHIPView, b::Vector{Complex{Float64}}) = ldiv!(V, copy(b))
+ldiv_batch!(V::PrecondHIPView, B::Matrix{Complex{Float64}}) = _with_op(P -> ldiv_batch!(P, B), V)
+
+# a solver call on the operator wrapper V with Pl: the library's own object needs the op of V (a wrapper of the same kind) and holds it
+# for the call; anything else is a caller's ldiv! and passes through
+_own_precond(Pl) = Pl isa SparsifyingPreconditionerHIP || Pl isa PrecondHIPView
+function _solve_with_ops(f, V, Pl)
+    _own_precond(Pl) && _op(Pl) != _op(V) &&
+        throw(ArgumentError("Pl approximates the inverse of another form of M than the operator given: use transpose(P) with transpose(M), P' with M'"))
+    Pl isa PrecondHIPView || return f(Pl)
+    _with_op(P -> f(P), Pl)
+end
 function gmres_hip!(x::Vector{Complex{Float64}}, V::FastMHIPView, b::Vector{Complex{Float64}}; Pl=nothing, kw...)
-    _no_own_precond(Pl)
-    _with_op(M -> gmres_hip!(x, M, b; Pl=Pl, kw...), V)
+    _solve_with_ops(P -> _with_op(M -> gmres_hip!(x, M, b; Pl=P, kw...), V), V, Pl)
+end
+function gmres_batch_hip!(X::Matrix{Complex{Float64}}, V::FastMHIPView, B::Matrix{Complex{Float64}}; Pl=nothing, kw...)
+    _solve_with_ops(P -> _with_op(M -> gmres_batch_hip!(X, M, B; Pl=P, kw...), V), V, Pl)
 end
 function bicgstabl_hip!(x::Vector{Complex{Float64}}, V::FastMHIPView, b::Vector{Complex{Float64}}, l::Int=2; Pl=nothing, kw...)
-    _no_own_precond(Pl)
-    _with_op(M -> bicgstabl_hip!(x, M, b, l; Pl=Pl, kw...), V)
+    _solve_with_ops(P -> _with_op(M -> bicgstabl_hip!(x, M, b, l; Pl=P, kw...), V), V, Pl)
+end
+function bicgstabl_batch_hip!(X::Matrix{Complex{Float64}}, V::FastMHIPView, B::Matrix{Complex{Float64}}, l::Int=2; Pl=nothing, kw...)
+    _solve_with_ops(P -> _with_op(M -> bicgstabl_batch_hip!(X, M, B, l; Pl=P, kw...), V), V, Pl)
 end
 
 end # module
