@@ -782,6 +782,38 @@ void plan_kernel0(lsfc_plan* p) {
     plan_convolve_dev(p, e.p, p->kernel0.p, conv_plain(false, 0.0, 1.0));
     LSFC_HIP(hipStreamSynchronize(p->stream));
 }
+
+// One convolution per further corner of the grid (2^ndim - 1 of them), once per plan.  A kernel that is even along x at
+// y >= 0 only is caught by the corner that is last along both, so every corner is visited: first those last along one axis
+// (their failure names that axis), then the others (which name their lowest axis).
+void plan_require_even_kernel(lsfc_plan* p, const char* who) {
+    static const char axis_name[3] = {'x', 'y', 'z'};
+    constexpr double TOL = 1e-10;
+    if (p->even_dev < 0.0) {
+        plan_kernel0(p);
+        const int64_t N = p->N;
+        DevBuf<cplx> e, r; e.alloc((size_t)N); r.alloc((size_t)N);
+        const cplx one = make_double2(1.0, 0.0);
+        const int order[7] = {1, 2, 4, 3, 5, 6, 7};
+        double worst = 0.0; int axis = 0;
+        for (int mask : order) {
+            if (mask >> p->ndim) continue;
+            int64_t corner = 0, stride = 1;
+            for (int a = 0; a < p->ndim; ++a) { if (mask >> a & 1) corner += stride * (p->dims[a] - 1); stride *= p->dims[a]; }
+            LSFC_HIP(hipMemsetAsync(e.p, 0, (size_t)N * sizeof(cplx), p->stream));
+            LSFC_HIP(hipMemcpyAsync(e.p + corner, &one, sizeof one, hipMemcpyHostToDevice, p->stream));
+            plan_convolve_dev(p, e.p, r.p, conv_plain(false, 0.0, 1.0));
+            const double d = pw_corner_deviation(r.p, p->kernel0.p, p->dims, mask, p->stream);
+            if (d > TOL && !(worst > TOL)) { axis = 0; while (!(mask >> axis & 1)) ++axis; }     // the first corner that fails
+            worst = std::max(worst, d);
+        }
+        p->even_dev = worst; p->even_axis = axis;
+    }
+    if (p->even_dev > TOL)
+        fail(LSFC_EINVAL, "%s: the kernel of this plan is not even along axis %c (deviation %.3e of its largest entry > 1e-10): the rows of its "
+                          "Green's matrix are not K[|i - j|], which this entry gathers; the builders' kernels are even, a literal symbol "
+                          "(lsfc_plan_create_2d/3d) has to be even in every axis", who, axis_name[p->even_axis], p->even_dev);
+}
 } // namespace lsfc
 
 using namespace lsfc;
@@ -857,6 +889,7 @@ int lsfc_plan_create_gv3d(lsfc_plan** out, int64_t n, int64_t m, int64_t l, doub
             plan_finish_symbol(p.get(), G2, false);
         }
         pt.mark("tables, symbol permutation, work arrays");
+        p->even_dev = 0.0;                 // a function of kx^2 + ky^2 + kz^2 (plan_require_even_kernel)
         *out = p.release();
     });
 }
@@ -874,6 +907,7 @@ int lsfc_plan_create_gv2d(lsfc_plan** out, int64_t n, int64_t m, double box, dou
             for (int d = 0; d < 3; ++d) { p->pads[d] = lit[d]; p->crop[d] = 0; }
             plan_finish_literal(p.get(), G.p, true);
         } else plan_finish_reduce(p.get(), G, lit, true, origin);
+        p->even_dev = 0.0;                 // a function of kx^2 + ky^2 (plan_require_even_kernel)
         *out = p.release();
     });
 }
@@ -893,6 +927,9 @@ int lsfc_plan_create_trap2d(lsfc_plan** out, int64_t n, int64_t m, double x0, do
             for (int d = 0; d < 3; ++d) { p->pads[d] = lit[d]; p->crop[d] = origin[d]; }
             plan_finish_literal(p.get(), G.p, false);
         } else plan_finish_reduce(p.get(), G, lit, false, origin);
+        // samples of a function of the distance to the centre of the extended grid (src/FastConvolution.jl:433-434): even where
+        // the caller's grid is centred at the origin; any other grid is measured on first use (plan_require_even_kernel)
+        if (fabs(x0 + (n - 1) / 2.0 * h) + fabs(y0 + (m - 1) / 2.0 * h) <= 1e-12 * fabs(h)) p->even_dev = 0.0;
         *out = p.release();
     });
 }
@@ -1051,6 +1088,7 @@ int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, d
         const int64_t N = p->N;
         for (int64_t s = 0; s < nsrc; ++s) LSFC_REQUIRE(sources[s] >= 0 && sources[s] < N, "source index %lld out of range", (long long)sources[s]);
         plan_kernel0(p);
+        plan_require_even_kernel(p, "lsfc_sample_sources");
         DevBuf<int64_t> dsrc; dsrc.alloc((size_t)nsrc);
         LSFC_HIP(hipMemcpyAsync(dsrc.p, sources, (size_t)nsrc * sizeof(int64_t), hipMemcpyHostToDevice, p->stream));
         if (memspace == LSFC_MEM_DEVICE) {

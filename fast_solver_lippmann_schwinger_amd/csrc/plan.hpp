@@ -135,6 +135,10 @@ struct lsfc_plan {
     // response to a unit source at grid index 0 (the spatial kernel on [0,n)^d), built on first use by
     // lsfc_sample_sources
     lsfc::DevBuf<lsfc::cplx> kernel0;
+    // how far that kernel is from even in every axis (plan_require_even_kernel): < 0: not measured yet; the builders,
+    // whose kernels are even by construction, set 0.  even_axis: the axis the deviation was found along
+    double even_dev = -1.0;
+    int even_axis = 0;
 
     // staging for host-resident vectors
     lsfc::DevBuf<lsfc::cplx> xs, ys;
@@ -224,6 +228,10 @@ void multi_profile(lsfc_plan* root, int reps, int max_stages, const char** names
 
 // the spatial kernel: p->kernel0 = convolution of a unit source at grid index 0 (no nu), built on first use (plan.hip)
 void plan_kernel0(lsfc_plan* p);
+// The gathers K[|i - s|] of lsfc_sample_sources and sparsify.hip are rows of G only for a kernel that is even in every axis.
+// The builders' kernels are; a literal symbol (lsfc_plan_create_2d/3d) is measured once per plan: the responses to unit sources
+// at the other corners of the grid, each against kernel0 mirrored.  LSFC_EINVAL under `who` beyond 1e-10 of max |kernel0|.
+void plan_require_even_kernel(lsfc_plan* p, const char* who);
 
 // GMRES (gmres.hip)
 void gmres_run(lsfc_plan* p, cplx* x_dev, const cplx* b_dev, const lsfc_gmres_opts* opts, double* resnorm, int64_t cap,

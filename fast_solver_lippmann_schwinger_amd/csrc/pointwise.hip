@@ -248,6 +248,49 @@ __global__ void k_gather_sources(const cplx* __restrict__ K, cplx* __restrict__ 
         out[idx] = K[d0 + (int64_t)n * (d1 + (int64_t)m * d2)];
     }
 }
+// R: the response to a unit source at the corner of the grid whose coordinate is the last one along every axis in `mask`
+// (bit a = axis a) and 0 along the others.  For a kernel that is even along the axes of `mask`, R[i] = K[i mirrored along them].
+// partial[2b] = max |R[i] - K[mirror(i)]|, partial[2b+1] = max |K| over the slice of block b
+__global__ void k_corner_dev(const cplx* __restrict__ R, const cplx* __restrict__ K, double* __restrict__ partial, int n, int m, int l, int mask) {
+    __shared__ double sh[2][4];
+    const int64_t total = (int64_t)n * m * l;
+    double dmax = 0.0, amax = 0.0;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int i = (int)(idx % n); const int64_t r = idx / n; const int j = (int)(r % m); const int k = (int)(r / m);
+        const int mi = (mask & 1) ? n - 1 - i : i, mj = (mask & 2) ? m - 1 - j : j, mk = (mask & 4) ? l - 1 - k : k;
+        const cplx a = R[idx], b = K[mi + (int64_t)n * (mj + (int64_t)m * mk)];
+        // (written so that a NaN on either side survives the max: fmax alone would drop it)
+        const double d = fmax(fabs(a.x - b.x), fabs(a.y - b.y)), e = fmax(fabs(b.x), fabs(b.y));
+        dmax = (d != d || a.x != a.x || a.y != a.y) ? NAN : fmax(dmax, d);
+        amax = (b.x != b.x || b.y != b.y) ? NAN : fmax(amax, e);
+        if (dmax != dmax || amax != amax) break;
+    }
+    const bool bad = dmax != dmax || amax != amax;
+    if (bad) { dmax = INFINITY; amax = INFINITY; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { dmax = fmax(dmax, __shfl_down(dmax, off, 64)); amax = fmax(amax, __shfl_down(amax, off, 64)); }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sh[0][wave] = dmax; sh[1][wave] = amax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) { dmax = fmax(dmax, sh[0][w]); amax = fmax(amax, sh[1][w]); }
+        partial[2 * blockIdx.x] = dmax; partial[2 * blockIdx.x + 1] = amax;
+    }
+}
+double pw_corner_deviation(const cplx* R, const cplx* K, const int dims[3], int mask, hipStream_t st) {
+    const int blocks = 256;
+    DevBuf<double> part; part.alloc(2 * blocks);
+    hipLaunchKernelGGL(k_corner_dev, dim3(blocks), dim3(256), 0, st, R, K, part.p, dims[0], dims[1], dims[2], mask);
+    LSFC_HIP(hipGetLastError());
+    std::vector<double> h(2 * blocks);
+    LSFC_HIP(hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    LSFC_HIP(hipStreamSynchronize(st));
+    double d = 0, a = 0;
+    for (int b = 0; b < blocks; ++b) { d = std::max(d, h[2 * b]); a = std::max(a, h[2 * b + 1]); }
+    if (!(d < INFINITY) || !(a < INFINITY)) return 1.0;           // a kernel with NaN or Inf in it is never even
+    return a > 0 ? d / a : 0.0;
+}
+
 void pw_gather_sources(const cplx* K, cplx* out, const int64_t* src, int nsrc, const int dims[3], hipStream_t st) {
     const int64_t total = (int64_t)dims[0] * dims[1] * dims[2] * nsrc;
     hipLaunchKernelGGL(k_gather_sources, dim3(grid_for(total)), dim3(256), 0, st, K, out, src, nsrc, dims[0], dims[1], dims[2]);

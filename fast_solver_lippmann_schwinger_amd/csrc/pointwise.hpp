@@ -23,6 +23,9 @@ double pw_mirror_deviation(const cplx* G, const int L[3], int axis, hipStream_t)
 void pw_scale(cplx* a, double s, int64_t total, hipStream_t);
 
 void pw_gather_sources(const cplx* K, cplx* out, const int64_t* src, int nsrc, const int dims[3], hipStream_t);
+// max |R[i] - K[i mirrored along the axes of mask]| / max |K| on the grid `dims` (1.0 if either holds NaN or Inf): R is the
+// response to a unit source at the corner that is last along the axes of `mask` (bit a = axis a), K the one at index 0
+double pw_corner_deviation(const cplx* R, const cplx* K, const int dims[3], int mask, hipStream_t);
 
 // GMRES BLAS-1 (results land in device scalars; `partial` is scratch of blas_partial_count() entries)
 int  blas_partial_count();

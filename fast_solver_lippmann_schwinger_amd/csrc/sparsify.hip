@@ -10,7 +10,8 @@
 //   2. host: cyclic complex Jacobi of each H_c (at most 27 x 27);
 //   3. k_refine: w_c = H_c u_c and |G_S^H u_c|^2 gathered again from the rows, one first-order correction of u_c
 //      against the Jacobi basis (the Gram route squares the condition number; this step removes the squared part
-//      of the error);
+//      of the error); the same pass returns |G_S^H u|^2 for the eigenvectors of the second smallest and the
+//      largest eigenvalue: the three singular values reported are these Rayleigh quotients, summed with compensation;
 //   4. k_gss: G[S_c, S_c] in the reference's entriesSparseG* source order, host: a_c G[S_c, S_c];
 //   5. k_stamp: one thread per row writes the CSR row (closed-form rowptr, sorted columns) of As, AG and Msp.
 #include "plan.hpp"
@@ -28,7 +29,10 @@ constexpr int MAXP = MAXS * (MAXS + 1) / 2;     // upper-triangle entries of one
 constexpr int GCOLS = 64;                       // columns per LDS tile
 constexpr int GWG = 256;                        // threads per workgroup of the Gram kernels
 constexpr int GPARTS = 256;                     // workgroups per class (partials of the first reduction)
-constexpr int RSLOT = MAXS + 1;                 // refine partials per class: w[0..ns), |y|^2
+constexpr int NVEC = 3;                         // vectors per class in the refinement pass: u of the smallest, the second smallest
+                                                // and the largest eigenvalue of H_c
+constexpr int RSLOT = MAXS + NVEC;              // refine partials per class: w[0..ns), then |G_S^H u_v|^2 for v < NVEC
+static_assert(RSLOT <= 32, "k_refine: one lane of a group of 32 per slot");
 
 enum { LO = 0, IN = 1, HI = 2 };
 
@@ -230,50 +234,63 @@ __global__ __launch_bounds__(GWG) void k_gram(const cplx* __restrict__ K, const 
     if (h1) out[tid + GWG] = acc1;
 }
 
-// refinement partials: y_j = sum_s conj(u_s) G[src_s, j]; w_s = sum_j G[src_s, j] conj(y_j) (= (H u)_s), and sum_j |y_j|^2
-// part[(c * gridDim.x + g) * RSLOT + s], slot ns = |y|^2.  Thread (s = tid % 32, column group tid / 32).
+// compensated summation: a sum of n positive terms keeps a relative error of about 2 eps whatever n is
+__device__ inline void kahan_add(double& sum, double& comp, double x) {
+    const double y = x - comp, t = sum + y;
+    comp = (t - sum) - y;
+    sum = t;
+}
+
+// refinement partials, for the NVEC vectors u_v of a class (u[(v * nclass + c) * MAXS + s]): y_vj = sum_s conj(u_vs) G[src_s, j];
+// for v = 0 (the smallest eigenvalue) w_s = sum_j G[src_s, j] conj(y_0j) (= (H u_0)_s); for every v the Rayleigh quotient
+// sum_j |y_vj|^2 = |G_S^H u_v|^2, which is the squared singular value to second order in the error of u_v: the eigenvalues of
+// the Gram matrix themselves are off by eps sigma_max^2, which is eps sigma_max (sigma_max / sigma) in sigma.
+// part[(c * gridDim.x + g) * RSLOT + s], slot ns + v = |y_v|^2.  Thread (s = tid % 32, column group tid / 32).
 __global__ __launch_bounds__(GWG) void k_refine(const cplx* __restrict__ K, const DevClass* __restrict__ cls, const cplx* __restrict__ u,
                                                cplx* __restrict__ part, int n, int m, int64_t N, int64_t nchunks) {
     __shared__ cplx T[GCOLS][MAXS];
-    __shared__ cplx Y[GCOLS];
+    __shared__ cplx Y[NVEC][GCOLS];
     __shared__ cplx red[GWG / 32][RSLOT];
     __shared__ int masked[GCOLS];
     const int c = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
     const DevClass& C = cls[c];
     const int ns = C.ns, s = tid % 32, cg = tid / 32;
-    const cplx* uc = u + c * MAXS;
-    cplx accw = make_double2(0.0, 0.0), accy = make_double2(0.0, 0.0);
+    const int nclass = gridDim.y;
+    cplx accw = make_double2(0.0, 0.0);
+    double accy = 0.0, compy = 0.0;
     for (int64_t q = g; q < nchunks; q += gridDim.x) {
         gather_tile(K, C, ns, q * GCOLS, N, n, m, T, masked);
-        if (tid < GCOLS) {
+        if (tid < NVEC * GCOLS) {
+            const int v = tid / GCOLS, col = tid % GCOLS;
+            const cplx* uv = u + ((int64_t)v * nclass + c) * MAXS;
             cplx y = make_double2(0.0, 0.0);
-            for (int t = 0; t < ns; ++t) cmac_conj(y, T[tid][t], uc[t]);      // conj(u_t) T[col][t]
-            Y[tid] = y;
+            for (int t = 0; t < ns; ++t) cmac_conj(y, T[col][t], uv[t]);      // conj(u_t) T[col][t]
+            Y[v][col] = y;
         }
         __syncthreads();
         for (int col = cg; col < GCOLS; col += GWG / 32) {
-            if (s < ns) cmac_conj(accw, T[col][s], Y[col]);
-            else if (s == ns) cmac_conj(accy, Y[col], Y[col]);
+            if (s < ns) cmac_conj(accw, T[col][s], Y[0][col]);
+            else if (s < ns + NVEC) { const cplx y = Y[s - ns][col]; kahan_add(accy, compy, fma(y.x, y.x, y.y * y.y)); }
         }
         __syncthreads();
     }
     if (s < ns) red[cg][s] = accw;
-    else if (s == ns) red[cg][s] = accy;
+    else if (s < ns + NVEC) red[cg][s] = make_double2(accy, 0.0);
     __syncthreads();
-    if (tid <= ns) {
-        cplx v = make_double2(0.0, 0.0);
-        for (int k = 0; k < GWG / 32; ++k) { v.x += red[k][tid].x; v.y += red[k][tid].y; }    // fixed order
+    if (tid < ns + NVEC) {
+        cplx v = make_double2(0.0, 0.0), e = make_double2(0.0, 0.0);
+        for (int k = 0; k < GWG / 32; ++k) { kahan_add(v.x, e.x, red[k][tid].x); kahan_add(v.y, e.y, red[k][tid].y); }    // fixed order
         part[((int64_t)c * gridDim.x + g) * RSLOT + tid] = v;
     }
 }
 
-// out[c * slots + p] = sum over g (in order) of part[(c * G + g) * slots + p], for p < count[c]
+// out[c * slots + p] = sum over g (in order, compensated) of part[(c * G + g) * slots + p]
 __global__ void k_sum_parts(const cplx* __restrict__ part, cplx* __restrict__ out, int G, int slots, int nclass) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nclass * slots) return;
     const int c = idx / slots, p = idx % slots;
-    cplx v = make_double2(0.0, 0.0);
-    for (int g = 0; g < G; ++g) { const cplx w = part[((int64_t)c * G + g) * slots + p]; v.x += w.x; v.y += w.y; }
+    cplx v = make_double2(0.0, 0.0), e = make_double2(0.0, 0.0);
+    for (int g = 0; g < G; ++g) { const cplx w = part[((int64_t)c * G + g) * slots + p]; kahan_add(v.x, e.x, w.x); kahan_add(v.y, e.y, w.y); }
     out[idx] = v;
 }
 
@@ -382,6 +399,7 @@ void sparsify_build(lsfc_plan* p, int64_t* rowptr, int64_t* col, cplx* As, cplx*
     check_space(AG, memspace, "AG_val"); check_space(Msp, memspace, "Msp_val"); check_space(sigma, memspace, "sigma");
     LSFC_HIP(hipSetDevice(p->device));
     plan_kernel0(p);
+    plan_require_even_kernel(p, "sparsify");        // kat() below reads K[|i - s|]
     const int nc = g.nclass, n = (int)g.n, m = (int)g.m;
     const int64_t N = g.N, nnz = total_nnz(g);
 
@@ -423,7 +441,7 @@ void sparsify_build(lsfc_plan* p, int64_t* rowptr, int64_t* col, cplx* As, cplx*
     std::vector<std::vector<zc>> V(nc);
     std::vector<std::vector<double>> lam(nc);
     std::vector<int> order_min(nc);
-    std::vector<cplx> hu((size_t)nc * MAXS, make_double2(0.0, 0.0));
+    std::vector<cplx> hu((size_t)NVEC * nc * MAXS, make_double2(0.0, 0.0));      // [NVEC][nc][MAXS]: smallest, second smallest, largest
     for (int c = 0; c < nc; ++c) {
         const int ns = hc[c].ns;
         std::vector<zc> A((size_t)ns * ns);
@@ -435,13 +453,27 @@ void sparsify_build(lsfc_plan* p, int64_t* rowptr, int64_t* col, cplx* As, cplx*
             }
         for (int a = 0; a < ns; ++a) A[(size_t)a * ns + a] = A[(size_t)a * ns + a].real();
         jacobi_herm(ns, A, lam[c], V[c]);
-        int imin = 0;
-        for (int i = 1; i < ns; ++i) if (lam[c][i] < lam[c][imin]) imin = i;
+        // the columns of V are products of a few thousand rotations and drift from unit norm by as many roundings; the Rayleigh
+        // quotients of k_refine carry that factor squared, so it is taken out here
+        for (int b = 0; b < ns; ++b) {
+            long double t = 0.0L;
+            for (int s = 0; s < ns; ++s) { const zc e = V[c][(size_t)s * ns + b]; t += (long double)e.real() * e.real() + (long double)e.imag() * e.imag(); }
+            const double r = (double)(1.0L / sqrtl(t));
+            for (int s = 0; s < ns; ++s) V[c][(size_t)s * ns + b] *= r;
+        }
+        std::vector<int> by(ns);
+        for (int i = 0; i < ns; ++i) by[i] = i;
+        std::stable_sort(by.begin(), by.end(), [&](int x, int y) { return lam[c][x] < lam[c][y]; });
+        const int imin = by[0], pick[NVEC] = {by[0], by[1], by[ns - 1]};
         order_min[c] = imin;
-        for (int s = 0; s < ns; ++s) hu[(size_t)c * MAXS + s] = make_double2(V[c][(size_t)s * ns + imin].real(), V[c][(size_t)s * ns + imin].imag());
+        for (int v = 0; v < NVEC; ++v)
+            for (int s = 0; s < ns; ++s) {
+                const zc e = V[c][(size_t)s * ns + pick[v]];
+                hu[((size_t)v * nc + c) * MAXS + s] = make_double2(e.real(), e.imag());
+            }
     }
     // refinement pass: w = H u and |G_S^H u|^2 from the rows themselves
-    DevBuf<cplx> du; du.alloc((size_t)nc * MAXS);
+    DevBuf<cplx> du; du.alloc(hu.size());
     LSFC_HIP(hipMemcpyAsync(du.p, hu.data(), hu.size() * sizeof(cplx), hipMemcpyHostToDevice, st));
     DevBuf<cplx> part2; part2.alloc((size_t)nc * G * RSLOT);
     DevBuf<cplx> sums2; sums2.alloc((size_t)nc * RSLOT);
@@ -502,10 +534,9 @@ void sparsify_build(lsfc_plan* p, int64_t* rowptr, int64_t* col, cplx* As, cplx*
             sc.a[t] = make_double2(a[perm[t]].real(), a[perm[t]].imag());
             sc.ag[t] = make_double2(ag[perm[t]].real(), ag[perm[t]].imag());
         }
-        std::vector<double> ls(lam[c]);
-        std::sort(ls.begin(), ls.end());
-        hsig[c * 3 + 0] = std::sqrt(std::max(ls[ns - 1], 0.0));
-        hsig[c * 3 + 1] = std::sqrt(std::max(ls[1], 0.0));
+        // singular values: the Rayleigh quotients of the refinement pass (k_refine), not the eigenvalues of the Gram matrix
+        hsig[c * 3 + 0] = std::sqrt(std::max(hw[(size_t)c * RSLOT + ns + 2].x, 0.0));
+        hsig[c * 3 + 1] = std::sqrt(std::max(hw[(size_t)c * RSLOT + ns + 1].x, 0.0));
         hsig[c * 3 + 2] = std::sqrt(std::max(lmin, 0.0));
     }
 

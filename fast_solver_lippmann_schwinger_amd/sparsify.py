@@ -75,15 +75,17 @@ def _check(k, M, dims):
 
 
 def _direct_plan(k, X, Y, D0, n, m):
-    """trapezoidal plan of the grid with nu = 0: its kernel is sampleG's (src/FastConvolution.jl:497-513 with D0)"""
+    """trapezoidal plan of the grid with nu = 0: its kernel is sampleG's (src/FastConvolution.jl:497-513 with D0).
+    sampleG reads distances between grid points only, so the plan is made for the same grid centred at the origin: the
+    builder's kernel is the distance to the centre of the extended grid, which is sampleG's only there."""
     from .operators import FastM
-    X, Y = np.asarray(X, float), np.asarray(Y, float)
+    X = np.asarray(X, float)
     n, m = int(n), int(m)
     h = abs(X[1] - X[0])
     D0 = complex(D0)
     nu = np.zeros(n * m)
     plan = C.c_void_p()
-    L.check(L.load().lsfc_plan_create_trap2d(C.byref(plan), n, m, float(X[0]), float(Y[0]), float(h), float(k),
+    L.check(L.load().lsfc_plan_create_trap2d(C.byref(plan), n, m, -(n - 1) / 2.0 * h, -(m - 1) / 2.0 * h, float(h), float(k),
                                              D0.real, D0.imag, nu.ctypes.data_as(C.c_void_p), 0, 0))
     return FastM(None, nu, 2 * n - 1, 2 * m - 1, n, m, k, quadRule="trapezoidal", _plan=plan)
 

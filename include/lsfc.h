@@ -145,7 +145,15 @@ int lsfc_apply_batch(lsfc_plan* plan, const double* x, double* y, int64_t nrhs, 
  * preconditioner set-up).  Here the spatial kernel is obtained ONCE (one convolution of a unit source at index 0)
  * and every row is a gather K[|i - j|] -- the kernel is even in every axis -- so the cost per source is one
  * N-vector write.  (2D trapezoidal plans: as in the reference's FFTconvolution, nu is NOT applied to a delta row
- * by this entry; use lsfc_apply_batch for that quirk.) */
+ * by this entry; use lsfc_apply_batch for that quirk.)
+ * The gather is a row of G only for a kernel that is even along every axis on its own, K(-dx, dy, dz) = K(dx, dy, dz) and so
+ * on.  The kernels of lsfc_plan_create_gv2d / gv3d are, and that of lsfc_plan_create_trap2d on a grid centred at the origin
+ * (x0 = -(n-1) h / 2, y0 = -(m-1) h / 2); they pay nothing.  Any other plan (lsfc_plan_create_2d / 3d take any symbol) is
+ * measured at the first call of this entry or of lsfc_sparsify_build, once per plan: one convolution of a unit source at each
+ * other corner of the grid (3 in 2D, 7 in 3D), compared with the response at index 0 mirrored, as max |difference| over the
+ * largest entry of the kernel.  Above 1e-10: LSFC_EINVAL, the message names the axis and the deviation, nothing is written.
+ * This is stronger than the symmetry of G that lsfc_plan_set_op asks for: G(-k) = G(k) over all axes jointly makes G
+ * symmetric and passes there, and is refused here. */
 int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, double* out, int memspace);
 
 /* ---- the transposed and the adjoint operator ------------------------------ */
@@ -477,7 +485,12 @@ int lsfc_sparsify_pattern(int64_t n, int64_t m, int64_t l, int64_t* nnz, int64_t
  * The rows are those of the plan's kernel (lsfc_sample_sources, no nu): a 2D trapezoidal plan gives the directly
  * sampled sampleG rows of buildSparseA / buildSparseAG, Greengard-Vico plans the Conv variants.  nu and omega are the
  * plan's.  LSFC_EINVAL: NULL, distributed or multi-device plan, unsupported grid (as lsfc_sparsify_pattern, or fewer
- * than twice as many points as a stencil has sources), an array that is detectably not in `memspace`.
+ * than twice as many points as a stencil has sources), an array that is detectably not in `memspace`, a kernel that is
+ * not even along every axis (lsfc_sample_sources above: the message names axis and deviation, nothing is written;
+ * lsfc_precond_create_from_plan* pass the refusal on).  The op of the plan (lsfc_plan_set_op) is neither read nor changed.
+ * sigma: the three values are Rayleigh quotients |G_S^H u| of the eigenvectors of the class's Gram matrix, summed with
+ * compensation from the rows themselves; they agree with an SVD of the rows to a few eps sigma_max, also where
+ * sigma_min / sigma_max is 1e-5 (the eigenvalues of the Gram matrix would be off by eps sigma_max^2 / sigma there).
  * Device memory: about 0.3 MB of tables plus, for LSFC_MEM_HOST, staging for the requested arrays. */
 int lsfc_sparsify_build(lsfc_plan* plan, int64_t* rowptr, int64_t* col, double* As_val, double* AG_val,
                         double* Msp_val, double* sigma, int memspace);

@@ -159,11 +159,13 @@ buildSparseAG3DConv(k, X, Y, Z, M::FastMHIP, n, m, l) = (_check_k(k, M); _sparsi
 # Msp and As of one device call, for SparsifyingPreconditioner(Msp, As) / SparsifyingPreconditionerHIP(Msp, As)
 sparsifying_pair(M::FastMHIP) = (_sparsify(M, :Msp), _sparsify(M, :As))
 # the direct-sampling builders (sampleG rows with the caller's D0): a trapezoidal plan with nu = 0 on the grid
+# (sampleG reads distances only: the plan is made for the same grid centred at the origin, where the builder's kernel is even)
 function _direct_plan(k, X, Y, D0, n, m)
     plan = Ref{Ptr{Cvoid}}(C_NULL); nuv = zeros(n * m)
+    h = abs(X[2] - X[1])
     check(ccall((:lsfc_plan_create_trap2d, liblsfc), Cint,
                 (Ref{Ptr{Cvoid}}, Int64, Int64, Float64, Float64, Float64, Float64, Float64, Float64, Ptr{Float64}, Cuint, Cint),
-                plan, n, m, X[1], Y[1], abs(X[2] - X[1]), k, real(D0), imag(D0), nuv, 0, 0))
+                plan, n, m, -(n - 1) / 2 * h, -(m - 1) / 2 * h, h, k, real(D0), imag(D0), nuv, 0, 0))
     FastMHIP(plan[], nuv, n, m, 1, k, "trapezoidal")
 end
 buildSparseA(k, X, Y, D0, n, m) = _sparsify(_direct_plan(k, X, Y, D0, n, m), :As)

@@ -42,17 +42,49 @@ def conv_rows(fastconv):
 def gv3d_rows(n, m, l, box, k):
     """sampleG3D of the 3D Greengard-Vico plan: reduced_symbol_gv3d + convolve_reduced on unit sources (covers odd and
     non-cube shapes, as lsfc_plan_create_gv3d does)."""
-    G2 = o.reduced_symbol_gv3d(n, m, l, box, k)
-    N = n * m * l
+    return literal_rows(o.reduced_symbol_gv3d(n, m, l, box, k), (n, m, l))
+
+
+def literal_rows(G2, dims):
+    """rows of an arbitrary reduced symbol G2 (plain FFT order, at least 2 n points per axis) on the grid `dims` (2D or
+    3D): o.convolve_reduced on unit sources, one FFT convolution per row.  Nothing here assumes a symmetry of G2."""
+    dims = tuple(int(v) for v in dims)
+    N = int(np.prod(dims))
 
     def rows(idx):
         out = np.empty((len(idx), N), dtype=np.complex128)
         for i, ii in enumerate(idx):
             e = np.zeros(N, dtype=np.complex128)
             e[ii] = 1.0
-            out[i] = o.convolve_reduced(G2, e, (n, m, l))
+            out[i] = o.convolve_reduced(G2, e, dims)
         return out
     return rows
+
+
+# ---- the device algorithm, restated ---------------------------------------------------------------------------------
+def gram_refine(Gs):
+    """csrc/sparsify.hip in numpy double, for one class: H = Gs Gs^H, its eigenpairs (eigh in place of the cyclic Jacobi),
+    the smallest pair (lam, u); from the rows themselves w = Gs (Gs^H u) and lam' = |Gs^H u|^2; one first-order correction
+    of u against the other eigenvectors, u + sum_b v_b (v_b^H w) / (lam' - lam_b).  Returns (corrected, uncorrected), both
+    of unit norm: approximations of the left singular vector of Gs for its smallest singular value."""
+    H = Gs @ Gs.conj().T
+    lam, V = np.linalg.eigh(H)
+    u0 = V[:, 0]
+    y = Gs.conj().T @ u0
+    w = Gs @ y
+    lmin = np.vdot(y, y).real
+    u = u0.copy()
+    for b in range(1, len(lam)):
+        den = lmin - lam[b]
+        if den != 0.0:
+            u = u + V[:, b] * (np.vdot(V[:, b], w) / den)
+    return u / np.linalg.norm(u), u0
+
+
+def phase_distance(v, u):
+    """2-norm distance of the unit vectors v and u after the unit factor that brings v closest to u"""
+    s = np.vdot(v, u)
+    return float(np.linalg.norm(v * (s / abs(s)) - u))
 
 
 # ---- class tables -------------------------------------------------------------------------------------------------
@@ -140,21 +172,29 @@ def create_indices(row, col, val):
     return Row, Col, Val
 
 
-def build(rows, n, m, l=1, nu=None, k=None):
+def build(rows, n, m, l=1, nu=None, k=None, per_class=None):
     """As, AG (and Msp = As + k^2 AG diag(nu) when nu is given) as CSC, per-class a_c, ag_c, sigma[nclass, 3]
-    (max, second smallest, min) and row_class[N]."""
+    (max, second smallest, min), row_class[N] and cancel[nclass] = |G[S,S]|_2 / |a_c G[S,S]|, the factor by which an error of
+    a_c can grow in the AG row.  per_class(c, R, Gs, U, s), if given, sees every class's rows
+    R = G[S_c, :], Gs = G[S_c, complement of S_c] and its SVD before they are dropped."""
     N = n * m * l
     cls = classes(n, m, l)
     ra, ca, va, vg = [], [], [], []
     row_class = np.full(N, -1, dtype=np.int64)
-    sig, avals, agvals = [], [], []
+    sig, avals, agvals, cancel = [], [], [], []
     for c, (sA, ind, sG, rws) in enumerate(cls):
         sA0 = np.asarray(sA) - 1
         comp = np.setdiff1d(np.arange(N), sA0)
-        U, s, _ = np.linalg.svd(rows(sA0)[:, comp], full_matrices=False)
+        R = rows(sA0)
+        Gs = R[:, comp]
+        U, s, _ = np.linalg.svd(Gs, full_matrices=False)
+        if per_class is not None:
+            per_class(c, R, Gs, U, s)
         a = U[:, -1].conj()                                         # U[:, end]'
         sG0 = np.asarray(sG) - 1
-        ag = a @ rows(sG0)[:, sG0]                                  # Values[c] * Entries[c]
+        Gss = rows(sG0)[:, sG0]
+        ag = a @ Gss                                                # Values[c] * Entries[c]
+        cancel.append(np.linalg.norm(Gss, 2) / np.linalg.norm(ag))  # |a| = 1
         sig.append((s[0], s[-2], s[-1]))
         avals.append(a)
         agvals.append(ag)
@@ -166,7 +206,8 @@ def build(rows, n, m, l=1, nu=None, k=None):
     Cc = np.concatenate(ca) - 1
     As = sp.coo_matrix((np.concatenate(va), (R, Cc)), shape=(N, N)).tocsc()
     AG = sp.coo_matrix((np.concatenate(vg), (R, Cc)), shape=(N, N)).tocsc()
-    out = dict(As=As, AG=AG, a=avals, ag=agvals, sigma=np.array(sig), row_class=row_class, classes=cls)
+    out = dict(As=As, AG=AG, a=avals, ag=agvals, sigma=np.array(sig), row_class=row_class, classes=cls,
+               cancel=np.array(cancel))
     if nu is not None:
         out["Msp"] = (As + k ** 2 * (AG @ sp.diags(np.asarray(nu, float)))).tocsc()
     return out
