@@ -21,7 +21,7 @@
 // solve alone.  The host reads all scalar blocks in one copy per cycle and drops the members that have stopped from
 // the list of the next cycle.  lsfc_bicgstabl is the call with one member.
 #include "plan.hpp"
-#include "pointwise.hpp"
+#include "krylov_blas.hpp"
 #include "reduce.hpp"
 #include <algorithm>
 #include <cmath>
@@ -32,7 +32,6 @@ namespace lsfc {
 namespace {
 
 constexpr int LMAX = 8, NVMAX = LMAX + 1;
-constexpr int NRHS_MAX = 64;                   // the bound of gmres_run_batch
 // device scalars (cplx each)
 enum { S_RHO = 0, S_SIGMA = 1, S_BETA = 2, S_ALPHA = 3, S_STATUS = 4 /* (code, cycle) */, S_RES = 5, S_GAMMA = 6 /* LMAX */,
        S_G = 16 /* NVMAX * NVMAX, row-major */, S_COUNT = 16 + NVMAX * NVMAX };
@@ -51,13 +50,6 @@ __device__ __forceinline__ cplx cdiv(cplx a, cplx b) {
     const double d = fma(b.x, b.x, b.y * b.y);
     return make_double2(fma(a.x, b.x, a.y * b.y) / d, fma(a.y, b.x, -a.x * b.y) / d);
 }
-// a - c * b
-__device__ __forceinline__ cplx csubmul(cplx a, cplx c, cplx b) {
-    return make_double2(a.x - fma(c.x, b.x, -c.y * b.y), a.y - fma(c.x, b.y, c.y * b.x));
-}
-__device__ __forceinline__ cplx caddmul(cplx a, cplx c, cplx b) {
-    return make_double2(a.x + fma(c.x, b.x, -c.y * b.y), a.y + fma(c.x, b.y, c.y * b.x));
-}
 
 // The members of one launch and where their data lives; by value in every kernel of the solve, member = m[blockIdx.y].
 // Member m: work vectors work + m wstride (rs[0..l], us[0..l], the shadow residual, n apart), x + m n,
@@ -65,38 +57,25 @@ __device__ __forceinline__ cplx caddmul(cplx a, cplx c, cplx b) {
 struct Members {
     cplx* work; cplx* x; cplx* scal; cplx* partial; const double* tol2;
     int64_t wstride, n;
-    int m[NRHS_MAX];
+    int m[KRYLOV_NRHS_MAX];
 };
 __device__ __forceinline__ cplx* m_work(const Members& B, int m) { return B.work + (int64_t)m * B.wstride; }
 __device__ __forceinline__ cplx* m_scal(const Members& B, int m) { return B.scal + (int64_t)m * S_COUNT; }
 __device__ __forceinline__ cplx* m_partial(const Members& B, int m) { return B.partial + (int64_t)m * (P_SLOTS * RED_BLOCKS); }
 
-// rs[0] = b - rs[0]  (initial residual from rs[0] = A x)
+// rs[0] = b - rs[0], in place  (initial residual from rs[0] = A x)
 __global__ void k_residual(Members B, const cplx* __restrict__ ball) {
     const int m = B.m[blockIdx.y];
-    const int64_t n = B.n;
-    cplx* __restrict__ y = m_work(B, m);
-    const cplx* __restrict__ b = ball + (int64_t)m * n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const cplx u = b[i], v = y[i]; y[i] = make_double2(u.x - v.x, u.y - v.y);
-    }
+    cplx* y = m_work(B, m);
+    sub_slice(y, ball + (int64_t)m * B.n, y, B.n);
 }
 
-// partial slot `slot`: slices of sum_i conj(a[i]) b[i], a and b the work vectors at offsets aoff and boff (the kernel
-// of blas_dot_partial with a member dimension: the same slices, the same order)
+// partial slot `slot`: slices of sum_i conj(a[i]) b[i], a and b the work vectors at offsets aoff and boff (dot_slice, as
+// blas_dot_partial, with a member dimension: the same slices, the same order)
 __global__ __launch_bounds__(RED_THREADS) void k_dot(Members B, int64_t aoff, int64_t boff, int slot) {
     __shared__ cplx sh[RED_THREADS / 64];
     const int m = B.m[blockIdx.y];
-    const int64_t n = B.n;
-    const cplx* __restrict__ a = m_work(B, m) + aoff;
-    const cplx* __restrict__ b = m_work(B, m) + boff;
-    cplx acc = make_double2(0.0, 0.0);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const cplx u = a[i], v = b[i];
-        acc.x = fma(u.x, v.x, fma(u.y, v.y, acc.x));
-        acc.y = fma(u.x, v.y, fma(-u.y, v.x, acc.y));
-    }
-    const cplx r = block_sum(acc, sh);
+    const cplx r = dot_slice(m_work(B, m) + aoff, m_work(B, m) + boff, B.n, sh);
     if (threadIdx.x == 0) m_partial(B, m)[(int64_t)slot * RED_BLOCKS + blockIdx.x] = r;
 }
 
@@ -204,13 +183,10 @@ __global__ __launch_bounds__(RED_THREADS) void k_gram(Members B) {
         int e = 0;
 #pragma unroll
         for (int a = 0; a < NV; ++a) {
-            acc[e].x = fma(v[a].x, v[a].x, fma(v[a].y, v[a].y, acc[e].x));      // the diagonal is real
+            cnorm_acc(acc[e], v[a]);                                            // the diagonal is real
             ++e;
 #pragma unroll
-            for (int b = a + 1; b < NV; ++b, ++e) {
-                acc[e].x = fma(v[a].x, v[b].x, fma(v[a].y, v[b].y, acc[e].x));
-                acc[e].y = fma(v[a].x, v[b].y, fma(-v[a].y, v[b].x, acc[e].y));
-            }
+            for (int b = a + 1; b < NV; ++b, ++e) cdot_acc(acc[e], v[a], v[b]);
         }
     }
 #pragma unroll
@@ -300,7 +276,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_mr_update(Members B, int64_t uo
             r0 = csubmul(r0, g[k], r[k + 1]);
         }
         us[i] = u0; x[i] = xv; rs[i] = r0;
-        nrm.x = fma(r0.x, r0.x, fma(r0.y, r0.y, nrm.x));
+        cnorm_acc(nrm, r0);
     }
     const cplx s = block_sum(nrm, sh);
     if (threadIdx.x == 0) m_partial(B, m)[(int64_t)P_NORM * RED_BLOCKS + blockIdx.x] = s;
@@ -312,11 +288,6 @@ __global__ __launch_bounds__(64) void k_res_finish(Members B, int nb) {
     cplx* scal = m_scal(B, m);
     const cplx s = finish_in_wave(m_partial(B, m) + (int64_t)P_NORM * RED_BLOCKS, nb);
     if (threadIdx.x == 0 && scal[S_STATUS].x == 0.0) scal[S_RES] = make_double2(sqrt(s.x), 0.0);
-}
-
-inline unsigned ew_grid(int64_t n) {
-    const int64_t g = (n + 255) / 256;
-    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
 struct Pinned {
@@ -401,7 +372,7 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
         for (int m = 0; m < nrhs; ++m) LSFC_HIP(hipMemcpyAsync(R(m, 0), b + (size_t)m * N, (size_t)N * sizeof(cplx), hipMemcpyDeviceToDevice, st));
     } else {
         apply(act, [&](int m) { return (const cplx*)(x + (size_t)m * N); }, [&](int m) { return R(m, 0); });
-        hipLaunchKernelGGL(k_residual, dim3(ew_grid(N), (unsigned)nrhs), dim3(256), 0, st, members(act), b);
+        hipLaunchKernelGGL(k_residual, dim3(grid_for(N), (unsigned)nrhs), dim3(256), 0, st, members(act), b);
         for (auto& s : S) s.mvps = 1;
     }
     precondition(act, [&](int m) { return R(m, 0); });
@@ -537,7 +508,7 @@ extern "C" int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const
 
 extern "C" int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts, double* resnorm,
                                     int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* status, int memspace) {
-    int64_t code[2 * NRHS_MAX] = { 0 };
+    int64_t code[2 * KRYLOV_NRHS_MAX] = { 0 };
     const int rc = guarded([&] {
         bicgstabl_entry("lsfc_bicgstabl_batch", true, plan, x, b, nrhs, opts, resnorm, resnorm_cap, results, code, memspace);
         if (status) for (int64_t i = 0; i < 2 * nrhs; ++i) status[i] = code[i];
@@ -556,7 +527,7 @@ extern "C" int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b,
 
 static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
                             double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* code, int memspace) {
-    if (batch) LSFC_REQUIRE(nrhs >= 1 && nrhs <= NRHS_MAX, "%s: nrhs = %lld is outside 1..%d", fn, (long long)nrhs, NRHS_MAX);
+    if (batch) LSFC_REQUIRE(nrhs >= 1 && nrhs <= KRYLOV_NRHS_MAX, "%s: nrhs = %lld is outside 1..%d", fn, (long long)nrhs, KRYLOV_NRHS_MAX);
     check_args(fn, plan, x, b, opts, resnorm, resnorm_cap, results, memspace);
     const int l = opts->l, n = (int)nrhs;
     const int64_t N = plan->N;
@@ -584,7 +555,7 @@ static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double*
     const cplx* xd = (const cplx*)x; const cplx* bd = (const cplx*)b;
     const size_t bytes = (size_t)n * (size_t)N * sizeof(cplx);
     if (host) {
-        if (stage) { plan->xs.alloc((size_t)n * (size_t)N); plan->ys.alloc((size_t)n * (size_t)N); }
+        if (stage) { plan->xs.alloc((size_t)n * (size_t)N); plan->ys.alloc((size_t)n * (size_t)N); }     // (plan_ensure_staging, with the `stage` the memory rule counted)
         LSFC_HIP(hipMemcpy(plan->xs.p, x, bytes, hipMemcpyHostToDevice));
         LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
         xd = plan->xs.p; bd = plan->ys.p;

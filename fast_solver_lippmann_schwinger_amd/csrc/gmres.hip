@@ -5,7 +5,7 @@
 // Givens least squares at restart or convergence.  The Krylov basis stays in HBM;
 // only O(restart) scalars per step cross to the host.
 #include "plan.hpp"
-#include "pointwise.hpp"
+#include "krylov_blas.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <complex>
@@ -181,10 +181,10 @@ struct Solve {
     Solve(Team& team, const Resolved& rr, double* resnorm_, int64_t cap_, lsfc_gmres_result* res_, bool batch)
         : T(team), r(rr), o(rr.o), resnorm(resnorm_), cap(cap_), res(res_), restart(rr.restart), ldh(rr.restart + 1), Ntot(T.root->N),
           H((size_t)(rr.restart + 1) * rr.restart, zc(0)), nullvec((size_t)rr.restart + 1, zc(1)), mvps(rr.o.initially_zero ? 1 : 0) {
-        // one device, no all-reduce between a reduction and its consumer: the fused kernels (pointwise.hip) sum block partials
+        // one device, no all-reduce between a reduction and its consumer: the fused kernels (krylov_blas.hip) sum block partials
         // inside the consuming kernel -- same summation order, bit-identical scalars, roughly half the launches
         fused = !T.reduce && T.mem.size() == 1;
-        // modified Gram-Schmidt in blocks (pointwise.hip: k_mgs_block) where the sweep is bound by HBM traffic: vectors of >= 2^22
+        // modified Gram-Schmidt in blocks (krylov_blas.hip: k_mgs_block) where the sweep is bound by HBM traffic: vectors of >= 2^22
         // entries (LSFC_MGS_BLOCK=0 / 1 forces the strict one-vector-at-a-time sweep / the blocked one)
         const char* mb_env = getenv("LSFC_MGS_BLOCK");
         mgs_blocked = mb_env ? atoi(mb_env) != 0 : Ntot >= ((int64_t)1 << 22);
@@ -512,7 +512,7 @@ void gmres_run_multi(lsfc_plan* root, cplx* x_host, const cplx* b_host, const ls
         lsfc_plan* p = sp.get();
         LSFC_HIP(hipSetDevice(p->device));
         GmresWorkspace* w = workspace(p, r.restart, false);
-        if (p->xs.n < (size_t)p->N) { p->xs.alloc((size_t)p->N); p->ys.alloc((size_t)p->N); }
+        plan_ensure_staging(p, p->N);
         LSFC_HIP(hipMemcpyAsync(p->xs.p, x_host + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
         LSFC_HIP(hipMemcpyAsync(p->ys.p, b_host + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
         T.mem.push_back({p, w, p->xs.p, p->ys.p});
@@ -530,3 +530,52 @@ void gmres_run_multi(lsfc_plan* root, cplx* x_host, const cplx* b_host, const ls
 }
 
 } // namespace lsfc
+
+using namespace lsfc;
+
+extern "C" int lsfc_gmres(lsfc_plan* plan, double* x, const double* b, const lsfc_gmres_opts* opts, double* resnorm, int64_t resnorm_cap,
+                          lsfc_gmres_result* result, int memspace) {
+    int conv_code = LSFC_OK;
+    int rc = guarded([&] {
+        LSFC_REQUIRE(plan && x && b, "NULL argument");
+        LSFC_HIP(hipSetDevice(plan->device));
+        lsfc_gmres_result local; lsfc_gmres_result* res = result ? result : &local;
+        if (plan->multi) {
+            LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "a multi-device plan takes host vectors");
+            gmres_run_multi(plan, (cplx*)x, (const cplx*)b, opts, resnorm, resnorm_cap, res);
+        } else if (memspace == LSFC_MEM_DEVICE) {
+            gmres_run(plan, (cplx*)x, (const cplx*)b, opts, resnorm, resnorm_cap, res);
+        } else {
+            LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "unknown memspace %d", memspace);
+            plan_ensure_staging(plan, plan->N);
+            LSFC_HIP(hipMemcpy(plan->xs.p, x, plan->N * sizeof(cplx), hipMemcpyHostToDevice));
+            LSFC_HIP(hipMemcpy(plan->ys.p, b, plan->N * sizeof(cplx), hipMemcpyHostToDevice));
+            gmres_run(plan, plan->xs.p, plan->ys.p, opts, resnorm, resnorm_cap, res);
+            LSFC_HIP(hipMemcpy(x, plan->xs.p, plan->N * sizeof(cplx), hipMemcpyDeviceToHost));
+        }
+        if (!res->converged) conv_code = LSFC_ENOTCONV;
+    });
+    if (rc == LSFC_OK && conv_code != LSFC_OK) { set_last_error("gmres: maxiter reached without convergence"); return conv_code; }
+    return rc;
+}
+
+extern "C" int lsfc_gmres_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_gmres_opts* opts, double* resnorm,
+                                int64_t resnorm_cap, lsfc_gmres_result* results, int memspace) {
+    return guarded([&] {
+        LSFC_REQUIRE(plan && x && b && results, "NULL argument");
+        LSFC_REQUIRE(nrhs >= 1 && nrhs <= KRYLOV_NRHS_MAX, "nrhs must be in 1..%d", KRYLOV_NRHS_MAX);
+        LSFC_REQUIRE(!plan->multi && !plan->dist, "batched GMRES runs on a single-device plan");
+        LSFC_HIP(hipSetDevice(plan->device));
+        if (memspace == LSFC_MEM_DEVICE) {
+            gmres_run_batch(plan, (cplx*)x, (const cplx*)b, (int)nrhs, opts, resnorm, resnorm_cap, results);
+        } else {
+            LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "unknown memspace %d", memspace);
+            const size_t bytes = (size_t)nrhs * plan->N * sizeof(cplx);
+            DevBuf<cplx> xd, bd; xd.alloc((size_t)nrhs * plan->N); bd.alloc((size_t)nrhs * plan->N);
+            LSFC_HIP(hipMemcpy(xd.p, x, bytes, hipMemcpyHostToDevice));
+            LSFC_HIP(hipMemcpy(bd.p, b, bytes, hipMemcpyHostToDevice));
+            gmres_run_batch(plan, xd.p, bd.p, (int)nrhs, opts, resnorm, resnorm_cap, results);
+            LSFC_HIP(hipMemcpy(x, xd.p, bytes, hipMemcpyDeviceToHost));
+        }
+    });
+}

@@ -1,6 +1,7 @@
 // lsfc C ABI: plan construction, the operator apply, timing helpers (gfx950).
 #include "plan.hpp"
 #include "pointwise.hpp"
+#include "krylov_blas.hpp"
 #include "blocktri.hpp"
 #include <cmath>
 #include <cstring>
@@ -583,7 +584,7 @@ void Precond::apply(cplx* const* v, size_t cnt, cplx* pinned, hipStream_t st) co
     }
 }
 
-static void ensure_staging(lsfc_plan* p, int64_t count) {
+void plan_ensure_staging(lsfc_plan* p, int64_t count) {
     if (p->xs.n < (size_t)count) { p->xs.alloc((size_t)count); p->ys.alloc((size_t)count); }
 }
 
@@ -635,7 +636,7 @@ static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_
         LSFC_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming)); hp->ev_down.push_back(b);
     }
     const int slots = nrhs > 1 ? 2 : 1;
-    if (p->xs.n < (size_t)(slots * p->N)) { LSFC_HIP(hipStreamSynchronize(p->stream)); p->xs.alloc((size_t)(slots * p->N)); p->ys.alloc((size_t)(slots * p->N)); }
+    if (p->xs.n < (size_t)(slots * p->N)) { LSFC_HIP(hipStreamSynchronize(p->stream)); plan_ensure_staging(p, slots * p->N); }
     hipStream_t st = p->stream;
     const int lz = p->dims[2] / K;
     const int64_t chunk = (int64_t)p->dims[0] * p->dims[1] * lz;
@@ -746,7 +747,7 @@ static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs,
     const int group = (int)std::min<int64_t>(LSFC_MAX_BATCH, nrhs);
     // large 3D vectors: the chunked pipeline above (two staging slots, allocated there)
     const int K = host_pipeline_chunks(p);
-    if (K <= 1) ensure_staging(p, p->N * group);
+    if (K <= 1) plan_ensure_staging(p, p->N * group);
     if (K > 1) {
         // (y aliasing x: right-hand side j + 1 is uploaded while j is downloaded into the same memory -- distinct vectors, no hazard)
         host_pipelined_convolve(p, (const cplx*)x, (cplx*)y, nrhs, op, K);
@@ -1104,53 +1105,6 @@ int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, d
                 LSFC_HIP(hipMemcpyAsync((cplx*)out + s0 * N, buf.p, (size_t)(cnt * N) * sizeof(cplx), hipMemcpyDeviceToHost, p->stream));
                 LSFC_HIP(hipStreamSynchronize(p->stream));
             }
-        }
-    });
-}
-
-int lsfc_gmres(lsfc_plan* plan, double* x, const double* b, const lsfc_gmres_opts* opts, double* resnorm, int64_t resnorm_cap,
-               lsfc_gmres_result* result, int memspace) {
-    int conv_code = LSFC_OK;
-    int rc = guarded([&] {
-        LSFC_REQUIRE(plan && x && b, "NULL argument");
-        LSFC_HIP(hipSetDevice(plan->device));
-        lsfc_gmres_result local; lsfc_gmres_result* res = result ? result : &local;
-        if (plan->multi) {
-            LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "a multi-device plan takes host vectors");
-            gmres_run_multi(plan, (cplx*)x, (const cplx*)b, opts, resnorm, resnorm_cap, res);
-        } else if (memspace == LSFC_MEM_DEVICE) {
-            gmres_run(plan, (cplx*)x, (const cplx*)b, opts, resnorm, resnorm_cap, res);
-        } else {
-            LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "unknown memspace %d", memspace);
-            ensure_staging(plan, plan->N);
-            LSFC_HIP(hipMemcpy(plan->xs.p, x, plan->N * sizeof(cplx), hipMemcpyHostToDevice));
-            LSFC_HIP(hipMemcpy(plan->ys.p, b, plan->N * sizeof(cplx), hipMemcpyHostToDevice));
-            gmres_run(plan, plan->xs.p, plan->ys.p, opts, resnorm, resnorm_cap, res);
-            LSFC_HIP(hipMemcpy(x, plan->xs.p, plan->N * sizeof(cplx), hipMemcpyDeviceToHost));
-        }
-        if (!res->converged) conv_code = LSFC_ENOTCONV;
-    });
-    if (rc == LSFC_OK && conv_code != LSFC_OK) { set_last_error("gmres: maxiter reached without convergence"); return conv_code; }
-    return rc;
-}
-
-int lsfc_gmres_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_gmres_opts* opts, double* resnorm,
-                     int64_t resnorm_cap, lsfc_gmres_result* results, int memspace) {
-    return guarded([&] {
-        LSFC_REQUIRE(plan && x && b && results, "NULL argument");
-        LSFC_REQUIRE(nrhs >= 1 && nrhs <= 64, "nrhs must be in 1..64");
-        LSFC_REQUIRE(!plan->multi && !plan->dist, "batched GMRES runs on a single-device plan");
-        LSFC_HIP(hipSetDevice(plan->device));
-        if (memspace == LSFC_MEM_DEVICE) {
-            gmres_run_batch(plan, (cplx*)x, (const cplx*)b, (int)nrhs, opts, resnorm, resnorm_cap, results);
-        } else {
-            LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "unknown memspace %d", memspace);
-            const size_t bytes = (size_t)nrhs * plan->N * sizeof(cplx);
-            DevBuf<cplx> xd, bd; xd.alloc((size_t)nrhs * plan->N); bd.alloc((size_t)nrhs * plan->N);
-            LSFC_HIP(hipMemcpy(xd.p, x, bytes, hipMemcpyHostToDevice));
-            LSFC_HIP(hipMemcpy(bd.p, b, bytes, hipMemcpyHostToDevice));
-            gmres_run_batch(plan, xd.p, bd.p, (int)nrhs, opts, resnorm, resnorm_cap, results);
-            LSFC_HIP(hipMemcpy(x, xd.p, bytes, hipMemcpyDeviceToHost));
         }
     });
 }

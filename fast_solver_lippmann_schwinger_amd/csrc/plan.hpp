@@ -180,6 +180,9 @@ void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out,
 // object on the device, where the members of a batch meet (`meet`): apply() hands it all cnt vectors for its group sweeps; any other
 // callback gets them one by one, in order, a host callback through `pinned`.  The size of an own object is checked here, under `who`.
 constexpr double DEFAULT_RELTOL = 0x1p-26;      // sqrt(eps)
+constexpr int KRYLOV_NRHS_MAX = 64;             // right-hand sides of one lsfc_gmres_batch / lsfc_bicgstabl_batch call
+// grows the plan's staging buffers xs and ys to `count` complex each (host vectors on their way to and from the device)
+void plan_ensure_staging(lsfc_plan* p, int64_t count);
 // The library's own preconditioner object (fn == lsfc_precond_callback) approximates the inverse of M, M^T or M^H as its own
 // op says (lsfc_precond_set_op): refused unless that is the plan's op.  A caller's callback passes.
 void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, void* precond_user, const char* who);
@@ -236,7 +239,7 @@ void plan_require_even_kernel(lsfc_plan* p, const char* who);
 // GMRES (gmres.hip)
 void gmres_run(lsfc_plan* p, cplx* x_dev, const cplx* b_dev, const lsfc_gmres_opts* opts, double* resnorm, int64_t cap,
                lsfc_gmres_result* res);
-// nrhs independent solves in lock step on the calling thread (device vectors back to back, nrhs <= 64): every Arnoldi step
+// nrhs independent solves in lock step on the calling thread (device vectors back to back, nrhs <= KRYLOV_NRHS_MAX): every Arnoldi step
 // applies the operator to all unconverged right-hand sides in one batch; the workspaces live for the call
 void gmres_run_batch(lsfc_plan* p, cplx* x_dev, const cplx* b_dev, int nrhs, const lsfc_gmres_opts* opts, double* resnorm, int64_t cap,
                      lsfc_gmres_result* res);

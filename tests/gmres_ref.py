@@ -1,4 +1,4 @@
-"""Test infrastructure for the device GMRES (csrc/gmres.hip, BLAS-1 kernels in csrc/pointwise.hip): a long-double
+"""Test infrastructure for the device GMRES (csrc/gmres.hip, BLAS-1 kernels in csrc/krylov_blas.hip): a long-double
 restatement of its solve() over a diagonal operator, and the problems that drive its code paths.
 
     gmres_ref(b, a, pl, counts, restart, maxiter, reltol, abstol, orth, x0, initially_zero, dtype)

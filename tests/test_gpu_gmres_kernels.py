@@ -1,4 +1,4 @@
-"""GPU tests of the device GMRES kernels (csrc/gmres.hip, csrc/pointwise.hip) against the long-double restatement of
+"""GPU tests of the device GMRES kernels (csrc/gmres.hip, csrc/krylov_blas.hip) against the long-double restatement of
 tests/gmres_ref.py, at the vector lengths, restart lengths and path switches where a Krylov kernel goes wrong.
 
 The operator: a plan with a finite symbol and nu == 0, so that M * x == x bitwise, and the left preconditioner
