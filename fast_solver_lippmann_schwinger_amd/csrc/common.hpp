@@ -65,6 +65,9 @@ template <int LO, int HI, class F> void dispatch(int v, const char* who, F&& f) 
     else dispatch<LO + 1, HI>(v, who, f);
 }
 
+// environment switches (developer knobs): the first character of the value, -1 when not set
+inline int env_switch(const char* name) { const char* e = getenv(name); return e ? (unsigned char)e[0] : -1; }
+
 inline bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
 // RAII device buffer

@@ -11,6 +11,7 @@
 // No pack/unpack/transposition kernel runs: the chunked addressing of the x passes does the packing,
 // and the exchange moves 2N complex per transpose, the minimum-volume point of the pipeline.
 #include "plan.hpp"
+#include "apply.hpp"
 #include "pointwise.hpp"
 #include "dist_schedule.hpp"
 #include <rccl/rccl.h>
@@ -100,7 +101,9 @@ static void exchange(lsfc_plan* p, int c, bool back, hipStream_t st, int part = 
     LSFC_NCCL(ncclGroupEnd());
 }
 
-void dist_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double alpha, double beta) {
+void dist_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op) {
+    LSFC_REQUIRE(conv_forward_only(op), "the transposed and the adjoint operator are not available on a distributed plan");
+    const bool use_nu = op.nu == NuSide::INPUT; const double alpha = op.alpha, beta = op.beta;
     DistState* d = p->dist.get();
     LSFC_REQUIRE(!d->sim, "simulated ranks are driven through lsfc_dist_sim_apply");
     LSFC_REQUIRE(!d->member, "the ranks of a multi-device plan are driven through their parent plan");
@@ -378,7 +381,9 @@ void multi_synchronize(lsfc_plan* root) {
     for (int r = 0; r < M.P; ++r) { M.dev(r); LSFC_HIP(hipDeviceSynchronize()); }
 }
 
-void multi_convolve_dev(lsfc_plan* root, const cplx* const* x, cplx* const* y, bool use_nu, double alpha, double beta) {
+void multi_convolve_dev(lsfc_plan* root, const cplx* const* x, cplx* const* y, const ConvOp& op) {
+    LSFC_REQUIRE(conv_forward_only(op), "the transposed and the adjoint operator are not available on a multi-device plan");
+    const bool use_nu = op.nu == NuSide::INPUT; const double alpha = op.alpha, beta = op.beta;
     Multi M(root);
     const int P = M.P, K = M.K;
     const bool overlap = !M.d(0)->no_overlap;
@@ -438,7 +443,8 @@ void multi_convolve_dev(lsfc_plan* root, const cplx* const* x, cplx* const* y, b
     }
 }
 
-void multi_convolve_host(lsfc_plan* root, const cplx* x, cplx* y, bool use_nu, double alpha, double beta) {
+void multi_convolve_host(lsfc_plan* root, const cplx* x, cplx* y, const ConvOp& op) {
+    LSFC_REQUIRE(conv_forward_only(op), "the transposed and the adjoint operator are not available on a multi-device plan");
     Multi M(root);
     std::vector<const cplx*> xd((size_t)M.P); std::vector<cplx*> yd((size_t)M.P);
     int64_t off = 0;
@@ -449,7 +455,7 @@ void multi_convolve_host(lsfc_plan* root, const cplx* x, cplx* y, bool use_nu, d
         LSFC_HIP(hipMemcpyAsync(p->xs.p, x + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
         xd[(size_t)r] = p->xs.p; yd[(size_t)r] = p->ys.p; off += p->N;
     }
-    multi_convolve_dev(root, xd.data(), yd.data(), use_nu, alpha, beta);
+    multi_convolve_dev(root, xd.data(), yd.data(), op);
     off = 0;
     for (int r = 0; r < M.P; ++r) {
         lsfc_plan* p = M.sub(r);
@@ -629,8 +635,7 @@ int lsfc_multi_apply_dev(lsfc_plan* plan, const double* const* x_dev, double* co
     return guarded([&] {
         LSFC_REQUIRE(plan && plan->multi && x_dev && y_dev, "not a multi-device plan / NULL argument");
         LSFC_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (apply), 1 (convolve) or 2 (convolve with nu)");
-        const double om2 = plan->omega * plan->omega;
-        multi_convolve_dev(plan, (const cplx* const*)x_dev, (cplx* const*)y_dev, mode != 1, mode == 0 ? 1.0 : 0.0, mode == 0 ? om2 : 1.0);
+        multi_convolve_dev(plan, (const cplx* const*)x_dev, (cplx* const*)y_dev, mode == 0 ? plan_operator(plan) : conv_plain(mode == 2, 0.0, 1.0));
     });
 }
 

@@ -144,7 +144,7 @@ void Team::apply(const Request& q) {
     if (!root->multi) { dev(mem[0]); plan_apply_dev(root, q.in(mem[0]), q.out(mem[0])); return; }
     std::vector<const cplx*> xi; std::vector<cplx*> yo;
     for (auto& m : mem) { xi.push_back(q.in(m)); yo.push_back(q.out(m)); }
-    multi_convolve_dev(root, xi.data(), yo.data(), true, 1.0, root->omega * root->omega);
+    multi_convolve_dev(root, xi.data(), yo.data(), plan_operator(root));
 }
 
 struct Resolved { lsfc_gmres_opts o; int restart; int64_t maxiter; double reltol, abstol; };

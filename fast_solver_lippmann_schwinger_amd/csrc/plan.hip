@@ -1,16 +1,10 @@
-// lsfc C ABI: plan construction, the operator apply, timing helpers (gfx950).
+// lsfc C ABI: what makes and owns a plan -- the error buffer, the rocFFT wrapper, the three ways a symbol becomes a plan, the
+// plan's settings, the memory helpers (gfx950).  Running a plan: apply.hip, host_apply.hip.
 #include "plan.hpp"
 #include "pointwise.hpp"
-#include "krylov_blas.hpp"
-#include "blocktri.hpp"
 #include <cmath>
 #include <cstring>
-#include <condition_variable>
-#include <deque>
-#include <thread>
-#include <functional>
 #include <mutex>
-#include <string>
 
 namespace lsfc {
 
@@ -81,8 +75,7 @@ void RocFft::exec(void* buf, hipStream_t stream) {
 // ---------------------------------------------------------------------------
 // plan construction helpers
 // ---------------------------------------------------------------------------
-// environment switches (developer knobs, read at plan creation): the first character of the value, -1 when not set
-static int env_switch(const char* name) { const char* e = getenv(name); return e ? (unsigned char)e[0] : -1; }
+// (environment switches, developer knobs, read at plan creation)
 // LSFC_SYM_EVEN_Y=0 / LSFC_SYM_EVEN_Z=0: store the full symbol although it is even in y / along the fused pass's axis
 static bool sym_even_y_enabled() { return env_switch("LSFC_SYM_EVEN_Y") != '0'; }
 static bool sym_even_z_enabled() { return env_switch("LSFC_SYM_EVEN_Z") != '0'; }
@@ -387,434 +380,15 @@ static void plan_finish_reduce(lsfc_plan* p, DevBuf<cplx>& Gd, const int lit[3],
     plan_finish_symbol(p, Gd, false);
 }
 
-// ---------------------------------------------------------------------------
-// the apply
-// ---------------------------------------------------------------------------
-// The passes of the single-device pruned pipeline: xfwd -> yfwd -> fused z -> yinv -> xinv in 3D, xfwd -> fused y -> xinv
-// in 2D (natural rows, or tiles: lsfc_plan::tile2d).  Every driver below -- device vectors, batches, the chunked host-vector
-// pipeline, the per-stage profile -- issues these and nothing else.  A one-member launch gets the batch strides a1_elems /
-// a2_elems like any other (the kernels only multiply them by the member index).
-struct Slab { int z0, nz; };            // z planes [z0, z0 + nz) of the grid: the x and y passes work plane by plane
-static Slab whole_grid(const lsfc_plan* p) { return Slab{0, p->dims[2]}; }
-// the members' vectors at the first plane of a slab
-static VecBatch slab_vectors(const lsfc_plan* p, const VecBatch& vb, int nrhs, Slab s) {
-    const int64_t off = (int64_t)s.z0 * p->dims[0] * p->dims[1];
-    VecBatch v = vb;
-    for (int j = 0; j < nrhs; ++j) { v.x[j] += off; v.y[j] += off; }
-    return v;
-}
-static cplx* slab_a1(const lsfc_plan* p, Slab s) { return p->A1.p + (int64_t)s.z0 * p->dims[1] * p->pitch1; }
-static cplx* slab_a2(const lsfc_plan* p, Slab s) { return p->A2.p + (int64_t)8 * s.z0; }
-
-// nu at the first plane of a slab, if the pass on side `side` of the convolution is the one that multiplies by it
-static const double* slab_nu(const lsfc_plan* p, const ConvOp& op, NuSide side, Slab s) {
-    return op.nu == side ? p->nu.p + (int64_t)s.z0 * p->dims[0] * p->dims[1] : nullptr;
-}
-static void pass_xfwd(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Slab s, hipStream_t st) {
-    const int Lx = p->pads[0], n = p->dims[0];
-    const int64_t nlines = (int64_t)p->dims[1] * s.nz;
-    const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    const double* nu = slab_nu(p, op, NuSide::INPUT, s);
-    if (p->tile2d) pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, op.conj);
-    else pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, slab_a1(p, s), p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, op.conj);
-}
-static void pass_yfwd(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {         // 3D only
-    pruned_yfwd(p->pads[1], p->tuning, slab_a1(p, s), slab_a2(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
-                nrhs, p->a1_elems, p->a2_elems);
-}
-static void pass_yinv(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {         // 3D only
-    pruned_yinv(p->pads[1], p->tuning, slab_a2(p, s), slab_a1(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
-                nrhs, p->a1_elems, p->a2_elems);
-}
-static void pass_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Slab s, hipStream_t st) {
-    const int Lx = p->pads[0], n = p->dims[0];
-    const int64_t nlines = (int64_t)p->dims[1] * s.nz;
-    const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    const double* nu = slab_nu(p, op, NuSide::OUTPUT, s);
-    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, nu, op.conj);
-    else pruned_xinv(Lx, p->tuning, slab_a1(p, s), v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, nu, op.conj);
+// Finish a plan from a symbol on its literal grid `lit` (on the device; centred or FFT order), the kernel's zero offset at index
+// kernel_origin: on that very grid under LSFC_FLAG_LITERAL_PAD -- the crop window starts at the kernel origin --, else reduced
+static void plan_finish_from_literal(lsfc_plan* p, DevBuf<cplx>& Gd, const int lit[3], bool centred, const int kernel_origin[3]) {
+    if (p->flags & LSFC_FLAG_LITERAL_PAD) {
+        for (int d = 0; d < 3; ++d) { p->pads[d] = lit[d]; p->crop[d] = kernel_origin[d]; }
+        plan_finish_literal(p, Gd.p, centred);
+    } else plan_finish_reduce(p, Gd, lit, centred, kernel_origin);
 }
 
-// The three geometries of the fused pass.  3D: A2 as tiles [x'/8][Ly][pitch2 >= 8*l] of 8 interleaved z lines, the symbol as
-// [x'/8][sym_rows][sym_hz][8]; `Wc` x' storage indices from the tile that `a2_off` / `sym_off` point to (a chunk of a
-// distributed plan; the whole range on one device).
-static FusedGeom geom_3d(const lsfc_plan* p, int Wc) {
-    const int Ly = p->pads[1];
-    return FusedGeom{Wc, Ly, (int64_t)p->pitch2 * Ly, (int64_t)p->pitch2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8,
-                     p->ytab.p, p->zmirror.p, p->dims[2]};
-}
-void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st) {
-    const FusedGeom g = geom_3d(p, Wc);
-    pruned_zfused(p->pads[2], p->tuning, p->A2.p + a2_off, p->sym.p + sym_off, p->tw[2].p, p->twl[2].p, g, st, nrhs, p->a2_elems);
-}
-// 2D, natural rows: A1 as [m][pitch1 >= Lx], the lines along y; the symbol likewise, [rows][Lx]
-static FusedGeom geom_2d_rows(const lsfc_plan* p) {
-    return FusedGeom{p->pads[0], 1, 8, 0, (int64_t)p->pitch1, 8, 0, (int64_t)p->pads[0], nullptr, p->zmirror.p, p->dims[1]};
-}
-// 2D, tiles: A1 as [Lx/8][tile2d >= 8*m] -- the 3D layout with one row per tile; the symbol as [Lx/8][sym_hz][8]
-static FusedGeom geom_2d_tiles(const lsfc_plan* p) {
-    return FusedGeom{p->pads[0], 1, p->tile2d, 0, 8, (int64_t)8 * p->sym_hz, 0, 8, nullptr, p->zmirror.p, p->dims[1]};
-}
-// whether a batch of nrhs right-hand sides shares one launch per pass (lsfc_apply_batch)
-static bool batch_fused(const lsfc_plan* p, int nrhs) {
-    const bool fuse = p->tuning.batch_fuse > 0 ||
-                      (p->tuning.batch_fuse < 0 && (int64_t)p->pads[0] * p->pads[1] * p->pads[2] <= ((int64_t)1 << 24));
-    return !(nrhs == 1 || p->dist || p->multi || p->pipeline != lsfc_plan::PRUNED || !fuse);
-}
-// The kernels an apply of nrhs right-hand sides launches, one line per pass (lsfc_plan_describe_passes): the PassForm of each
-// pass from the very arguments pass_xfwd ... pass_xinv hand to the launchers
-static std::string describe_passes(const lsfc_plan* p, int nrhs) {
-    std::string out = std::string("pipeline=") + lsfc_plan_pipeline(p);
-    if (p->multi) return out + " multi-device\n";
-    if (p->dist) return out + " distributed\n";
-    out += "\n";
-    if (p->pipeline != lsfc_plan::PRUNED) return out;
-    const bool fused = batch_fused(p, nrhs);
-    const int per_launch = fused ? nrhs : 1;
-    char line[512];
-    auto add = [&](const PassForm& f) { pass_form_print(f, line, sizeof line); out += line; out += "\n"; };
-    const bool d3 = p->ndim == 3;
-    add(pruned_xfwd_form(p->pads[0], p->tuning, p->dims[0]));
-    if (d3) add(pruned_yfwd_form(p->pads[1], p->tuning, p->pads[0], p->dims[1], p->dims[2]));
-    const int fa = d3 ? 2 : 1;
-    add(pruned_zfused_form(p->pads[fa], p->tuning, d3 ? geom_3d(p, p->pads[0]) : (p->tile2d ? geom_2d_tiles(p) : geom_2d_rows(p)),
-                           p->twl[fa].p != nullptr, per_launch));
-    if (d3) add(pruned_yinv_form(p->pads[1], p->tuning, p->pads[0], p->dims[1], p->dims[2]));
-    add(pruned_xinv_form(p->pads[0], p->tuning, p->dims[0]));
-    // storage: ytab = 1 the y-even half of the symbol rows (each stored row serves a row and its mirror), zmirror = 1 the even half
-    // of every symbol line along the fused pass's axis; batch: how nrhs > 1 right-hand sides run through the passes
-    snprintf(line, sizeof line, "pitch1=%d pitch2=%d sym_rows=%d sym_hz=%d ytab=%d zmirror=%d tile2d=%lld batch=%s\n", p->pitch1, p->pitch2, p->sym_rows,
-             p->sym_hz, (int)(d3 && p->sym_rows != p->pads[1]), (int)(p->zmirror.p != nullptr), (long long)p->tile2d,
-             nrhs == 1 ? "none" : (fused ? "fused" : "per_member"));
-    out += line;
-    return out;
-}
-static void pass_fused(lsfc_plan* p, int nrhs, hipStream_t st) {
-    if (p->ndim == 3) { plan_zfused_3d(p, p->pads[0], 0, 0, nrhs, st); return; }
-    pruned_zfused(p->pads[1], p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, p->tile2d ? geom_2d_tiles(p) : geom_2d_rows(p), st, nrhs, p->a1_elems);
-}
-
-// nrhs <= batch_cap right-hand sides through the pruned pipeline on the plan's stream
-static void pruned_convolve(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op) {
-    // (round 3, measured slower and removed again -- profiles/r03_experiment_a1_window.log: the x and y passes chunk by chunk over
-    // groups of z planes through one chunk-sized window of A1, hoping the Infinity Cache would absorb the 2 x 4.3 GB of A1 traffic)
-    hipStream_t st = p->stream;
-    const Slab all = whole_grid(p);
-    pass_xfwd(p, vb, nrhs, op, all, st);
-    if (p->ndim == 3) pass_yfwd(p, nrhs, all, st);
-    pass_fused(p, nrhs, st);
-    if (p->ndim == 3) pass_yinv(p, nrhs, all, st);
-    pass_xinv(p, vb, nrhs, op, all, st);
-}
-
-// (distributed and multi-device plans know M and the bare convolutions only: lsfc_plan_set_op refuses them)
-static bool forward_only(const ConvOp& op) { return op.nu != NuSide::OUTPUT && !op.conj; }
-
-void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op) {
-    if (p->dist) {
-        LSFC_REQUIRE(forward_only(op), "the transposed and the adjoint operator are not available on a distributed plan");
-        dist_convolve_dev(p, x, y, op.nu == NuSide::INPUT, op.alpha, op.beta);
-        return;
-    }
-    if (p->pipeline == lsfc_plan::PRUNED) {
-        VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
-        pruned_convolve(p, 1, vb, op);
-    } else {
-        hipStream_t st = p->stream;
-        const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
-        pw_embed(x, op.nu == NuSide::INPUT ? p->nu.p : nullptr, p->W.p, p->dims, p->pads, st, op.conj);
-        p->fwd->exec(p->W.p, st);
-        pw_mul_inplace(p->W.p, p->sym.p, total, st);
-        p->inv->exec(p->W.p, st);
-        pw_crop_axpy(p->W.p, x, y, op.alpha, op.beta, p->dims, p->pads, p->crop, st, op.nu == NuSide::OUTPUT ? p->nu.p : nullptr, op.conj);
-    }
-}
-
-void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op) {
-    LSFC_REQUIRE(nrhs >= 1 && nrhs <= LSFC_MAX_BATCH, "batch of %d right-hand sides (1..%d per pass)", nrhs, LSFC_MAX_BATCH);
-    if (!batch_fused(p, nrhs)) {
-        for (int j = 0; j < nrhs; ++j) plan_convolve_dev(p, vb.x[j], vb.y[j], op);
-        return;
-    }
-    if (nrhs > p->batch_cap) {
-        // the work arrays hold the batch back to back: grow them (the plan is idle once its stream has drained)
-        LSFC_HIP(hipStreamSynchronize(p->stream));
-        p->A1.alloc((size_t)(p->a1_elems * nrhs));
-        if (p->ndim == 3) p->A2.alloc((size_t)(p->a2_elems * nrhs));
-        p->batch_cap = nrhs;
-    }
-    pruned_convolve(p, nrhs, vb, op);
-}
-
-void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out, size_t cnt) {
-    for (size_t j0 = 0; j0 < cnt; j0 += LSFC_MAX_BATCH) {
-        const int n = (int)std::min<size_t>(LSFC_MAX_BATCH, cnt - j0);
-        VecBatch vb{};
-        for (int j = 0; j < n; ++j) { vb.x[j] = in[j0 + j]; vb.y[j] = out[j0 + j]; }
-        plan_convolve_batch_dev(p, n, vb, plan_operator(p));
-    }
-}
-
-void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, void* precond_user, const char* who) {
-    if (fn != &lsfc_precond_callback) return;
-    static const char* const names[] = {"LSFC_OP_N", "LSFC_OP_T", "LSFC_OP_H"};
-    const int pop = precond_user ? precond_op((const lsfc_precond*)precond_user) : LSFC_OP_N;
-    LSFC_REQUIRE(pop == p->op, "%s%sthe library's preconditioner object is set to %s and approximates the inverse of that form of M, the plan is set to %s: "
-                 "lsfc_precond_set_op and lsfc_plan_set_op must agree", who ? who : "", who ? ": " : "", names[pop], names[p->op]);
-}
-
-Precond::Precond(lsfc_precond_fn f, void* u, bool dev, bool meet, int64_t n, const char* who)
-    : fn(f), user(u), on_device(dev), own(meet && dev && f == &lsfc_precond_callback), N(n) {
-    const int64_t have = own && user ? precond_size((lsfc_precond*)user) : -1;
-    if (own) LSFC_REQUIRE(have == N, "%s%spreconditioner: size mismatch (%lld vs %lld)", who ? who : "", who ? ": " : "", (long long)N, (long long)have);
-}
-
-void Precond::apply(cplx* const* v, size_t cnt, cplx* pinned, hipStream_t st) const {
-    if (!fn) return;
-    if (own) { precond_apply_batch_dev((lsfc_precond*)user, v, (int)cnt, st); return; }
-    for (size_t j = 0; j < cnt; ++j) {
-        if (!on_device) {
-            LSFC_HIP(hipMemcpyAsync(pinned, v[j], (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
-            LSFC_HIP(hipStreamSynchronize(st));
-        }
-        const int rc = fn(user, (double*)(on_device ? v[j] : pinned), N);
-        if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-        // (whatever next goes into the pinned vector is ordered after this copy on st)
-        if (!on_device) LSFC_HIP(hipMemcpyAsync(v[j], pinned, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));
-    }
-}
-
-void plan_ensure_staging(lsfc_plan* p, int64_t count) {
-    if (p->xs.n < (size_t)count) { p->xs.alloc((size_t)count); p->ys.alloc((size_t)count); }
-}
-
-HostPipe::~HostPipe() {
-    for (hipEvent_t e : ev_up) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_down) (void)hipEventDestroy(e);
-    if (ev_free) (void)hipEventDestroy(ev_free);
-    for (hipEvent_t e : { ev_xfree[0], ev_xfree[1], ev_yfree[0], ev_yfree[1] }) if (e) (void)hipEventDestroy(e);
-    if (up) (void)hipStreamDestroy(up);
-    if (down) (void)hipStreamDestroy(down);
-}
-
-// The drop-in path the reference exercises, mul!(Y, M, b) with HOST vectors (src/FastConvolution.jl:50-54), as a pipeline over
-// K chunks of z planes: chunk c of x travels host -> device on its own stream while the x and y passes of the chunks already
-// landed run (those passes work plane by plane: yfwd of plane z needs xfwd of plane z only); then the fused z pass, which needs
-// every plane; then the inverse y and x passes chunk by chunk, each chunk of y leaving for the host as soon as it exists.
-// What cannot overlap: the first byte of y depends on the last byte of x (the Green's kernel is dense), so the upload and
-// the download of ONE apply are strictly one after the other -- the floor is 2 N 16 B / PCIe rate + the fused pass
-// (512^3: 2 x 37.5 ms at the 57 GB/s this box moves per direction + 4.7 ms), not the full-duplex rate.
-// Caller memory: pageable vectors go through the runtime's staged copies (measured 56 / 50 GB/s up / down, no slower than
-// pinned on this box); vectors registered with lsfc_host_register (or allocated pinned) are read and written by DMA directly.
-static int host_pipeline_chunks(const lsfc_plan* p) {
-    const char* e = getenv("LSFC_HOST_PIPELINE");                  // developer switch: 0 / 1 off, K >= 2 chunks whatever the size
-    const int forced = e ? atoi(e) : -1;
-    if (forced == 0 || forced == 1) return 1;
-    if (p->pipeline != lsfc_plan::PRUNED || p->ndim != 3 || p->dist || p->multi) return 1;
-    if (forced < 0 && p->N * (int64_t)sizeof(cplx) < ((int64_t)64 << 20)) return 1;       // small vectors: one copy each way
-    const int l = p->dims[2];
-    for (int K = forced > 1 ? forced : 8; K >= 2; --K) if (l % K == 0) return K;
-    return 1;
-}
-
-// nrhs right-hand sides through the pipeline with TWO staging slots: while right-hand side j is transformed back and its chunks leave
-// for the host, the chunks of right-hand side j + 1 arrive -- across right-hand sides the two PCIe directions do overlap (512^3: 53-55
-// ms per right-hand side against 83-87 for one alone).
-static void host_pipelined_convolve(lsfc_plan* p, const cplx* x, cplx* y, int64_t nrhs, const ConvOp& op, int K) {
-    if (!p->hostpipe) {
-        std::unique_ptr<HostPipe> hp(new HostPipe());
-        LSFC_HIP(hipStreamCreateWithFlags(&hp->up, hipStreamNonBlocking));
-        LSFC_HIP(hipStreamCreateWithFlags(&hp->down, hipStreamNonBlocking));
-        LSFC_HIP(hipEventCreateWithFlags(&hp->ev_free, hipEventDisableTiming));
-        for (hipEvent_t* e : { &hp->ev_xfree[0], &hp->ev_xfree[1], &hp->ev_yfree[0], &hp->ev_yfree[1] }) LSFC_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        p->hostpipe = std::move(hp);
-    }
-    HostPipe* hp = p->hostpipe.get();
-    while ((int)hp->ev_up.size() < 2 * K) {
-        hipEvent_t a, b;
-        LSFC_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming)); hp->ev_up.push_back(a);
-        LSFC_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming)); hp->ev_down.push_back(b);
-    }
-    const int slots = nrhs > 1 ? 2 : 1;
-    if (p->xs.n < (size_t)(slots * p->N)) { LSFC_HIP(hipStreamSynchronize(p->stream)); plan_ensure_staging(p, slots * p->N); }
-    hipStream_t st = p->stream;
-    const int lz = p->dims[2] / K;
-    const int64_t chunk = (int64_t)p->dims[0] * p->dims[1] * lz;
-    // the staging buffers may still be read by work queued earlier on the plan's stream (device-memory calls are asynchronous)
-    LSFC_HIP(hipEventRecord(hp->ev_free, st));
-    LSFC_HIP(hipStreamWaitEvent(hp->up, hp->ev_free, 0));
-    // Several right-hand sides: the downloads are issued from a helper thread.  With pageable caller memory the runtime stages every
-    // copy through pinned buffers ON THE CALLING THREAD and returns when it is done, so downloads issued here would keep the
-    // uploads of the next right-hand side from even starting; from a second thread the two directions run side by side.
-    struct Down { hipEvent_t ev; cplx* dst; const cplx* src; int slot; bool last; int64_t rhs; };
-    std::mutex dmu; std::condition_variable dcv; std::deque<Down> dq; bool ddone = false; std::exception_ptr derr;
-    int64_t yfree_recorded[2] = { 0, 0 };              // slot s: 1 + the last right-hand side whose final download has been issued (and ev_yfree recorded)
-    std::thread dthread;
-    const bool helper = nrhs > 1;
-    if (helper) dthread = std::thread([&] {
-        try {
-            LSFC_HIP(hipSetDevice(p->device));
-            for (;;) {
-                Down d;
-                { std::unique_lock<std::mutex> lk(dmu); dcv.wait(lk, [&] { return !dq.empty() || ddone; }); if (dq.empty()) return; d = dq.front(); dq.pop_front(); }
-                LSFC_HIP(hipStreamWaitEvent(hp->down, d.ev, 0));
-                LSFC_HIP(hipMemcpyAsync(d.dst, d.src, (size_t)chunk * sizeof(cplx), hipMemcpyDeviceToHost, hp->down));
-                if (d.last) {
-                    LSFC_HIP(hipEventRecord(hp->ev_yfree[d.slot], hp->down));
-                    { std::lock_guard<std::mutex> lk(dmu); yfree_recorded[d.slot] = d.rhs + 1; }
-                    dcv.notify_all();
-                }
-            }
-        } catch (...) { { std::lock_guard<std::mutex> lk(dmu); derr = std::current_exception(); } dcv.notify_all(); }
-    });
-    struct Join { std::thread& t; std::mutex& mu; std::condition_variable& cv; bool& done;
-                  ~Join() { if (t.joinable()) { { std::lock_guard<std::mutex> lk(mu); done = true; } cv.notify_all(); t.join(); } } } join{dthread, dmu, dcv, ddone};
-    for (int64_t j = 0; j < nrhs; ++j) {
-        const int sl = (int)(j % slots);
-        const cplx* xj = x + j * p->N; cplx* yj = y + j * p->N;
-        cplx* xs = p->xs.p + (int64_t)sl * p->N; cplx* ys = p->ys.p + (int64_t)sl * p->N;
-        VecBatch sv{}; sv.x[0] = xs; sv.y[0] = ys;
-        // slot sl was last used by right-hand side j - 2: its inverse x pass (which reads xs) and its downloads (which read ys) must be over
-        if (j >= slots) {
-            LSFC_HIP(hipStreamWaitEvent(hp->up, hp->ev_xfree[sl], 0));
-            if (helper) {
-                // (the event of the slot's last download is recorded by the helper: wait until it has been, then order the stream behind it)
-                std::unique_lock<std::mutex> lk(dmu);
-                dcv.wait(lk, [&] { return yfree_recorded[sl] >= j - slots + 1 || derr; });
-                if (derr) std::rethrow_exception(derr);
-            }
-            LSFC_HIP(hipStreamWaitEvent(st, hp->ev_yfree[sl], 0));
-        }
-        for (int c = 0; c < K; ++c) {
-            const int64_t off = c * chunk;
-            hipEvent_t ev = hp->ev_up[(size_t)(sl * K + c)];
-            LSFC_HIP(hipMemcpyAsync(xs + off, xj + off, (size_t)chunk * sizeof(cplx), hipMemcpyHostToDevice, hp->up));
-            LSFC_HIP(hipEventRecord(ev, hp->up));
-            LSFC_HIP(hipStreamWaitEvent(st, ev, 0));
-            pass_xfwd(p, sv, 1, op, Slab{c * lz, lz}, st);
-            pass_yfwd(p, 1, Slab{c * lz, lz}, st);
-        }
-        pass_fused(p, 1, st);
-        for (int c = 0; c < K; ++c) {
-            const int64_t off = c * chunk;
-            hipEvent_t ev = hp->ev_down[(size_t)(sl * K + c)];
-            pass_yinv(p, 1, Slab{c * lz, lz}, st);
-            pass_xinv(p, sv, 1, op, Slab{c * lz, lz}, st);
-            LSFC_HIP(hipEventRecord(ev, st));
-            if (helper) {
-                { std::lock_guard<std::mutex> lk(dmu); dq.push_back(Down{ev, yj + off, ys + off, sl, c == K - 1, j}); }
-                dcv.notify_all();
-            } else {
-                LSFC_HIP(hipStreamWaitEvent(hp->down, ev, 0));
-                LSFC_HIP(hipMemcpyAsync(yj + off, ys + off, (size_t)chunk * sizeof(cplx), hipMemcpyDeviceToHost, hp->down));
-            }
-        }
-        LSFC_HIP(hipEventRecord(hp->ev_xfree[sl], st));
-        if (!helper) LSFC_HIP(hipEventRecord(hp->ev_yfree[sl], hp->down));
-    }
-    if (helper) {
-        { std::lock_guard<std::mutex> lk(dmu); ddone = true; }
-        dcv.notify_all();
-        dthread.join();
-        if (derr) std::rethrow_exception(derr);
-    }
-    LSFC_HIP(hipStreamSynchronize(hp->down));
-    LSFC_HIP(hipStreamSynchronize(st));
-}
-
-static void convolve_any(lsfc_plan* p, const double* x, double* y, int64_t nrhs, const ConvOp& op, int memspace) {
-    LSFC_REQUIRE(p && x && y, "NULL argument");
-    LSFC_REQUIRE(nrhs >= 1, "nrhs must be >= 1");
-    if (p->multi) {
-        // one host process, several devices: the vector is scattered over the ranks' z-slabs, applied, gathered
-        LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "a multi-device plan takes host vectors here; per-device slabs go through lsfc_multi_apply_dev");
-        LSFC_REQUIRE(forward_only(op), "the transposed and the adjoint operator are not available on a multi-device plan");
-        for (int64_t j = 0; j < nrhs; ++j) multi_convolve_host(p, (const cplx*)x + j * p->N, (cplx*)y + j * p->N, op.nu == NuSide::INPUT, op.alpha, op.beta);
-        return;
-    }
-    LSFC_HIP(hipSetDevice(p->device));
-    // groups of up to LSFC_MAX_BATCH right-hand sides share one pass of the pipeline (one symbol read per group)
-    if (memspace == LSFC_MEM_DEVICE) {
-        for (int64_t j0 = 0; j0 < nrhs; j0 += LSFC_MAX_BATCH) {
-            const int cnt = (int)std::min<int64_t>(LSFC_MAX_BATCH, nrhs - j0);
-            VecBatch vb{};
-            for (int j = 0; j < cnt; ++j) { vb.x[j] = (const cplx*)x + (j0 + j) * p->N; vb.y[j] = (cplx*)y + (j0 + j) * p->N; }
-            plan_convolve_batch_dev(p, cnt, vb, op);
-        }
-        return;
-    }
-    LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "unknown memspace %d", memspace);
-    const int group = (int)std::min<int64_t>(LSFC_MAX_BATCH, nrhs);
-    // large 3D vectors: the chunked pipeline above (two staging slots, allocated there)
-    const int K = host_pipeline_chunks(p);
-    if (K <= 1) plan_ensure_staging(p, p->N * group);
-    if (K > 1) {
-        // (y aliasing x: right-hand side j + 1 is uploaded while j is downloaded into the same memory -- distinct vectors, no hazard)
-        host_pipelined_convolve(p, (const cplx*)x, (cplx*)y, nrhs, op, K);
-        return;
-    }
-    // LSFC_HOST_COPY=sync (developer switch, diagnostics of the round-2 first-apply fault): the round-2 workaround, a
-    // synchronous copy behind a drained stream, instead of the stream-ordered copy
-    static const bool sync_copy = env_switch("LSFC_HOST_COPY") == 's';
-    for (int64_t j0 = 0; j0 < nrhs; j0 += group) {
-        const int cnt = (int)std::min<int64_t>(group, nrhs - j0);
-        const size_t bytes = (size_t)cnt * p->N * sizeof(cplx);
-        if (sync_copy) {
-            LSFC_HIP(hipStreamSynchronize(p->stream));
-            LSFC_HIP(hipMemcpy(p->xs.p, (const cplx*)x + j0 * p->N, bytes, hipMemcpyHostToDevice));
-        } else LSFC_HIP(hipMemcpyAsync(p->xs.p, (const cplx*)x + j0 * p->N, bytes, hipMemcpyHostToDevice, p->stream));
-        VecBatch vb{};
-        for (int j = 0; j < cnt; ++j) { vb.x[j] = p->xs.p + (int64_t)j * p->N; vb.y[j] = p->ys.p + (int64_t)j * p->N; }
-        plan_convolve_batch_dev(p, cnt, vb, op);
-        LSFC_HIP(hipMemcpyAsync((cplx*)y + j0 * p->N, p->ys.p, bytes, hipMemcpyDeviceToHost, p->stream));
-        LSFC_HIP(hipStreamSynchronize(p->stream));
-    }
-}
-
-// kernel samples: the response to a unit source at grid index 0 (one FFT convolution, no nu), built once per plan
-void plan_kernel0(lsfc_plan* p) {
-    const int64_t N = p->N;
-    if (p->kernel0.n == (size_t)N) return;
-    p->kernel0.alloc((size_t)N);
-    DevBuf<cplx> e; e.alloc((size_t)N);
-    LSFC_HIP(hipMemsetAsync(e.p, 0, (size_t)N * sizeof(cplx), p->stream));
-    const cplx one = make_double2(1.0, 0.0);
-    LSFC_HIP(hipMemcpyAsync(e.p, &one, sizeof one, hipMemcpyHostToDevice, p->stream));
-    plan_convolve_dev(p, e.p, p->kernel0.p, conv_plain(false, 0.0, 1.0));
-    LSFC_HIP(hipStreamSynchronize(p->stream));
-}
-
-// One convolution per further corner of the grid (2^ndim - 1 of them), once per plan.  A kernel that is even along x at
-// y >= 0 only is caught by the corner that is last along both, so every corner is visited: first those last along one axis
-// (their failure names that axis), then the others (which name their lowest axis).
-void plan_require_even_kernel(lsfc_plan* p, const char* who) {
-    static const char axis_name[3] = {'x', 'y', 'z'};
-    constexpr double TOL = 1e-10;
-    if (p->even_dev < 0.0) {
-        plan_kernel0(p);
-        const int64_t N = p->N;
-        DevBuf<cplx> e, r; e.alloc((size_t)N); r.alloc((size_t)N);
-        const cplx one = make_double2(1.0, 0.0);
-        const int order[7] = {1, 2, 4, 3, 5, 6, 7};
-        double worst = 0.0; int axis = 0;
-        for (int mask : order) {
-            if (mask >> p->ndim) continue;
-            int64_t corner = 0, stride = 1;
-            for (int a = 0; a < p->ndim; ++a) { if (mask >> a & 1) corner += stride * (p->dims[a] - 1); stride *= p->dims[a]; }
-            LSFC_HIP(hipMemsetAsync(e.p, 0, (size_t)N * sizeof(cplx), p->stream));
-            LSFC_HIP(hipMemcpyAsync(e.p + corner, &one, sizeof one, hipMemcpyHostToDevice, p->stream));
-            plan_convolve_dev(p, e.p, r.p, conv_plain(false, 0.0, 1.0));
-            const double d = pw_corner_deviation(r.p, p->kernel0.p, p->dims, mask, p->stream);
-            if (d > TOL && !(worst > TOL)) { axis = 0; while (!(mask >> axis & 1)) ++axis; }     // the first corner that fails
-            worst = std::max(worst, d);
-        }
-        p->even_dev = worst; p->even_axis = axis;
-    }
-    if (p->even_dev > TOL)
-        fail(LSFC_EINVAL, "%s: the kernel of this plan is not even along axis %c (deviation %.3e of its largest entry > 1e-10): the rows of its "
-                          "Green's matrix are not K[|i - j|], which this entry gathers; the builders' kernels are even, a literal symbol "
-                          "(lsfc_plan_create_2d/3d) has to be even in every axis", who, axis_name[p->even_axis], p->even_dev);
-}
 } // namespace lsfc
 
 using namespace lsfc;
@@ -849,12 +423,7 @@ static int create_from_literal(lsfc_plan** out, int ndim, int64_t n, int64_t m, 
         for (int d = 0; d < ndim; ++d)
             LSFC_REQUIRE(lit[d] >= (trap ? 2 * p->dims[d] - 1 : p->dims[d]), "padded size %d too small along axis %d", lit[d], d);
         int origin[3]; for (int d = 0; d < 3; ++d) origin[d] = (trap && d < ndim) ? p->dims[d] - 1 : 0;
-        if (flags & LSFC_FLAG_LITERAL_PAD) {
-            for (int d = 0; d < 3; ++d) { p->pads[d] = lit[d]; p->crop[d] = origin[d]; }
-            plan_finish_literal(p.get(), Gd.p, !trap);
-        } else {
-            plan_finish_reduce(p.get(), Gd, lit, !trap, origin);
-        }
+        plan_finish_from_literal(p.get(), Gd, lit, !trap, origin);
         *out = p.release();
     });
 }
@@ -904,10 +473,7 @@ int lsfc_plan_create_gv2d(lsfc_plan** out, int64_t n, int64_t m, double box, dou
         DevBuf<cplx> G; int lit[3];
         symbol_gv2d_literal(p.get(), box, G, lit);
         const int origin[3] = { 0, 0, 0 };
-        if (flags & LSFC_FLAG_LITERAL_PAD) {
-            for (int d = 0; d < 3; ++d) { p->pads[d] = lit[d]; p->crop[d] = 0; }
-            plan_finish_literal(p.get(), G.p, true);
-        } else plan_finish_reduce(p.get(), G, lit, true, origin);
+        plan_finish_from_literal(p.get(), G, lit, true, origin);
         p->even_dev = 0.0;                 // a function of kx^2 + ky^2 (plan_require_even_kernel)
         *out = p.release();
     });
@@ -924,10 +490,7 @@ int lsfc_plan_create_trap2d(lsfc_plan** out, int64_t n, int64_t m, double x0, do
         symbol_trap2d_literal(p.get(), x0, y0, h, make_double2(d0_re, d0_im), G);
         const int lit[3] = { 2 * (int)n - 1, 2 * (int)m - 1, 1 };
         const int origin[3] = { (int)n - 1, (int)m - 1, 0 };
-        if (flags & LSFC_FLAG_LITERAL_PAD) {
-            for (int d = 0; d < 3; ++d) { p->pads[d] = lit[d]; p->crop[d] = origin[d]; }
-            plan_finish_literal(p.get(), G.p, false);
-        } else plan_finish_reduce(p.get(), G, lit, false, origin);
+        plan_finish_from_literal(p.get(), G, lit, false, origin);
         // samples of a function of the distance to the centre of the extended grid (src/FastConvolution.jl:433-434): even where
         // the caller's grid is centred at the origin; any other grid is measured on first use (plan_require_even_kernel)
         if (fabs(x0 + (n - 1) / 2.0 * h) + fabs(y0 + (m - 1) / 2.0 * h) <= 1e-12 * fabs(h)) p->even_dev = 0.0;
@@ -995,120 +558,6 @@ int lsfc_plan_get_symbol(const lsfc_plan* plan, double* out, int64_t capacity_co
     });
 }
 
-int lsfc_plan_describe_passes(const lsfc_plan* plan, int nrhs, char* buf, int64_t capacity, int64_t* need) {
-    return guarded([&] {
-        LSFC_REQUIRE(plan && need, "NULL argument");
-        LSFC_REQUIRE(nrhs >= 1 && nrhs <= LSFC_MAX_BATCH, "nrhs must be 1..%d (the right-hand sides of one group of lsfc_apply_batch)", LSFC_MAX_BATCH);
-        const std::string text = describe_passes(plan, nrhs);
-        *need = (int64_t)text.size() + 1;
-        if (buf) {
-            LSFC_REQUIRE(capacity >= *need, "buffer too small");
-            memcpy(buf, text.c_str(), text.size() + 1);
-        }
-    });
-}
-
-int lsfc_apply(lsfc_plan* plan, const double* x, double* y, int memspace) {
-    return guarded([&] { LSFC_REQUIRE(plan, "NULL plan"); convolve_any(plan, x, y, 1, plan_operator(plan), memspace); });
-}
-int lsfc_convolve(lsfc_plan* plan, const double* x, double* y, int apply_nu, int memspace) {
-    return guarded([&] { convolve_any(plan, x, y, 1, conv_plain(apply_nu != 0, 0.0, 1.0), memspace); });
-}
-int lsfc_apply_batch(lsfc_plan* plan, const double* x, double* y, int64_t nrhs, int mode, int memspace) {
-    return guarded([&] {
-        LSFC_REQUIRE(plan, "NULL plan");
-        LSFC_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (apply), 1 (convolve) or 2 (convolve with nu)");
-        if (mode == 0) convolve_any(plan, x, y, nrhs, plan_operator(plan), memspace);
-        else convolve_any(plan, x, y, nrhs, conv_plain(mode == 2, 0.0, 1.0), memspace);
-    });
-}
-
-// The symmetry defect of G as this plan convolves with it (lsfc.h), measured once per plan: two bare convolutions of the probe
-// vectors and four reductions on the fixed-order tree.  NaN (an unpatched singular symbol) is kept as NaN and never passes.
-static double symmetry_defect(lsfc_plan* p) {
-    if (p->sym_defect >= 0.0 || p->sym_defect != p->sym_defect) return p->sym_defect;
-    LSFC_HIP(hipSetDevice(p->device));
-    const int64_t N = p->N;
-    hipStream_t st = p->stream;
-    DevBuf<cplx> x, xbar, y, ybar, gx, gy, partial, out;
-    for (DevBuf<cplx>* b : { &x, &xbar, &y, &ybar, &gx, &gy }) b->alloc((size_t)N);
-    partial.alloc((size_t)blas_partial_count()); out.alloc(4);
-    pw_probe(x.p, xbar.p, N, 0, st);
-    pw_probe(y.p, ybar.p, N, 1, st);
-    const ConvOp bare = conv_plain(false, 0.0, 1.0);
-    plan_convolve_dev(p, x.p, gx.p, bare);
-    plan_convolve_dev(p, y.p, gy.p, bare);
-    blas_dot(ybar.p, gx.p, partial.p, out.p + 0, N, st);          // sum y .* (G x): blas_dot conjugates its first argument
-    blas_dot(xbar.p, gy.p, partial.p, out.p + 1, N, st);          // sum x .* (G y)
-    blas_nrm2(gx.p, partial.p, out.p + 2, N, st);
-    blas_nrm2(y.p, partial.p, out.p + 3, N, st);
-    cplx h[4];
-    LSFC_HIP(hipMemcpyAsync(h, out.p, sizeof h, hipMemcpyDeviceToHost, st));
-    LSFC_HIP(hipStreamSynchronize(st));
-    const double den = h[2].x * h[3].x;
-    const double num = hypot(h[0].x - h[1].x, h[0].y - h[1].y);
-    p->sym_defect = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : NAN);
-    return p->sym_defect;
-}
-static void require_single_device(const lsfc_plan* plan) {
-    LSFC_REQUIRE(!plan->multi, "the transposed and the adjoint operator are not available on a multi-device plan");
-    LSFC_REQUIRE(!plan->dist, "the transposed and the adjoint operator are not available on a distributed (or simulated-rank) plan");
-}
-
-int lsfc_plan_set_op(lsfc_plan* plan, int op) {
-    return guarded([&] {
-        LSFC_REQUIRE(op == LSFC_OP_N || op == LSFC_OP_T || op == LSFC_OP_H, "op must be LSFC_OP_N, LSFC_OP_T or LSFC_OP_H (got %d)", op);
-        LSFC_REQUIRE(plan, "NULL plan");
-        if (op != LSFC_OP_N) {
-            require_single_device(plan);
-            const double d = symmetry_defect(plan);
-            // (the op stays what it was: N, since nothing but N gets past this line on such a plan)
-            if (!(d <= 1e-10)) fail(LSFC_EINVAL, "the Green's matrix of this plan is not symmetric (symmetry defect %.3e > 1e-10): "
-                                                 "I + w^2 diag(nu) G is not its transpose", d);
-        }
-        plan->op = op;
-    });
-}
-int lsfc_plan_get_op(const lsfc_plan* plan, int* op) {
-    return guarded([&] { LSFC_REQUIRE(plan && op, "NULL argument"); *op = plan->op; });
-}
-int lsfc_plan_symmetry_defect(lsfc_plan* plan, double* defect) {
-    return guarded([&] {
-        LSFC_REQUIRE(plan && defect, "NULL argument");
-        require_single_device(plan);
-        *defect = symmetry_defect(plan);
-    });
-}
-
-int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, double* out, int memspace) {
-    return guarded([&] {
-        LSFC_REQUIRE(plan && sources && out && nsrc >= 1, "bad argument");
-        LSFC_REQUIRE(!plan->dist && !plan->multi, "not available on a distributed plan");
-        LSFC_HIP(hipSetDevice(plan->device));
-        lsfc_plan* p = plan;
-        const int64_t N = p->N;
-        for (int64_t s = 0; s < nsrc; ++s) LSFC_REQUIRE(sources[s] >= 0 && sources[s] < N, "source index %lld out of range", (long long)sources[s]);
-        plan_kernel0(p);
-        plan_require_even_kernel(p, "lsfc_sample_sources");
-        DevBuf<int64_t> dsrc; dsrc.alloc((size_t)nsrc);
-        LSFC_HIP(hipMemcpyAsync(dsrc.p, sources, (size_t)nsrc * sizeof(int64_t), hipMemcpyHostToDevice, p->stream));
-        if (memspace == LSFC_MEM_DEVICE) {
-            pw_gather_sources(p->kernel0.p, (cplx*)out, dsrc.p, (int)nsrc, p->dims, p->stream);
-            LSFC_HIP(hipStreamSynchronize(p->stream));
-        } else {
-            // stage in batches of at most ~256 MiB
-            const int64_t per = std::max<int64_t>(1, ((int64_t)1 << 24) / N);
-            DevBuf<cplx> buf; buf.alloc((size_t)(std::min(per, nsrc) * N));
-            for (int64_t s0 = 0; s0 < nsrc; s0 += per) {
-                const int64_t cnt = std::min(per, nsrc - s0);
-                pw_gather_sources(p->kernel0.p, buf.p, dsrc.p + s0, (int)cnt, p->dims, p->stream);
-                LSFC_HIP(hipMemcpyAsync((cplx*)out + s0 * N, buf.p, (size_t)(cnt * N) * sizeof(cplx), hipMemcpyDeviceToHost, p->stream));
-                LSFC_HIP(hipStreamSynchronize(p->stream));
-            }
-        }
-    });
-}
-
 int lsfc_plan_set_stream(lsfc_plan* plan, void* hip_stream) {
     return guarded([&] {
         LSFC_REQUIRE(plan, "NULL plan");
@@ -1128,93 +577,13 @@ int lsfc_plan_set_tuning(lsfc_plan* plan, const char* key, int value) {
     return guarded([&] {
         LSFC_REQUIRE(plan && key, "NULL argument");
         if (plan->multi) { for (auto& sp : plan->multi->sub) { const int rc = lsfc_plan_set_tuning(sp.get(), key, value); if (rc != LSFC_OK) fail(rc, "%s", lsfc_last_error()); } return; }
-        const std::string k(key);
-        if (k == "split_x") plan->tuning.split_x = value != 0;
-        else if (k == "split_s") plan->tuning.split_s = value != 0;
-        else if (k == "split_z") plan->tuning.split_z = value;
-        else if (k == "z_half") plan->tuning.z_half = value;
-        else if (k == "tw_lds") plan->tuning.tw_lds = value;
-        else if (k == "sym_prefetch") plan->tuning.sym_prefetch = value;
-        else if (k == "ytile_g") plan->tuning.ytile_g = value;
-        else if (k == "ytile_z") plan->tuning.ytile_z = value;
-        else if (k == "batch_fuse") plan->tuning.batch_fuse = value;
-        else if (k == "z_persist") plan->tuning.z_persist = value;
-        else if (k == "xlane") plan->tuning.xlane = value;
-        else fail(LSFC_EINVAL, "unknown tuning key '%s'", key);
-    });
-}
-
-int lsfc_time_apply(lsfc_plan* plan, const double* x_dev, double* y_dev, int reps, double* ms_total) {
-    return guarded([&] {
-        LSFC_REQUIRE(plan && x_dev && y_dev && ms_total && reps >= 1, "bad argument");
-        LSFC_REQUIRE(!plan->multi, "time a multi-device plan from the host around lsfc_multi_apply_dev + lsfc_plan_synchronize");
-        LSFC_HIP(hipSetDevice(plan->device));
-        hipEvent_t e0, e1;
-        LSFC_HIP(hipEventCreate(&e0)); LSFC_HIP(hipEventCreate(&e1));
-        LSFC_HIP(hipEventRecord(e0, plan->stream));
-        for (int r = 0; r < reps; ++r) plan_apply_dev(plan, (const cplx*)x_dev, (cplx*)y_dev);
-        LSFC_HIP(hipEventRecord(e1, plan->stream));
-        LSFC_HIP(hipEventSynchronize(e1));
-        float ms = 0; LSFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-        *ms_total = ms;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    });
-}
-
-int lsfc_profile_apply(lsfc_plan* plan, const double* x_dev, double* y_dev, int reps, int max_stages, const char** names,
-                       double* ms, double* bytes, int* nstages) {
-    return guarded([&] {
-        LSFC_REQUIRE(plan && names && ms && bytes && nstages && reps >= 1, "bad argument");
-        if (plan->multi) { multi_profile(plan, reps, max_stages, names, ms, bytes, nstages); return; }    // (on the ranks' staging vectors)
-        LSFC_REQUIRE(x_dev && y_dev, "bad argument");
-        LSFC_HIP(hipSetDevice(plan->device));
-        lsfc_plan* p = plan;
-        const cplx* x = (const cplx*)x_dev; cplx* y = (cplx*)y_dev;
-        hipStream_t st = p->stream;
-        const double N = (double)p->N, C = 16.0;
-        struct Stage { const char* name; double bytes; std::function<void()> run; };
-        std::vector<Stage> stages;
-        auto stages_add_fn = [](std::vector<Stage>& v) {
-            return [&v](const char* name, double bytes, std::function<void()> run) { v.push_back({name, bytes, std::move(run)}); };
-        };
-        // the operator lsfc_plan_set_op selected; nub = the 8 B per point of nu, in the pass that multiplies by it
-        const ConvOp op = plan_operator(p);
-        const double nu_in = op.nu == NuSide::INPUT ? 8 * N : 0.0, nu_out = op.nu == NuSide::OUTPUT ? 8 * N : 0.0;
-        if (p->dist) {
-            dist_profile_stages(p, x, y, stages_add_fn(stages));
-        } else if (p->pipeline == lsfc_plan::PRUNED) {
-            // the production passes, one stage each
-            VecBatch vb{}; vb.x[0] = x; vb.y[0] = y;
-            const Slab all = whole_grid(p);
-            const bool d3 = p->ndim == 3;
-            stages.push_back({"xfwd", N * C + nu_in + 2 * N * C, [=] { pass_xfwd(p, vb, 1, op, all, st); }});
-            if (d3) stages.push_back({"yfwd", (2 + 4) * N * C, [=] { pass_yfwd(p, 1, all, st); }});
-            stages.push_back({d3 ? "zfused" : "yfused", d3 ? (4 + 8 + 4) * N * C : (2 + 4 + 2) * N * C, [=] { pass_fused(p, 1, st); }});
-            if (d3) stages.push_back({"yinv", (4 + 2) * N * C, [=] { pass_yinv(p, 1, all, st); }});
-            stages.push_back({"xinv", (2 + 1 + 1) * N * C + nu_out, [=] { pass_xinv(p, vb, 1, op, all, st); }});
-        } else {
-            const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
-            const double P = (double)total;
-            const double* nui = op.nu == NuSide::INPUT ? p->nu.p : nullptr; const double* nuo = op.nu == NuSide::OUTPUT ? p->nu.p : nullptr;
-            stages.push_back({"embed", N * C + nu_in + P * C, [=] { pw_embed(x, nui, p->W.p, p->dims, p->pads, st, op.conj); }});
-            stages.push_back({"rocfft_fwd", 2 * P * C, [=] { p->fwd->exec(p->W.p, st); }});
-            stages.push_back({"symbol_mul", 3 * P * C, [=] { pw_mul_inplace(p->W.p, p->sym.p, total, st); }});
-            stages.push_back({"rocfft_inv", 2 * P * C, [=] { p->inv->exec(p->W.p, st); }});
-            stages.push_back({"crop_axpy", 3 * N * C + nu_out, [=] { pw_crop_axpy(p->W.p, x, y, op.alpha, op.beta, p->dims, p->pads, p->crop, st, nuo, op.conj); }});
+        for (const TuningKnob& k : TUNING_KNOBS) {
+            if (!k.settable || strcmp(k.key, key) != 0) continue;
+            if (k.flag) plan->tuning.*k.flag = value != 0;
+            else plan->tuning.*k.value = value;
+            return;
         }
-        LSFC_REQUIRE((int)stages.size() <= max_stages, "max_stages too small (need %d)", (int)stages.size());
-        *nstages = (int)stages.size();
-        std::vector<hipEvent_t> ev(stages.size() + 1);
-        for (auto& e : ev) LSFC_HIP(hipEventCreate(&e));
-        for (size_t i = 0; i < stages.size(); ++i) { names[i] = stages[i].name; bytes[i] = stages[i].bytes; ms[i] = 0.0; }
-        for (int r = 0; r < reps; ++r) {
-            LSFC_HIP(hipEventRecord(ev[0], st));
-            for (size_t i = 0; i < stages.size(); ++i) { stages[i].run(); LSFC_HIP(hipEventRecord(ev[i + 1], st)); }
-            LSFC_HIP(hipEventSynchronize(ev[stages.size()]));
-            for (size_t i = 0; i < stages.size(); ++i) { float t = 0; LSFC_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1])); ms[i] += t; }
-        }
-        for (size_t i = 0; i < stages.size(); ++i) ms[i] /= reps;
-        for (auto& e : ev) (void)hipEventDestroy(e);
+        fail(LSFC_EINVAL, "unknown tuning key '%s'", key);
     });
 }
 

@@ -45,7 +45,7 @@ struct GmresWorkspace {
     ~GmresWorkspace();
 };
 
-// Host-vector apply as a pipeline (plan.hip: host_pipelined_convolve): copy streams and per-chunk events
+// Host-vector apply as a pipeline (host_apply.hip: host_pipelined_convolve): copy streams and per-chunk events
 struct HostPipe {
     hipStream_t up = nullptr, down = nullptr;      // non-blocking: ordered against the plan's stream by the events only
     std::vector<hipEvent_t> ev_up, ev_down;        // chunk c of x has landed / chunk c of y is ready
@@ -161,12 +161,14 @@ namespace lsfc {
 enum class NuSide { NONE, INPUT, OUTPUT };
 struct ConvOp { NuSide nu; bool conj; double alpha, beta; };
 inline ConvOp conv_plain(bool use_nu, double alpha, double beta) { return ConvOp{use_nu ? NuSide::INPUT : NuSide::NONE, false, alpha, beta}; }
+// M or a bare convolution, which is all that distributed and multi-device plans know (lsfc_plan_set_op refuses them)
+inline bool conv_forward_only(const ConvOp& op) { return op.nu != NuSide::OUTPUT && !op.conj; }
 // "the operator" of the plan: M, or what lsfc_plan_set_op selected
 inline ConvOp plan_operator(const lsfc_plan* p) {
     const double w2 = p->omega * p->omega;
     return p->op == LSFC_OP_N ? ConvOp{NuSide::INPUT, false, 1.0, w2} : ConvOp{NuSide::OUTPUT, p->op == LSFC_OP_H, 1.0, w2};
 }
-// device pointers, stream-ordered.
+// device pointers, stream-ordered (apply.hip).
 void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op);
 // nrhs <= LSFC_MAX_BATCH right-hand sides in one pass of the pipeline: y_j = alpha*x_j + beta*conv(...x_j); the symbol is read
 // once per batch in the fused pass (pruned pipeline; the other pipelines run the members one after the other)
@@ -181,20 +183,16 @@ void plan_apply_batch_dev(lsfc_plan* p, const cplx* const* in, cplx* const* out,
 // callback gets them one by one, in order, a host callback through `pinned`.  The size of an own object is checked here, under `who`.
 constexpr double DEFAULT_RELTOL = 0x1p-26;      // sqrt(eps)
 constexpr int KRYLOV_NRHS_MAX = 64;             // right-hand sides of one lsfc_gmres_batch / lsfc_bicgstabl_batch call
-// grows the plan's staging buffers xs and ys to `count` complex each (host vectors on their way to and from the device)
+// grows the plan's staging buffers xs and ys to `count` complex each (host vectors on their way to and from the device; host_apply.hip)
 void plan_ensure_staging(lsfc_plan* p, int64_t count);
 // The library's own preconditioner object (fn == lsfc_precond_callback) approximates the inverse of M, M^T or M^H as its own
-// op says (lsfc_precond_set_op): refused unless that is the plan's op.  A caller's callback passes.
+// op says (lsfc_precond_set_op): refused unless that is the plan's op.  A caller's callback passes.  (precond.hip, like Precond)
 void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, void* precond_user, const char* who);
 struct Precond {
     lsfc_precond_fn fn; void* user; bool on_device, own; int64_t N;
     Precond(lsfc_precond_fn fn, void* user, bool on_device, bool meet, int64_t N, const char* who);
     void apply(cplx* const* v, size_t cnt, cplx* pinned, hipStream_t st) const;
 };
-
-// The fused z pass of the 3D tiled layout on `Wc` x' storage indices, starting at the tile that the offsets into A2 and
-// the symbol point to (the whole range on one device; dist.hip: one chunk of the owned range)
-void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st);
 
 // makes `device` current.  Without any device: LSFC_ENODEV, "no HIP device available: the <what> has no CPU fallback", with HIP's
 // reason in brackets after "available" if say_why.  The caller warms up (pruned_warmup) where work follows.
@@ -210,8 +208,9 @@ bool plan_quarter_symbol_ok(const lsfc_plan* p);                                
 void symbol_gv2d_literal(lsfc_plan* p, double box, DevBuf<cplx>& G, int lit[3]);       // -> (4n,4m) centred
 void symbol_trap2d_literal(lsfc_plan* p, double x0, double y0, double h, cplx d0, DevBuf<cplx>& G); // -> fft(Ge), (2n-1,2m-1)
 
-// slab-distributed operator (dist.hip)
-void dist_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double alpha, double beta);
+// slab-distributed operator (dist.hip).  Distributed and multi-device plans know M and the bare convolutions only: an op with nu
+// on the output or with conj is refused (LSFC_EINVAL)
+void dist_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op);
 void dist_allreduce_sum(lsfc_plan* p, cplx* dev, int count);           // no-op unless a real multi-rank plan
 void dist_profile_stages(lsfc_plan* p, const cplx* x, cplx* y,
                          std::function<void(const char*, double, std::function<void()>)> add);
@@ -223,13 +222,13 @@ void plan_make_twiddles(lsfc_plan* p, int axis, int L);
 void plan_setup_symbol_rows(lsfc_plan* p, const cplx* G2, const std::vector<int>& perm_y, const std::vector<int>& perm_z, DevBuf<int>& pyrow);
 
 // single-process multi-device plan (dist.hip): x[r], y[r] = device pointers of rank r's slab on devices[r]
-void multi_convolve_dev(lsfc_plan* root, const cplx* const* x, cplx* const* y, bool use_nu, double alpha, double beta);
-void multi_convolve_host(lsfc_plan* root, const cplx* x, cplx* y, bool use_nu, double alpha, double beta);   // scatter, apply, gather
+void multi_convolve_dev(lsfc_plan* root, const cplx* const* x, cplx* const* y, const ConvOp& op);
+void multi_convolve_host(lsfc_plan* root, const cplx* x, cplx* y, const ConvOp& op);   // scatter, apply, gather
 void multi_allreduce_sum(lsfc_plan* root, cplx* const* dev, int count);   // dev[r] on devices[r], stream-ordered on the sub-plan streams
 void multi_synchronize(lsfc_plan* root);
 void multi_profile(lsfc_plan* root, int reps, int max_stages, const char** names, double* ms, double* bytes, int* nstages);
 
-// the spatial kernel: p->kernel0 = convolution of a unit source at grid index 0 (no nu), built on first use (plan.hip)
+// the spatial kernel: p->kernel0 = convolution of a unit source at grid index 0 (no nu), built on first use (apply.hip)
 void plan_kernel0(lsfc_plan* p);
 // The gathers K[|i - s|] of lsfc_sample_sources and sparsify.hip are rows of G only for a kernel that is even in every axis.
 // The builders' kernels are; a literal symbol (lsfc_plan_create_2d/3d) is measured once per plan: the responses to unit sources

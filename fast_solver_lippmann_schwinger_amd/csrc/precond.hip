@@ -684,6 +684,36 @@ void precond_apply_batch_dev(lsfc_precond* pc, cplx* const* v, int cnt, hipStrea
 int64_t precond_size(const lsfc_precond* pc) { return pc->N; }
 int precond_op(const lsfc_precond* pc) { return pc->op; }
 
+// the preconditioner hand-off of the Krylov solvers (plan.hpp)
+void plan_check_precond_op(const lsfc_plan* p, lsfc_precond_fn fn, void* precond_user, const char* who) {
+    if (fn != &lsfc_precond_callback) return;
+    static const char* const names[] = {"LSFC_OP_N", "LSFC_OP_T", "LSFC_OP_H"};
+    const int pop = precond_user ? precond_op((const lsfc_precond*)precond_user) : LSFC_OP_N;
+    LSFC_REQUIRE(pop == p->op, "%s%sthe library's preconditioner object is set to %s and approximates the inverse of that form of M, the plan is set to %s: "
+                 "lsfc_precond_set_op and lsfc_plan_set_op must agree", who ? who : "", who ? ": " : "", names[pop], names[p->op]);
+}
+
+Precond::Precond(lsfc_precond_fn f, void* u, bool dev, bool meet, int64_t n, const char* who)
+    : fn(f), user(u), on_device(dev), own(meet && dev && f == &lsfc_precond_callback), N(n) {
+    const int64_t have = own && user ? precond_size((lsfc_precond*)user) : -1;
+    if (own) LSFC_REQUIRE(have == N, "%s%spreconditioner: size mismatch (%lld vs %lld)", who ? who : "", who ? ": " : "", (long long)N, (long long)have);
+}
+
+void Precond::apply(cplx* const* v, size_t cnt, cplx* pinned, hipStream_t st) const {
+    if (!fn) return;
+    if (own) { precond_apply_batch_dev((lsfc_precond*)user, v, (int)cnt, st); return; }
+    for (size_t j = 0; j < cnt; ++j) {
+        if (!on_device) {
+            LSFC_HIP(hipMemcpyAsync(pinned, v[j], (size_t)N * sizeof(cplx), hipMemcpyDeviceToHost, st));
+            LSFC_HIP(hipStreamSynchronize(st));
+        }
+        const int rc = fn(user, (double*)(on_device ? v[j] : pinned), N);
+        if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+        // (whatever next goes into the pinned vector is ordered after this copy on st)
+        if (!on_device) LSFC_HIP(hipMemcpyAsync(v[j], pinned, (size_t)N * sizeof(cplx), hipMemcpyHostToDevice, st));
+    }
+}
+
 // loads this translation unit's code object on the current device (pruned.hip: pruned_warmup -- every code object of the library is
 // resident before the first transfer or pass of a process exists; DESIGN 3, "The round-2 first-apply GPU fault")
 __global__ void k_warmup_precond(int* p) { if (p) *p = 0; }

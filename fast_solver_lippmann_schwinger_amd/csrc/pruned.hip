@@ -162,19 +162,10 @@ static bool env_flag(const char* name, bool dflt) {
 
 PrunedTuning pruned_default_tuning() {
     PrunedTuning t;
-    t.split_x = env_flag("LSFC_SPLIT_X", true);
-    t.split_s = env_flag("LSFC_SPLIT_S", true);
-    if (const char* v = getenv("LSFC_SPLIT_Z")) t.split_z = atoi(v);
-    if (const char* v = getenv("LSFC_PAD1")) t.pad1 = atoi(v);
-    if (const char* v = getenv("LSFC_PAD2")) t.pad2 = atoi(v);
-    if (const char* v = getenv("LSFC_Z_HALF")) t.z_half = atoi(v);
-    if (const char* v = getenv("LSFC_TW_LDS")) t.tw_lds = atoi(v);
-    if (const char* v = getenv("LSFC_SYM_PREFETCH")) t.sym_prefetch = atoi(v);
-    if (const char* v = getenv("LSFC_YTILE_G")) t.ytile_g = atoi(v);
-    if (const char* v = getenv("LSFC_YTILE_Z")) t.ytile_z = atoi(v);
-    if (const char* v = getenv("LSFC_BATCH_FUSE")) t.batch_fuse = atoi(v);
-    if (const char* v = getenv("LSFC_Z_PERSIST")) t.z_persist = atoi(v);
-    if (const char* v = getenv("LSFC_XLANE")) t.xlane = atoi(v);
+    for (const TuningKnob& k : TUNING_KNOBS) {
+        if (k.flag) t.*k.flag = env_flag(k.env, t.*k.flag);
+        else if (const char* v = getenv(k.env)) t.*k.value = atoi(v);
+    }
     return t;
 }
 

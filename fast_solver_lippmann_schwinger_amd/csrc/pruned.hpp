@@ -33,6 +33,27 @@ struct PrunedTuning {
                                     // the padded grid has <= 2^24 points, where launches and not bytes bound the apply:
                                     // profiles/r02_batch_apply.jsonl -- 2.3x per right-hand side at 48^3, -5 % at 256^3)
 };
+// Every knob once: its lsfc_plan_set_tuning key, the environment variable that sets its default at plan creation
+// (pruned_default_tuning), its field -- a flag or an integer --, and whether it can still be set on a finished plan.
+//   environment, flag:    unset or empty keeps the default; a first character 1, y or t is true, anything else false
+//   environment, integer: atoi whenever the variable is set
+//   set_tuning:           value != 0 for a flag, the value itself for an integer
+struct TuningKnob { const char* key; const char* env; bool PrunedTuning::* flag; int PrunedTuning::* value; bool settable; };
+inline constexpr TuningKnob TUNING_KNOBS[] = {
+    {"split_x", "LSFC_SPLIT_X", &PrunedTuning::split_x, nullptr, true},
+    {"split_s", "LSFC_SPLIT_S", &PrunedTuning::split_s, nullptr, true},
+    {"split_z", "LSFC_SPLIT_Z", nullptr, &PrunedTuning::split_z, true},
+    {"pad1", "LSFC_PAD1", nullptr, &PrunedTuning::pad1, false},          // (the work arrays are laid out at plan creation)
+    {"pad2", "LSFC_PAD2", nullptr, &PrunedTuning::pad2, false},
+    {"z_half", "LSFC_Z_HALF", nullptr, &PrunedTuning::z_half, true},
+    {"tw_lds", "LSFC_TW_LDS", nullptr, &PrunedTuning::tw_lds, true},
+    {"sym_prefetch", "LSFC_SYM_PREFETCH", nullptr, &PrunedTuning::sym_prefetch, true},
+    {"ytile_g", "LSFC_YTILE_G", nullptr, &PrunedTuning::ytile_g, true},
+    {"ytile_z", "LSFC_YTILE_Z", nullptr, &PrunedTuning::ytile_z, true},
+    {"batch_fuse", "LSFC_BATCH_FUSE", nullptr, &PrunedTuning::batch_fuse, true},
+    {"z_persist", "LSFC_Z_PERSIST", nullptr, &PrunedTuning::z_persist, true},
+    {"xlane", "LSFC_XLANE", nullptr, &PrunedTuning::xlane, true},
+};
 
 bool pruned_length_supported(int64_t L);
 // load EVERY code object of the library on `device` (the current device) once, ahead of the first transfer or pass (fft_kernels.hip)

@@ -417,3 +417,122 @@ def test_symbol_storage_switches(lsfc, even_y, even_z, monkeypatch):
         # the persistent forms need the z-even half symbol
         expect(z, family="zfused_persist" if (zp and even_z is None) else "zfused")
         c.check(f"even_y={even_y} even_z={even_z} z_persist={zp}", convolve=True)
+
+
+# ---------------------------------------------------------------------------- e. the knobs: environment route = set_tuning route
+_OPERANDS = {}
+
+
+def operands(grid, dims, axes):
+    """a random symbol on `grid`, even along `axes`, with nu and b for `dims`; built once (no oracle: the two routes are compared with each other)"""
+    key = (grid, dims, axes)
+    if key not in _OPERANDS:
+        rng = np.random.default_rng(sum(grid) + sum(dims))
+        G = np.fft.fftshift(symmetrise(rng.standard_normal(grid) + 1j * rng.standard_normal(grid), axes))
+        N = int(np.prod(dims))
+        _OPERANDS[key] = (G, rng.uniform(-0.3, 0.3, N), rng.standard_normal(N) + 1j * rng.standard_normal(N))
+    return _OPERANDS[key]
+
+
+class Routes:
+    """plans of one operator, their knobs set through the environment at creation or through set_tuning afterwards"""
+
+    def __init__(self, lsfc, monkeypatch, shape):
+        # "z": z_case at 1024 points, 6 short of a full line; "cube": 16^3
+        self.grid, self.dims = {"z": ((32, 32, 1024), (16, 16, 506)), "cube": ((32, 32, 32), (16, 16, 16))}[shape]
+        self.G, self.nu, self.b = operands(self.grid, self.dims, (0, 1, 2))
+        self.lsfc, self.mp = lsfc, monkeypatch
+
+    def plan(self, env=None, **knobs):
+        for k, v in (env or {}).items():
+            self.mp.setenv(k, v)
+        M = self.lsfc.FastM3D(self.G, self.nu, *self.grid, *self.dims, 2.0)
+        for k in env or {}:
+            self.mp.delenv(k)
+        M.set_tuning(**knobs)
+        assert M.pipeline == "pruned-hip"
+        return M
+
+    def look(self, M):
+        """what the plan runs for 1 and 3 right-hand sides, and M * b"""
+        got = (M.describe_passes(1), M.describe_passes(3), M * self.b)
+        M.close()
+        return got
+
+
+# knob -> (shape, value, knobs that both routes set beside it so that it bites)
+KNOB_CASES = {
+    "split_x": ("cube", 0, {}), "split_s": ("cube", 0, {}), "ytile_g": ("cube", 1, {}), "ytile_z": ("cube", 2, {}), "batch_fuse": ("cube", 0, {}),
+    "split_z": ("z", 1, {}), "sym_prefetch": ("z", 0, {}), "tw_lds": ("z", 0, {}), "z_half": ("z", 1, {}), "z_persist": ("z", 3, {}),
+    # the lane exchanges are a choice of the persistent forms only: the ticketed whole tiles (auto there: 5)
+    "xlane": ("z", 0, {"z_persist": 6}),
+}
+assert set(KNOB_CASES) == set(DEFAULTS)
+
+
+@pytest.mark.parametrize("knob", sorted(KNOB_CASES))
+def test_knob_from_environment_equals_set_tuning(lsfc, monkeypatch, knob):
+    shape, v, beside = KNOB_CASES[knob]
+    R = Routes(lsfc, monkeypatch, shape)
+    knobs = {**beside, knob: v}
+    env1, env3, yenv = R.look(R.plan(env={"LSFC_" + k.upper(): str(val) for k, val in knobs.items()}))
+    set1, set3, yset = R.look(R.plan(**knobs))
+    base1, base3, _ = R.look(R.plan(**beside))
+    assert env1 == set1 and env3 == set3, (knob, env1, set1, env3, set3)
+    assert np.array_equal(yenv, yset), knob
+    # the knob bites at this shape: wired to another field, neither route would change what runs
+    assert (set1, set3) != (base1, base3), (knob, set1, set3)
+
+
+def test_knob_parsing_edges(lsfc, monkeypatch):
+    R = Routes(lsfc, monkeypatch, "cube")
+    base1, base3, ybase = R.look(R.plan())
+    assert pass_of(parse(base1), "xfwd")["SPLIT"] == 1 and pass_of(parse(base1), "zfused")["SPLIT"] == 1      # the defaults at 32 points
+    # a flag: empty keeps the default, "y" is true, anything else is false
+    assert R.look(R.plan(env={"LSFC_SPLIT_X": ""}))[:2] == (base1, base3)
+    d1, d3, y = R.look(R.plan(env={"LSFC_SPLIT_X": "y"}))
+    assert (d1, d3) == R.look(R.plan(split_x=1))[:2] and pass_of(parse(d1), "xfwd")["SPLIT"] == 1
+    d1, d3, y = R.look(R.plan(env={"LSFC_SPLIT_X": "n"}))
+    assert (d1, d3) == R.look(R.plan(split_x=0))[:2] and pass_of(parse(d1), "xfwd")["SPLIT"] == 0
+    # an integer: atoi of whatever is set, so empty is 0 -- whole-complex exchanges where auto (-1) splits
+    d1, d3, y = R.look(R.plan(env={"LSFC_SPLIT_Z": ""}))
+    s1, s3, ys = R.look(R.plan(split_z=0))
+    assert (d1, d3) == (s1, s3) and pass_of(parse(d1), "zfused")["SPLIT"] == 0 and np.array_equal(y, ys)
+    # the row paddings are read at plan creation only; an unknown key
+    M = R.plan()
+    for key in ("pad1", "no_such_knob"):
+        with pytest.raises(lsfc._lib.LsfcError, match="unknown tuning key") as e:
+            M.set_tuning(**{key: 8})
+        assert e.value.code == lsfc._lib.LSFC_EINVAL
+    assert (M.describe_passes(1), M.describe_passes(3)) == (base1, base3)
+    M.close()
+
+
+# ---------------------------------------------------------------------------- f. the stages of the profile = the apply
+STAGES = {"pruned-hip": ["xfwd", "yfwd", "zfused", "yinv", "xinv"], "rocfft-reduced": ["embed", "rocfft_fwd", "symbol_mul", "rocfft_inv", "crop_axpy"]}
+
+
+@pytest.mark.parametrize("dims,pipeline,names", [((16, 12, 10), "pruned-hip", STAGES["pruned-hip"]), ((5, 4, 3), "rocfft-reduced", STAGES["rocfft-reduced"]),
+                                                 ((24, 20), "pruned-hip", ["xfwd", "yfused", "xinv"])])
+def test_profile_stages_are_the_apply(lsfc, dims, pipeline, names):
+    import torch
+    grid = tuple(2 * v for v in dims)
+    G, nu, b = operands(grid, dims, tuple(range(len(dims))))          # even in every axis: M.T and M.H exist
+    if len(dims) == 3:
+        M = lsfc.FastM3D(G, nu, *grid, *dims, 2.0)
+    else:
+        M = lsfc.FastM(G, nu, *grid, *dims, 2.0, quadRule="Greengard_Vico")
+    assert M.pipeline == pipeline
+    x = torch.from_numpy(b).cuda()
+    for V in (M, M.T, M.H):
+        want = V * x
+        y = torch.full_like(x, float("nan"))
+        stages = lsfc.profile_apply(V, x, y, reps=1)
+        assert [s[0] for s in stages] == names, stages
+        assert all(nbytes > 0 and ms >= 0 for _, ms, nbytes in stages), stages
+        assert torch.equal(y, want)
+    # nu, 8 B per point, is counted in the pass that multiplies by it: the first stage of M, the last of M.T and M.H
+    N = M.N
+    sN, sT = lsfc.profile_apply(M, x, y, reps=1), lsfc.profile_apply(M.T, x, y, reps=1)
+    assert sN[0][2] - sT[0][2] == 8 * N and sT[-1][2] - sN[-1][2] == 8 * N
+    M.close()

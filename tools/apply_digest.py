@@ -1,0 +1,167 @@
+"""SHA-256 of the output of a fixed list of small applies: the bitwise fingerprint of the host side of a plan (csrc/plan.hip,
+csrc/apply.hip, csrc/host_apply.hip).  Two builds of the library that print the same lines create the same plans, choose the same
+kernels and hand them the same arguments.
+
+The applies (seeded inputs; device vectors unless "host" is said):
+  3D pruned            Greengard-Vico on 16^3 and on 24 x 20 x 40: M * b and the bare convolution
+  2D pruned            Greengard-Vico on 64 x 64, natural rows and tiles (LSFC_2D_TILED=1)
+  rocFFT-reduced       a random even symbol on 5 x 4 x 3
+  LSFC_FLAG_LITERAL_PAD   the same kind of symbol in 2D, on its own (48 x 40) grid
+  apply_batch          16^3, three right-hand sides, modes 0, 1, 2, fused (batch_fuse = 1) and member by member (0)
+  host vectors         16^3 with LSFC_HOST_PIPELINE = 0 and 2, one and three right-hand sides
+  M.T, M.H             16^3 and 5 x 4 x 3
+  sampleG3D            16^3, three sources
+  describe_passes      every plan above under the defaults, one and three right-hand sides
+
+    python tools/apply_digest.py                                    one JSON line per apply, this tree's library
+    python tools/apply_digest.py --libs parent=/path/to/liblsfc.so,this= [--out profiles/plan_split_refactor.jsonl]
+                                                                    one fresh child process per build (LSFC_LIBRARY; an empty
+                                                                    path is the library of this tree), one line per apply
+                                                                    with both digests and "equal"; exit status 1 if any differ"""
+import argparse
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+ENV = ("LSFC_2D_TILED", "LSFC_HOST_PIPELINE", "LSFC_BATCH_FUSE", "LSFC_HOST_COPY")
+
+
+def emit(label, a):
+    a = a.cpu().numpy() if hasattr(a, "cpu") else a
+    data = a.encode() if isinstance(a, str) else np.ascontiguousarray(a).tobytes()
+    print("DIGEST " + json.dumps({"apply": label, "sha256": hashlib.sha256(data).hexdigest()}), flush=True)
+
+
+def child():
+    import torch
+    import fast_solver_lippmann_schwinger_amd as lsfc
+
+    for k in ENV:
+        os.environ.pop(k, None)
+    rng = np.random.default_rng(2024)
+
+    def vec(N, rows=None):
+        shape = (N,) if rows is None else (rows, N)
+        return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+
+    def bump(*axes):
+        g = [np.exp(-40 * a ** 2) for a in axes]
+        out = 0.3 * g[0]
+        for a in g[1:]:
+            out = out[..., None] * a
+        return out.reshape(-1)
+
+    def even_symbol(grid):                              # centred order, even in every axis: the Green's matrix is symmetric
+        G = rng.standard_normal(grid) + 1j * rng.standard_normal(grid)
+        for ax in range(len(grid)):
+            G = 0.5 * (G + np.roll(np.flip(G, axis=ax), 1, axis=ax))
+        return np.fft.fftshift(G)
+
+    def describe(label, M):
+        emit(f"{label} describe_passes", M.pipeline + "\n" + M.describe_passes(1) + M.describe_passes(3))
+
+    def applies(label, M, convolve=True):
+        describe(label, M)
+        b = torch.from_numpy(vec(M.N)).cuda()
+        emit(f"{label} M*b", M * b)
+        if convolve:
+            emit(f"{label} convolution", lsfc.FFTconvolution(M, b))
+        return b
+
+    def axis(n):
+        return -0.5 + np.arange(n) / 16.0
+
+    # 3D pruned
+    x = axis(16)
+    M16 = lsfc.buildFastConvolution3D(x, x, x, None, None, None, 1.0 / 16, 16.0, bump(x, x, x))
+    b16 = applies("3D 16^3", M16)
+    x, y, z = axis(24), axis(20), axis(40)
+    M = lsfc.buildFastConvolution3D(x, y, z, None, None, None, 1.0 / 16, 12.0, bump(x, y, z))
+    applies("3D 24x20x40", M)
+    M.close()
+
+    # 2D pruned: natural rows, tiles
+    x = -0.5 + np.arange(64) / 64.0
+    for tiled in ("0", "1"):
+        os.environ["LSFC_2D_TILED"] = tiled
+        M = lsfc.buildFastConvolution(x, x, 1.0 / 64, 40.0, lambda X, Y: 0.3 * np.exp(-40 * (X ** 2 + Y ** 2)), quadRule="Greengard_Vico")
+        applies(f"2D 64x64 LSFC_2D_TILED={tiled}", M)
+        M.close()
+    os.environ.pop("LSFC_2D_TILED")
+
+    # rocFFT-reduced, and the literal grid in 2D
+    Mr = lsfc.FastM3D(even_symbol((10, 8, 6)), rng.uniform(-0.3, 0.3, 60), 10, 8, 6, 5, 4, 3, 2.0)
+    br = applies("rocFFT 5x4x3", Mr)
+    M = lsfc.FastM(even_symbol((48, 40)), rng.uniform(-0.3, 0.3, 24 * 20), 48, 40, 24, 20, 2.0, quadRule="Greengard_Vico", flags=lsfc._lib.LSFC_FLAG_LITERAL_PAD)
+    applies("2D 24x20 LITERAL_PAD", M, convolve=False)
+    M.close()
+
+    # transpose and adjoint
+    for label, M, b in (("3D 16^3", M16, b16), ("rocFFT 5x4x3", Mr, br)):
+        emit(f"{label} M.T*b", M.T * b)
+        emit(f"{label} M.H*b", M.H * b)
+    Mr.close()
+
+    # batches of three
+    B = vec(M16.N, 3)
+    Bd = torch.from_numpy(B).cuda()
+    for fuse in (1, 0):
+        M16.set_tuning(batch_fuse=fuse)
+        for mode in (0, 1, 2):
+            emit(f"apply_batch 16^3 nrhs=3 mode={mode} batch_fuse={fuse}", lsfc.apply_batch(M16, Bd, mode))
+    M16.set_tuning(batch_fuse=-1)
+
+    # host vectors: one staged copy each way, the chunked pipeline
+    for K in ("0", "2"):
+        os.environ["LSFC_HOST_PIPELINE"] = K
+        emit(f"host 16^3 LSFC_HOST_PIPELINE={K} nrhs=1", M16 * B[0])
+        emit(f"host 16^3 LSFC_HOST_PIPELINE={K} nrhs=3", lsfc.apply_batch(M16, B, 0))
+    os.environ.pop("LSFC_HOST_PIPELINE")
+
+    emit("sampleG3D 16^3 three sources", lsfc.sampleG3D(16.0, None, None, None, [0, M16.N // 2 + 3, M16.N - 1], M16))
+    M16.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--libs", default="", help="name=path,name=path: compare two builds, a fresh child process each; an empty path: this tree's library")
+    ap.add_argument("--out", default="", help="append the comparison lines to this file")
+    args = ap.parse_args()
+    if not args.libs:
+        return child()
+    (na, pa), (nb, pb) = [spec.split("=", 1) for spec in args.libs.split(",")]
+    got = {}
+    for name, path in ((na, pa), (nb, pb)):
+        env = dict(os.environ)
+        env.pop("LSFC_LIBRARY", None)
+        if path:
+            env["LSFC_LIBRARY"] = os.path.abspath(path)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=300)
+        if r.returncode != 0:                              # (nothing more is started on the device after a child that failed)
+            sys.exit(f"{name}: exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}")
+        got[name] = [json.loads(ln[len("DIGEST "):]) for ln in r.stdout.splitlines() if ln.startswith("DIGEST ")]
+    a, b = got[na], got[nb]
+    if [d["apply"] for d in a] != [d["apply"] for d in b]:
+        sys.exit("the two builds ran different lists of applies")
+    bad = 0
+    for da, db in zip(a, b):
+        equal = da["sha256"] == db["sha256"]
+        bad += not equal
+        line = json.dumps({"check": "apply_digest", "apply": da["apply"], f"sha256_{na}": da["sha256"], f"sha256_{nb}": db["sha256"], "equal": equal})
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    print(f"# {len(a)} applies, {bad} differ", file=sys.stderr)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
