@@ -54,11 +54,4 @@ void blocktri_get_block(const BlockTri*, int64_t k, cplx* host_out);  // the sto
 void blocktri_get_pivots(const BlockTri*, int64_t k, int64_t* host_out);
 void warmup_blocktri();
 
-// precond.hip: pc applied to cnt >= 1 device vectors at arbitrary addresses, in place, stream-ordered on st.  A
-// block-tridiagonal object takes them in groups of up to 8 through blocktri_enqueue_batch; an object of
-// lsfc_precond_create member by member through the single-vector path.
-void precond_apply_batch_dev(lsfc_precond* pc, cplx* const* v, int cnt, hipStream_t st);
-int64_t precond_size(const lsfc_precond* pc);
-int precond_op(const lsfc_precond* pc);                // LSFC_OP_N | _T | _H: what the applies of pc compute (lsfc_precond_set_op)
-
 } // namespace lsfc

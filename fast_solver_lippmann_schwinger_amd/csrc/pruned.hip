@@ -21,7 +21,7 @@ namespace lsfc {
     void pruned_warmup_f##F();                                                                                         \
     int pruned_twfull_len_f##F(int);                                                                                            \
     void pruned_twfull_f##F(int, const cplx*, cplx*);
-void warmup_pointwise(); void warmup_krylov_blas(); void warmup_symbol(); void warmup_precond(); void warmup_blocktri();      // pointwise.hip, krylov_blas.hip, symbol.hip, precond.hip, blocktri.hip
+void warmup_pointwise(); void warmup_krylov_blas(); void warmup_symbol(); void warmup_precond(); void warmup_trisolve(); void warmup_blocktri();      // pointwise.hip, krylov_blas.hip, symbol.hip, precond.hip, trisolve.hip, blocktri.hip
 LSFC_FAMILY_DECLS(2)
 LSFC_FAMILY_DECLS(3)
 LSFC_FAMILY_DECLS(5)
@@ -45,7 +45,7 @@ void pruned_warmup(int device) {
     // LSFC_EAGER_LOAD=0 (developer switch, diagnostics only): leave the code objects to HIP's lazy loading at first launch
     if (const char* e = getenv("LSFC_EAGER_LOAD")) if (e[0] == '0') return;
     pruned_warmup_f2(); pruned_warmup_f3(); pruned_warmup_f5();
-    warmup_pointwise(); warmup_krylov_blas(); warmup_symbol(); warmup_precond(); warmup_blocktri();
+    warmup_pointwise(); warmup_krylov_blas(); warmup_symbol(); warmup_precond(); warmup_trisolve(); warmup_blocktri();
     LSFC_HIP(hipDeviceSynchronize());
     done.insert(device);
 }

@@ -5,7 +5,7 @@
 
 The sparse LU stays on the host, as in the reference (UMFPACK there; scipy's SuperLU here -- any LU of Msp gives
 the same operator).  Its factors and As are uploaded once; `ldiv_` then runs entirely on the device (csrc/precond.hip:
-CSR SpMV + two level-scheduled sparse triangular solves replayed from one hipGraph), so under `gmres_` the Krylov
+CSR SpMV + the two level-scheduled sparse triangular solves of csrc/trisolve.hip, replayed from one hipGraph), so under `gmres_` the Krylov
 vector never crosses PCIe.  Msp / As are assembled on the device by sparsify.py (src/SparsifyingMatrix*.jl).
 
 A second route factorises on the device as well (csrc/blocktri.hip, lsfc_precond_create_blocktri): with the slowest grid

@@ -1,5 +1,5 @@
-"""Test infrastructure for the device preconditioner apply (csrc/precond.hip): a high-precision restatement of the
-operator lsfc_precond_create / lsfc_precond_apply define (include/lsfc.h), and a generator of triangular factors whose
+"""Test infrastructure for the device preconditioner apply (csrc/precond.hip, csrc/trisolve.hip): a high-precision
+restatement of the operator lsfc_precond_create / lsfc_precond_apply define (include/lsfc.h), and a generator of triangular factors whose
 dependency levels have prescribed sizes, so that a test can steer the launch schedule into each kind of segment.
 
     apply_ref(As, L, U, row_gather, col_scatter, row_scale, b, dtype)

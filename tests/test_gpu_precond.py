@@ -1,4 +1,4 @@
-"""GPU parity of the device-resident SparsifyingPreconditioner apply (csrc/precond.hip, through the C ABI) against
+"""GPU parity of the device-resident SparsifyingPreconditioner apply (csrc/precond.hip, csrc/trisolve.hip, through the C ABI) against
 the oracle's restatement of src/preconditioner.jl:132-170 (host sparse LU), and its use as Pl of the device GMRES.
 Tolerance 1e-10 relative l2 on the apply (observed ~1e-14: two sparse triangular solves of a well-conditioned pair)."""
 import ctypes as C
@@ -150,7 +150,7 @@ def test_gmres_with_device_preconditioner(lsfc):
     print("iterations with / without the sparsifying stand-in:", hist.iters, h0.iters)
 
 
-# ---- every schedule of the two triangular solves (csrc/precond.hip, build_factor) against a long-double reference ----
+# ---- every schedule of the two triangular solves (csrc/trisolve.hip, trisolve_build) against a long-double reference ----
 #
 # Synthetic factors (tests/precond_ref.py: make_factor) whose dependency levels steer the launch schedule into each of
 # its four segment kinds; every recipe is solved as L and, mirrored, as U in the same apply.  Criterion: the device

@@ -1,5 +1,5 @@
 """GPU tests of the device preconditioner applied to several right-hand sides at once (csrc/blocktri.hip:
-blocktri_enqueue_batch; csrc/precond.hip: lsfc_precond_apply_batch; csrc/gmres.hip: the second rendezvous of
+blocktri_enqueue_batch; csrc/precond.hip: lsfc_precond_apply_batch and the one apply sequence; csrc/gmres.hip: the second rendezvous of
 lsfc_gmres_batch): groups of up to 8 vectors go through one sweep that reads every S_k^{-1} once.
 
 References: scipy's sparse LU of the same Msp, the numpy restatement of the elimination (tests/blocktri_ref.py) and the

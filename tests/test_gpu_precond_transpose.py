@@ -130,6 +130,41 @@ def _get_op(lsfc, P):
     return op.value, nbytes.value
 
 
+# the smallest shape of the walk kernels (b <= 96) and the first of the step kernels
+@pytest.mark.parametrize("shape", [min(s for s in bc.SHAPES if s[0] <= 96), (97, 3, "scattered")], ids=bc.shape_id)
+def test_one_object_through_every_captured_sequence(lsfc, shape):
+    """One object replays the single apply and groups of 2 and 8 under N, T, H and N again, the group work space growing
+    under T (which drops the group graphs and keeps those of the single apply): every result is bitwise that of the same
+    call on a fresh object that has seen nothing else."""
+    L = lsfc._lib
+    lib = L.load()
+    b, K, _ = shape
+    Msp, As, _ = bc.built(shape)
+    B = bc.right_hand_sides(b * K, 8, seed=9)
+
+    def fresh():
+        return lsfc.SparsifyingPreconditioner(Msp, As, factor="blocktri", nblocks=K)
+
+    def call(P, R):                                        # R = 0: the single apply
+        return P.solve(B[0]) if R == 0 else P.solve_batch(B[:R])
+
+    steps = [(L.LSFC_OP_N, 0), (L.LSFC_OP_N, 2), (L.LSFC_OP_T, 8), (L.LSFC_OP_T, 0), (L.LSFC_OP_H, 2), (L.LSFC_OP_N, 0), (L.LSFC_OP_N, 8)]
+    P = fresh()
+    try:
+        for i, (op, R) in enumerate(steps):
+            L.check(lib.lsfc_precond_set_op(P._pc, op))
+            got = call(P, R)
+            Q = fresh()
+            try:
+                L.check(lib.lsfc_precond_set_op(Q._pc, op))
+                assert np.array_equal(got, call(Q, R)), f"step {i}: op {op}, {'single apply' if R == 0 else f'group of {R}'}"
+            finally:
+                Q.close()
+        assert P.batch_info()["largest_group"] == 8 and _get_op(lsfc, P)[0] == L.LSFC_OP_N
+    finally:
+        P.close()
+
+
 def _bb_cols(b):                                           # columns per workgroup of the N group product (csrc/blocktri.hip)
     return 32 if b < 1024 else (64 if b < 2048 else 128)
 
