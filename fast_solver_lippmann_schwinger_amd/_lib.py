@@ -66,6 +66,8 @@ SIGNATURES = {
     "lsfc_plan_dims": (_I, [_P, C.POINTER(_L), C.POINTER(_L)]),
     "lsfc_plan_pipeline": (C.c_char_p, [_P]),
     "lsfc_plan_set_nu": (_I, [_P, _P, _I]),
+    "lsfc_plan_set_nu_complex": (_I, [_P, _P, _I]),
+    "lsfc_plan_nu_is_complex": (_I, [_P, C.POINTER(C.c_int)]),
     "lsfc_plan_get_symbol": (_I, [_P, _P, _L, C.POINTER(_L)]),
     "lsfc_plan_set_op": (_I, [_P, _I]),
     "lsfc_plan_get_op": (_I, [_P, C.POINTER(_I)]),

@@ -25,17 +25,20 @@ static VecBatch slab_vectors(const lsfc_plan* p, const VecBatch& vb, int nrhs, S
 static cplx* slab_a1(const lsfc_plan* p, Slab s) { return p->A1.p + (int64_t)s.z0 * p->dims[1] * p->pitch1; }
 static cplx* slab_a2(const lsfc_plan* p, Slab s) { return p->A2.p + (int64_t)8 * s.z0; }
 
-// nu at the first plane of a slab, if the pass on side `side` of the convolution is the one that multiplies by it
-static const double* slab_nu(const lsfc_plan* p, const ConvOp& op, NuSide side, Slab s) {
-    return op.nu == side ? p->nu.p + (int64_t)s.z0 * p->dims[0] * p->dims[1] : nullptr;
+// nu (both planes; im null for real nu) at the first plane of a slab, if the pass on side `side` of the convolution is the one
+// that multiplies by it
+static NuPlanes slab_nu(const lsfc_plan* p, const ConvOp& op, NuSide side, Slab s) {
+    if (op.nu != side) return NuPlanes{nullptr, nullptr};
+    const int64_t off = (int64_t)s.z0 * p->dims[0] * p->dims[1];
+    return NuPlanes{p->nu.p + off, p->nu_im.p ? p->nu_im.p + off : nullptr};
 }
 void pass_xfwd(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Slab s, hipStream_t st) {
     const int Lx = p->pads[0], n = p->dims[0];
     const int64_t nlines = (int64_t)p->dims[1] * s.nz;
     const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    const double* nu = slab_nu(p, op, NuSide::INPUT, s);
-    if (p->tile2d) pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, p->A1.p, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, op.conj);
-    else pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu, slab_a1(p, s), p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, op.conj);
+    const NuPlanes nu = slab_nu(p, op, NuSide::INPUT, s);
+    if (p->tile2d) pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu.re, p->A1.p, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, op.conj, nu.im);
+    else pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu.re, slab_a1(p, s), p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, op.conj, nu.im);
 }
 void pass_yfwd(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {
     pruned_yfwd(p->pads[1], p->tuning, slab_a1(p, s), slab_a2(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
@@ -49,9 +52,9 @@ void pass_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Sla
     const int Lx = p->pads[0], n = p->dims[0];
     const int64_t nlines = (int64_t)p->dims[1] * s.nz;
     const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    const double* nu = slab_nu(p, op, NuSide::OUTPUT, s);
-    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, nu, op.conj);
-    else pruned_xinv(Lx, p->tuning, slab_a1(p, s), v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, nu, op.conj);
+    const NuPlanes nu = slab_nu(p, op, NuSide::OUTPUT, s);
+    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, nu.re, op.conj, nu.im);
+    else pruned_xinv(Lx, p->tuning, slab_a1(p, s), v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, nu.re, op.conj, nu.im);
 }
 
 // The three geometries of the fused pass.  3D: A2 as tiles [x'/8][Ly][pitch2 >= 8*l] of 8 interleaved z lines, the symbol as
@@ -121,9 +124,9 @@ void pass_fused(lsfc_plan* p, int nrhs, hipStream_t st) {
 // the per-stage profile are both visitors of this list, so a pass added here is run and timed alike.  (A template: the apply's
 // visitor inlines to the bare calls -- at 48^3 an apply is 36 us of launches, bounded by the host's enqueue time.)
 template <class Visit> static void for_each_stage(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op, Visit&& visit) {
-    // nu_in / nu_out: the 8 B per point of nu, in the pass that multiplies by it
-    const double N = (double)p->N, C = 16.0;
-    const double nu_in = op.nu == NuSide::INPUT ? 8 * N : 0.0, nu_out = op.nu == NuSide::OUTPUT ? 8 * N : 0.0;
+    // nu_in / nu_out: the 8 B per point of a real nu, the 16 B (two planes) of a complex one, in the pass that multiplies by it
+    const double N = (double)p->N, C = 16.0, nu_bytes = p->nu_im.p ? 16 * N : 8 * N;
+    const double nu_in = op.nu == NuSide::INPUT ? nu_bytes : 0.0, nu_out = op.nu == NuSide::OUTPUT ? nu_bytes : 0.0;
     if (p->pipeline == lsfc_plan::PRUNED) {
         // (round 3, measured slower and removed again -- profiles/r03_experiment_a1_window.log: the x and y passes chunk by chunk over
         // groups of z planes through one chunk-sized window of A1, hoping the Infinity Cache would absorb the 2 x 4.3 GB of A1 traffic)
@@ -138,12 +141,13 @@ template <class Visit> static void for_each_stage(lsfc_plan* p, int nrhs, const 
         const int64_t total = (int64_t)p->pads[0] * p->pads[1] * p->pads[2];
         const double P = (double)total;
         const cplx* x = vb.x[0]; cplx* y = vb.y[0];
-        const double* nui = op.nu == NuSide::INPUT ? p->nu.p : nullptr; const double* nuo = op.nu == NuSide::OUTPUT ? p->nu.p : nullptr;
-        visit("embed", N * C + nu_in + P * C, [&](hipStream_t st) { pw_embed(x, nui, p->W.p, p->dims, p->pads, st, op.conj); });
+        const Slab all = whole_grid(p);
+        const NuPlanes nui = slab_nu(p, op, NuSide::INPUT, all), nuo = slab_nu(p, op, NuSide::OUTPUT, all);
+        visit("embed", N * C + nu_in + P * C, [&](hipStream_t st) { pw_embed(x, nui.re, p->W.p, p->dims, p->pads, st, op.conj, nui.im); });
         visit("rocfft_fwd", 2 * P * C, [&](hipStream_t st) { p->fwd->exec(p->W.p, st); });
         visit("symbol_mul", 3 * P * C, [&](hipStream_t st) { pw_mul_inplace(p->W.p, p->sym.p, total, st); });
         visit("rocfft_inv", 2 * P * C, [&](hipStream_t st) { p->inv->exec(p->W.p, st); });
-        visit("crop_axpy", 3 * N * C + nu_out, [&](hipStream_t st) { pw_crop_axpy(p->W.p, x, y, op.alpha, op.beta, p->dims, p->pads, p->crop, st, nuo, op.conj); });
+        visit("crop_axpy", 3 * N * C + nu_out, [&](hipStream_t st) { pw_crop_axpy(p->W.p, x, y, op.alpha, op.beta, p->dims, p->pads, p->crop, st, nuo.re, op.conj, nuo.im); });
     }
 }
 

@@ -130,6 +130,90 @@ void k_xinv(const cplx* __restrict__ in, const VecBatch vb, int64_t ibatch, doub
     }
 }
 
+// The x passes of a plan whose nu is complex (lsfc_plan_set_nu_complex): kernels of their own, so that k_xfwd and k_xinv above are,
+// instruction for instruction, what they were before there was a complex nu.  Same template arguments, same forms, same launch
+// geometry and LDS; nu (the real plane) and nu_im (the imaginary one) are both non-null here.  The conjugation is outermost
+// (plan.hpp, ConvOp): with cj the input pass hands G the vector nu .* conj(x) = conj(conj(nu) .* x), the output pass stores
+// conj(nu) .* conj(v).  The imaginary loads use the end-of-line predicate and the clamped line index of the real ones.
+template <class C, int LPW, bool SPLIT, bool EXACT>
+__global__ __launch_bounds__(C::T * LPW)
+void k_xfwd_c(const VecBatch vb, int64_t obatch, const double* __restrict__ nu, const double* __restrict__ nu_im, cplx* __restrict__ out,
+              const cplx* __restrict__ tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, int cj) {
+    const cplx* __restrict__ x = vb.x[blockIdx.y];
+    out += (int64_t)blockIdx.y * obatch;
+    using LL = LdsLayout<1, 3, SPLIT>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int T = C::T, E = C::E;
+    const int t = threadIdx.x % T, ll = threadIdx.x / T;
+    const int64_t line = (int64_t)blockIdx.x * LPW + ll;
+    const bool valid = line < nlines;
+    const int64_t lc = valid ? line : nlines - 1;
+    const cplx* xin = x + lc * n;
+    const double* nin = nu + lc * n;
+    const double* iin = nu_im + lc * n;
+    cplx v[E];
+#pragma unroll
+    for (int e = 0; e < E / 2; ++e) {
+        const bool in = EXACT || t + T * e < n;
+        const cplx xv = in ? xin[t + T * e] : make_double2(0.0, 0.0);
+        const double a = in ? nin[t + T * e] : 0.0, b = in ? iin[t + T * e] : 0.0;
+        const double xr = xv.x, xi = cj ? -xv.y : xv.y;
+        v[e] = make_double2(fma(-b, xi, a * xr), fma(b, xr, a * xi));
+    }
+#pragma unroll
+    for (int e = E / 2; e < E; ++e) v[e] = make_double2(0.0, 0.0);
+    fft_forward<C, LL, true>(v, t, tw, smem, ll * LL::line_elems(C::L), 0);
+    if (valid) {
+        // (the chunked store of k_xfwd)
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int s = t + T * e;
+            const int c = (int)(((unsigned)s * (unsigned)wmagic) >> 22);
+            out[(int64_t)c * bstride + line * Wp + (s - c * W)] = v[e];
+        }
+    }
+}
+
+template <class C, int LPW, bool SPLIT, bool EXACT>
+__global__ __launch_bounds__(C::T * LPW)
+void k_xinv_c(const cplx* __restrict__ in, const VecBatch vb, int64_t ibatch, double alpha, double beta,
+              const cplx* __restrict__ tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride,
+              const double* nu, const double* nu_im, int cj) {
+    const cplx* xorig = vb.x[blockIdx.y];
+    cplx* y = vb.y[blockIdx.y];
+    in += (int64_t)blockIdx.y * ibatch;
+    using LL = LdsLayout<1, 3, SPLIT>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int T = C::T, E = C::E;
+    const int t = threadIdx.x % T, ll = threadIdx.x / T;
+    const int64_t line = (int64_t)blockIdx.x * LPW + ll;
+    const bool valid = line < nlines;
+    const int64_t lc = valid ? line : nlines - 1;
+    cplx v[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int s = t + T * e;
+        const int c = (int)(((unsigned)s * (unsigned)wmagic) >> 22);
+        v[e] = in[(int64_t)c * bstride + lc * Wp + (s - c * W)];
+    }
+    fft_inverse<C, LL, true>(v, t, tw, smem, ll * LL::line_elems(C::L), 0);
+    // y = alpha*x + beta * nu .* v, with cj beta * conj(nu) .* conj(v); nu and nu_im, like x, are read at the very index this thread
+    // then stores to (not __restrict__)
+    if (valid) {
+#pragma unroll
+        for (int e = 0; e < E / 2; ++e) {
+            if (EXACT || t + T * e < n) {
+                const int64_t idx = line * n + t + T * e;
+                const double vr = v[e].x, vi = cj ? -v[e].y : v[e].y;
+                const double br = beta * nu[idx], bi = cj ? -(beta * nu_im[idx]) : beta * nu_im[idx];
+                cplx r = make_double2(fma(-bi, vi, br * vr), fma(bi, vr, br * vi));
+                if (alpha != 0.0) { const cplx xo = xorig[idx]; r.x = fma(alpha, xo.x, r.x); r.y = fma(alpha, xo.y, r.y); }
+                y[idx] = r;
+            }
+        }
+    }
+}
+
 // (two 512-thread workgroups of the y passes per CU -- 128 registers, split exchanges, chained twiddle powers, no spills -- change
 // nothing at 512^3: yfwd 2.53 -> 2.51 ms, profiles/r02_experiment_ticketed_half_tiles.log; the passes are bound by their access pattern)
 // A1[Lx][m][l] (natural) -> A2[XB][l][Ly][Lx/XB]
@@ -647,21 +731,35 @@ template <class C> struct Tune {
 #endif
 };
 
-template <class C, bool SPLIT> static void xfwd_t(const PassForm& f, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, bool cj) {
+template <class C, bool SPLIT> static void xfwd_t(const PassForm& f, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, const double* nu_im, cplx* out, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, bool cj) {
     constexpr int LPW = Tune<C>::LPW;
     using LL = LdsLayout<1, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
+    const dim3 grid((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), block(C::T * LPW);
+    if (nu_im) {                    // a complex nu: the kernel of the same form that multiplies by both planes
+        auto k = f.full ? k_xfwd_c<C, LPW, SPLIT, true> : k_xfwd_c<C, LPW, SPLIT, false>;
+        allow_lds(k, lds);
+        hipLaunchKernelGGL(k, grid, block, lds, st, vb, obatch, nu, nu_im, out, tw, nlines, wmagic, W, Wp, n, bstride, (int)cj);
+        return;
+    }
     auto k = f.full ? k_xfwd<C, LPW, SPLIT, true> : k_xfwd<C, LPW, SPLIT, false>;
     allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, vb, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, (int)cj);
+    hipLaunchKernelGGL(k, grid, block, lds, st, vb, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, (int)cj);
 }
-template <class C, bool SPLIT> static void xinv_t(const PassForm& f, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, const double* nu, bool cj) {
+template <class C, bool SPLIT> static void xinv_t(const PassForm& f, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, const double* nu, const double* nu_im, bool cj) {
     constexpr int LPW = Tune<C>::LPW;
     using LL = LdsLayout<1, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
+    const dim3 grid((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), block(C::T * LPW);
+    if (nu_im) {
+        auto k = f.full ? k_xinv_c<C, LPW, SPLIT, true> : k_xinv_c<C, LPW, SPLIT, false>;
+        allow_lds(k, lds);
+        hipLaunchKernelGGL(k, grid, block, lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, nu, nu_im, (int)cj);
+        return;
+    }
     auto k = f.full ? k_xinv<C, LPW, SPLIT, true> : k_xinv<C, LPW, SPLIT, false>;
     allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), dim3(C::T * LPW), lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, nu, (int)cj);
+    hipLaunchKernelGGL(k, grid, block, lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, nu, (int)cj);
 }
 static void ytile(const PrunedTuning& tn, int L, int ngrp, int l, int& TG, int& TZ) {
     // auto (0): all groups x 1 plane, except at L >= 1024 where 32 groups x 8 planes keeps the 128-B chunks that the
@@ -939,20 +1037,20 @@ static int chunk_magic(int L, int W) {
     LSFC_REQUIRE(W >= 8 && W <= L && L % W == 0 && L <= 2048, "chunk width %d does not divide the line length %d", W, L);
     return (1 << 22) / W + 1;
 }
-void FAM(pruned_xfwd)(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, bool cj) {
+void FAM(pruned_xfwd)(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, bool cj, const double* nu_im) {
     const int wmagic = chunk_magic(L, W);
     if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
     const PassForm f = FAM(pruned_xform)(PassFamily::XFWD, L, tn, n);
-    if (f.split) { LSFC_DISPATCH_L(L, (xfwd_t<C, true>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
-    else         { LSFC_DISPATCH_L(L, (xfwd_t<C, false>(f, vb, nrhs, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
+    if (f.split) { LSFC_DISPATCH_L(L, (xfwd_t<C, true>(f, vb, nrhs, obatch, nu, nu_im, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
+    else         { LSFC_DISPATCH_L(L, (xfwd_t<C, false>(f, vb, nrhs, obatch, nu, nu_im, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
     LSFC_HIP(hipGetLastError());
 }
-void FAM(pruned_xinv)(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, const double* nu, bool cj) {
+void FAM(pruned_xinv)(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, const double* nu, bool cj, const double* nu_im) {
     const int wmagic = chunk_magic(L, W);
     if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
     const PassForm f = FAM(pruned_xform)(PassFamily::XINV, L, tn, n);
-    if (f.split) { LSFC_DISPATCH_L(L, (xinv_t<C, true>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, cj))); }
-    else         { LSFC_DISPATCH_L(L, (xinv_t<C, false>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, cj))); }
+    if (f.split) { LSFC_DISPATCH_L(L, (xinv_t<C, true>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, nu_im, cj))); }
+    else         { LSFC_DISPATCH_L(L, (xinv_t<C, false>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, nu_im, cj))); }
     LSFC_HIP(hipGetLastError());
 }
 void FAM(pruned_yfwd)(int L, const PrunedTuning& tn, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {

@@ -543,7 +543,35 @@ int lsfc_plan_set_nu(lsfc_plan* plan, const double* nu, int memspace) {
         LSFC_HIP(hipMemcpyAsync(plan->nu.p, nu, plan->N * sizeof(double),
                                 memspace == LSFC_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, plan->stream));
         LSFC_HIP(hipStreamSynchronize(plan->stream));
+        plan->nu_im.release();           // back on the real path (the stream has drained: no pass still reads the plane)
     });
+}
+// N (re, im) pairs -> the planes nu and nu_im; every pass that multiplies by nu takes both from here on (apply.hip: slab_nu)
+int lsfc_plan_set_nu_complex(lsfc_plan* plan, const double* nu, int memspace) {
+    return guarded([&] {
+        LSFC_REQUIRE(plan && nu, "NULL argument");
+        LSFC_REQUIRE(!plan->multi, "complex nu is not available on a multi-device plan");
+        LSFC_REQUIRE(!plan->dist, "complex nu is not available on a distributed (or simulated-rank) plan");
+        LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "unknown memspace %d", memspace);
+        LSFC_HIP(hipSetDevice(plan->device));
+        const cplx* pairs = (const cplx*)nu;
+        DevBuf<cplx> staged;
+        if (memspace == LSFC_MEM_HOST) {
+            staged.alloc((size_t)plan->N);
+            LSFC_HIP(hipMemcpyAsync(staged.p, nu, (size_t)plan->N * sizeof(cplx), hipMemcpyHostToDevice, plan->stream));
+            pairs = staged.p;
+        }
+        // both planes are made next to the plan's and swapped in together once they are complete: after an error the plan has
+        // the nu it had
+        DevBuf<double> re, im; re.alloc((size_t)plan->N); im.alloc((size_t)plan->N);
+        pw_split_planes(pairs, re.p, im.p, plan->N, plan->stream);
+        LSFC_HIP(hipStreamSynchronize(plan->stream));
+        plan->nu = std::move(re);
+        plan->nu_im = std::move(im);
+    });
+}
+int lsfc_plan_nu_is_complex(const lsfc_plan* plan, int* is_complex) {
+    return guarded([&] { LSFC_REQUIRE(plan && is_complex, "NULL argument"); *is_complex = plan->nu_im.p != nullptr; });
 }
 
 int lsfc_plan_get_symbol(const lsfc_plan* plan, double* out, int64_t capacity_complex, int64_t* count) {

@@ -107,7 +107,8 @@ struct lsfc_plan {
     double sym_defect = -1.0;        // symmetry defect of G through the plan's own convolution; < 0: not measured yet
     enum Pipeline { PRUNED = 0, ROCFFT_REDUCED = 1, ROCFFT_LITERAL = 2 } pipeline = PRUNED;
 
-    lsfc::DevBuf<double> nu;
+    lsfc::DevBuf<double> nu;             // Re nu
+    lsfc::DevBuf<double> nu_im;          // Im nu: allocated only while the plan's nu is complex (lsfc_plan_set_nu_complex)
     lsfc::DevBuf<lsfc::cplx> sym;        // pruned: storage-order tiled layout incl. 1/|pads|; rocFFT: FFT order incl. 1/|pads|
 
     // pruned pipeline
@@ -158,6 +159,11 @@ namespace lsfc {
 //   y = alpha*x + beta * [nu .*] c( G ( [nu .*] c(x) ) ),   c = conj or the identity,
 // nu on the input (M, lsfc_convolve with apply_nu), on the output (the transpose I + w^2 diag(nu) G) or nowhere.  The adjoint
 // conj(T conj(.)) is the transpose with c = conj: conj(alpha*conj(x)) = alpha*x for the real alpha, beta used here.
+// Complex nu: THE CONJUGATION IS OUTERMOST.  With conj the whole of [nu .*] G [nu .*] is conjugated entry by entry, so the pass
+// that multiplies by nu multiplies by conj(nu), on either side: the input pass hands G the vector conj(conj(nu) .* x) =
+// nu .* conj(x), the output pass stores conj(nu) .* conj(v).  The adjoint is then b + w^2 conj(nu) .* conj(G conj(b)).  What
+// describes G and the nu multiply literally (lsfc_convolve, mode 2 of lsfc_apply_batch, lsfc_sample_sources) has conj = false
+// and so multiplies by nu itself.
 enum class NuSide { NONE, INPUT, OUTPUT };
 struct ConvOp { NuSide nu; bool conj; double alpha, beta; };
 inline ConvOp conv_plain(bool use_nu, double alpha, double beta) { return ConvOp{use_nu ? NuSide::INPUT : NuSide::NONE, false, alpha, beta}; }
@@ -173,6 +179,8 @@ void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op);
 // nrhs <= LSFC_MAX_BATCH right-hand sides in one pass of the pipeline: y_j = alpha*x_j + beta*conv(...x_j); the symbol is read
 // once per batch in the fused pass (pruned pipeline; the other pipelines run the members one after the other)
 void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op);
+// Re nu and Im nu (null: nu is real) of the plan, or of a pass: both null where the pass does not multiply
+struct NuPlanes { const double* re; const double* im; };
 // the operator M = I + omega^2 G nu, or its transpose / adjoint (lsfc_plan_set_op)
 inline void plan_apply_dev(lsfc_plan* p, const cplx* x, cplx* y) { plan_convolve_dev(p, x, y, plan_operator(p)); }
 // ... on cnt (in, out) pairs, in groups of LSFC_MAX_BATCH that share one pass of the pipeline (the batched solvers)

@@ -11,8 +11,8 @@ namespace lsfc {
 
 // ---- rocFFT pipelines: embed and crop ---------------------------------------
 
-// W[p0][p1][p2] (x fastest) = (i<n && j<m && k<l) ? (nu?nu:1)*(cj ? conj(x) : x) : 0
-__global__ void k_embed(const cplx* __restrict__ x, const double* __restrict__ nu, cplx* __restrict__ W,
+// W[p0][p1][p2] (x fastest) = (i<n && j<m && k<l) ? (nu?nu:1)*(cj ? conj(x) : x) : 0; nu_im (null: real nu) the imaginary plane
+__global__ void k_embed(const cplx* __restrict__ x, const double* __restrict__ nu, const double* __restrict__ nu_im, cplx* __restrict__ W,
                         int n, int m, int l, int p0, int p1, int p2, int cj) {
     const int64_t total = (int64_t)p0 * p1 * p2;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -21,8 +21,13 @@ __global__ void k_embed(const cplx* __restrict__ x, const double* __restrict__ n
         if (i < n && j < m && k < l) {
             const int64_t s = i + (int64_t)n * (j + (int64_t)m * k);
             v = x[s];
-            if (nu) { const double c = nu[s]; v.x *= c; v.y *= c; }
-            if (cj) v.y = -v.y;
+            if (nu_im) {
+                const double a = nu[s], b = nu_im[s], xr = v.x, xi = cj ? -v.y : v.y;
+                v = make_double2(fma(-b, xi, a * xr), fma(b, xr, a * xi));
+            } else {
+                if (nu) { const double c = nu[s]; v.x *= c; v.y *= c; }
+                if (cj) v.y = -v.y;
+            }
         }
         W[idx] = v;
     }
@@ -35,23 +40,40 @@ __global__ void k_mul_inplace(cplx* __restrict__ W, const cplx* __restrict__ S, 
     }
 }
 
-// y = alpha*x + beta*(nu?nu:1)*(cj ? conj(w) : w), w = W[o0+i][o1+j][o2+k]
+// y = alpha*x + beta*(nu?nu:1)*(cj ? conj(w) : w), w = W[o0+i][o1+j][o2+k]; with nu_im the factor is nu, or conj(nu) with cj
 __global__ void k_crop_axpy(const cplx* __restrict__ W, const cplx* x, cplx* y, double alpha, double beta,
-                            int n, int m, int l, int p0, int p1, int o0, int o1, int o2, const double* __restrict__ nu, int cj) {
+                            int n, int m, int l, int p0, int p1, int o0, int o1, int o2, const double* __restrict__ nu, const double* __restrict__ nu_im, int cj) {
     const int64_t total = (int64_t)n * m * l;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         const int i = (int)(idx % n); const int64_t r = idx / n; const int j = (int)(r % m); const int k = (int)(r / m);
         const cplx w = W[(o0 + i) + (int64_t)p0 * ((o1 + j) + (int64_t)p1 * (o2 + k))];
-        const double bs = nu ? beta * nu[idx] : beta;
-        cplx v = make_double2(bs * w.x, bs * (cj ? -w.y : w.y));
+        cplx v;
+        if (nu_im) {
+            const double wi = cj ? -w.y : w.y, br = beta * nu[idx], bi = cj ? -(beta * nu_im[idx]) : beta * nu_im[idx];
+            v = make_double2(fma(-bi, wi, br * w.x), fma(bi, w.x, br * wi));
+        } else {
+            const double bs = nu ? beta * nu[idx] : beta;
+            v = make_double2(bs * w.x, bs * (cj ? -w.y : w.y));
+        }
         if (alpha != 0.0) { const cplx xo = x[idx]; v.x = fma(alpha, xo.x, v.x); v.y = fma(alpha, xo.y, v.y); }
         y[idx] = v;
     }
 }
 
-void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t st, bool conj) {
+__global__ void k_split_planes(const cplx* __restrict__ pairs, double* __restrict__ re, double* __restrict__ im, int64_t n) {
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        const cplx v = pairs[idx];
+        re[idx] = v.x; im[idx] = v.y;
+    }
+}
+void pw_split_planes(const cplx* pairs, double* re, double* im, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_split_planes, dim3(grid_for(n)), dim3(256), 0, st, pairs, re, im, n);
+    LSFC_HIP(hipGetLastError());
+}
+
+void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t st, bool conj, const double* nu_im) {
     const int64_t total = (int64_t)pads[0] * pads[1] * pads[2];
-    hipLaunchKernelGGL(k_embed, dim3(grid_for(total)), dim3(256), 0, st, x, nu, W, dims[0], dims[1], dims[2], pads[0], pads[1], pads[2], (int)conj);
+    hipLaunchKernelGGL(k_embed, dim3(grid_for(total)), dim3(256), 0, st, x, nu, nu_im, W, dims[0], dims[1], dims[2], pads[0], pads[1], pads[2], (int)conj);
     LSFC_HIP(hipGetLastError());
 }
 void pw_mul_inplace(cplx* W, const cplx* S, int64_t total, hipStream_t st) {
@@ -59,10 +81,10 @@ void pw_mul_inplace(cplx* W, const cplx* S, int64_t total, hipStream_t st) {
     LSFC_HIP(hipGetLastError());
 }
 void pw_crop_axpy(const cplx* W, const cplx* x, cplx* y, double alpha, double beta, const int dims[3], const int pads[3],
-                  const int off[3], hipStream_t st, const double* nu, bool conj) {
+                  const int off[3], hipStream_t st, const double* nu, bool conj, const double* nu_im) {
     const int64_t total = (int64_t)dims[0] * dims[1] * dims[2];
     hipLaunchKernelGGL(k_crop_axpy, dim3(grid_for(total)), dim3(256), 0, st, W, x, y, alpha, beta, dims[0], dims[1], dims[2],
-                       pads[0], pads[1], off[0], off[1], off[2], nu, (int)conj);
+                       pads[0], pads[1], off[0], off[1], off[2], nu, nu_im, (int)conj);
     LSFC_HIP(hipGetLastError());
 }
 

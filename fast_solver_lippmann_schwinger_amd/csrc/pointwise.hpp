@@ -4,11 +4,15 @@
 
 namespace lsfc {
 
-// rocFFT pipelines: W = pad((nu ? nu : 1) .* (conj ? conj(x) : x)) ...
-void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t, bool conj = false);
+// complex nu as the plan stores it: n (re, im) pairs -> the two planes re[n], im[n] (lsfc_plan_set_nu_complex)
+void pw_split_planes(const cplx* pairs, double* re, double* im, int64_t n, hipStream_t);
+// rocFFT pipelines: W = pad((nu ? nu : 1) .* (conj ? conj(x) : x)) ...  (nu_im: Im nu, with nu its real part; the factor of
+// conj(x) is then nu itself and that of conj(W) below conj(nu): the conjugation is outermost, plan.hpp)
+void pw_embed(const cplx* x, const double* nu, cplx* W, const int dims[3], const int pads[3], hipStream_t, bool conj = false,
+              const double* nu_im = nullptr);
 void pw_mul_inplace(cplx* W, const cplx* S, int64_t total, hipStream_t);
 void pw_crop_axpy(const cplx* W, const cplx* x, cplx* y, double alpha, double beta, const int dims[3], const int pads[3],
-                  const int off[3], hipStream_t, const double* nu = nullptr, bool conj = false);   // ... y = alpha*x + beta * nu .* (conj) crop(W)
+                  const int off[3], hipStream_t, const double* nu = nullptr, bool conj = false, const double* nu_im = nullptr);   // ... y = alpha*x + beta * nu .* (conj) crop(W)
 // unit-modulus probe vector number `which` and its conjugate, a function of the index only (the symmetry check of a plan)
 void pw_probe(cplx* v, cplx* vbar, int64_t n, int which, hipStream_t);
 // symbol preparation

@@ -9,8 +9,8 @@
 namespace lsfc {
 
 #define LSFC_FAMILY_DECLS(F)                                                                                                   \
-    void pruned_xfwd_f##F(int, const PrunedTuning&, const VecBatch&, int, int64_t, const double*, cplx*, const cplx*, int64_t, int, int, int, hipStream_t, int64_t, bool); \
-    void pruned_xinv_f##F(int, const PrunedTuning&, const cplx*, const VecBatch&, int, int64_t, double, double, const cplx*, int64_t, int, int, int, hipStream_t, int64_t, const double*, bool); \
+    void pruned_xfwd_f##F(int, const PrunedTuning&, const VecBatch&, int, int64_t, const double*, cplx*, const cplx*, int64_t, int, int, int, hipStream_t, int64_t, bool, const double*); \
+    void pruned_xinv_f##F(int, const PrunedTuning&, const cplx*, const VecBatch&, int, int64_t, double, double, const cplx*, int64_t, int, int, int, hipStream_t, int64_t, const double*, bool, const double*); \
     void pruned_yfwd_f##F(int, const PrunedTuning&, const cplx*, cplx*, const cplx*, int, int, int, int, int, hipStream_t, int, int64_t, int64_t);     \
     void pruned_yinv_f##F(int, const PrunedTuning&, const cplx*, cplx*, const cplx*, int, int, int, int, int, hipStream_t, int, int64_t, int64_t);     \
     void pruned_zfused_f##F(int, const PrunedTuning&, cplx*, const cplx*, const cplx*, const cplx*, const FusedGeom&, hipStream_t, int, int64_t); \
@@ -75,13 +75,13 @@ static void debug_check(const char* pass, int L) {
     default: fail(LSFC_EINVAL, "pruned pipeline: unsupported padded length %d", (int)(L)); } \
     debug_check(#NAME, (int)(L));
 
-void pruned_xfwd(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, bool conj) {
+void pruned_xfwd(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, bool conj, const double* nu_im) {
     LSFC_REQUIRE(nrhs >= 1 && nrhs <= LSFC_MAX_BATCH, "batch of %d right-hand sides (1..%d per launch)", nrhs, LSFC_MAX_BATCH);
-    LSFC_ROUTE(L, pruned_xfwd, L, tn, vb, nrhs, obatch, nu, out, tw, nlines, W, Wp, n, st, bstride, conj);
+    LSFC_ROUTE(L, pruned_xfwd, L, tn, vb, nrhs, obatch, nu, out, tw, nlines, W, Wp, n, st, bstride, conj, nu_im);
 }
-void pruned_xinv(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, const double* nu, bool conj) {
+void pruned_xinv(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, const double* nu, bool conj, const double* nu_im) {
     LSFC_REQUIRE(nrhs >= 1 && nrhs <= LSFC_MAX_BATCH, "batch of %d right-hand sides (1..%d per launch)", nrhs, LSFC_MAX_BATCH);
-    LSFC_ROUTE(L, pruned_xinv, L, tn, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, W, Wp, n, st, bstride, nu, conj);
+    LSFC_ROUTE(L, pruned_xinv, L, tn, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, W, Wp, n, st, bstride, nu, conj, nu_im);
 }
 void pruned_yfwd(int L, const PrunedTuning& tn, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
     LSFC_ROUTE(L, pruned_yfwd, L, tn, a1, a2, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2);

@@ -72,10 +72,13 @@ PrunedTuning pruned_default_tuning();
 // batch members in the work arrays
 void pruned_xfwd(int L, const PrunedTuning&, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t,
                  int64_t bstride = 0,      // bstride: distance between chunks of the storage axis (0: dense, Wp * nlines)
-                 bool conj = false);       // conj: transform conj(nu .* x)
-// y = alpha*x + beta * (nu ? nu : 1) .* (conj ? conj(v) : v), v the cropped inverse transform; nu like x is indexed as y is
+                 bool conj = false,        // conj: transform conj(nu .* x)
+                 const double* nu_im = nullptr);   // Im nu, with nu its real part: transform nu .* x, with conj nu .* conj(x)
+// y = alpha*x + beta * (nu ? nu : 1) .* (conj ? conj(v) : v), v the cropped inverse transform; nu like x is indexed as y is.
+// nu_im: Im nu, with nu its real part; with conj the factor is conj(nu) (the conjugation is outermost: plan.hpp, ConvOp)
 void pruned_xinv(int L, const PrunedTuning&, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta,
-                 const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t, int64_t bstride = 0, const double* nu = nullptr, bool conj = false);
+                 const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t, int64_t bstride = 0, const double* nu = nullptr, bool conj = false,
+                 const double* nu_im = nullptr);
 // p1: row pitch of A1 (>= Lx), p2: pitch of one storage-y row of an A2 tile (>= 8*l); both multiples of 8 elements
 void pruned_yfwd(int L, const PrunedTuning&, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t,
                  int nrhs = 1, int64_t batch1 = 0, int64_t batch2 = 0);

@@ -305,7 +305,7 @@ __global__ void k_gss(const cplx* __restrict__ K, const DevClass* __restrict__ c
 }
 
 __global__ void k_stamp(const StampClass* __restrict__ cls, const int* __restrict__ cls_of, int64_t n, int64_t m, int64_t l, int ndim,
-                        int64_t nnz, const double* __restrict__ nu, double w2, int64_t* __restrict__ rowptr, int64_t* __restrict__ col,
+                        int64_t nnz, const double* __restrict__ nu, const double* __restrict__ nu_im, double w2, int64_t* __restrict__ rowptr, int64_t* __restrict__ col,
                         cplx* __restrict__ As, cplx* __restrict__ AG, cplx* __restrict__ Msp) {
     const int64_t N = n * m * l;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < N; r += (int64_t)gridDim.x * blockDim.x) {
@@ -319,7 +319,10 @@ __global__ void k_stamp(const StampClass* __restrict__ cls, const int* __restric
             if (col) col[e] = j;
             if (As) As[e] = C.a[t];
             if (AG) AG[e] = C.ag[t];
-            if (Msp) { const double f = w2 * nu[j]; Msp[e] = make_double2(C.a[t].x + f * C.ag[t].x, C.a[t].y + f * C.ag[t].y); }
+            if (Msp && nu_im) {          // complex nu (nu_im a kernel argument, null for real nu): a + (w2 nu[j]) * ag, a complex multiply-add
+                const double fr = w2 * nu[j], fi = w2 * nu_im[j];
+                Msp[e] = make_double2(fma(-fi, C.ag[t].y, fma(fr, C.ag[t].x, C.a[t].x)), fma(fi, C.ag[t].x, fma(fr, C.ag[t].y, C.a[t].y)));
+            } else if (Msp) { const double f = w2 * nu[j]; Msp[e] = make_double2(C.a[t].x + f * C.ag[t].x, C.a[t].y + f * C.ag[t].y); }
         }
     }
 }
@@ -558,7 +561,7 @@ void sparsify_build(lsfc_plan* p, int64_t* rowptr, int64_t* col, cplx* As, cplx*
     }
     if (drp || dcol || das || dag || dmsp) {
         const int64_t blocks = std::min<int64_t>((N + 255) / 256, 1 << 16);
-        hipLaunchKernelGGL(k_stamp, dim3((unsigned)blocks), dim3(256), 0, st, dst.p, dof.p, g.n, g.m, g.l, g.ndim, nnz, p->nu.p,
+        hipLaunchKernelGGL(k_stamp, dim3((unsigned)blocks), dim3(256), 0, st, dst.p, dof.p, g.n, g.m, g.l, g.ndim, nnz, p->nu.p, p->nu_im.p,
                            p->omega * p->omega, drp, dcol, das, dag, dmsp);
         LSFC_HIP(hipGetLastError());
     }

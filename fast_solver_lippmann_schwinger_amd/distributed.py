@@ -14,6 +14,14 @@ from . import _lib as L
 from .operators import FastM3D
 
 
+def _real_nu(nu):
+    """distributed and multi-device plans take a real nu only (lsfc_plan_set_nu_complex refuses them): a complex dtype is an
+    error here, never a silently dropped imaginary part"""
+    if np.iscomplexobj(nu):
+        raise TypeError("complex nu is not available on a distributed or multi-device plan")
+    return np.ascontiguousarray(nu, dtype=np.float64).reshape(-1)
+
+
 def slab_range(l, rank, nranks):
     """z planes [lo, hi) owned by `rank` (the library requires nranks | l)."""
     if l % nranks:
@@ -49,7 +57,7 @@ def build_distributed_3d(n, h, k, nu_local, rank, nranks, device, m=None, l=None
     m = n if m is None else m
     l = n if l is None else l
     lo, hi = slab_range(l, rank, nranks)
-    nuv = np.ascontiguousarray(nu_local, dtype=np.float64).reshape(-1)
+    nuv = _real_nu(nu_local)
     if nuv.size != n * m * (hi - lo):
         raise ValueError("DimensionMismatch: nu_local")
     box = n * h                                   # |x[end] - x[1]| + h
@@ -73,7 +81,7 @@ class MultiDeviceFastM3D(FastM3D):
     def __init__(self, n, h, k, nu, devices, m=None, l=None, flags=0):
         m = n if m is None else m
         l = n if l is None else l
-        nuv = np.ascontiguousarray(nu, dtype=np.float64).reshape(-1)
+        nuv = _real_nu(nu)
         if nuv.size != n * m * l:
             raise ValueError("DimensionMismatch: nu")
         devs = (C.c_int * len(devices))(*[int(d) for d in devices])
@@ -134,7 +142,7 @@ class SimulatedRanks:
 
     def __init__(self, n, m, l, h, k, nu, nranks, device=0, flags=0):
         self.n, self.m, self.l, self.nranks = n, m, l, nranks
-        nu = np.ascontiguousarray(nu, dtype=np.float64).reshape(-1)
+        nu = _real_nu(nu)
         self.plans = (C.c_void_p * nranks)()
         self.bounds = [slab_range(l, r, nranks) for r in range(nranks)]
         for r, (lo, hi) in enumerate(self.bounds):

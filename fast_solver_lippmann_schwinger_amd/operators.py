@@ -14,6 +14,7 @@ Names, argument meaning and error behaviour follow the Julia reference
   gmres_ (= gmres!)                   IterativeSolvers.jl, call sites examples/example.jl:85,91
   bicgstabl_ (= bicgstabl!)           IterativeSolvers.jl (the short-recurrence alternative; same Pl hook)
   M.T, M.H, M.rmatvec                 transpose(M), M' of LinearMaps / rmatvec of scipy's LinearOperator (lsfc_plan_set_op)
+  complex nu, M.nu_is_complex         beyond the reference's nu::Array{Float64,1}: an absorbing medium (lsfc_plan_set_nu_complex)
 
 Vectors are flat complex128 arrays in column-major (x fastest) order: numpy
 arrays (host memory, copied through PCIe inside the call) or torch CUDA tensors
@@ -49,6 +50,28 @@ def _vec(a, N, name, count=1, plan=None):
     if arr.size != N * count:
         raise ValueError(f"DimensionMismatch: {name} has {arr.size} entries, operator needs {N * count}")
     return arr.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST, arr
+
+
+def _nu_array(nu):
+    """nu as the plan takes it, flat: a complex dtype stays complex128 (the complex path, even if every imaginary part is 0),
+    anything else becomes float64 (the real path)"""
+    nu = np.asarray(nu)
+    return np.ascontiguousarray(nu, dtype=np.complex128 if np.iscomplexobj(nu) else np.float64).reshape(-1)
+
+
+def _nu_real_part(nu):
+    """what the creators take (they are real: a complex plan is a created plan plus one lsfc_plan_set_nu_complex)"""
+    return np.ascontiguousarray(nu.real) if np.iscomplexobj(nu) else nu
+
+
+def _upload_complex_nu(plan, nu):
+    """second half of creating an operator with a complex nu; the plan, which no object owns yet, is destroyed if it fails"""
+    if np.iscomplexobj(nu):
+        rc = L.load().lsfc_plan_set_nu_complex(plan, nu.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST)
+        if rc != 0:
+            message = L.load().lsfc_last_error()             # (before the destroy, which may overwrite it)
+            L.load().lsfc_plan_destroy(plan)
+            raise L.LsfcError(rc, message.decode(errors="replace"))
 
 
 _QUAD = {"trapezoidal": L.LSFC_QUAD_TRAPEZOIDAL, "Greengard_Vico": L.LSFC_QUAD_GREENGARD_VICO}
@@ -143,7 +166,8 @@ class _Operator:
         return OperatorView(self, L.LSFC_OP_T)
 
     def adjoint(self):
-        """conj(M.T conj(.)), the adjoint of M (nu and omega are real)"""
+        """conj(M.T conj(.)), the adjoint of M (omega is real): b + omega^2 conj(nu) .* conj(G conj(b)), so a complex nu enters
+        conjugated"""
         return OperatorView(self, L.LSFC_OP_H)
 
     T = property(transpose)
@@ -167,11 +191,36 @@ class _Operator:
                               rmatvec=lambda v: H * np.asarray(v).reshape(-1), dtype=np.complex128)
 
     def set_nu(self, nu):
-        nu = np.ascontiguousarray(nu, dtype=np.float64)
+        """Replace the contrast.  A real dtype takes the real path (and leaves the complex one, if the plan was on it), a complex
+        dtype the complex path (lsfc_plan_set_nu_complex).  A torch CUDA tensor (float64 or complex128) is read on the device; as
+        with every device vector handed to an operator, the plan is moved onto torch's current stream first and stays there
+        (lsfc_plan_set_stream)."""
+        lib = L.load()
+        if _is_torch(nu):
+            import torch
+            if nu.dtype not in (torch.float64, torch.complex128) or not nu.is_contiguous():
+                raise TypeError("nu: need a contiguous float64 or complex128 tensor")
+            if nu.numel() != self.N:
+                raise ValueError("DimensionMismatch: nu")
+            entry = lib.lsfc_plan_set_nu_complex if nu.dtype == torch.complex128 else lib.lsfc_plan_set_nu
+            if nu.is_cuda:
+                L.check(lib.lsfc_plan_set_stream(self._plan, C.c_void_p(torch.cuda.current_stream(nu.device).cuda_stream)))
+            L.check(entry(self._plan, C.c_void_p(nu.data_ptr()), L.LSFC_MEM_DEVICE if nu.is_cuda else L.LSFC_MEM_HOST))
+            self.nu = nu.detach().cpu().numpy().reshape(-1)
+            return
+        nu = _nu_array(nu)
         if nu.size != self.N:
             raise ValueError("DimensionMismatch: nu")
-        L.check(L.load().lsfc_plan_set_nu(self._plan, nu.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST))
+        entry = lib.lsfc_plan_set_nu_complex if np.iscomplexobj(nu) else lib.lsfc_plan_set_nu
+        L.check(entry(self._plan, nu.ctypes.data_as(C.c_void_p), L.LSFC_MEM_HOST))
         self.nu = nu
+
+    @property
+    def nu_is_complex(self):
+        """whether the plan multiplies by a complex nu (lsfc_plan_nu_is_complex): follows the dtype last given, not its values"""
+        flag = C.c_int(0)
+        L.check(L.load().lsfc_plan_nu_is_complex(self._plan, C.byref(flag)))
+        return bool(flag.value)
 
     def working_symbol(self):
         """The symbol as the device pipeline stores it (tests / debugging)."""
@@ -272,7 +321,7 @@ class FastM(_Operator):
     def __init__(self, GFFT, nu, ne, me, n, m, k, quadRule="trapezoidal", flags=0, device=0, _plan=None):
         self.GFFT, self.ne, self.me, self.n, self.m = GFFT, int(ne), int(me), int(n), int(m)
         self.omega, self.quadRule = float(k), quadRule
-        self.nu = np.ascontiguousarray(nu, dtype=np.float64).reshape(-1)
+        self.nu = _nu_array(nu)
         if _plan is not None:
             self._plan = _plan
             return
@@ -287,8 +336,9 @@ class FastM(_Operator):
         Gf = np.asfortranarray(G)
         plan = C.c_void_p()
         L.check(L.load().lsfc_plan_create_2d(C.byref(plan), self.n, self.m, self.ne, self.me,
-                                             self.nu.ctypes.data_as(C.c_void_p), Gf.ctypes.data_as(C.c_void_p),
+                                             _nu_real_part(self.nu).ctypes.data_as(C.c_void_p), Gf.ctypes.data_as(C.c_void_p),
                                              self.omega, _QUAD[quadRule], flags, device))
+        _upload_complex_nu(plan, self.nu)
         self._plan = plan
 
 
@@ -299,7 +349,7 @@ class FastM3D(_Operator):
         self.GFFT = GFFT
         self.ne, self.me, self.le, self.n, self.m, self.l = int(ne), int(me), int(le), int(n), int(m), int(l)
         self.omega, self.quadRule = float(k), quadRule
-        self.nu = np.ascontiguousarray(nu, dtype=np.float64).reshape(-1)
+        self.nu = _nu_array(nu)
         if _plan is not None:
             self._plan = _plan
             return
@@ -313,8 +363,9 @@ class FastM3D(_Operator):
         Gf = np.asfortranarray(G)
         plan = C.c_void_p()
         L.check(L.load().lsfc_plan_create_3d(C.byref(plan), self.n, self.m, self.l, self.ne, self.me, self.le,
-                                             self.nu.ctypes.data_as(C.c_void_p), Gf.ctypes.data_as(C.c_void_p),
+                                             _nu_real_part(self.nu).ctypes.data_as(C.c_void_p), Gf.ctypes.data_as(C.c_void_p),
                                              self.omega, _QUAD[quadRule], flags, device))
+        _upload_complex_nu(plan, self.nu)
         self._plan = plan
 
 
@@ -373,11 +424,13 @@ def _grid2d(x, y):
 
 
 def buildFastConvolution(x, y, h, k, nu, quadRule="trapezoidal", flags=0, device=0):
-    """src/FastConvolution.jl:170-236.  ``nu`` is a callable nu(X, Y); the symbol is generated on the device."""
+    """src/FastConvolution.jl:170-236.  ``nu`` is a callable nu(X, Y), real or complex (an absorbing medium); the symbol is
+    generated on the device."""
     x, y = np.asarray(x, float), np.asarray(y, float)
     n, m = len(x), len(y)
     X, Y = _grid2d(x, y)
-    nuv = np.ascontiguousarray(nu(X, Y), dtype=np.float64)
+    nuc = _nu_array(nu(X, Y))                    # the dtype given; the creators take its real part, the complex path follows
+    nuv = _nu_real_part(nuc)
     plan = C.c_void_p()
     if quadRule == "trapezoidal":
         _, D = referenceValsTrapRule()
@@ -388,11 +441,13 @@ def buildFastConvolution(x, y, h, k, nu, quadRule="trapezoidal", flags=0, device
         D0 = D[idx - 1]
         L.check(L.load().lsfc_plan_create_trap2d(C.byref(plan), n, m, float(x[0]), float(y[0]), float(h), float(k),
                                                  float(D0.real), float(D0.imag), nuv.ctypes.data_as(C.c_void_p), flags, device))
-        return FastM(None, nuv, 2 * n - 1, 2 * m - 1, n, m, k, quadRule="trapezoidal", _plan=plan)
+        _upload_complex_nu(plan, nuc)
+        return FastM(None, nuc, 2 * n - 1, 2 * m - 1, n, m, k, quadRule="trapezoidal", _plan=plan)
     if quadRule == "Greengard_Vico":
         box = abs(x[-1] - x[0]) + h
         L.check(L.load().lsfc_plan_create_gv2d(C.byref(plan), n, m, float(box), float(k), nuv.ctypes.data_as(C.c_void_p), flags, device))
-        return FastM(None, nuv, 4 * n, 4 * m, n, m, k, quadRule="Greengard_Vico", _plan=plan)
+        _upload_complex_nu(plan, nuc)
+        return FastM(None, nuc, 4 * n, 4 * m, n, m, k, quadRule="Greengard_Vico", _plan=plan)
     raise NameError(f"UndefVarError: unknown quadRule {quadRule!r}")
 
 
@@ -403,11 +458,13 @@ def buildFastConvolution3D(x, y, z, X, Y, Z, h, k, nu, quadRule="Greengard_Vico"
         raise NameError(f"UndefVarError: unknown quadRule {quadRule!r}")
     x = np.asarray(x, float)
     n, m, l = len(x), len(y), len(z)
-    nuv = np.ascontiguousarray(nu(X, Y, Z) if callable(nu) else nu, dtype=np.float64).reshape(-1)
+    nuc = _nu_array(nu(X, Y, Z) if callable(nu) else nu)
+    nuv = _nu_real_part(nuc)
     box = abs(x[-1] - x[0]) + h
     plan = C.c_void_p()
     L.check(L.load().lsfc_plan_create_gv3d(C.byref(plan), n, m, l, float(box), float(k), nuv.ctypes.data_as(C.c_void_p), flags, device))
-    return FastM3D(None, nuv, 4 * n, 4 * m, 4 * l, n, m, l, k, _plan=plan)
+    _upload_complex_nu(plan, nuc)
+    return FastM3D(None, nuc, 4 * n, 4 * m, 4 * l, n, m, l, k, _plan=plan)
 
 
 def sampleGConv(k, X, Y, indS, fastconv):

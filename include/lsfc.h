@@ -113,8 +113,24 @@ int64_t lsfc_plan_size(const lsfc_plan* plan);
 int lsfc_plan_dims(const lsfc_plan* plan, int64_t dims[3], int64_t pads[3]);
 /* name of the transform pipeline in use: "pruned-hip", "rocfft-reduced", "rocfft-literal" */
 const char* lsfc_plan_pipeline(const lsfc_plan* plan);
-/* replace the contrast (nu is a mutable field of the reference struct) */
+/* replace the contrast (nu is a mutable field of the reference struct).  N doubles: the plan's nu is REAL from here on (after
+ * lsfc_plan_set_nu_complex this frees the imaginary plane, and every result is bit for bit that of a plan that never saw a
+ * complex nu). */
 int lsfc_plan_set_nu(lsfc_plan* plan, const double* nu, int memspace);
+/* Complex nu: an absorbing (lossy) medium.  This goes beyond the reference, whose nu is an Array{Float64,1}.
+ * nu: N (re, im) pairs, interleaved like every complex vector of this ABI.  The plan's nu is complex from here on.
+ * The creators take a real nu: a complex plan is a created plan plus one call of this entry.  The plan keeps Re nu and Im nu
+ * as two planes of N doubles (the real path keeps its 8 B per point and its instructions); every entry that reads the plan's
+ * nu honours both: lsfc_apply, lsfc_apply_batch modes 0 and 2, lsfc_convolve with apply_nu, lsfc_time_apply,
+ * lsfc_profile_apply (whose byte model counts 16 B per point of nu), host and device vectors alike, lsfc_sparsify_build
+ * (Msp = As + omega^2 AG diag(nu), a complex multiply-add), lsfc_precond_create_from_plan* and the four Krylov entry points.
+ * M^T and M^H with a complex nu: see lsfc_plan_set_op below.
+ * After an error of this entry the plan has the nu it had before the call.
+ * LSFC_EINVAL: NULL argument (before any device call); a distributed, simulated-rank or multi-device plan ("complex nu is not
+ * available on ..."; such a plan keeps working with its real nu). */
+int lsfc_plan_set_nu_complex(lsfc_plan* plan, const double* nu, int memspace);
+/* *is_complex = 1 after lsfc_plan_set_nu_complex, 0 after a creator or lsfc_plan_set_nu */
+int lsfc_plan_nu_is_complex(const lsfc_plan* plan, int* is_complex);
 /* copy the working symbol out (debug / tests): count complex entries written */
 int lsfc_plan_get_symbol(const lsfc_plan* plan, double* out, int64_t capacity_complex, int64_t* count);
 
@@ -158,8 +174,11 @@ int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, d
 
 /* ---- the transposed and the adjoint operator ------------------------------ */
 
-/* nu and omega are real and the Green's matrix G of every builder is complex symmetric, so
- *     M^T = I + omega^2 diag(nu) G        and        M^H y = conj(M^T conj(y)).
+/* omega is real and the Green's matrix G of every builder is complex symmetric, so
+ *     M^T = I + omega^2 diag(nu) G        and        M^H y = conj(M^T conj(y)) = y + omega^2 conj(nu) .* conj(G conj(y)).
+ * nu may be complex (lsfc_plan_set_nu_complex).  The rule is: THE CONJUGATION IS OUTERMOST.  M^T multiplies by nu itself,
+ * M^H by conj(nu); whatever describes G and the nu multiply literally (lsfc_convolve with apply_nu, lsfc_apply_batch mode 2,
+ * the trapezoidal FFTconvolution quirk) multiplies by nu itself under every op.
  * In the pipeline only the nu multiply moves, from the loads of the first x pass to the stores of the last one; M^H adds
  * two conjugations there.  The y passes, the fused pass and the HBM traffic per point are those of M.
  *
@@ -181,7 +200,7 @@ int lsfc_sample_sources(lsfc_plan* plan, const int64_t* sources, int64_t nsrc, d
  * message names both ops.  Caller callbacks pass through unchanged.
  *
  * The transposed and the adjoint preconditioner As^T Msp^-T exist for block-tridiagonal objects (lsfc_precond_set_op).
- * Out of scope: complex nu; the transposed apply of an object of lsfc_precond_create (host LU factors); right
+ * Out of scope: the transposed apply of an object of lsfc_precond_create (host LU factors); right
  * preconditioning; distributed and multi-device plans; non-symmetric kernels (they would need the reflected symbol). */
 #define LSFC_OP_N 0   /* M           (default)                         */
 #define LSFC_OP_T 1   /* transpose   I + w^2 diag(nu) G                */

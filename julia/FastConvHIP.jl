@@ -17,7 +17,7 @@ check(rc) = rc == 0 ? nothing : error("lsfc error $rc: $(lasterror())")
 
 mutable struct FastMHIP            # mirrors FastM / FastM3D field names (src/FastConvolution.jl:11-27)
     plan::Ptr{Cvoid}
-    nu::Vector{Float64}
+    nu::Union{Vector{Float64},Vector{Complex{Float64}}}    # complex: an absorbing medium (beyond the reference's Array{Float64,1})
     n::Int64; m::Int64; l::Int64
     omega::Float64
     quadRule::String
@@ -28,30 +28,61 @@ mutable struct FastMHIP            # mirrors FastM / FastM3D field names (src/Fa
     end
 end
 
+# Complex nu (lsfc_plan_set_nu_complex): the creators take a real nu, so a complex operator is created with real.(nu) and then
+# handed the (re, im) pairs.  A Vector{Float64} takes the real path exactly as before; a Vector{Complex{Float64}} takes the
+# complex path even if every imaginary part is 0.  transpose(M) multiplies by nu itself, M' by conj(nu) (include/lsfc.h).
+const NuVector = Union{Vector{Float64},Vector{Complex{Float64}}}
+_real_nu(nu::Vector{Float64}) = nu
+_real_nu(nu::Vector{Complex{Float64}}) = Vector{Float64}(real.(nu))
+_nu_vector(v) = eltype(v) <: Complex ? Vector{Complex{Float64}}(vec(v)) : Vector{Float64}(vec(v))
+_upload_complex_nu(plan, nu::Vector{Float64}) = nothing
+_upload_complex_nu(plan, nu::Vector{Complex{Float64}}) =
+    check(ccall((:lsfc_plan_set_nu_complex, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Complex{Float64}}, Cint), plan, nu, 0))
+
+# set_nu!(M, nu): replace the contrast (nu is a mutable field of the reference struct); the element type chooses the path
+function set_nu!(M::FastMHIP, nu::Vector{Float64})
+    length(nu) == length(M.nu) || throw(DimensionMismatch("nu"))
+    check(ccall((:lsfc_plan_set_nu, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), M.plan, nu, 0))
+    M.nu = nu; M
+end
+function set_nu!(M::FastMHIP, nu::Vector{Complex{Float64}})
+    length(nu) == length(M.nu) || throw(DimensionMismatch("nu"))
+    _upload_complex_nu(M.plan, nu)
+    M.nu = nu; M
+end
+function nu_is_complex(M::FastMHIP)
+    flag = Ref{Cint}(0)
+    check(ccall((:lsfc_plan_nu_is_complex, liblsfc), Cint, (Ptr{Cvoid}, Ref{Cint}), M.plan, flag))
+    flag[] != 0
+end
+
 # FastM(GFFT,nu,ne,me,n,m,k; quadRule) -- src/FastConvolution.jl:24
-function FastM(GFFT::Array{Complex{Float64},2}, nu::Vector{Float64}, ne, me, n, m, k; quadRule::String="trapezoidal", flags=0, device=0)
+function FastM(GFFT::Array{Complex{Float64},2}, nu::NuVector, ne, me, n, m, k; quadRule::String="trapezoidal", flags=0, device=0)
     plan = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:lsfc_plan_create_2d, liblsfc), Cint,
                 (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Int64, Ptr{Float64}, Ptr{Complex{Float64}}, Float64, Cint, Cuint, Cint),
-                plan, n, m, ne, me, nu, GFFT, k, QUAD[quadRule], flags, device))
+                plan, n, m, ne, me, _real_nu(nu), GFFT, k, QUAD[quadRule], flags, device))
+    _upload_complex_nu(plan[], nu)
     FastMHIP(plan[], nu, n, m, 1, k, quadRule)
 end
 
 # FastM3D(GFFT,nu,ne,me,le,n,m,l,k; quadRule) -- src/FastConvolution3D.jl:23
-function FastM3D(GFFT::Array{Complex{Float64},3}, nu::Vector{Float64}, ne, me, le, n, m, l, k; quadRule::String="Greengard_Vico", flags=0, device=0)
+function FastM3D(GFFT::Array{Complex{Float64},3}, nu::NuVector, ne, me, le, n, m, l, k; quadRule::String="Greengard_Vico", flags=0, device=0)
     plan = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:lsfc_plan_create_3d, liblsfc), Cint,
                 (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Float64}, Ptr{Complex{Float64}}, Float64, Cint, Cuint, Cint),
-                plan, n, m, l, ne, me, le, nu, GFFT, k, QUAD[quadRule], flags, device))
+                plan, n, m, l, ne, me, le, _real_nu(nu), GFFT, k, QUAD[quadRule], flags, device))
+    _upload_complex_nu(plan[], nu)
     FastMHIP(plan[], nu, n, m, l, k, quadRule)
 end
 
 # buildFastConvolution3D(x,y,z,X,Y,Z,h,k,nu) -- src/FastConvolution3D.jl:68 (symbol generated on the device)
 function buildFastConvolution3D(x, y, z, X, Y, Z, h, k, nu; quadRule::String="Greengard_Vico", flags=0, device=0)
-    nuv = Vector{Float64}(nu(X, Y, Z)); plan = Ref{Ptr{Cvoid}}(C_NULL)
+    nuv = _nu_vector(nu(X, Y, Z)); plan = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:lsfc_plan_create_gv3d, liblsfc), Cint,
                 (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Float64, Float64, Ptr{Float64}, Cuint, Cint),
-                plan, length(x), length(y), length(z), abs(x[end] - x[1]) + h, k, nuv, flags, device))
+                plan, length(x), length(y), length(z), abs(x[end] - x[1]) + h, k, _real_nu(nuv), flags, device))
+    _upload_complex_nu(plan[], nuv)
     FastMHIP(plan[], nuv, length(x), length(y), length(z), k, quadRule)
 end
 
@@ -70,17 +101,18 @@ end
 function buildFastConvolution(x, y, h, k, nu::Function; quadRule::String="trapezoidal", flags=0, device=0)
     n, m = length(x), length(y)
     X = repeat(x, 1, m)[:]; Y = repeat(y', n, 1)[:]
-    nuv = Vector{Float64}(nu(X, Y)); plan = Ref{Ptr{Cvoid}}(C_NULL)
+    nuv = _nu_vector(nu(X, Y)); plan = Ref{Ptr{Cvoid}}(C_NULL)
     if quadRule == "trapezoidal"
         D = [1-0.892im, 1-1.35im, 1-1.79im, 1-2.23im, 1-2.67im, 1-3.11im]; D0 = D[round(Int, k*h)]
         check(ccall((:lsfc_plan_create_trap2d, liblsfc), Cint,
                     (Ref{Ptr{Cvoid}}, Int64, Int64, Float64, Float64, Float64, Float64, Float64, Float64, Ptr{Float64}, Cuint, Cint),
-                    plan, n, m, x[1], y[1], h, k, real(D0), imag(D0), nuv, flags, device))
+                    plan, n, m, x[1], y[1], h, k, real(D0), imag(D0), _real_nu(nuv), flags, device))
     else
         check(ccall((:lsfc_plan_create_gv2d, liblsfc), Cint,
                     (Ref{Ptr{Cvoid}}, Int64, Int64, Float64, Float64, Ptr{Float64}, Cuint, Cint),
-                    plan, n, m, abs(x[end] - x[1]) + h, k, nuv, flags, device))
+                    plan, n, m, abs(x[end] - x[1]) + h, k, _real_nu(nuv), flags, device))
     end
+    _upload_complex_nu(plan[], nuv)
     FastMHIP(plan[], nuv, n, m, 1, k, quadRule)
 end
 
@@ -414,8 +446,8 @@ function bicgstabl_batch_hip!(X::Matrix{Complex{Float64}}, M::FastMHIP, B::Matri
     X, [resnorm[1:min(res[j].iters, cap), j] for j in 1:nrhs], status
 end
 
-# transpose(M) and M' -- lsfc_plan_set_op (include/lsfc.h).  nu and omega are real and the Green's matrix is complex symmetric, so
-# transpose(M) = I + omega^2 diag(nu) G and M' y = conj(transpose(M) conj(y)): the same pipeline with the nu multiply moved from
+# transpose(M) and M' -- lsfc_plan_set_op (include/lsfc.h).  omega is real and the Green's matrix is complex symmetric, so
+# transpose(M) = I + omega^2 diag(nu) G and M' y = conj(transpose(M) conj(y)) (a complex nu enters M' conjugated): the same pipeline with the nu multiply moved from
 # the first x pass to the last, plus two conjugations for M'.  The wrappers hold the parent and an op, no second plan; a call
 # through one sets the op of the parent's plan, calls, and restores M (also when the call throws).  The library measures the
 # symmetry of G through the plan's own convolution at the first such call and refuses (rc -1) a plan whose symbol is not
