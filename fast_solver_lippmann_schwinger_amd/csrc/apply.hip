@@ -32,29 +32,26 @@ static NuPlanes slab_nu(const lsfc_plan* p, const ConvOp& op, NuSide side, Slab 
     const int64_t off = (int64_t)s.z0 * p->dims[0] * p->dims[1];
     return NuPlanes{p->nu.p + off, p->nu_im.p ? p->nu_im.p + off : nullptr};
 }
+// What the passes take (pruned.hpp), for the launches below and for describe_passes alike.
+// The x pass on side `side` of the convolution: A1 in rows [line][pitch1 >= Lx], or in the 2D tiles [Lx/8][tile2d] as chunks of width 8
+static XPass xpass_args(const lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, NuSide side, Slab s) {
+    const int Lx = p->pads[0];
+    const bool tiles = p->tile2d != 0;
+    return XPass{.L = Lx, .vb = slab_vectors(p, vb, nrhs, s), .nrhs = nrhs, .work = slab_a1(p, s), .wbatch = p->a1_elems, .tw = p->tw[0].p,
+                 .nlines = (int64_t)p->dims[1] * s.nz, .W = tiles ? 8 : Lx, .Wp = tiles ? 8 : p->pitch1, .n = p->dims[0], .bstride = p->tile2d,
+                 .nu = slab_nu(p, op, side, s), .conj = op.conj, .alpha = op.alpha, .beta = op.beta};
+}
+static YPass ypass_args(const lsfc_plan* p, int nrhs, Slab s) {
+    return YPass{.L = p->pads[1], .a1 = slab_a1(p, s), .a2 = slab_a2(p, s), .tw = p->tw[1].p, .Lx = p->pads[0], .m = p->dims[1], .l = s.nz,
+                 .p1 = p->pitch1, .p2 = p->pitch2, .nrhs = nrhs, .batch1 = p->a1_elems, .batch2 = p->a2_elems};
+}
 void pass_xfwd(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Slab s, hipStream_t st) {
-    const int Lx = p->pads[0], n = p->dims[0];
-    const int64_t nlines = (int64_t)p->dims[1] * s.nz;
-    const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    const NuPlanes nu = slab_nu(p, op, NuSide::INPUT, s);
-    if (p->tile2d) pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu.re, p->A1.p, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, op.conj, nu.im);
-    else pruned_xfwd(Lx, p->tuning, v, nrhs, p->a1_elems, nu.re, slab_a1(p, s), p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, op.conj, nu.im);
+    pruned_xfwd(p->tuning, xpass_args(p, vb, nrhs, op, NuSide::INPUT, s), st);
 }
-void pass_yfwd(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {
-    pruned_yfwd(p->pads[1], p->tuning, slab_a1(p, s), slab_a2(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
-                nrhs, p->a1_elems, p->a2_elems);
-}
-void pass_yinv(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) {
-    pruned_yinv(p->pads[1], p->tuning, slab_a2(p, s), slab_a1(p, s), p->tw[1].p, p->pads[0], p->dims[1], s.nz, p->pitch1, p->pitch2, st,
-                nrhs, p->a1_elems, p->a2_elems);
-}
+void pass_yfwd(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) { pruned_yfwd(p->tuning, ypass_args(p, nrhs, s), st); }
+void pass_yinv(lsfc_plan* p, int nrhs, Slab s, hipStream_t st) { pruned_yinv(p->tuning, ypass_args(p, nrhs, s), st); }
 void pass_xinv(lsfc_plan* p, const VecBatch& vb, int nrhs, const ConvOp& op, Slab s, hipStream_t st) {
-    const int Lx = p->pads[0], n = p->dims[0];
-    const int64_t nlines = (int64_t)p->dims[1] * s.nz;
-    const VecBatch v = slab_vectors(p, vb, nrhs, s);
-    const NuPlanes nu = slab_nu(p, op, NuSide::OUTPUT, s);
-    if (p->tile2d) pruned_xinv(Lx, p->tuning, p->A1.p, v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, 8, 8, n, st, p->tile2d, nu.re, op.conj, nu.im);
-    else pruned_xinv(Lx, p->tuning, slab_a1(p, s), v, nrhs, p->a1_elems, op.alpha, op.beta, p->tw[0].p, nlines, Lx, p->pitch1, n, st, 0, nu.re, op.conj, nu.im);
+    pruned_xinv(p->tuning, xpass_args(p, vb, nrhs, op, NuSide::OUTPUT, s), st);
 }
 
 // The three geometries of the fused pass.  3D: A2 as tiles [x'/8][Ly][pitch2 >= 8*l] of 8 interleaved z lines, the symbol as
@@ -65,9 +62,12 @@ static FusedGeom geom_3d(const lsfc_plan* p, int Wc) {
     return FusedGeom{Wc, Ly, (int64_t)p->pitch2 * Ly, (int64_t)p->pitch2, 8, (int64_t)8 * p->sym_hz * p->sym_rows, (int64_t)8 * p->sym_hz, 8,
                      p->ytab.p, p->zmirror.p, p->dims[2]};
 }
+static FusedPass fused_args_3d(const lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs) {
+    return FusedPass{.L = p->pads[2], .data = p->A2.p + a2_off, .sym = p->sym.p + sym_off, .tw = p->tw[2].p, .twl = p->twl[2].p, .g = geom_3d(p, Wc),
+                     .nrhs = nrhs, .dBatch = p->a2_elems};
+}
 void plan_zfused_3d(lsfc_plan* p, int Wc, int64_t a2_off, int64_t sym_off, int nrhs, hipStream_t st) {
-    const FusedGeom g = geom_3d(p, Wc);
-    pruned_zfused(p->pads[2], p->tuning, p->A2.p + a2_off, p->sym.p + sym_off, p->tw[2].p, p->twl[2].p, g, st, nrhs, p->a2_elems);
+    pruned_zfused(p->tuning, fused_args_3d(p, Wc, a2_off, sym_off, nrhs), st);
 }
 // 2D, natural rows: A1 as [m][pitch1 >= Lx], the lines along y; the symbol likewise, [rows][Lx]
 static FusedGeom geom_2d_rows(const lsfc_plan* p) {
@@ -76,6 +76,12 @@ static FusedGeom geom_2d_rows(const lsfc_plan* p) {
 // 2D, tiles: A1 as [Lx/8][tile2d >= 8*m] -- the 3D layout with one row per tile; the symbol as [Lx/8][sym_hz][8]
 static FusedGeom geom_2d_tiles(const lsfc_plan* p) {
     return FusedGeom{p->pads[0], 1, p->tile2d, 0, 8, (int64_t)8 * p->sym_hz, 0, 8, nullptr, p->zmirror.p, p->dims[1]};
+}
+// the fused pass of the whole grid: along z on A2 in 3D, along y on A1 in 2D
+static FusedPass fused_args(const lsfc_plan* p, int nrhs) {
+    if (p->ndim == 3) return fused_args_3d(p, p->pads[0], 0, 0, nrhs);
+    return FusedPass{.L = p->pads[1], .data = p->A1.p, .sym = p->sym.p, .tw = p->tw[1].p, .twl = p->twl[1].p,
+                     .g = p->tile2d ? geom_2d_tiles(p) : geom_2d_rows(p), .nrhs = nrhs, .dBatch = p->a1_elems};
 }
 // whether a batch of nrhs right-hand sides shares one launch per pass (lsfc_apply_batch)
 static bool batch_fused(const lsfc_plan* p, int nrhs) {
@@ -96,13 +102,13 @@ static std::string describe_passes(const lsfc_plan* p, int nrhs) {
     char line[512];
     auto add = [&](const PassForm& f) { pass_form_print(f, line, sizeof line); out += line; out += "\n"; };
     const bool d3 = p->ndim == 3;
-    add(pruned_xfwd_form(p->pads[0], p->tuning, p->dims[0]));
-    if (d3) add(pruned_yfwd_form(p->pads[1], p->tuning, p->pads[0], p->dims[1], p->dims[2]));
-    const int fa = d3 ? 2 : 1;
-    add(pruned_zfused_form(p->pads[fa], p->tuning, d3 ? geom_3d(p, p->pads[0]) : (p->tile2d ? geom_2d_tiles(p) : geom_2d_rows(p)),
-                           p->twl[fa].p != nullptr, per_launch));
-    if (d3) add(pruned_yinv_form(p->pads[1], p->tuning, p->pads[0], p->dims[1], p->dims[2]));
-    add(pruned_xinv_form(p->pads[0], p->tuning, p->dims[0]));
+    const Slab all = whole_grid(p);
+    const ConvOp op = plan_operator(p);
+    add(pruned_xfwd_form(p->tuning, xpass_args(p, VecBatch{}, per_launch, op, NuSide::INPUT, all)));
+    if (d3) add(pruned_yfwd_form(p->tuning, ypass_args(p, per_launch, all)));
+    add(pruned_zfused_form(p->tuning, fused_args(p, per_launch)));
+    if (d3) add(pruned_yinv_form(p->tuning, ypass_args(p, per_launch, all)));
+    add(pruned_xinv_form(p->tuning, xpass_args(p, VecBatch{}, per_launch, op, NuSide::OUTPUT, all)));
     // storage: ytab = 1 the y-even half of the symbol rows (each stored row serves a row and its mirror), zmirror = 1 the even half
     // of every symbol line along the fused pass's axis; batch: how nrhs > 1 right-hand sides run through the passes
     snprintf(line, sizeof line, "pitch1=%d pitch2=%d sym_rows=%d sym_hz=%d ytab=%d zmirror=%d tile2d=%lld batch=%s\n", p->pitch1, p->pitch2, p->sym_rows,
@@ -111,10 +117,7 @@ static std::string describe_passes(const lsfc_plan* p, int nrhs) {
     out += line;
     return out;
 }
-void pass_fused(lsfc_plan* p, int nrhs, hipStream_t st) {
-    if (p->ndim == 3) { plan_zfused_3d(p, p->pads[0], 0, 0, nrhs, st); return; }
-    pruned_zfused(p->pads[1], p->tuning, p->A1.p, p->sym.p, p->tw[1].p, p->twl[1].p, p->tile2d ? geom_2d_tiles(p) : geom_2d_rows(p), st, nrhs, p->a1_elems);
-}
+void pass_fused(lsfc_plan* p, int nrhs, hipStream_t st) { pruned_zfused(p->tuning, fused_args(p, nrhs), st); }
 
 // ---------------------------------------------------------------------------
 // the stages of an apply

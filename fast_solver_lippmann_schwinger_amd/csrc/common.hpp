@@ -64,6 +64,12 @@ template <int LO, int HI, class F> void dispatch(int v, const char* who, F&& f) 
     else if (v == LO) f(std::integral_constant<int, LO>{});
     else dispatch<LO + 1, HI>(v, who, f);
 }
+// run-time flags -> template arguments: dispatch_flags({a, b}, f) calls f(std::bool_constant<a>{}, std::bool_constant<b>{})
+template <int N, class F, class... Done> void dispatch_flags(const bool (&v)[N], F&& f, Done... done) {
+    if constexpr (sizeof...(Done) == N) f(done...);
+    else if (v[sizeof...(Done)]) dispatch_flags(v, f, done..., std::true_type{});
+    else dispatch_flags(v, f, done..., std::false_type{});
+}
 
 // environment switches (developer knobs): the first character of the value, -1 when not set
 inline int env_switch(const char* name) { const char* e = getenv(name); return e ? (unsigned char)e[0] : -1; }

@@ -38,38 +38,37 @@ DistState::~DistState() {
 // block of one (rank, chunk) pair in S1 / R1: [Wc][m][lz]
 static int64_t block_elems(const lsfc_plan* p) { return (int64_t)p->dist->Wc * p->dims[1] * p->dist->lz; }
 
-// part = -1: all own planes; part = 0 / 1: the lower / upper half of them (the z halves of every S1 block)
-static void phase1(lsfc_plan* p, const cplx* x, bool use_nu, hipStream_t st, int part = -1) {
+// The x passes on the own planes (part = -1), or on their lower / upper half (0 / 1: the z halves of every S1 block): lines of S1
+// in blocks [Wc][m][lz].  x, y: the rank's vectors (y null for the forward pass).  M and the bare convolution only (a real nu on
+// the input side, no conjugation: plan.hpp, conv_forward_only)
+static XPass slab_xpass(const lsfc_plan* p, const cplx* x, cplx* y, bool use_nu, double alpha, double beta, int part) {
     const DistState* d = p->dist.get();
     const int64_t all = (int64_t)p->dims[1] * d->lz, nl = part < 0 ? all : all / 2, l0 = part == 1 ? all / 2 : 0;
+    const int64_t off = l0 * p->dims[0];            // the part's first line in the vectors and in nu
+    VecBatch vb{}; vb.x[0] = x + off; if (y) vb.y[0] = y + off;
     // chunk width Wc: storage index s of a line lands in block s / Wc = dest_rank * K + chunk
-    VecBatch vb{}; vb.x[0] = x + l0 * p->dims[0];
-    pruned_xfwd(p->pads[0], p->tuning, vb, 1, 0, use_nu ? p->nu.p + l0 * p->dims[0] : nullptr, d->S1.p + l0 * d->Wc, p->tw[0].p,
-                nl, d->Wc, d->Wc, p->dims[0], st, all * d->Wc);
+    return XPass{.L = p->pads[0], .vb = vb, .nrhs = 1, .work = d->S1.p + l0 * d->Wc, .wbatch = 0, .tw = p->tw[0].p, .nlines = nl, .W = d->Wc, .Wp = d->Wc,
+                 .n = p->dims[0], .bstride = all * d->Wc, .nu = NuPlanes{use_nu ? p->nu.p + off : nullptr, nullptr}, .conj = false, .alpha = alpha, .beta = beta};
 }
-static void phase2_yfwd(lsfc_plan* p, int c, hipStream_t st) {
+static void phase1(lsfc_plan* p, const cplx* x, bool use_nu, hipStream_t st, int part = -1) {
+    pruned_xfwd(p->tuning, slab_xpass(p, x, nullptr, use_nu, 0.0, 0.0, part), st);
+}
+// the y passes of chunk c: R1 chunk [m][l][Wc] <-> the chunk's tiles of A2
+static YPass chunk_ypass(const lsfc_plan* p, int c) {
     const DistState* d = p->dist.get();
     const int m = p->dims[1], l = p->dims[2];
-    pruned_yfwd(p->pads[1], p->tuning, d->R1.p + (int64_t)c * d->Wc * m * l, p->A2.p + (int64_t)c * (d->Wc / 8) * p->pads[1] * p->pitch2,
-                p->tw[1].p, d->Wc, m, l, d->Wc, p->pitch2, st);
+    return YPass{.L = p->pads[1], .a1 = d->R1.p + (int64_t)c * d->Wc * m * l, .a2 = p->A2.p + (int64_t)c * (d->Wc / 8) * p->pads[1] * p->pitch2, .tw = p->tw[1].p,
+                 .Lx = d->Wc, .m = m, .l = l, .p1 = d->Wc, .p2 = p->pitch2, .nrhs = 1, .batch1 = 0, .batch2 = 0};
 }
+static void phase2_yfwd(lsfc_plan* p, int c, hipStream_t st) { pruned_yfwd(p->tuning, chunk_ypass(p, c), st); }
 static void phase2_zfused(lsfc_plan* p, int c, hipStream_t st) {
     const DistState* d = p->dist.get();
     plan_zfused_3d(p, d->Wc, (int64_t)c * (d->Wc / 8) * p->pads[1] * p->pitch2, (int64_t)c * d->Wc * p->sym_rows * p->sym_hz, 1, st);
 }
-static void phase2_yinv(lsfc_plan* p, int c, hipStream_t st) {
-    const DistState* d = p->dist.get();
-    const int m = p->dims[1], l = p->dims[2];
-    pruned_yinv(p->pads[1], p->tuning, p->A2.p + (int64_t)c * (d->Wc / 8) * p->pads[1] * p->pitch2, d->R1.p + (int64_t)c * d->Wc * m * l,
-                p->tw[1].p, d->Wc, m, l, d->Wc, p->pitch2, st);
-}
+static void phase2_yinv(lsfc_plan* p, int c, hipStream_t st) { pruned_yinv(p->tuning, chunk_ypass(p, c), st); }
 static void phase2(lsfc_plan* p, int c, hipStream_t st) { phase2_yfwd(p, c, st); phase2_zfused(p, c, st); phase2_yinv(p, c, st); }
 static void phase3(lsfc_plan* p, const cplx* x, cplx* y, double alpha, double beta, hipStream_t st, int part = -1) {
-    const DistState* d = p->dist.get();
-    const int64_t all = (int64_t)p->dims[1] * d->lz, nl = part < 0 ? all : all / 2, l0 = part == 1 ? all / 2 : 0;
-    VecBatch vb{}; vb.x[0] = x + l0 * p->dims[0]; vb.y[0] = y + l0 * p->dims[0];
-    pruned_xinv(p->pads[0], p->tuning, d->S1.p + l0 * d->Wc, vb, 1, 0, alpha, beta, p->tw[0].p,
-                nl, d->Wc, d->Wc, p->dims[0], st, all * d->Wc);
+    pruned_xinv(p->tuning, slab_xpass(p, x, y, false, alpha, beta, part), st);
 }
 
 // Exchange of chunk c.  way in : S1 block (q*K + c)  -> rank q, lands in R1 chunk c at slot <source rank>

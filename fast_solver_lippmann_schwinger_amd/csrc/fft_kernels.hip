@@ -731,35 +731,35 @@ template <class C> struct Tune {
 #endif
 };
 
-template <class C, bool SPLIT> static void xfwd_t(const PassForm& f, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, const double* nu_im, cplx* out, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, bool cj) {
-    constexpr int LPW = Tune<C>::LPW;
-    using LL = LdsLayout<1, 3, SPLIT>;
-    const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
-    const dim3 grid((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), block(C::T * LPW);
-    if (nu_im) {                    // a complex nu: the kernel of the same form that multiplies by both planes
-        auto k = f.full ? k_xfwd_c<C, LPW, SPLIT, true> : k_xfwd_c<C, LPW, SPLIT, false>;
-        allow_lds(k, lds);
-        hipLaunchKernelGGL(k, grid, block, lds, st, vb, obatch, nu, nu_im, out, tw, nlines, wmagic, W, Wp, n, bstride, (int)cj);
-        return;
-    }
-    auto k = f.full ? k_xfwd<C, LPW, SPLIT, true> : k_xfwd<C, LPW, SPLIT, false>;
-    allow_lds(k, lds);
-    hipLaunchKernelGGL(k, grid, block, lds, st, vb, obatch, nu, out, tw, nlines, wmagic, W, Wp, n, bstride, (int)cj);
+// The lines of this family, and the way from a run-time line length to its Cfg: f(C{})
+template <class... C> struct Lines {};
+#if LSFC_FAMILY == 2
+using FamilyLines = Lines<Cfg32, Cfg64, Cfg128, Cfg256, Cfg512, Cfg1024, Cfg2048>;
+#elif LSFC_FAMILY == 3
+using FamilyLines = Lines<Cfg48, Cfg96, Cfg192, Cfg384, Cfg768, Cfg1536>;
+#else
+using FamilyLines = Lines<Cfg80, Cfg160, Cfg320, Cfg640, Cfg1280>;
+#endif
+template <class... C, class F> static void dispatch_line(Lines<C...>, int L, F&& f) {
+    if (!((L == C::L && (f(C{}), true)) || ...)) fail(LSFC_EINVAL, "pruned pipeline: unsupported padded length %d", L);
 }
-template <class C, bool SPLIT> static void xinv_t(const PassForm& f, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int wmagic, int W, int Wp, int n, int64_t bstride, hipStream_t st, const double* nu, const double* nu_im, bool cj) {
+template <class F> static void dispatch_line(int L, F&& f) { dispatch_line(FamilyLines{}, L, f); }
+
+// the two x passes: INV = false xfwd, true xinv
+template <bool INV, class C, bool SPLIT, bool FULL> static void xpass_t(const XPass& a, int wmagic, int64_t bstride, hipStream_t st) {
     constexpr int LPW = Tune<C>::LPW;
     using LL = LdsLayout<1, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LPW * LL::elem_bytes();
-    const dim3 grid((unsigned)((nlines + LPW - 1) / LPW), (unsigned)nrhs), block(C::T * LPW);
-    if (nu_im) {
-        auto k = f.full ? k_xinv_c<C, LPW, SPLIT, true> : k_xinv_c<C, LPW, SPLIT, false>;
-        allow_lds(k, lds);
-        hipLaunchKernelGGL(k, grid, block, lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, nu, nu_im, (int)cj);
-        return;
+    const dim3 grid((unsigned)((a.nlines + LPW - 1) / LPW), (unsigned)a.nrhs), block(C::T * LPW);
+    auto launch = [&](auto k, auto... args) { allow_lds(k, lds); hipLaunchKernelGGL(k, grid, block, lds, st, args...); };
+    // a complex nu (nu.im): the kernel of the same form that multiplies by both planes
+    if constexpr (INV) {
+        if (a.nu.im) launch(k_xinv_c<C, LPW, SPLIT, FULL>, (const cplx*)a.work, a.vb, a.wbatch, a.alpha, a.beta, a.tw, a.nlines, wmagic, a.W, a.Wp, a.n, bstride, a.nu.re, a.nu.im, (int)a.conj);
+        else launch(k_xinv<C, LPW, SPLIT, FULL>, (const cplx*)a.work, a.vb, a.wbatch, a.alpha, a.beta, a.tw, a.nlines, wmagic, a.W, a.Wp, a.n, bstride, a.nu.re, (int)a.conj);
+    } else {
+        if (a.nu.im) launch(k_xfwd_c<C, LPW, SPLIT, FULL>, a.vb, a.wbatch, a.nu.re, a.nu.im, a.work, a.tw, a.nlines, wmagic, a.W, a.Wp, a.n, bstride, (int)a.conj);
+        else launch(k_xfwd<C, LPW, SPLIT, FULL>, a.vb, a.wbatch, a.nu.re, a.work, a.tw, a.nlines, wmagic, a.W, a.Wp, a.n, bstride, (int)a.conj);
     }
-    auto k = f.full ? k_xinv<C, LPW, SPLIT, true> : k_xinv<C, LPW, SPLIT, false>;
-    allow_lds(k, lds);
-    hipLaunchKernelGGL(k, grid, block, lds, st, in, vb, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, nu, (int)cj);
 }
 static void ytile(const PrunedTuning& tn, int L, int ngrp, int l, int& TG, int& TZ) {
     // auto (0): all groups x 1 plane, except at L >= 1024 where 32 groups x 8 planes keeps the 128-B chunks that the
@@ -768,49 +768,37 @@ static void ytile(const PrunedTuning& tn, int L, int ngrp, int l, int& TG, int& 
     TG = tn.ytile_g > 0 ? tn.ytile_g : ag; if (TG > ngrp) TG = ngrp; while (ngrp % TG) --TG;
     TZ = tn.ytile_z > 0 ? tn.ytile_z : az; if (TZ > l) TZ = l;       while (l % TZ) --TZ;
 }
-template <class C, bool SPLIT, int WPE> static void yfwd_t(const PassForm& f, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
+// the two y passes: INV = false yfwd (a1 -> a2), true yinv (a2 -> a1)
+template <bool INV, class C, bool SPLIT, int WPE, bool FULL> static void ypass_t(const PassForm& f, const YPass& a, hipStream_t st) {
     constexpr int LINES = Tune<C>::YLINES;
     using LL = LdsLayout<LINES, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = f.full ? k_yfwd<C, LINES, SPLIT, WPE, true> : k_yfwd<C, LINES, SPLIT, WPE, false>;
+    auto k = INV ? k_yinv<C, LINES, SPLIT, WPE, FULL> : k_yfwd<C, LINES, SPLIT, WPE, FULL>;
     allow_lds(k, lds);
-    const int TG = f.tg, TZ = f.tz;
-    hipLaunchKernelGGL(k, dim3((unsigned)((Lx / LINES) * l), (unsigned)nrhs), dim3(C::T * LINES), lds, st, a1, a2, tw, Lx, m, l, TG, TZ, p1, p2, b1, b2);
+    hipLaunchKernelGGL(k, dim3((unsigned)((a.Lx / LINES) * a.l), (unsigned)a.nrhs), dim3(C::T * LINES), lds, st, (const cplx*)(INV ? a.a2 : a.a1), INV ? a.a1 : a.a2,
+                       a.tw, a.Lx, a.m, a.l, f.tg, f.tz, a.p1, a.p2, a.batch1, a.batch2);
 }
-template <class C, bool SPLIT, int WPE> static void yinv_t(const PassForm& f, const cplx* a2, cplx* a1, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
-    constexpr int LINES = Tune<C>::YLINES;
-    using LL = LdsLayout<LINES, 3, SPLIT>;
-    const size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = f.full ? k_yinv<C, LINES, SPLIT, WPE, true> : k_yinv<C, LINES, SPLIT, WPE, false>;
-    allow_lds(k, lds);
-    const int TG = f.tg, TZ = f.tz;
-    hipLaunchKernelGGL(k, dim3((unsigned)((Lx / LINES) * l), (unsigned)nrhs), dim3(C::T * LINES), lds, st, a2, a1, tw, Lx, m, l, TG, TZ, p1, p2, b1, b2);
-}
-template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false> static void zfused_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
-                                                    const FusedGeom& g, hipStream_t st, int nrhs, int64_t dBatch) {
+template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE> static void zfused_t(const PassForm& f, const FusedPass& a, hipStream_t st) {
+    const FusedGeom& g = a.g;
     // g.dTile / g.sTile are strides per XB-tile of x'; a workgroup covers LINES of the XB lines of a tile.
     // twl != NULL: full stage-twiddle table, staged in LDS by the kernel.
     constexpr int LINES = Tune<C>::LINES;
     static_assert(XB % LINES == 0, "LINES must divide XB");
     using LL = LdsLayout<LINES, 3, SPLIT>;
     size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = f.full ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, false>;
-    if (!f.twl) twl = nullptr;               // (switched off, or the table does not fit beside the exchange buffer: z_form)
-    if (twl) {
-        k = f.full ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, true, true> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, true>;
-        lds += (size_t)C::TWLEN * sizeof(cplx);
-        tw = twl;
-    }
-    if (f.batch) {
+    const cplx* twl = f.twl ? a.twl : nullptr;  // (switched off, or the table does not fit beside the exchange buffer: z_form)
+    const cplx* tw = twl ? twl : a.tw;
+    if (twl) lds += (size_t)C::TWLEN * sizeof(cplx);
+    decltype(&k_zfused<C, LINES, SPLIT, PREFETCH, WPE, false, ZE, false, false>) k = nullptr;
+    dispatch_flags({f.full, twl != nullptr, f.batch}, [&](auto FULL, auto TWL, auto BATCH) {
         // batch: one symbol load per tile for all right-hand sides (the symbol is always loaded up front there, so the
         // PREFETCH flavours share one instantiation)
-        if (twl) k = f.full ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, true, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, true, true>;
-        else     k = f.full ? k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, true, false, true> : k_zfused<C, LINES, SPLIT, false, WPE, false, ZE, false, false, true>;
-    }
+        k = k_zfused<C, LINES, SPLIT, PREFETCH && !BATCH, WPE, false, ZE, FULL, TWL, BATCH>;
+    });
     allow_lds(k, lds);
     if (LINES == XB) {
-        hipLaunchKernelGGL(k, dim3((unsigned)((g.Lx / XB) * g.nouter)), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
-                           g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, nrhs, dBatch,
+        hipLaunchKernelGGL(k, dim3((unsigned)((g.Lx / XB) * g.nouter)), dim3(C::T * LINES), lds, st, a.data, a.sym, tw, g.nouter,
+                           g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, a.nrhs, a.dBatch,
                            // (pairing a row with its mirror row on one XCD here too -- blocks b and b + 8 -- measured neutral on the
                            // one-tile and the multi-right-hand-side forms at 48^3 ... 256^3: left off)
                            0);
@@ -818,8 +806,8 @@ template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false> static v
         // split each tile into XB/LINES sub-groups: sub-group h starts at xi offset h*LINES
         // (tile, sub-group) collapse to one group index only when tiles are XB-contiguous in xi (2D natural layout)
         LSFC_REQUIRE(g.dTile == XB && g.sTile == XB, "sub-tile groups need the natural (2D) layout");
-        hipLaunchKernelGGL(k, dim3((unsigned)((g.Lx / LINES) * g.nouter)), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
-                           (int64_t)LINES, g.dOuter, g.dLine, (int64_t)LINES, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, nrhs, dBatch,
+        hipLaunchKernelGGL(k, dim3((unsigned)((g.Lx / LINES) * g.nouter)), dim3(C::T * LINES), lds, st, a.data, a.sym, tw, g.nouter,
+                           (int64_t)LINES, g.dOuter, g.dLine, (int64_t)LINES, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, a.nrhs, a.dBatch,
                            (XB / LINES == 2 && g.nouter == 1 && (g.Lx / LINES) % 16 == 0 && !env_flag_no_sibling_pairs()) ? 1 : 0);
     }
 }
@@ -831,31 +819,28 @@ static int cu_count() {
     return cus;
 }
 static unsigned* ticket_set(hipStream_t st);
-template <class C, bool SPLIT, bool LATE_SYM = false, bool TICKETS = false> static void zfused_persist_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl,
-                                                            const FusedGeom& g, hipStream_t st) {
+template <class C, bool SPLIT, bool LATE_SYM, bool TICKETS> static void zfused_persist_t(const PassForm& f, const FusedPass& a, hipStream_t st) {
+    const FusedGeom& g = a.g;
     constexpr int LINES = XB;
     using LL = LdsLayout<LINES, 3, SPLIT>;
     size_t lds = persist_xbuf_bytes<C, LINES, SPLIT, false>();
-    if (!f.twl) twl = nullptr;
+    const cplx* twl = f.twl ? a.twl : nullptr;
+    const cplx* tw = twl ? twl : a.tw;
+    if (twl) lds += (size_t)C::TWLEN * sizeof(cplx);
     const int xl = f.xl;                     // resolved by z_form: 0, 1, and with the table 3 or (ticketed) 5
-    auto k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS>;
-    if (twl) {
-        k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS>;
-        lds += (size_t)C::TWLEN * sizeof(cplx);
-        tw = twl;
-    }
     // lane exchanges between stages of equal radix (whole-complex whole tiles, symbol after the first stage: the 512^3 and 256^3 forms)
-    if constexpr (xlane_ok<C, LL>() && !SPLIT && LATE_SYM) {
-        if (xl == 1) {
-            if (twl) k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 1>;
-            else     k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, false, LATE_SYM, false, TICKETS, 1> : k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS, 1>;
-        } else if (xl >= 2 && twl) {
-            // 3: + mirror symbol values from L2 (XL & 2; measured slower, profiles/r03_experiment_fused_pass_variants.log)
-            if (xl == 5 && TICKETS) k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 5> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 5>;
-            else if (xl == 3) k = f.full ? k_zfused_persist<C, LINES, SPLIT, true, true, LATE_SYM, false, TICKETS, 3> : k_zfused_persist<C, LINES, SPLIT, false, true, LATE_SYM, false, TICKETS, 3>;
-            else fail(LSFC_EINVAL, "internal: persistent fused pass with lane-exchange form %d", xl);
-        }
-    } else LSFC_REQUIRE(xl == 0, "internal: lane exchanges requested from a persistent form that has none");
+    constexpr bool XLANE = xlane_ok<C, LL>() && !SPLIT && LATE_SYM;
+    decltype(&k_zfused_persist<C, LINES, SPLIT, false, false, LATE_SYM, false, TICKETS>) k = nullptr;
+    dispatch_flags({f.full, twl != nullptr}, [&](auto FULL, auto TWL) {
+        if (xl == 0) k = k_zfused_persist<C, LINES, SPLIT, FULL, TWL, LATE_SYM, false, TICKETS>;
+        else if constexpr (!XLANE) fail(LSFC_EINVAL, "internal: lane exchanges requested from a persistent form that has none");
+        else if (xl == 1) k = k_zfused_persist<C, LINES, SPLIT, FULL, TWL, LATE_SYM, false, TICKETS, 1>;
+        // 3: + mirror symbol values from L2 (XL & 2; measured slower, profiles/r03_experiment_fused_pass_variants.log)
+        else if constexpr (!TWL) fail(LSFC_EINVAL, "internal: persistent fused pass with lane-exchange form %d", xl);
+        else if (xl == 5 && TICKETS) k = k_zfused_persist<C, LINES, SPLIT, FULL, TWL, LATE_SYM, false, TICKETS, 5>;
+        else if (xl == 3) k = k_zfused_persist<C, LINES, SPLIT, FULL, TWL, LATE_SYM, false, TICKETS, 3>;
+        else fail(LSFC_EINVAL, "internal: persistent fused pass with lane-exchange form %d", xl);
+    });
     if (TICKETS) lds += 16;                             // the ticket slots
     allow_lds(k, lds);
     const int cus = cu_count();
@@ -863,7 +848,7 @@ template <class C, bool SPLIT, bool LATE_SYM = false, bool TICKETS = false> stat
     // workgroups per CU that fit (LDS-limited); the walk stays interleaved so that co-resident workgroups touch neighbouring tiles
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, ((size_t)160 * 1024) / lds));
     const unsigned grid = std::min<unsigned>(ntiles, (unsigned)(cus * per_cu));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
+    hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, a.data, a.sym, tw, g.nouter,
                        g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, ntiles, TICKETS ? ticket_set(st) : (unsigned*)nullptr);
 }
 // Ticket counters of the half-tile pass: 8 (one per XCD) per launch, zeroed on the launch's stream just before it.  A ring of
@@ -888,27 +873,29 @@ static unsigned* ticket_set(hipStream_t st) {
     return set;
 }
 // the same on half tiles: 4-line workgroups with the twiddle table, as many per CU as the LDS holds (two at L = 1024)
-template <class C> static void zfused_persist_half_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* twl, const FusedGeom& g, hipStream_t st) {
+template <class C> static void zfused_persist_half_t(const PassForm& f, const FusedPass& a, hipStream_t st) {
+    const FusedGeom& g = a.g;
     if constexpr (C::L >= 1024) {
         constexpr int LINES = XB / 2;
         constexpr size_t lds = persist_lds_bytes<C, LINES, false, true, true>() + 16;   // + the ticket slot
         static_assert(lds <= (size_t)160 * 1024, "half-tile persistent pass: exchange buffer exceeds the LDS");
-        auto k = f.full ? k_zfused_persist<C, LINES, false, true, true, true, true> : k_zfused_persist<C, LINES, false, false, true, true, true>;
-        if constexpr (xlane_ok<C, LdsLayout<LINES, -1, false>>()) {
-            if (f.xl) k = f.full ? k_zfused_persist<C, LINES, false, true, true, true, true, true, 1> : k_zfused_persist<C, LINES, false, false, true, true, true, true, 1>;
-        }
+        constexpr bool XLANE = xlane_ok<C, LdsLayout<LINES, -1, false>>();
+        decltype(&k_zfused_persist<C, LINES, false, false, true, true, true>) k = nullptr;
+        dispatch_flags({f.full, XLANE && f.xl != 0}, [&](auto FULL, auto XL) {
+            if constexpr (XLANE || !XL) k = k_zfused_persist<C, LINES, false, FULL, true, true, true, true, XL ? 1 : 0>;
+        });
         // (tried in round 3: the ONE LDS exchange left per direction run split -- real parts, then imaginary parts, through half the
         // buffer -- so that TWO half-tile workgroups fit a CU at 1280 / 1536 points: without the in-stage stores every output of the
         // widest butterfly stays live next to the symbol values in flight, the kernels spill (240 / 472 bytes per lane), 640^3 ties
         // at 30.4 ms and 768^3 loses 49.3 -> 60.7 ms; removed, profiles/r03_experiment_lane_exchange_radix4.log)
-        LSFC_REQUIRE(twl != nullptr, "half-tile persistent pass: twiddle table missing");
+        LSFC_REQUIRE(a.twl != nullptr, "half-tile persistent pass: twiddle table missing");
         allow_lds(k, lds);
         const unsigned ntiles = (unsigned)((g.Lx / XB) * g.nouter);
         LSFC_REQUIRE(ntiles % 16 == 0 && (g.nouter % 2 == 0 || !g.ytab), "ticketed half-tile z pass needs a multiple of 16 tiles in row pairs");
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ((size_t)160 * 1024) / lds));
         const unsigned grid = std::min<unsigned>(2 * ntiles, (unsigned)(cu_count() * per_cu));
         unsigned* tickets = ticket_set(st);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, data, sym, twl, g.nouter,
+        hipLaunchKernelGGL(k, dim3(grid), dim3(C::T * LINES), lds, st, a.data, a.sym, a.twl, g.nouter,
                            g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, ntiles, tickets);
     } else {
         fail(LSFC_EINVAL, "half-tile persistent pass: lines of %d points run as whole tiles", (int)C::L);
@@ -917,61 +904,29 @@ template <class C> static void zfused_persist_half_t(const PassForm& f, cplx* da
 
 // half-tile z pass (L = 1024 and L = 1536 in the 3D tiled layout only): 4-line workgroups, sibling halves 8 blocks apart
 // (LINES = 2: quarter tiles -- four sibling workgroups per tile, 32 blocks per group of 8 tiles)
-template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE = false, int LINES = 4> static void zfused_half_t(const PassForm& f, cplx* data, const cplx* sym, const cplx* tw,
-                                                         const FusedGeom& g, hipStream_t st) {
+template <class C, bool SPLIT, bool PREFETCH, int WPE, bool ZE, int LINES, bool FULL> static void zfused_half_t(const FusedPass& a, hipStream_t st) {
+    const FusedGeom& g = a.g;
     using LL = LdsLayout<LINES, 3, SPLIT>;
     const size_t lds = (size_t)LL::line_elems(C::L) * LINES * LL::elem_bytes();
-    auto k = f.full ? k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, true, false> : k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, false, false>;
+    auto k = k_zfused<C, LINES, SPLIT, PREFETCH, WPE, true, ZE, FULL, false>;
     allow_lds(k, lds);
     const int64_t ntiles = (int64_t)(g.Lx / XB) * g.nouter;
     LSFC_REQUIRE(ntiles % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
-    hipLaunchKernelGGL(k, dim3((unsigned)((XB / LINES) * ntiles)), dim3(C::T * LINES), lds, st, data, sym, tw, g.nouter,
+    hipLaunchKernelGGL(k, dim3((unsigned)((XB / LINES) * ntiles)), dim3(C::T * LINES), lds, st, a.data, a.sym, a.tw, g.nouter,
                        g.dTile, g.dOuter, g.dLine, g.sTile, g.sOuter, g.sLine, g.ytab, g.zm, g.nin, 1, (int64_t)0, 0);
 }
-
-#if LSFC_FAMILY == 2
-#define LSFC_DISPATCH_L(L, CALL)                                           \
-    switch (L) {                                                           \
-    case 32:   { using C = Cfg32;   CALL; } break;                         \
-    case 64:   { using C = Cfg64;   CALL; } break;                         \
-    case 128:  { using C = Cfg128;  CALL; } break;                         \
-    case 256:  { using C = Cfg256;  CALL; } break;                         \
-    case 512:  { using C = Cfg512;  CALL; } break;                         \
-    case 1024: { using C = Cfg1024; CALL; } break;                         \
-    case 2048: { using C = Cfg2048; CALL; } break;                         \
-    default: fail(LSFC_EINVAL, "pruned pipeline: unsupported padded length %d", (int)(L)); }
-#elif LSFC_FAMILY == 3
-#define LSFC_DISPATCH_L(L, CALL)                                           \
-    switch (L) {                                                           \
-    case 48:   { using C = Cfg48;   CALL; } break;                         \
-    case 96:   { using C = Cfg96;   CALL; } break;                         \
-    case 192:  { using C = Cfg192;  CALL; } break;                         \
-    case 384:  { using C = Cfg384;  CALL; } break;                         \
-    case 768:  { using C = Cfg768;  CALL; } break;                         \
-    case 1536: { using C = Cfg1536; CALL; } break;                         \
-    default: fail(LSFC_EINVAL, "pruned pipeline: unsupported padded length %d", (int)(L)); }
-#else
-#define LSFC_DISPATCH_L(L, CALL)                                           \
-    switch (L) {                                                           \
-    case 80:   { using C = Cfg80;   CALL; } break;                         \
-    case 160:  { using C = Cfg160;  CALL; } break;                         \
-    case 320:  { using C = Cfg320;  CALL; } break;                         \
-    case 640:  { using C = Cfg640;  CALL; } break;                         \
-    case 1280: { using C = Cfg1280; CALL; } break;                         \
-    default: fail(LSFC_EINVAL, "pruned pipeline: unsupported padded length %d", (int)(L)); }
-#endif
 
 // Loads this family's code object (several MB: hundreds of kernel instantiations) on the current device.  HIP loads code
 // objects lazily at the first launch from them; done here, once per device at plan creation and followed by a device
 // synchronisation, the load never runs concurrently with a caller's transfers or the first real pass.
 __global__ void FAM(k_warmup)(int* p) { if (p) *p = 0; }
-void FAM(pruned_warmup)() {
+static void warmup() {
     hipLaunchKernelGGL(FAM(k_warmup), dim3(1), dim3(64), 0, 0, (int*)nullptr);
     LSFC_HIP(hipGetLastError());
 }
 
-void FAM(pruned_perm)(int L, int* freq_of_storage) {
-    LSFC_DISPATCH_L(L, perm_table<C>(freq_of_storage));
+static void perm(int L, int* freq_of_storage) {
+    dispatch_line(L, [&](auto c) { perm_table<decltype(c)>(freq_of_storage); });
 }
 
 // ---------------------------------------------------------------------------
@@ -1011,16 +966,18 @@ template <class C> static LineTraits line_traits_t() {
 }
 static LineTraits line_traits(int L) {
     LineTraits t{};
-    LSFC_DISPATCH_L(L, t = line_traits_t<C>());
+    dispatch_line(L, [&](auto c) { t = line_traits_t<decltype(c)>(); });
     return t;
 }
 
-PassForm FAM(pruned_xform)(PassFamily family, int L, const PrunedTuning& tn, int n) {
+static PassForm xform(PassFamily family, const PrunedTuning& tn, const XPass& a) {
+    const int L = a.L, n = a.n;
     PassForm f;
     f.family = family; f.L = L; f.split = tn.split_x; f.full = n == L / 2;
     return f;
 }
-PassForm FAM(pruned_yform)(PassFamily family, int L, const PrunedTuning& tn, int Lx, int m, int l) {
+static PassForm yform(PassFamily family, const PrunedTuning& tn, const YPass& a) {
+    const int L = a.L, Lx = a.Lx, m = a.m, l = a.l;
     const LineTraits t = line_traits(L);
     PassForm f;
     f.family = family; f.L = L; f.full = m == L / 2; f.lines = t.ylines;
@@ -1037,41 +994,35 @@ static int chunk_magic(int L, int W) {
     LSFC_REQUIRE(W >= 8 && W <= L && L % W == 0 && L <= 2048, "chunk width %d does not divide the line length %d", W, L);
     return (1 << 22) / W + 1;
 }
-void FAM(pruned_xfwd)(int L, const PrunedTuning& tn, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, bool cj, const double* nu_im) {
-    const int wmagic = chunk_magic(L, W);
-    if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
-    const PassForm f = FAM(pruned_xform)(PassFamily::XFWD, L, tn, n);
-    if (f.split) { LSFC_DISPATCH_L(L, (xfwd_t<C, true>(f, vb, nrhs, obatch, nu, nu_im, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
-    else         { LSFC_DISPATCH_L(L, (xfwd_t<C, false>(f, vb, nrhs, obatch, nu, nu_im, out, tw, nlines, wmagic, W, Wp, n, bstride, st, cj))); }
+template <bool INV> static void xpass(const PrunedTuning& tn, const XPass& a, hipStream_t st) {
+    const int wmagic = chunk_magic(a.L, a.W);
+    const int64_t bstride = a.bstride > 0 ? a.bstride : (int64_t)a.Wp * a.nlines;       // dense chunks: [chunk][line][Wp]
+    const PassForm f = xform(INV ? PassFamily::XINV : PassFamily::XFWD, tn, a);
+    dispatch_line(a.L, [&](auto c) { dispatch_flags({f.split, f.full}, [&](auto SPLIT, auto FULL) {
+        xpass_t<INV, decltype(c), SPLIT, FULL>(a, wmagic, bstride, st);
+    }); });
     LSFC_HIP(hipGetLastError());
 }
-void FAM(pruned_xinv)(int L, const PrunedTuning& tn, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t st, int64_t bstride, const double* nu, bool cj, const double* nu_im) {
-    const int wmagic = chunk_magic(L, W);
-    if (bstride <= 0) bstride = (int64_t)Wp * nlines;       // dense chunks: [chunk][line][Wp]
-    const PassForm f = FAM(pruned_xform)(PassFamily::XINV, L, tn, n);
-    if (f.split) { LSFC_DISPATCH_L(L, (xinv_t<C, true>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, nu_im, cj))); }
-    else         { LSFC_DISPATCH_L(L, (xinv_t<C, false>(f, in, vb, nrhs, ibatch, alpha, beta, tw, nlines, wmagic, W, Wp, n, bstride, st, nu, nu_im, cj))); }
+template <bool INV> static void ypass(const PrunedTuning& tn, const YPass& a, hipStream_t st) {
+    const PassForm f = yform(INV ? PassFamily::YINV : PassFamily::YFWD, tn, a);
+    dispatch_line(a.L, [&](auto c) { dispatch_flags({f.split, f.full}, [&](auto SPLIT, auto FULL) {
+        ypass_t<INV, decltype(c), SPLIT, 1, FULL>(f, a, st);
+    }); });
     LSFC_HIP(hipGetLastError());
 }
-void FAM(pruned_yfwd)(int L, const PrunedTuning& tn, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
-    const PassForm f = FAM(pruned_yform)(PassFamily::YFWD, L, tn, Lx, m, l);
-    if (f.split) { LSFC_DISPATCH_L(L, (yfwd_t<C, true, 1>(f, a1, a2, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
-    else         { LSFC_DISPATCH_L(L, (yfwd_t<C, false, 1>(f, a1, a2, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
-    LSFC_HIP(hipGetLastError());
-}
-void FAM(pruned_yinv)(int L, const PrunedTuning& tn, const cplx* a2, cplx* a1, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t st, int nrhs, int64_t b1, int64_t b2) {
-    const PassForm f = FAM(pruned_yform)(PassFamily::YINV, L, tn, Lx, m, l);
-    if (f.split) { LSFC_DISPATCH_L(L, (yinv_t<C, true, 1>(f, a2, a1, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
-    else         { LSFC_DISPATCH_L(L, (yinv_t<C, false, 1>(f, a2, a1, tw, Lx, m, l, p1, p2, st, nrhs, b1, b2))); }
-    LSFC_HIP(hipGetLastError());
-}
-int FAM(pruned_twfull_len)(int L) {
+// (functions of their own, not xpass<false> ... in the table: the table is host code only, and the device pass instantiates the
+// kernels of a launcher template only where something it compiles names the launcher)
+static void xfwd(const PrunedTuning& tn, const XPass& a, hipStream_t st) { xpass<false>(tn, a, st); }
+static void xinv(const PrunedTuning& tn, const XPass& a, hipStream_t st) { xpass<true>(tn, a, st); }
+static void yfwd(const PrunedTuning& tn, const YPass& a, hipStream_t st) { ypass<false>(tn, a, st); }
+static void yinv(const PrunedTuning& tn, const YPass& a, hipStream_t st) { ypass<true>(tn, a, st); }
+static int twfull_len(int L) {
     int len = 0;
-    LSFC_DISPATCH_L(L, len = C::TWLEN);
+    dispatch_line(L, [&](auto c) { len = decltype(c)::TWLEN; });
     return len;
 }
-void FAM(pruned_twfull)(int L, const cplx* tw, cplx* out) {
-    LSFC_DISPATCH_L(L, twfull_table<C>(out, tw));
+static void twfull(int L, const cplx* tw, cplx* out) {
+    dispatch_line(L, [&](auto c) { twfull_table<decltype(c)>(out, tw); });
 }
 
 // the lane-exchange form a persistent whole-tile kernel runs for the request `req` (knob "xlane")
@@ -1083,7 +1034,10 @@ static int persist_xl(int req, bool available, bool twl, bool tickets) {
     if (req >= 2 && twl) return (req == 5 && tickets) ? 5 : (req == 3 ? 3 : 1);
     return 0;
 }
-PassForm FAM(pruned_zfused_form)(int L, const PrunedTuning& tn, const FusedGeom& g, bool have_twl, int nrhs) {
+static PassForm zfused_form(const PrunedTuning& tn, const FusedPass& a) {
+    const int L = a.L, nrhs = a.nrhs;
+    const FusedGeom& g = a.g;
+    const bool have_twl = a.twl != nullptr;       // the caller holds the full stage-twiddle table of the line
     const LineTraits t = line_traits(L);
     const int64_t ntiles = (int64_t)(g.Lx / XB) * g.nouter;
     PassForm f;
@@ -1143,7 +1097,8 @@ PassForm FAM(pruned_zfused_form)(int L, const PrunedTuning& tn, const FusedGeom&
         }
     }
     if (nrhs > 1 && half_form) {
-        f = FAM(pruned_zfused_form)(L, tn, g, have_twl, 1);
+        FusedPass one = a; one.nrhs = 1;
+        f = zfused_form(tn, one);
         f.per_member = true;
         return f;
     }
@@ -1191,74 +1146,76 @@ PassForm FAM(pruned_zfused_form)(int L, const PrunedTuning& tn, const FusedGeom&
     return f;
 }
 
-void FAM(pruned_zfused)(int L, const PrunedTuning& tn, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom& g, hipStream_t st,
-                        int nrhs, int64_t dBatch) {
-    const PassForm f = FAM(pruned_zfused_form)(L, tn, g, twl != nullptr, nrhs);
+// The half-tile one-tile kernels that exist, (line, SPLIT, PREFETCH, WPE, LINES): each with the full and the z-even symbol, the
+// quarter tiles of the 2048-point line with the z-even symbol only
+template <class C_, bool SPLIT_, bool PREFETCH_, int WPE_, int LINES_ = 4> struct HalfTile {
+    using C = C_;
+    static constexpr bool SPLIT = SPLIT_, PREFETCH = PREFETCH_;
+    static constexpr int WPE = WPE_, LINES = LINES_;
+};
+template <class... H> struct HalfTiles {};
+#if LSFC_FAMILY == 2
+using FamilyHalfTiles = HalfTiles<HalfTile<Cfg1024, true, true, 2>, HalfTile<Cfg1024, true, false, 3>, HalfTile<Cfg1024, false, true, 2>, HalfTile<Cfg1024, false, false, 2>,
+                                  HalfTile<Cfg2048, false, false, 2>, HalfTile<Cfg2048, false, false, 2, 2>>;
+#elif LSFC_FAMILY == 3
+using FamilyHalfTiles = HalfTiles<HalfTile<Cfg1536, true, true, 1>, HalfTile<Cfg1536, true, false, 1>, HalfTile<Cfg1536, false, true, 1>, HalfTile<Cfg1536, false, false, 1>>;
+#else
+using FamilyHalfTiles = HalfTiles<>;
+#endif
+template <class H> static bool zfused_half_try(const PassForm& f, const FusedPass& a, hipStream_t st) {
+    if (f.L != H::C::L || f.split != H::SPLIT || f.prefetch != H::PREFETCH || f.wpe != H::WPE || f.lines != H::LINES) return false;
+    LSFC_REQUIRE(H::LINES == 4 || f.ze, "internal: quarter-tile fused pass without the z-even symbol");
+    dispatch_flags({f.ze, f.full}, [&](auto ZE, auto FULL) {
+        if constexpr (H::LINES == 4 || ZE) zfused_half_t<typename H::C, H::SPLIT, H::PREFETCH, H::WPE, ZE, H::LINES, FULL>(a, st);
+    });
+    return true;
+}
+template <class... H> static void zfused_half(HalfTiles<H...>, const PassForm& f, const FusedPass& a, hipStream_t st) {
+    if (!(zfused_half_try<H>(f, a, st) || ...))
+        fail(LSFC_EINVAL, "internal: no half-tile fused kernel of flavour %d at %d points", (f.split ? 100 : 0) + (f.prefetch ? 10 : 0) + f.wpe, f.L);
+}
+
+static void zfused(const PrunedTuning& tn, const FusedPass& a, hipStream_t st) {
+    const PassForm f = zfused_form(tn, a);
     if (f.per_member) {
-        for (int r = 0; r < nrhs; ++r)
-            FAM(pruned_zfused)(L, tn, data + (int64_t)r * dBatch, sym, tw, twl, g, st, 1, 0);
+        for (int r = 0; r < a.nrhs; ++r) {
+            FusedPass one = a; one.data = a.data + (int64_t)r * a.dBatch; one.nrhs = 1; one.dBatch = 0;
+            zfused(tn, one, st);
+        }
         return;
     }
     switch (f.family) {
     case PassFamily::ZFUSED_PERSIST_HALF:
-        LSFC_DISPATCH_L(L, (zfused_persist_half_t<C>(f, data, sym, twl, g, st)));
+        dispatch_line(a.L, [&](auto c) { zfused_persist_half_t<decltype(c)>(f, a, st); });
         break;
     case PassFamily::ZFUSED_PERSIST:
         LSFC_REQUIRE(f.wpe == 1 && f.lines == XB, "internal: persistent whole tiles run %d lines, %d workgroups per CU", f.lines, f.wpe);
-        if (f.tickets)                     { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true, true>(f, data, sym, tw, twl, g, st))); }
-        else if (f.late_sym && !f.split)   { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false, true>(f, data, sym, tw, twl, g, st))); }
-        else if (f.late_sym)               { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true, true>(f, data, sym, tw, twl, g, st))); }
-        else if (f.split)                  { LSFC_DISPATCH_L(L, (zfused_persist_t<C, true>(f, data, sym, tw, twl, g, st))); }
-        else                               { LSFC_DISPATCH_L(L, (zfused_persist_t<C, false>(f, data, sym, tw, twl, g, st))); }
+        dispatch_line(a.L, [&](auto c) { dispatch_flags({f.split, f.late_sym, f.tickets}, [&](auto SPLIT, auto LATE_SYM, auto TICKETS) {
+            // (tickets: whole-complex exchanges with the symbol after the first stage only)
+            if constexpr (!TICKETS || (!SPLIT && LATE_SYM)) zfused_persist_t<decltype(c), SPLIT, LATE_SYM, TICKETS>(f, a, st);
+            else fail(LSFC_EINVAL, "internal: no ticketed persistent fused kernel with SPLIT=%d LATE_SYM=%d", (int)SPLIT, (int)LATE_SYM);
+        }); });
         break;
-    case PassFamily::ZFUSED_HALF: {
-        // the instantiated flavours: (SPLIT, PREFETCH, WPE) of the description picks one, anything else is an internal error
-        const int flavour = (f.split ? 100 : 0) + (f.prefetch ? 10 : 0) + f.wpe;
-#define LSFC_ZH(C, SP, PF, W) do { if (f.ze) zfused_half_t<C, SP, PF, W, true>(f, data, sym, tw, g, st); \
-                                   else zfused_half_t<C, SP, PF, W, false>(f, data, sym, tw, g, st); } while (0)
-#if LSFC_FAMILY == 2
-        if (L == 1024) {
-            switch (flavour) {
-            case 112: LSFC_ZH(Cfg1024, true, true, 2); break;
-            case 103: LSFC_ZH(Cfg1024, true, false, 3); break;
-            case 12:  LSFC_ZH(Cfg1024, false, true, 2); break;
-            case 2:   LSFC_ZH(Cfg1024, false, false, 2); break;
-            default: fail(LSFC_EINVAL, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
-            }
-        } else {
-            LSFC_REQUIRE(L == 2048, "internal: half-tile fused pass at %d points", L);
-            LSFC_REQUIRE(((int64_t)(g.Lx / XB) * g.nouter) % 8 == 0, "half-tile z pass needs a multiple of 8 tiles");
-            LSFC_REQUIRE(flavour == 2, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
-            if (f.lines == 2) zfused_half_t<Cfg2048, false, false, 2, true, 2>(f, data, sym, tw, g, st);
-            else LSFC_ZH(Cfg2048, false, false, 2);
-        }
-#elif LSFC_FAMILY == 3
-        LSFC_REQUIRE(L == 1536, "internal: half-tile fused pass at %d points", L);
-        switch (flavour) {
-        case 111: LSFC_ZH(Cfg1536, true, true, 1); break;
-        case 101: LSFC_ZH(Cfg1536, true, false, 1); break;
-        case 11:  LSFC_ZH(Cfg1536, false, true, 1); break;
-        case 1:   LSFC_ZH(Cfg1536, false, false, 1); break;
-        default: fail(LSFC_EINVAL, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
-        }
-#else
-        fail(LSFC_EINVAL, "internal: no half-tile fused kernel of flavour %d at %d points", flavour, L);
-#endif
-#undef LSFC_ZH
+    case PassFamily::ZFUSED_HALF:
+        zfused_half(FamilyHalfTiles{}, f, a, st);
         break;
-    }
     case PassFamily::ZFUSED:
         LSFC_REQUIRE(f.wpe == 1, "internal: one-tile fused kernels are bounded for one workgroup per CU, not %d", f.wpe);
-#define LSFC_ZF(SP, PF) do { if (f.ze) { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, true>(f, data, sym, tw, twl, g, st, nrhs, dBatch))); } \
-                             else      { LSFC_DISPATCH_L(L, (zfused_t<C, SP, PF, 1, false>(f, data, sym, tw, twl, g, st, nrhs, dBatch))); } } while (0)
-        if (f.split) { if (f.prefetch) { LSFC_ZF(true, true); } else { LSFC_ZF(true, false); } }
-        else         { if (f.prefetch) { LSFC_ZF(false, true); } else { LSFC_ZF(false, false); } }
-#undef LSFC_ZF
+        dispatch_line(a.L, [&](auto c) { dispatch_flags({f.split, f.prefetch, f.ze}, [&](auto SPLIT, auto PREFETCH, auto ZE) {
+            zfused_t<decltype(c), SPLIT, PREFETCH, 1, ZE>(f, a, st);
+        }); });
         break;
     default:
         fail(LSFC_EINVAL, "internal: %s is not a form of the fused pass", pass_family_name(f.family));
     }
     LSFC_HIP(hipGetLastError());
 }
+
+// the one symbol this compilation exports (pruned.hpp); host only -- the device pass would emit the constant into the code object too
+#ifndef __HIP_DEVICE_COMPILE__
+extern const PrunedFamily FAM(pruned_family) = {.xfwd = xfwd, .xinv = xinv, .yfwd = yfwd, .yinv = yinv, .zfused = zfused,
+                                                .xform = xform, .yform = yform, .zfused_form = zfused_form,
+                                                .perm = perm, .twfull_len = twfull_len, .twfull = twfull, .warmup = warmup};
+#endif
 
 } // namespace lsfc

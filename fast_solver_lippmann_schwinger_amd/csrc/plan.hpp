@@ -179,8 +179,6 @@ void plan_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op);
 // nrhs <= LSFC_MAX_BATCH right-hand sides in one pass of the pipeline: y_j = alpha*x_j + beta*conv(...x_j); the symbol is read
 // once per batch in the fused pass (pruned pipeline; the other pipelines run the members one after the other)
 void plan_convolve_batch_dev(lsfc_plan* p, int nrhs, const VecBatch& vb, const ConvOp& op);
-// Re nu and Im nu (null: nu is real) of the plan, or of a pass: both null where the pass does not multiply
-struct NuPlanes { const double* re; const double* im; };
 // the operator M = I + omega^2 G nu, or its transpose / adjoint (lsfc_plan_set_op)
 inline void plan_apply_dev(lsfc_plan* p, const cplx* x, cplx* y) { plan_convolve_dev(p, x, y, plan_operator(p)); }
 // ... on cnt (in, out) pairs, in groups of LSFC_MAX_BATCH that share one pass of the pipeline (the batched solvers)

@@ -68,22 +68,38 @@ int pruned_best_length(int64_t n);
 void pruned_perm(int L, int* freq_of_storage);
 PrunedTuning pruned_default_tuning();
 
+// Re nu and Im nu (null: nu is real) of the plan, or of a pass: both null where the pass does not multiply
+struct NuPlanes { const double* re; const double* im; };
+
+// What a pass takes, by name: plain aggregates (no defaults -- a site that fills one names every field).
 // nrhs / vb / *batch: right-hand sides per launch (<= LSFC_MAX_BATCH), their vectors, and the distance between the
-// batch members in the work arrays
-void pruned_xfwd(int L, const PrunedTuning&, const VecBatch& vb, int nrhs, int64_t obatch, const double* nu, cplx* out, const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t,
-                 int64_t bstride = 0,      // bstride: distance between chunks of the storage axis (0: dense, Wp * nlines)
-                 bool conj = false,        // conj: transform conj(nu .* x)
-                 const double* nu_im = nullptr);   // Im nu, with nu its real part: transform nu .* x, with conj nu .* conj(x)
-// y = alpha*x + beta * (nu ? nu : 1) .* (conj ? conj(v) : v), v the cropped inverse transform; nu like x is indexed as y is.
-// nu_im: Im nu, with nu its real part; with conj the factor is conj(nu) (the conjugation is outermost: plan.hpp, ConvOp)
-void pruned_xinv(int L, const PrunedTuning&, const cplx* in, const VecBatch& vb, int nrhs, int64_t ibatch, double alpha, double beta,
-                 const cplx* tw, int64_t nlines, int W, int Wp, int n, hipStream_t, int64_t bstride = 0, const double* nu = nullptr, bool conj = false,
-                 const double* nu_im = nullptr);
-// p1: row pitch of A1 (>= Lx), p2: pitch of one storage-y row of an A2 tile (>= 8*l); both multiples of 8 elements
-void pruned_yfwd(int L, const PrunedTuning&, const cplx* a1, cplx* a2, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t,
-                 int nrhs = 1, int64_t batch1 = 0, int64_t batch2 = 0);
-void pruned_yinv(int L, const PrunedTuning&, const cplx* a2, cplx* a1, const cplx* tw, int Lx, int m, int l, int p1, int p2, hipStream_t,
-                 int nrhs = 1, int64_t batch1 = 0, int64_t batch2 = 0);
+// batch members in the work arrays.
+// The x passes.  xfwd: work = transform of (nu ? nu : 1) .* x, with conj of conj(nu .* x) for a real nu and of nu .* conj(x) for a
+// complex one.  xinv: y = alpha*x + beta * (nu ? nu : 1) .* (conj ? conj(v) : v), v the cropped inverse transform of work; with
+// conj the factor of a complex nu is conj(nu) (the conjugation is outermost: plan.hpp, ConvOp).  nu like x is indexed as y is.
+struct XPass {
+    int L;                  // line length
+    VecBatch vb; int nrhs;
+    cplx* work;             // [chunk][line][Wp]: written by xfwd, read by xinv
+    int64_t wbatch;
+    const cplx* tw;
+    int64_t nlines;
+    int W, Wp, n;
+    int64_t bstride;        // distance between chunks of the storage axis (0: dense, Wp * nlines)
+    NuPlanes nu;
+    bool conj;
+    double alpha, beta;     // (xinv only)
+};
+// The y passes, yfwd a1 -> a2 and yinv a2 -> a1.  p1: row pitch of A1 (>= Lx), p2: pitch of one storage-y row of an A2 tile
+// (>= 8*l); both multiples of 8 elements
+struct YPass {
+    int L;
+    cplx* a1; cplx* a2;
+    const cplx* tw;
+    int Lx, m, l, p1, p2;
+    int nrhs;
+    int64_t batch1, batch2;
+};
 // full stage-twiddle table of the factorisation used for length L (host side; tw[j] = exp(-2 pi i j / L))
 int pruned_twfull_len(int L);
 void pruned_twfull(int L, const cplx* tw, cplx* out);
@@ -125,17 +141,46 @@ struct PassForm {
     int tg = 0, tz = 0;            // y passes: resolved block-order tile (x'-groups x z planes)
     bool per_member = false;       // a batch that runs through this form member by member (one launch per right-hand side)
 };
-PassForm pruned_xfwd_form(int L, const PrunedTuning&, int n);
-PassForm pruned_xinv_form(int L, const PrunedTuning&, int n);
-PassForm pruned_yfwd_form(int L, const PrunedTuning&, int Lx, int m, int l);
-PassForm pruned_yinv_form(int L, const PrunedTuning&, int Lx, int m, int l);
-// have_twl: the caller holds the full stage-twiddle table of the line
-PassForm pruned_zfused_form(int L, const PrunedTuning&, const FusedGeom&, bool have_twl, int nrhs);
+// The fused pass.  twl: full stage-twiddle table of the line, or NULL; dBatch: distance between the batch members in `data`
+struct FusedPass {
+    int L;
+    cplx* data;
+    const cplx* sym;
+    const cplx* tw;
+    const cplx* twl;
+    FusedGeom g;
+    int nrhs;
+    int64_t dBatch;
+};
+PassForm pruned_xfwd_form(const PrunedTuning&, const XPass&);
+PassForm pruned_xinv_form(const PrunedTuning&, const XPass&);
+PassForm pruned_yfwd_form(const PrunedTuning&, const YPass&);
+PassForm pruned_yinv_form(const PrunedTuning&, const YPass&);
+PassForm pruned_zfused_form(const PrunedTuning&, const FusedPass&);
 // "family L=.. SPLIT=.. ..." (one line, no newline) into buf; returns the length written
 int pass_form_print(const PassForm&, char* buf, size_t cap);
 
-// twl: full stage-twiddle table or NULL; dBatch: distance between the batch members in `data`
-void pruned_zfused(int L, const PrunedTuning&, cplx* data, const cplx* sym, const cplx* tw, const cplx* twl, const FusedGeom&, hipStream_t,
-                   int nrhs = 1, int64_t dBatch = 0);
+void pruned_xfwd(const PrunedTuning&, const XPass&, hipStream_t);
+void pruned_xinv(const PrunedTuning&, const XPass&, hipStream_t);
+void pruned_yfwd(const PrunedTuning&, const YPass&, hipStream_t);
+void pruned_yinv(const PrunedTuning&, const YPass&, hipStream_t);
+void pruned_zfused(const PrunedTuning&, const FusedPass&, hipStream_t);
+
+// What one compilation of fft_kernels.hip exports (pruned_family_f2, _f3, _f5): the launchers and the host tables of its lines.
+// pruned.hip routes every call above through the table of the line's family.
+struct PrunedFamily {
+    void (*xfwd)(const PrunedTuning&, const XPass&, hipStream_t);
+    void (*xinv)(const PrunedTuning&, const XPass&, hipStream_t);
+    void (*yfwd)(const PrunedTuning&, const YPass&, hipStream_t);
+    void (*yinv)(const PrunedTuning&, const YPass&, hipStream_t);
+    void (*zfused)(const PrunedTuning&, const FusedPass&, hipStream_t);
+    PassForm (*xform)(PassFamily, const PrunedTuning&, const XPass&);
+    PassForm (*yform)(PassFamily, const PrunedTuning&, const YPass&);
+    PassForm (*zfused_form)(const PrunedTuning&, const FusedPass&);
+    void (*perm)(int L, int* freq_of_storage);
+    int (*twfull_len)(int L);
+    void (*twfull)(int L, const cplx* tw, cplx* out);
+    void (*warmup)();
+};
 
 } // namespace lsfc

@@ -12,6 +12,10 @@ The applies (seeded inputs; device vectors unless "host" is said):
   M.T, M.H             16^3 and 5 x 4 x 3
   sampleG3D            16^3, three sources
   describe_passes      every plan above under the defaults, one and three right-hand sides
+  line lengths         every line length of tests/test_gpu_apply_forms.py (LENGTHS) as the long axis L/2 of thin plans -- 3D along
+                       x, y and z, 2D along y (the fused axis), 16 points along the other axes -- on random even symbols: M * b, the
+                       bare convolution and describe_passes under the default tuning and under z_persist = 3, 5, 6; apply_batch of
+                       three right-hand sides under the default tuning
 
     python tools/apply_digest.py                                    one JSON line per apply, this tree's library
     python tools/apply_digest.py --libs parent=/path/to/liblsfc.so,this= [--out profiles/plan_split_refactor.jsonl]
@@ -128,6 +132,35 @@ def child():
     emit("sampleG3D 16^3 three sources", lsfc.sampleG3D(16.0, None, None, None, [0, M16.N // 2 + 3, M16.N - 1], M16))
     M16.close()
 
+    # every line length, in every pass that can run it (the bare convolution as a batch of one: FFTconvolution takes square
+    # grids only in 2D)
+    from test_gpu_apply_forms import LENGTHS
+
+    def conv(M, b):
+        return lsfc.apply_batch(M, b.reshape(1, -1), 1)
+
+    for L in LENGTHS:
+        thin = {f"3D long {'xyz'[a]}": tuple(L // 2 if d == a else 16 for d in range(3)) for a in range(3)}
+        thin["2D long y"] = (16, L // 2)
+        for name, dims in thin.items():
+            grid = tuple(2 * d for d in dims)
+            nu = rng.uniform(-0.3, 0.3, int(np.prod(dims)))
+            if len(dims) == 3:
+                M = lsfc.FastM3D(even_symbol(grid), nu, *grid, *dims, 2.0)
+            else:
+                M = lsfc.FastM(even_symbol(grid), nu, *grid, *dims, 2.0, quadRule="Greengard_Vico")
+            assert M.pipeline == "pruned-hip", M.pipeline
+            label = f"L={L} {name}"
+            b = applies(label, M, convolve=False)
+            emit(f"{label} convolution", conv(M, b))
+            emit(f"{label} apply_batch nrhs=3", lsfc.apply_batch(M, torch.from_numpy(vec(M.N, 3)).cuda(), 0))
+            for zp in (3, 5, 6):
+                M.set_tuning(z_persist=zp)
+                describe(f"{label} z_persist={zp}", M)
+                emit(f"{label} z_persist={zp} M*b", M * b)
+                emit(f"{label} z_persist={zp} convolution", conv(M, b))
+            M.close()
+
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
@@ -143,7 +176,7 @@ def main():
         env.pop("LSFC_LIBRARY", None)
         if path:
             env["LSFC_LIBRARY"] = os.path.abspath(path)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:                              # (nothing more is started on the device after a child that failed)
             sys.exit(f"{name}: exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}")
         got[name] = [json.loads(ln[len("DIGEST "):]) for ln in r.stdout.splitlines() if ln.startswith("DIGEST ")]
