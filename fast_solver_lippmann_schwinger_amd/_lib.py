@@ -127,6 +127,7 @@ SIGNATURES = {
     "lsfc_multi_apply_dev": (_I, [_P, _PP, _PP, _I]),
     "lsfc_last_error": (C.c_char_p, []),
     "lsfc_padded_length": (_I, [C.c_int64]),
+    "lsfc_storage_order": (_I, [_L, C.POINTER(_L)]),
     "lsfc_version": (C.c_char_p, []),
 }
 

@@ -403,6 +403,15 @@ extern "C" {
 
 const char* lsfc_last_error(void) { return g_last_error; }
 int lsfc_padded_length(int64_t n) { return (n >= 1 && n <= 1024) ? lsfc::pruned_best_length(n) : 0; }
+int lsfc_storage_order(int64_t L, int64_t* freq_of_slot) {
+    return guarded([&] {
+        LSFC_REQUIRE(freq_of_slot, "NULL argument");
+        LSFC_REQUIRE(L >= 1 && L <= 2048 && pruned_length_supported(L), "the pruned pipeline has no lines of %lld points", (long long)L);
+        std::vector<int> perm((size_t)L);
+        pruned_perm((int)L, perm.data());
+        for (int64_t s = 0; s < L; ++s) freq_of_slot[s] = perm[(size_t)s];
+    });
+}
 
 const char* lsfc_version(void) { return "lsfc 0.1 (gfx950, rocFFT + hand-written pruned FFT passes)"; }
 

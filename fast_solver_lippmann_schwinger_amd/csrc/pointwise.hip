@@ -216,9 +216,14 @@ __global__ void k_mirror_dev(const cplx* __restrict__ G, double* __restrict__ pa
         const int i = (int)(idx % Lx); const int64_t r = idx / Lx; const int j = (int)(r % Ly); const int k = (int)(r / Ly);
         const int mj = axis == 1 ? (Ly - j) % Ly : j, mk = axis == 2 ? (Lz - k) % Lz : k, mi = axis == 0 ? (Lx - i) % Lx : i;
         const cplx a = G[idx], b = G[mi + (int64_t)Lx * (mj + (int64_t)Ly * mk)];
-        dmax = fmax(dmax, fmax(fabs(a.x - b.x), fabs(a.y - b.y)));
-        amax = fmax(amax, fmax(fabs(a.x), fabs(a.y)));
+        // (as in k_corner_dev below: a NaN on either side survives the max, which fmax alone would drop)
+        const double d = fmax(fabs(a.x - b.x), fabs(a.y - b.y)), e = fmax(fabs(a.x), fabs(a.y));
+        dmax = (d != d || b.x != b.x || b.y != b.y) ? NAN : fmax(dmax, d);
+        amax = (a.x != a.x || a.y != a.y) ? NAN : fmax(amax, e);
+        if (dmax != dmax || amax != amax) break;
     }
+    const bool bad = dmax != dmax || amax != amax;
+    if (bad) { dmax = INFINITY; amax = INFINITY; }
     max2_tail(dmax, amax, partial);
 }
 double pw_mirror_deviation(const cplx* G, const int L[3], int axis, hipStream_t st) {
@@ -228,7 +233,7 @@ double pw_mirror_deviation(const cplx* G, const int L[3], int axis, hipStream_t 
     LSFC_HIP(hipGetLastError());
     double d, a;
     max2_fold(part.p, blocks, st, d, a);
-    if (!(d == d) || !(a == a)) return 1.0;                       // NaN symbol (unpatched singular omega): never treat as even
+    if (!(d < INFINITY) || !(a < INFINITY)) return 1.0;           // NaN or Inf in the symbol (unpatched singular omega): never treat as even
     return a > 0 ? d / a : 0.0;
 }
 

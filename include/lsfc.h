@@ -133,6 +133,11 @@ int lsfc_plan_set_nu_complex(lsfc_plan* plan, const double* nu, int memspace);
 int lsfc_plan_nu_is_complex(const lsfc_plan* plan, int* is_complex);
 /* copy the working symbol out (debug / tests): count complex entries written */
 int lsfc_plan_get_symbol(const lsfc_plan* plan, double* out, int64_t capacity_complex, int64_t* count);
+/* The order in which the hand-written passes keep a line of L points (debug / tests; with it and the last line of
+ * lsfc_plan_describe_passes the working symbol decodes to natural order): freq_of_slot[s] = frequency index, 0 .. L-1, held at
+ * storage slot s, for s < L.  Pure host arithmetic, no device needed.  LSFC_EINVAL: NULL, or a length that the pipeline does not
+ * have (anything but 2^k, 3*2^k, 5*2^k of lsfc_padded_length). */
+int lsfc_storage_order(int64_t L, int64_t* freq_of_slot);
 
 /* ---- the apply ------------------------------------------------------------ */
 

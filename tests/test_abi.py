@@ -114,6 +114,24 @@ def test_padded_length_rule():
     assert max(lib.lsfc_padded_length(n) / (2 * n) for n in range(24, 1025)) < 4 / 3
 
 
+def test_storage_order_is_a_permutation_of_every_line_length():
+    # host arithmetic only: lsfc_storage_order gives, for every length the pipeline has, each frequency once, and the lower
+    # half of the slots holds the frequencies below L/2 (what the half storage of an even symbol relies on)
+    import fast_solver_lippmann_schwinger_amd._lib as L
+    lib = L.load()
+    for n in (16, 24, 32, 40, 48, 64, 80, 96, 128, 160, 192, 256, 320, 384, 512, 640, 768, 1024):
+        Lp = lib.lsfc_padded_length(n)
+        perm = (ctypes.c_int64 * Lp)()
+        assert lib.lsfc_storage_order(Lp, perm) == 0, Lp
+        perm = np.array(perm)
+        assert sorted(perm) == list(range(Lp)), Lp
+        assert np.all(perm[:Lp // 2] < Lp // 2), Lp
+    one = (ctypes.c_int64 * 4096)()
+    for bad in (0, -32, 16, 33, 40, 56, 3 * 1024, 5 * 512, 4096):
+        assert lib.lsfc_storage_order(bad, one) == L.LSFC_EINVAL, bad
+    assert lib.lsfc_storage_order(32, None) == L.LSFC_EINVAL
+
+
 def test_header_compiles_as_c():
     src = '#include "lsfc.h"\nint main(void){ lsfc_gmres_opts o; (void)o; return LSFC_OK; }\n'
     r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), "-x", "c", "-"],
