@@ -79,6 +79,7 @@ SIGNATURES = {
     "lsfc_gmres": (_I, [_P, _P, _P, C.POINTER(GmresOpts), _P, _L, C.POINTER(GmresResult), _I]),
     "lsfc_gmres_batch": (_I, [_P, _P, _P, _L, C.POINTER(GmresOpts), _P, _L, C.POINTER(GmresResult), _I]),
     "lsfc_bicgstabl": (_I, [_P, _P, _P, C.POINTER(BicgstablOpts), _P, _L, C.POINTER(GmresResult), _I]),
+    "lsfc_bicgstabl_multi": (_I, [_P, _P, _P, C.POINTER(BicgstablOpts), _P, _L, C.POINTER(GmresResult), _I]),
     "lsfc_bicgstabl_batch": (_I, [_P, _P, _P, _L, C.POINTER(BicgstablOpts), _P, _L, C.POINTER(GmresResult), _P, _I]),
     "lsfc_precond_create": (_I, [_PP, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_precond_destroy": (_I, [_P]),

@@ -20,6 +20,10 @@
 // mapping, the slots and the order of summation do not depend on the other members, so a member's bits are those of its
 // solve alone.  The host reads all scalar blocks in one copy per cycle and drops the members that have stopped from
 // the list of the next cycle.  lsfc_bicgstabl is the call with one member.
+//
+// The cycle is written once, over RANKS (struct Rank, bicgstabl_run): one rank is the plan itself -- the launches above, nothing
+// else -- and the P ranks of a single-process multi-device plan (lsfc_bicgstabl_multi) each hold the z slab of every vector on their own device (the
+// team form, k_rank_sum below: sums completed across the ranks in device memory, ordered by events, no host in between).
 #include "plan.hpp"
 #include "krylov_blas.hpp"
 #include "reduce.hpp"
@@ -56,12 +60,36 @@ __device__ __forceinline__ cplx cdiv(cplx a, cplx b) {
 // scal + m S_COUNT, partial + m P_SLOTS RED_BLOCKS, tol2[m].
 struct Members {
     cplx* work; cplx* x; cplx* scal; cplx* partial; const double* tol2;
+    cplx* table; int rank, nranks;                       // the team form only (below)
     int64_t wstride, n;
     int m[KRYLOV_NRHS_MAX];
 };
 __device__ __forceinline__ cplx* m_work(const Members& B, int m) { return B.work + (int64_t)m * B.wstride; }
 __device__ __forceinline__ cplx* m_scal(const Members& B, int m) { return B.scal + (int64_t)m * S_COUNT; }
 __device__ __forceinline__ cplx* m_partial(const Members& B, int m) { return B.partial + (int64_t)m * (P_SLOTS * RED_BLOCKS); }
+
+// The team form (TEAM; lsfc_bicgstabl_multi, on a multi-device plan): the vectors are cut into the z slabs of P ranks, every rank runs
+// the kernels below on its slab with its own scalars, partials and tol^2 (one member), and a sum is completed in two levels.
+// k_rank_sum reduces the nb partials of a slot to the RANK SUM, entry (slot, rank) of the rank's table; the rank copies it
+// into the same entry of the table of every other rank; the kernel that consumes the sum adds the P entries in rank order.
+// Every rank forms every scalar from the same numbers in the same order, so all ranks skip alike and their status words agree.
+// table[r * P_SLOTS + slot]: the slots of one reduction lie side by side in a rank's row, so one copy per pair of ranks moves them.
+__global__ __launch_bounds__(64) void k_rank_sum(Members B, int slot0, int nb) {
+    const int slot = slot0 + blockIdx.x;
+    const cplx s = finish_in_wave(m_partial(B, B.m[0]) + (int64_t)slot * RED_BLOCKS, nb);
+    if (threadIdx.x == 0) B.table[(int64_t)B.rank * P_SLOTS + slot] = s;
+}
+// the sum behind partial slot `slot` of member m in all lanes of the calling wave: the nb block partials in the order of
+// finish_in_wave, or (TEAM) the rank sums in rank order -- with one rank that is the entry itself, the bits of the other form
+template <bool TEAM>
+__device__ __forceinline__ cplx slot_sum(const Members& B, int m, int slot, int nb) {
+    if constexpr (!TEAM) return finish_in_wave(m_partial(B, m) + (int64_t)slot * RED_BLOCKS, nb);
+    else {
+        cplx acc = B.table[slot];
+        for (int r = 1; r < B.nranks; ++r) { const cplx v = B.table[(int64_t)r * P_SLOTS + slot]; acc.x += v.x; acc.y += v.y; }
+        return acc;
+    }
+}
 
 // rs[0] = b - rs[0], in place  (initial residual from rs[0] = A x)
 __global__ void k_residual(Members B, const cplx* __restrict__ ball) {
@@ -80,14 +108,15 @@ __global__ __launch_bounds__(RED_THREADS) void k_dot(Members B, int64_t aoff, in
 }
 
 // scal[S_RES] = sqrt(sum of the P_NORM partials), whatever the status: the initial norm and the norm after a breakdown
+template <bool TEAM>
 __global__ __launch_bounds__(64) void k_norm_finish(Members B, int nb) {
     const int m = B.m[blockIdx.y];
-    const cplx s = finish_in_wave(m_partial(B, m) + (int64_t)P_NORM * RED_BLOCKS, nb);
+    const cplx s = slot_sum<TEAM>(B, m, P_NORM, nb);
     if (threadIdx.x == 0) m_scal(B, m)[S_RES] = make_double2(sqrt(s.x), 0.0);
 }
 
 // rho = sum of the P_RHO partials, beta = rho / sigma; us[i] = rs[i] - beta us[i] for i < NV (= j + 1); block 0 publishes rho, beta
-template <int NV>
+template <int NV, bool TEAM>
 __global__ __launch_bounds__(RED_THREADS) void k_bicg_u(Members B, int64_t uoff, int nb, int cycle) {
     __shared__ cplx bs; __shared__ int skip;
     const int m = B.m[blockIdx.y];
@@ -96,7 +125,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_bicg_u(Members B, int64_t uoff,
     cplx* __restrict__ us = m_work(B, m) + uoff;
     cplx* scal = m_scal(B, m);
     if (threadIdx.x < 64) {
-        const cplx rho = finish_in_wave(m_partial(B, m) + (int64_t)P_RHO * RED_BLOCKS, nb);
+        const cplx rho = slot_sum<TEAM>(B, m, P_RHO, nb);
         if (threadIdx.x == 0) {
             const cplx sg = scal[S_SIGMA]; const double st = scal[S_STATUS].x;
             const cplx beta = cdiv(rho, sg);
@@ -125,7 +154,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_bicg_u(Members B, int64_t uoff,
 
 // sigma = sum of the P_SIGMA partials, alpha = rho / sigma; rs[i] -= alpha us[i+1] for i < NV (= j + 1), x += alpha us[0];
 // block 0 publishes sigma, alpha
-template <int NV>
+template <int NV, bool TEAM>
 __global__ __launch_bounds__(RED_THREADS) void k_bicg_rx(Members B, int64_t uoff, int nb, int cycle) {
     __shared__ cplx as; __shared__ int skip;
     const int m = B.m[blockIdx.y];
@@ -135,7 +164,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_bicg_rx(Members B, int64_t uoff
     cplx* __restrict__ x = B.x + (int64_t)m * n;
     cplx* scal = m_scal(B, m);
     if (threadIdx.x < 64) {
-        const cplx sg = finish_in_wave(m_partial(B, m) + (int64_t)P_SIGMA * RED_BLOCKS, nb);
+        const cplx sg = slot_sum<TEAM>(B, m, P_SIGMA, nb);
         if (threadIdx.x == 0) {
             const cplx rho = scal[S_RHO]; const double st = scal[S_STATUS].x;
             const cplx alpha = cdiv(rho, sg);
@@ -201,15 +230,15 @@ __global__ __launch_bounds__(RED_THREADS) void k_gram(Members B) {
 // Krylov space is exhausted, status ST_EXHAUSTED and no solve of a singular G.  Otherwise gamma = G[1:,1:] \ G[1:,0] by LU
 // with partial pivoting (largest |.|^2 of the column, the lowest row on a tie) and sigma = -(sigma gamma_{l-1}): the
 // factor of the MR part and the sign flip that opens the next cycle.
+template <bool TEAM>
 __global__ __launch_bounds__(64) void k_mr_solve(Members B, int nb, int nv, int cycle) {
     __shared__ cplx G[NVMAX][NVMAX];
     const int m = B.m[blockIdx.y];
-    const cplx* __restrict__ partial = m_partial(B, m);
     cplx* scal = m_scal(B, m);
     int e = 0;
     for (int a = 0; a < nv; ++a)
         for (int b = a; b < nv; ++b, ++e) {
-            const cplx g = finish_in_wave(partial + (int64_t)(P_GRAM + e) * RED_BLOCKS, nb);
+            const cplx g = slot_sum<TEAM>(B, m, P_GRAM + e, nb);
             if (threadIdx.x == 0) { G[a][b] = g; G[b][a] = make_double2(g.x, -g.y); }
         }
     __syncthreads();
@@ -283,10 +312,11 @@ __global__ __launch_bounds__(RED_THREADS) void k_mr_update(Members B, int64_t uo
 }
 
 // scal[S_RES] = sqrt(sum of the P_NORM partials), unless the cycle ended without an MR update
+template <bool TEAM>
 __global__ __launch_bounds__(64) void k_res_finish(Members B, int nb) {
     const int m = B.m[blockIdx.y];
     cplx* scal = m_scal(B, m);
-    const cplx s = finish_in_wave(m_partial(B, m) + (int64_t)P_NORM * RED_BLOCKS, nb);
+    const cplx s = slot_sum<TEAM>(B, m, P_NORM, nb);
     if (threadIdx.x == 0 && scal[S_STATUS].x == 0.0) scal[S_RES] = make_double2(sqrt(s.x), 0.0);
 }
 
@@ -309,81 +339,152 @@ struct Solve {
     int64_t cycles = 0, mvps = 0;
 };
 
+// One slab of every vector on its own device, with what the kernels of that device work on: the plan itself with all nrhs
+// members (n = N, off = 0), or rank `rank` of a multi-device plan with its z slab of the one member.
+struct Rank {
+    lsfc_plan* p = nullptr; int device = 0, rank = 0;
+    int64_t n = 0, off = 0;                 // entries of the slab and its place in the whole vector
+    cplx* x = nullptr; const cplx* b = nullptr;
+    DevBuf<cplx> work, scal, partial, table;
+    DevBuf<double> tol2;
+    Event ready, consumed;                  // TEAM: my rank sums have reached every table / my kernels so far have read my table
+    Members B{};                            // of this rank's launches; B.m: the member list of the round
+    hipStream_t st() const { return p->stream; }
+};
+using Ranks = std::vector<std::unique_ptr<Rank>>;
+
 } // namespace
 
-// nrhs solves in lock step.  x (in/out) and b: nrhs device vectors back to back; r_shadow (may be NULL): nrhs vectors of N
-// complex on the device, or on the host (shadow_on_host); resnorm: nrhs rows of cap entries.  pc takes the active members
-// of every round (Precond::apply).  code[2 j], code[2 j + 1]: LSFC_BICG_* of member j and its cycle (of the breakdown,
-// else the last one).
-static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
+// nrhs solves in lock step over the ranks: one (the plan; TEAM = false) or the P ranks of a multi-device plan (TEAM, nrhs = 1,
+// the form of k_rank_sum), every step enqueued rank by rank from the calling thread.  Per rank: x (in/out) and b, nrhs
+// device vectors of n back to back.  r_shadow (may be NULL): nrhs vectors of N complex on the device, or on the host
+// (shadow_on_host; TEAM: always, the whole vector); resnorm: nrhs rows of cap entries.  pc takes the active members of every
+// round (Precond::apply; TEAM: a host callback on the whole vector, gathered from the slabs and scattered back).
+// code[2 j], code[2 j + 1]: LSFC_BICG_* of member j and its cycle (of the breakdown, else the last one).
+template <bool TEAM>
+static void bicgstabl_run_as(lsfc_plan* root, Ranks& ranks, int nrhs, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
                           const lsfc_bicgstabl_opts& o, int l, int64_t maxmv, double reltol, double abstol, double* resnorm, int64_t cap,
                           lsfc_gmres_result* res, int64_t* code) {
-    const int64_t N = p->N;
-    hipStream_t st = p->stream;
-    const int nb = blas_red_blocks(N), nv = l + 1;
-    const int64_t wstride = (int64_t)(2 * l + 3) * N, uoff = (int64_t)nv * N, toff = 2 * (int64_t)nv * N;
-    DevBuf<cplx> work, scal, partial;
-    DevBuf<double> tol2;
-    work.alloc((size_t)nrhs * (size_t)wstride);
-    scal.alloc((size_t)nrhs * S_COUNT);
-    partial.alloc((size_t)nrhs * P_SLOTS * RED_BLOCKS);
-    tol2.alloc((size_t)nrhs);
-    auto R = [&](int m, int i) { return work.p + (size_t)m * (size_t)wstride + (size_t)i * N; };
-    auto U = [&](int m, int i) { return R(m, nv + i); };
-    Pinned hs, ht, vpin; hs.alloc((size_t)nrhs * S_COUNT); ht.alloc((size_t)(nrhs + 1) / 2);
+    const int P = (int)ranks.size(), nv = l + 1;
+    Rank& k0 = *ranks[0];
+    const int64_t N = root->N, n = k0.n;                // (the slabs of a multi-device plan are equal)
+    const int nb = blas_red_blocks(n);
+    const int64_t wstride = (int64_t)(2 * l + 3) * n, uoff = (int64_t)nv * n, toff = 2 * (int64_t)nv * n;
+    auto each = [&](auto&& f) { for (auto& k : ranks) { if constexpr (TEAM) LSFC_HIP(hipSetDevice(k->device)); f(*k); } };
+    each([&](Rank& k) {
+        k.work.alloc((size_t)nrhs * (size_t)wstride);
+        k.scal.alloc((size_t)nrhs * S_COUNT);
+        k.partial.alloc((size_t)nrhs * P_SLOTS * RED_BLOCKS);
+        k.tol2.alloc((size_t)nrhs);
+        k.B.work = k.work.p; k.B.x = k.x; k.B.scal = k.scal.p; k.B.partial = k.partial.p; k.B.tol2 = k.tol2.p; k.B.wstride = wstride; k.B.n = n;
+        k.B.rank = k.rank; k.B.nranks = P;
+        if constexpr (TEAM) {
+            k.table.alloc((size_t)P * P_SLOTS);
+            LSFC_HIP(hipMemsetAsync(k.table.p, 0, k.table.bytes(), k.st()));
+            k.B.table = k.table.p;
+            k.ready.create(); k.consumed.create();
+        }
+    });
+    auto R = [&](Rank& k, int m, int i) { return k.work.p + (size_t)m * (size_t)wstride + (size_t)i * (size_t)n; };
+    auto U = [&](Rank& k, int m, int i) { return R(k, m, nv + i); };
+    if constexpr (TEAM) LSFC_HIP(hipSetDevice(k0.device));
+    // hs: the scalar blocks as fetched; TEAM: a second block, the initial scalars that every rank uploads (rank 0's fetch must not land on them)
+    Pinned hs, ht, vpin; hs.alloc((size_t)(TEAM ? 2 : 1) * (size_t)nrhs * S_COUNT); ht.alloc((size_t)(nrhs + 1) / 2);
+    cplx* const hinit = hs.p + (TEAM ? (size_t)nrhs * S_COUNT : 0);
     if (pc.fn && !pc.on_device) vpin.alloc((size_t)N);
     Event fetched; fetched.create();
-    Members base{};
-    base.work = work.p; base.x = x; base.scal = scal.p; base.partial = partial.p; base.tol2 = tol2.p; base.wstride = wstride; base.n = N;
-    auto members = [&](const std::vector<int>& list) { Members B = base; for (size_t a = 0; a < list.size(); ++a) B.m[a] = list[a]; return B; };
+    // the member list of the launches that follow
+    auto select = [&](const std::vector<int>& list) { each([&](Rank& k) { for (size_t a = 0; a < list.size(); ++a) k.B.m[a] = list[a]; }); };
 
-    // the operator on vector `in(m)` of every member of the list, in groups that share one pass of the pipeline
+    // the operator on vector `in(k, m)` of every member of the list, in groups that share one pass of the pipeline
     std::vector<const cplx*> av;
     std::vector<cplx*> pv;
     auto apply = [&](const std::vector<int>& list, auto&& in, auto&& out) {
         av.clear(); pv.clear();
-        for (int m : list) { av.push_back(in(m)); pv.push_back(out(m)); }
-        plan_apply_batch_dev(p, av.data(), pv.data(), list.size());
+        if constexpr (TEAM) {
+            for (auto& k : ranks) { av.push_back(in(*k, 0)); pv.push_back(out(*k, 0)); }
+            multi_convolve_dev(root, av.data(), pv.data(), plan_operator(root));
+        } else {
+            for (int m : list) { av.push_back(in(k0, m)); pv.push_back(out(k0, m)); }
+            plan_apply_batch_dev(root, av.data(), pv.data(), list.size());
+        }
     };
     auto precondition = [&](const std::vector<int>& list, auto&& v) {
-        pv.clear();
-        for (int m : list) pv.push_back(v(m));
-        pc.apply(pv.data(), pv.size(), vpin.p, st);
+        if constexpr (TEAM) {
+            // host callback, in place on the whole vector (the two-argument ldiv!): gather the slabs, call, scatter
+            if (!pc.fn) return;
+            each([&](Rank& k) { LSFC_HIP(hipMemcpyAsync(vpin.p + k.off, v(k, 0), (size_t)n * sizeof(cplx), hipMemcpyDeviceToHost, k.st())); });
+            each([&](Rank& k) { LSFC_HIP(hipStreamSynchronize(k.st())); });
+            const int rc = pc.fn(pc.user, (double*)vpin.p, N);
+            if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
+            each([&](Rank& k) { LSFC_HIP(hipMemcpyAsync(v(k, 0), vpin.p + k.off, (size_t)n * sizeof(cplx), hipMemcpyHostToDevice, k.st())); });
+        } else {
+            pv.clear();
+            for (int m : list) pv.push_back(v(k0, m));
+            pc.apply(pv.data(), pv.size(), vpin.p, k0.st());
+        }
     };
-    // all members' scalars in one copy
+    // TEAM: completes the partial slots [slot0, slot0 + cnt) across the ranks, between the kernels that wrote the partials and
+    // the one that consumes the sums.  Ordered by events alone, both ways: a rank's copies wait until every other rank has got
+    // past the kernels that read the entries they replace (consumed), the consumer waits for the copies of all ranks (ready).
+    auto reduce = [&](int slot0, int cnt) {
+        if constexpr (TEAM) {
+            each([&](Rank& k) { LSFC_HIP(hipEventRecord(k.consumed.e, k.st())); });
+            each([&](Rank& k) {
+                hipLaunchKernelGGL(k_rank_sum, dim3((unsigned)cnt), dim3(64), 0, k.st(), k.B, slot0, nb);
+                const size_t row = (size_t)k.rank * P_SLOTS + (size_t)slot0, bytes = (size_t)cnt * sizeof(cplx);
+                for (int s = 1; s < P; ++s) {               // every source starts with a different peer
+                    Rank& q = *ranks[(size_t)((k.rank + s) % P)];
+                    LSFC_HIP(hipStreamWaitEvent(k.st(), q.consumed.e, 0));
+                    if (q.device == k.device) LSFC_HIP(hipMemcpyAsync(q.table.p + row, k.table.p + row, bytes, hipMemcpyDeviceToDevice, k.st()));
+                    else LSFC_HIP(hipMemcpyPeerAsync(q.table.p + row, q.device, k.table.p + row, k.device, bytes, k.st()));
+                }
+                LSFC_HIP(hipEventRecord(k.ready.e, k.st()));
+            });
+            each([&](Rank& k) { for (auto& q : ranks) if (q->rank != k.rank) LSFC_HIP(hipStreamWaitEvent(k.st(), q->ready.e, 0)); });
+        } else { (void)slot0; (void)cnt; }
+    };
+    // all members' scalars in one copy (the ranks' scalar blocks agree: rank 0's)
     auto fetch = [&]() {
-        LSFC_HIP(hipMemcpyAsync(hs.p, scal.p, (size_t)nrhs * S_COUNT * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        LSFC_HIP(hipEventRecord(fetched.e, st));
+        if constexpr (TEAM) LSFC_HIP(hipSetDevice(k0.device));
+        LSFC_HIP(hipMemcpyAsync(hs.p, k0.scal.p, (size_t)nrhs * S_COUNT * sizeof(cplx), hipMemcpyDeviceToHost, k0.st()));
+        LSFC_HIP(hipEventRecord(fetched.e, k0.st()));
         LSFC_HIP(hipEventSynchronize(fetched.e));
     };
     auto H = [&](int m) { return hs.p + (size_t)m * S_COUNT; };
     // scal[S_RES] = ||rs[0]|| of the members of the list
     auto norm0 = [&](const std::vector<int>& list) {
-        const Members B = members(list);
-        hipLaunchKernelGGL(k_dot, dim3(nb, (unsigned)list.size()), dim3(RED_THREADS), 0, st, B, (int64_t)0, (int64_t)0, (int)P_NORM);
-        hipLaunchKernelGGL(k_norm_finish, dim3(1, (unsigned)list.size()), dim3(64), 0, st, B, nb);
+        select(list);
+        each([&](Rank& k) { hipLaunchKernelGGL(k_dot, dim3(nb, (unsigned)list.size()), dim3(RED_THREADS), 0, k.st(), k.B, (int64_t)0, (int64_t)0, (int)P_NORM); });
+        reduce(P_NORM, 1);
+        each([&](Rank& k) { hipLaunchKernelGGL(k_norm_finish<TEAM>, dim3(1, (unsigned)list.size()), dim3(64), 0, k.st(), k.B, nb); });
     };
 
     // init: rs[0] = Pl \ (b - A x), us = 0, shadow residual, sigma = -1 (sigma = 1, negated by the first cycle)
     std::vector<Solve> S((size_t)nrhs);
     std::vector<int> act((size_t)nrhs);
     for (int m = 0; m < nrhs; ++m) act[(size_t)m] = m;
+    select(act);
     if (o.initially_zero) {
-        for (int m = 0; m < nrhs; ++m) LSFC_HIP(hipMemcpyAsync(R(m, 0), b + (size_t)m * N, (size_t)N * sizeof(cplx), hipMemcpyDeviceToDevice, st));
+        each([&](Rank& k) {
+            for (int m = 0; m < nrhs; ++m) LSFC_HIP(hipMemcpyAsync(R(k, m, 0), k.b + (size_t)m * n, (size_t)n * sizeof(cplx), hipMemcpyDeviceToDevice, k.st()));
+        });
     } else {
-        apply(act, [&](int m) { return (const cplx*)(x + (size_t)m * N); }, [&](int m) { return R(m, 0); });
-        hipLaunchKernelGGL(k_residual, dim3(grid_for(N), (unsigned)nrhs), dim3(256), 0, st, members(act), b);
+        apply(act, [&](Rank& k, int m) { return (const cplx*)(k.x + (size_t)m * n); }, [&](Rank& k, int m) { return R(k, m, 0); });
+        each([&](Rank& k) { hipLaunchKernelGGL(k_residual, dim3(grid_for(n), (unsigned)nrhs), dim3(256), 0, k.st(), k.B, k.b); });
         for (auto& s : S) s.mvps = 1;
     }
-    precondition(act, [&](int m) { return R(m, 0); });
-    for (int m = 0; m < nrhs; ++m) {
-        LSFC_HIP(hipMemsetAsync(U(m, 0), 0, (size_t)nv * (size_t)N * sizeof(cplx), st));
-        const cplx* sh = r_shadow ? r_shadow + (size_t)m * N : R(m, 0);
-        LSFC_HIP(hipMemcpyAsync(R(m, 2 * nv), sh, (size_t)N * sizeof(cplx), r_shadow && shadow_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-    }
-    for (size_t i = 0; i < (size_t)nrhs * S_COUNT; ++i) hs.p[i] = make_double2(0.0, 0.0);
-    for (int m = 0; m < nrhs; ++m) H(m)[S_SIGMA] = make_double2(-1.0, 0.0);
-    LSFC_HIP(hipMemcpyAsync(scal.p, hs.p, (size_t)nrhs * S_COUNT * sizeof(cplx), hipMemcpyHostToDevice, st));
+    precondition(act, [&](Rank& k, int m) { return R(k, m, 0); });
+    for (size_t i = 0; i < (size_t)nrhs * S_COUNT; ++i) hinit[i] = make_double2(0.0, 0.0);
+    for (int m = 0; m < nrhs; ++m) hinit[(size_t)m * S_COUNT + S_SIGMA] = make_double2(-1.0, 0.0);
+    each([&](Rank& k) {
+        for (int m = 0; m < nrhs; ++m) {
+            LSFC_HIP(hipMemsetAsync(U(k, m, 0), 0, (size_t)nv * (size_t)n * sizeof(cplx), k.st()));
+            const cplx* sh = r_shadow ? r_shadow + (size_t)m * N + k.off : R(k, m, 0);
+            LSFC_HIP(hipMemcpyAsync(R(k, m, 2 * nv), sh, (size_t)n * sizeof(cplx), r_shadow && shadow_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, k.st()));
+        }
+        LSFC_HIP(hipMemcpyAsync(k.scal.p, hinit, (size_t)nrhs * S_COUNT * sizeof(cplx), hipMemcpyHostToDevice, k.st()));
+    });
     norm0(act);
     LSFC_HIP(hipGetLastError());
     fetch();
@@ -397,7 +498,7 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
         s.bad = std::isfinite(beta0) ? ST_OK : ST_RESIDUAL;
         t2[m] = s.tol * s.tol;
     }
-    LSFC_HIP(hipMemcpyAsync(tol2.p, t2, (size_t)nrhs * sizeof(double), hipMemcpyHostToDevice, st));
+    each([&](Rank& k) { LSFC_HIP(hipMemcpyAsync(k.tol2.p, t2, (size_t)nrhs * sizeof(double), hipMemcpyHostToDevice, k.st())); });
     auto running = [&](const Solve& s) { return !s.converged && s.bad == ST_OK && s.mvps < maxmv; };
     auto still_active = [&]() { std::vector<int> a; for (int m = 0; m < nrhs; ++m) if (running(S[(size_t)m])) a.push_back(m); return a; };
     act = still_active();
@@ -406,30 +507,34 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
     // every member of the list is in the same cycle: all start at 0 and a member never rejoins
     for (int64_t cycles = 0; !act.empty(); ++cycles) {
         const int cyc = (int)std::min<int64_t>(cycles + 1, 1 << 30);
-        const Members B = members(act);
+        select(act);
         const dim3 grid((unsigned)nb, (unsigned)act.size()), one(1, (unsigned)act.size());
         for (int j = 0; j < l; ++j) {                       // BiCG part
-            hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, st, B, toff, (int64_t)j * N, (int)P_RHO);
+            each([&](Rank& k) { hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, k.st(), k.B, toff, (int64_t)j * n, (int)P_RHO); });
+            reduce(P_RHO, 1);
             dispatch<1, LMAX>(j + 1, "bicgstabl", [&](auto nvj) {
-                hipLaunchKernelGGL((k_bicg_u<decltype(nvj)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff, nb, cyc);
+                each([&](Rank& k) { hipLaunchKernelGGL((k_bicg_u<decltype(nvj)::value, TEAM>), grid, dim3(RED_THREADS), 0, k.st(), k.B, uoff, nb, cyc); });
             });
-            apply(act, [&](int m) { return (const cplx*)U(m, j); }, [&](int m) { return U(m, j + 1); });
-            precondition(act, [&](int m) { return U(m, j + 1); });
-            hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, st, B, toff, uoff + (int64_t)(j + 1) * N, (int)P_SIGMA);
+            apply(act, [&](Rank& k, int m) { return (const cplx*)U(k, m, j); }, [&](Rank& k, int m) { return U(k, m, j + 1); });
+            precondition(act, [&](Rank& k, int m) { return U(k, m, j + 1); });
+            each([&](Rank& k) { hipLaunchKernelGGL(k_dot, grid, dim3(RED_THREADS), 0, k.st(), k.B, toff, uoff + (int64_t)(j + 1) * n, (int)P_SIGMA); });
+            reduce(P_SIGMA, 1);
             dispatch<1, LMAX>(j + 1, "bicgstabl", [&](auto nvj) {
-                hipLaunchKernelGGL((k_bicg_rx<decltype(nvj)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff, nb, cyc);
+                each([&](Rank& k) { hipLaunchKernelGGL((k_bicg_rx<decltype(nvj)::value, TEAM>), grid, dim3(RED_THREADS), 0, k.st(), k.B, uoff, nb, cyc); });
             });
-            apply(act, [&](int m) { return (const cplx*)R(m, j); }, [&](int m) { return R(m, j + 1); });
-            precondition(act, [&](int m) { return R(m, j + 1); });
+            apply(act, [&](Rank& k, int m) { return (const cplx*)R(k, m, j); }, [&](Rank& k, int m) { return R(k, m, j + 1); });
+            precondition(act, [&](Rank& k, int m) { return R(k, m, j + 1); });
         }
         dispatch<2, NVMAX>(nv, "bicgstabl", [&](auto nvc) {              // MR part
-            hipLaunchKernelGGL((k_gram<decltype(nvc)::value>), grid, dim3(RED_THREADS), 0, st, B);
+            each([&](Rank& k) { hipLaunchKernelGGL((k_gram<decltype(nvc)::value>), grid, dim3(RED_THREADS), 0, k.st(), k.B); });
         });
-        hipLaunchKernelGGL(k_mr_solve, one, dim3(64), 0, st, B, nb, nv, cyc);
+        reduce(P_GRAM, nv * (nv + 1) / 2);
+        each([&](Rank& k) { hipLaunchKernelGGL(k_mr_solve<TEAM>, one, dim3(64), 0, k.st(), k.B, nb, nv, cyc); });
         dispatch<1, LMAX>(l, "bicgstabl", [&](auto lc) {
-            hipLaunchKernelGGL((k_mr_update<decltype(lc)::value>), grid, dim3(RED_THREADS), 0, st, B, uoff);
+            each([&](Rank& k) { hipLaunchKernelGGL((k_mr_update<decltype(lc)::value>), grid, dim3(RED_THREADS), 0, k.st(), k.B, uoff); });
         });
-        hipLaunchKernelGGL(k_res_finish, one, dim3(64), 0, st, B, nb);
+        reduce(P_NORM, 1);
+        each([&](Rank& k) { hipLaunchKernelGGL(k_res_finish<TEAM>, one, dim3(64), 0, k.st(), k.B, nb); });
         LSFC_HIP(hipGetLastError());
         fetch();
         broke.clear();
@@ -464,7 +569,7 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
         }
         act = still_active();
     }
-    LSFC_HIP(hipStreamSynchronize(st));
+    each([&](Rank& k) { LSFC_HIP(hipStreamSynchronize(k.st())); });
     for (int m = 0; m < nrhs; ++m) {
         const Solve& s = S[(size_t)m];
         res[m].iters = s.cycles; res[m].mvps = s.mvps; res[m].converged = s.converged ? 1 : 0; res[m].final_resnorm = s.current;
@@ -473,16 +578,80 @@ static void bicgstabl_run(lsfc_plan* p, int nrhs, cplx* x, const cplx* b, const 
     }
 }
 
-// the argument checks of both entry points, before any device call
-static void check_args(const char* fn, lsfc_plan* plan, const double* x, const double* b, const lsfc_bicgstabl_opts* opts, const double* resnorm,
-                       int64_t resnorm_cap, const lsfc_gmres_result* result, int memspace) {
+// the form of the solve follows the plan: the team form on a multi-device plan (whatever its number of ranks)
+static void bicgstabl_run(lsfc_plan* root, Ranks& ranks, int nrhs, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
+                          const lsfc_bicgstabl_opts& o, int l, int64_t maxmv, double reltol, double abstol, double* resnorm, int64_t cap,
+                          lsfc_gmres_result* res, int64_t* code) {
+    if (root->multi) bicgstabl_run_as<true>(root, ranks, nrhs, r_shadow, shadow_on_host, pc, o, l, maxmv, reltol, abstol, resnorm, cap, res, code);
+    else bicgstabl_run_as<false>(root, ranks, nrhs, r_shadow, shadow_on_host, pc, o, l, maxmv, reltol, abstol, resnorm, cap, res, code);
+}
+
+// The ranks of a multi-device plan, each with its z slab of the host vectors x and b staged on its device.  First the memory rule,
+// per DEVICE: every rank on it needs 2 l + 3 work vectors of N / P complex, and its staged x and b where its staging buffers do not
+// hold them yet.
+static void team_stage(lsfc_plan* plan, const cplx* x, const cplx* b, int l, Ranks& ranks) {
+    MultiState* ms = plan->multi.get();
+    std::vector<bool> stage((size_t)ms->P);
+    for (int r = 0; r < ms->P; ++r) stage[(size_t)r] = ms->sub[(size_t)r]->xs.n < (size_t)ms->sub[(size_t)r]->N;
+    for (int r = 0; r < ms->P; ++r) {
+        const int dev = ms->devices[(size_t)r];
+        int first = r, on = 0; double need = 0.0;
+        for (int q = 0; q < ms->P; ++q) if (ms->devices[(size_t)q] == dev) {
+            first = std::min(first, q); ++on;
+            need += ((double)(2 * l + 3) + (stage[(size_t)q] ? 2.0 : 0.0)) * (double)ms->sub[(size_t)q]->N * sizeof(cplx);
+        }
+        if (first != r) continue;                       // (a device is checked once, at its first rank)
+        size_t free_b = 0, total_b = 0;
+        LSFC_HIP(hipSetDevice(dev));
+        LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (need > (double)free_b)
+            fail(LSFC_ENOMEM, "lsfc_bicgstabl_multi: device %d: %d rank%s x (2 l + 3 = %d work vectors, + staged x and b) of %lld complex need %.1f GB of "
+                 "device memory, %.1f GB are free there -- lower l or spread the plan over more devices", dev, on, on == 1 ? "" : "s", 2 * l + 3,
+                 (long long)ms->sub[(size_t)r]->N, need / 1e9, (double)free_b / 1e9);
+    }
+    int64_t off = 0;
+    for (int r = 0; r < ms->P; ++r) {
+        lsfc_plan* p = ms->sub[(size_t)r].get();
+        LSFC_HIP(hipSetDevice(ms->devices[(size_t)r]));
+        plan_ensure_staging(p, p->N);
+        LSFC_HIP(hipMemcpyAsync(p->xs.p, x + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
+        LSFC_HIP(hipMemcpyAsync(p->ys.p, b + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
+        ranks.emplace_back(new Rank());
+        Rank& k = *ranks.back();
+        k.p = p; k.device = ms->devices[(size_t)r]; k.rank = r; k.n = p->N; k.off = off; k.x = p->xs.p; k.b = p->ys.p;
+        off += p->N;
+    }
+}
+// ... and x gathered back from the slabs
+static void team_gather(lsfc_plan* plan, Ranks& ranks, cplx* x) {
+    for (auto& k : ranks) {
+        LSFC_HIP(hipSetDevice(k->device));
+        LSFC_HIP(hipMemcpyAsync(x + k->off, k->x, (size_t)k->n * sizeof(cplx), hipMemcpyDeviceToHost, k->st()));
+    }
+    for (auto& k : ranks) { LSFC_HIP(hipSetDevice(k->device)); LSFC_HIP(hipStreamSynchronize(k->st())); }
+    LSFC_HIP(hipSetDevice(plan->device));
+}
+
+// the argument checks of the entry points, before any device call.  team: lsfc_bicgstabl_multi, the entry point of multi-device plans --
+// lsfc_bicgstabl and lsfc_bicgstabl_batch refuse them as they always have, so what a caller of those sees does not change
+static void check_args(const char* fn, bool batch, bool team, lsfc_plan* plan, const double* x, const double* b, const lsfc_bicgstabl_opts* opts,
+                       const double* resnorm, int64_t resnorm_cap, const lsfc_gmres_result* result, int memspace) {
     LSFC_REQUIRE(opts, "%s: NULL opts", fn);
     LSFC_REQUIRE(opts->l >= 1 && opts->l <= LMAX, "%s: l = %d is outside 1..%d", fn, opts->l, LMAX);
     for (int i = 0; i < 4; ++i) LSFC_REQUIRE(opts->reserved[i] == 0, "%s: reserved[%d] is not zero", fn, i);
     LSFC_REQUIRE(memspace == LSFC_MEM_HOST || memspace == LSFC_MEM_DEVICE, "%s: unknown memspace %d", fn, memspace);
     LSFC_REQUIRE(plan && x && b && result, "%s: NULL argument", fn);
     LSFC_REQUIRE(resnorm || resnorm_cap <= 0, "%s: NULL resnorm with a capacity of %lld", fn, (long long)resnorm_cap);
-    LSFC_REQUIRE(!plan->multi && !plan->dist, "%s runs on a single-device plan (not a distributed or multi-device one)", fn);
+    if (!team) {
+        LSFC_REQUIRE(!plan->multi && !plan->dist, "%s runs on a single-device plan (not a distributed or multi-device one)%s", fn,
+                     batch ? ": batched BiCGStab(l) is not offered there" : "; lsfc_bicgstabl_multi solves on a single-process multi-device plan");
+        return;
+    }
+    LSFC_REQUIRE(plan->multi, "%s runs on a single-process multi-device plan (lsfc_plan_create_gv3d_multi): %s", fn,
+                 plan->dist ? "a multi-process distributed plan (lsfc_dist_plan_create_gv3d) is not offered" : "lsfc_bicgstabl solves on a single-device plan");
+    LSFC_REQUIRE(memspace == LSFC_MEM_HOST, "%s: a multi-device plan takes host vectors (LSFC_MEM_DEVICE is not offered there)", fn);
+    LSFC_REQUIRE(!(opts->precond && opts->precond_on_device), "%s: a multi-device plan takes a host preconditioner callback "
+                 "(precond_on_device = 1 is not offered there)", fn);
 }
 
 } // namespace lsfc
@@ -491,26 +660,37 @@ using namespace lsfc;
 
 // Both entry points (defined below them): the argument checks, the option defaults, the memory rule (nrhs (2 l + 3) work vectors; host vectors:
 // the staged x and b, 2 nrhs vectors, on top -- r_shadow is uploaded into its work vector), host staging through
-// plan->xs / plan->ys, and the solve.  batch: the texts of lsfc_bicgstabl_batch, and its members meet at the library's
+// plan->xs / plan->ys, and the solve.  A multi-device plan (lsfc_bicgstabl_multi): the same per rank and slab, the memory rule per device.  batch: the texts of lsfc_bicgstabl_batch, and its members meet at the library's
 // own preconditioner; the single call has nobody to meet there and calls the callback as given.
-static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
+static void bicgstabl_entry(const char* fn, bool batch, bool team, lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
                             double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* code, int memspace);
 
-extern "C" int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts, double* resnorm,
-                              int64_t resnorm_cap, lsfc_gmres_result* result, int memspace) {
+// one solve: lsfc_bicgstabl, or (team) lsfc_bicgstabl_multi
+static int bicgstabl_single(const char* fn, bool team, lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts, double* resnorm,
+                            int64_t resnorm_cap, lsfc_gmres_result* result, int memspace) {
     int64_t code[2] = { 0, 0 };
-    const int rc = guarded([&] { bicgstabl_entry("lsfc_bicgstabl", false, plan, x, b, 1, opts, resnorm, resnorm_cap, result, code, memspace); });
+    const int rc = guarded([&] { bicgstabl_entry(fn, false, team, plan, x, b, 1, opts, resnorm, resnorm_cap, result, code, memspace); });
     if (rc != LSFC_OK || result->converged) return rc;
     if (code[0] != LSFC_BICG_MAX_MV) set_last_error("bicgstabl: breakdown in cycle %d: %s; x is the last finite iterate", (int)code[1], ST_NAME[code[0]]);
     else set_last_error("bicgstabl: max_mv_products reached without convergence");
     return LSFC_ENOTCONV;
 }
 
+extern "C" int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts, double* resnorm,
+                              int64_t resnorm_cap, lsfc_gmres_result* result, int memspace) {
+    return bicgstabl_single("lsfc_bicgstabl", false, plan, x, b, opts, resnorm, resnorm_cap, result, memspace);
+}
+
+extern "C" int lsfc_bicgstabl_multi(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts, double* resnorm,
+                                    int64_t resnorm_cap, lsfc_gmres_result* result, int memspace) {
+    return bicgstabl_single("lsfc_bicgstabl_multi", true, plan, x, b, opts, resnorm, resnorm_cap, result, memspace);
+}
+
 extern "C" int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts, double* resnorm,
                                     int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* status, int memspace) {
     int64_t code[2 * KRYLOV_NRHS_MAX] = { 0 };
     const int rc = guarded([&] {
-        bicgstabl_entry("lsfc_bicgstabl_batch", true, plan, x, b, nrhs, opts, resnorm, resnorm_cap, results, code, memspace);
+        bicgstabl_entry("lsfc_bicgstabl_batch", true, false, plan, x, b, nrhs, opts, resnorm, resnorm_cap, results, code, memspace);
         if (status) for (int64_t i = 0; i < 2 * nrhs; ++i) status[i] = code[i];
     });
     if (rc != LSFC_OK) return rc;
@@ -525,21 +705,25 @@ extern "C" int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b,
     return LSFC_OK;
 }
 
-static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
+static void bicgstabl_entry(const char* fn, bool batch, bool team, lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,
                             double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* results, int64_t* code, int memspace) {
     if (batch) LSFC_REQUIRE(nrhs >= 1 && nrhs <= KRYLOV_NRHS_MAX, "%s: nrhs = %lld is outside 1..%d", fn, (long long)nrhs, KRYLOV_NRHS_MAX);
-    check_args(fn, plan, x, b, opts, resnorm, resnorm_cap, results, memspace);
+    check_args(fn, batch, team, plan, x, b, opts, resnorm, resnorm_cap, results, memspace);
     const int l = opts->l, n = (int)nrhs;
     const int64_t N = plan->N;
     const int64_t maxmv = opts->max_mv_products > 0 ? opts->max_mv_products : N;
     const double reltol = opts->reltol >= 0 ? opts->reltol : DEFAULT_RELTOL;
     const double abstol = opts->abstol > 0 ? opts->abstol : 0.0;
+    const int64_t cap = resnorm_cap > 0 ? resnorm_cap : 0;
     plan_check_precond_op(plan, opts->precond, opts->precond_user, fn);
     const Precond pc(opts->precond, opts->precond_user, opts->precond_on_device != 0, batch, N, fn);
-    LSFC_HIP(hipSetDevice(plan->device));
-    const bool host = memspace == LSFC_MEM_HOST;
-    const bool stage = host && plan->xs.n < (size_t)n * (size_t)N;
-    {
+    Ranks ranks;
+    const bool multi = plan->multi != nullptr, host = memspace == LSFC_MEM_HOST;
+    const size_t bytes = (size_t)n * (size_t)N * sizeof(cplx);
+    if (multi) team_stage(plan, (const cplx*)x, (const cplx*)b, l, ranks);
+    else {
+        LSFC_HIP(hipSetDevice(plan->device));
+        const bool stage = host && plan->xs.n < (size_t)n * (size_t)N;
         size_t free_b = 0, total_b = 0;
         LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
         const double per = ((double)(2 * l + 3) + (stage ? 2.0 : 0.0)) * (double)N * sizeof(cplx);
@@ -551,16 +735,18 @@ static void bicgstabl_entry(const char* fn, bool batch, lsfc_plan* plan, double*
                  "%.1f GB are free -- %lld right-hand sides would fit; solve fewer per call or lower l", n, 2 * l + 3, stage ? " + staged x and b" : "",
                  (long long)N, (double)n * per / 1e9, (double)free_b / 1e9, (long long)((double)free_b / per));
         }
+        const cplx* xd = (const cplx*)x; const cplx* bd = (const cplx*)b;
+        if (host) {
+            if (stage) { plan->xs.alloc((size_t)n * (size_t)N); plan->ys.alloc((size_t)n * (size_t)N); }     // (plan_ensure_staging, with the `stage` the memory rule counted)
+            LSFC_HIP(hipMemcpy(plan->xs.p, x, bytes, hipMemcpyHostToDevice));
+            LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
+            xd = plan->xs.p; bd = plan->ys.p;
+        }
+        ranks.emplace_back(new Rank());
+        Rank& k = *ranks.back();
+        k.p = plan; k.device = plan->device; k.n = N; k.x = (cplx*)xd; k.b = bd;
     }
-    const cplx* xd = (const cplx*)x; const cplx* bd = (const cplx*)b;
-    const size_t bytes = (size_t)n * (size_t)N * sizeof(cplx);
-    if (host) {
-        if (stage) { plan->xs.alloc((size_t)n * (size_t)N); plan->ys.alloc((size_t)n * (size_t)N); }     // (plan_ensure_staging, with the `stage` the memory rule counted)
-        LSFC_HIP(hipMemcpy(plan->xs.p, x, bytes, hipMemcpyHostToDevice));
-        LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
-        xd = plan->xs.p; bd = plan->ys.p;
-    }
-    bicgstabl_run(plan, n, (cplx*)xd, bd, (const cplx*)opts->r_shadow, host, pc, *opts, l, maxmv, reltol, abstol, resnorm,
-                  resnorm_cap > 0 ? resnorm_cap : 0, results, code);
-    if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, bytes, hipMemcpyDeviceToHost));
+    bicgstabl_run(plan, ranks, n, (const cplx*)opts->r_shadow, host, pc, *opts, l, maxmv, reltol, abstol, resnorm, cap, results, code);
+    if (multi) team_gather(plan, ranks, (cplx*)x);
+    else if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, bytes, hipMemcpyDeviceToHost));
 }

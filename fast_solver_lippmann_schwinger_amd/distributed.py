@@ -75,7 +75,7 @@ class MultiDeviceFastM3D(FastM3D):
     """`buildFastConvolution3D` on several GPUs driven from THIS one process (lsfc_plan_create_gv3d_multi): the form a
     single-process host -- the reference is one Julia process, examples/example3D.jl:54,78 -- uses to reach the
     multi-GPU path.  Behaves like FastM3D with host (numpy) vectors: ``M * b``, ``mul_``, ``FFTconvolution``,
-    ``gmres_`` (host preconditioner callback).  ``devices`` may list a device more than once (logical ranks on one GPU,
+    ``gmres_`` and ``bicgstabl_multi_`` (host preconditioner callback).  ``devices`` may list a device more than once (logical ranks on one GPU,
     peer-copy transport): that is how the path is tested where only one GPU is visible."""
 
     def __init__(self, n, h, k, nu, devices, m=None, l=None, flags=0):

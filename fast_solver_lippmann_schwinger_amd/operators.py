@@ -701,11 +701,27 @@ def bicgstabl_(x, A, b, l=2, Pl=None, max_mv_products=None, abstol=0.0, reltol=N
     ``r_shadow`` (N complex, in the memory space of x), so that a solve is reproducible bit for bit.
     A breakdown (rho, sigma or gamma zero where it divides, or not finite) ends the solve with x the last finite iterate;
     the history then reports ``isconverged == False`` unless that iterate is within the tolerance already.  x is
-    updated in place."""
+    updated in place.
+    Single-device plans; on a ``MultiDeviceFastM3D`` the library refuses (LsfcError) and ``bicgstabl_multi_`` solves."""
+    return _bicgstabl("lsfc_bicgstabl", x, A, b, l, Pl, max_mv_products, abstol, reltol, log, Pl_on_device, r_shadow, initially_zero)
+
+
+def bicgstabl_multi_(x, A, b, l=2, Pl=None, max_mv_products=None, abstol=0.0, reltol=None, log=False, Pl_on_device=False,
+                     r_shadow=None, initially_zero=False):
+    """``bicgstabl_`` on a ``MultiDeviceFastM3D`` (lsfc_bicgstabl_multi): the solver for grids whose GMRES basis does not fit even
+    spread over the devices.  x, b and r_shadow are host (numpy) vectors of the full size, ``Pl`` is None or a callable on the
+    WHOLE host vector, and every device keeps its slab of the 2 l + 3 work vectors (checked against the free memory of each
+    device); iterates, history, defaults and breakdown rules are those of ``bicgstabl_``.  Nothing is refused on the Python
+    side: device tensors, ``Pl_on_device=True``, a ``SparsifyingPreconditioner`` or a single-device operator raise the
+    library's LsfcError.  Its own function, so that ``bicgstabl_`` keeps doing what it did with such an operator."""
+    return _bicgstabl("lsfc_bicgstabl_multi", x, A, b, l, Pl, max_mv_products, abstol, reltol, log, Pl_on_device, r_shadow, initially_zero)
+
+
+def _bicgstabl(entry, x, A, b, l, Pl, max_mv_products, abstol, reltol, log, Pl_on_device, r_shadow, initially_zero):
     vecs = _solve_vecs(x, b, A)
     opts, keeps = _bicgstabl_opts(l, max_mv_products, abstol, reltol, initially_zero, r_shadow, A.N, 1, vecs[2], "x")
     cap = _bicgstabl_cap(opts, A.N)
-    rc, res, resnorm = _solve("lsfc_bicgstabl", A, x, vecs, None, opts, Pl, Pl_on_device, cap, ok=(0, L.LSFC_ENOTCONV))
+    rc, res, resnorm = _solve(entry, A, x, vecs, None, opts, Pl, Pl_on_device, cap, ok=(0, L.LSFC_ENOTCONV))
     if log:
         hist = _history(res[0], resnorm[0], cap)
         hist.message = L.load().lsfc_last_error().decode(errors="replace") if rc == L.LSFC_ENOTCONV else ""
@@ -727,7 +743,8 @@ def bicgstabl_batch_(X, A, B, l=2, Pl=None, max_mv_products=None, abstol=0.0, re
     Each row has its own tolerance and stopping test and its iterates are those of ``bicgstabl_`` on that row alone.
     ``r_shadow``: None or one shadow residual per row, in the memory space of X.  nrhs <= 64; device memory
     nrhs (2 l + 3) vectors.  Returns X or (X, [ConvergenceHistory per row]); ``.message`` of a row that did not converge
-    names the reason (max_mv_products, or the scalar of the breakdown) and the cycle."""
+    names the reason (max_mv_products, or the scalar of the breakdown) and the cycle.  Single-device plans only: on a
+    ``MultiDeviceFastM3D`` the library refuses the batch (LsfcError); ``bicgstabl_multi_`` solves there, one right-hand side at a time."""
     torch_in = _is_torch(X)
     if torch_in and (X.dim() != 2 or tuple(B.shape) != tuple(X.shape)):
         raise ValueError(f"DimensionMismatch: X and B must both be (nrhs, {A.N})")

@@ -286,8 +286,8 @@ int lsfc_gmres_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, 
  * already within the tolerance the solve has converged; otherwise LSFC_ENOTCONV, and lsfc_last_error names the scalar and
  * the cycle.  LSFC_ENOTCONV also when max_mv_products is reached (x still updated).
  * LSFC_EINVAL, before any device call: NULL opts, l outside 1..8, a non-zero reserved word, a bad memspace, NULL plan, x,
- * b or result, a distributed or multi-device plan.
- * Out of scope: multi-device / distributed plans. */
+ * b or result, a distributed or multi-device plan (lsfc_bicgstabl_multi solves on a multi-device plan).
+ * Out of scope: multi-process distributed plans. */
 typedef struct lsfc_bicgstabl_opts {
     int     l;               /* 1..8; IterativeSolvers' default is 2                                   */
     int64_t max_mv_products; /* <=0: N                                                                 */
@@ -302,6 +302,29 @@ typedef struct lsfc_bicgstabl_opts {
 
 int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts,
                    double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* result, int memspace);
+
+/* lsfc_bicgstabl on a single-process MULTI-DEVICE plan (lsfc_plan_create_gv3d_multi), under the rules lsfc_gmres has there: x, b
+ * and opts->r_shadow are LSFC_MEM_HOST vectors of the full size N, scattered over the ranks' z slabs (x is gathered back on
+ * return), and the preconditioner is a host callback, called on the calling thread with the WHOLE vector (the slabs are gathered
+ * into a pinned host vector and scattered back) at the places where lsfc_bicgstabl preconditions.  A separate entry point, so
+ * that what lsfc_bicgstabl does with such a plan (LSFC_EINVAL) does not change.  Every rank keeps its slab of the 2 l + 3 work
+ * vectors and its own scalars; a sum is completed in two levels -- each rank reduces its block partials to a rank sum, copies
+ * it into a small table on every other rank (event-ordered device copies: (2 l + 2) reductions of P (P - 1) copies per cycle),
+ * and the kernel that consumes the sum adds the P entries in rank order.  So every rank forms every scalar from the same
+ * numbers in the same order, the host reads the scalars of rank 0 once per cycle, and every documented property of
+ * lsfc_bicgstabl carries over unchanged: iteration semantics, history, mvps, tolerances, the exhausted-space exit, the breakdown
+ * rules and messages, the shadow-residual departure, bitwise repeatability; one rank on an operator whose apply is bitwise the
+ * identity gives the bits of lsfc_bicgstabl on a single-device plan.
+ * Memory rule, checked before anything is allocated: each rank needs 2 l + 3 work vectors of N / P complex plus its staged
+ * x and b slabs, against the free memory of ITS device (ranks that share a device are summed); LSFC_ENOMEM names the device
+ * and gives the figures.
+ * LSFC_EINVAL, before any device call: the checks of lsfc_bicgstabl on opts and the pointers; a plan that is not a multi-device
+ * one (a single-device plan: lsfc_bicgstabl solves there; a multi-process distributed plan, lsfc_dist_plan_create_gv3d: not
+ * offered); LSFC_MEM_DEVICE; precond_on_device = 1 ("a multi-device plan takes a host preconditioner callback").
+ * Out of scope: a batched form, multi-process plans, a device preconditioner, the transposed / adjoint operator and complex nu
+ * on multi-device plans. */
+int lsfc_bicgstabl_multi(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgstabl_opts* opts,
+                         double* resnorm, int64_t resnorm_cap, lsfc_gmres_result* result, int memspace);
 
 /* How a member of lsfc_bicgstabl_batch ended (status[2 j]); 2..7 name the scalar of a breakdown. */
 #define LSFC_BICG_CONVERGED 0   /* within its tolerance (an exhausted Krylov space included)          */
@@ -331,7 +354,7 @@ int lsfc_bicgstabl(lsfc_plan* plan, double* x, const double* b, const lsfc_bicgs
  * number of cycles run.
  * Returns LSFC_OK even if some member did not converge (check results[j].converged); lsfc_last_error then names the first
  * such member, its reason and its cycle.  LSFC_EINVAL, before any device call: the checks of lsfc_bicgstabl, nrhs outside
- * 1..64, NULL results.  Device memory: nrhs * (2 l + 3) work vectors of N complex, with LSFC_MEM_HOST the staged x and b
+ * 1..64, NULL results (a multi-device plan included: the batched solve is not offered there).  Device memory: nrhs * (2 l + 3) work vectors of N complex, with LSFC_MEM_HOST the staged x and b
  * (2 nrhs vectors) on top, checked before anything is allocated: LSFC_ENOMEM with the figures and the largest nrhs that
  * fits. */
 int lsfc_bicgstabl_batch(lsfc_plan* plan, double* x, const double* b, int64_t nrhs, const lsfc_bicgstabl_opts* opts,

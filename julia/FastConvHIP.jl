@@ -88,7 +88,7 @@ end
 
 # The same builder on several GPUs, driven from THIS one Julia process (lsfc_plan_create_gv3d_multi): z-slabs over
 # `devices` (0-based HIP device ids), RCCL exchanges over xGMI inside the library.  The returned object is an ordinary
-# FastMHIP: `*`, `mul!`, `FFTconvolution`, `gmres_hip!` take and return full host vectors.
+# FastMHIP: `*`, `mul!`, `FFTconvolution`, `gmres_hip!`, `bicgstabl_multi_hip!` take and return full host vectors.
 function buildFastConvolution3D(x, y, z, X, Y, Z, h, k, nu, devices::Vector{<:Integer}; quadRule::String="Greengard_Vico", flags=0)
     nuv = Vector{Float64}(nu(X, Y, Z)); plan = Ref{Ptr{Cvoid}}(C_NULL); devs = Cint.(devices)
     check(ccall((:lsfc_plan_create_gv3d_multi, liblsfc), Cint,
@@ -383,13 +383,20 @@ end
 # minimal-residual step, 2 l operator applications).  A breakdown (rho, sigma or gamma zero where it divides, or not finite)
 # ends the solve with x the last finite iterate; like the cap it shows as a history that stops above the tolerance (rc -5).
 # `log` is accepted for the upstream signature: true (the default here, as gmres_hip! always does) returns (x, history), false x alone.
+# bicgstabl_multi_hip! (lsfc_bicgstabl_multi) is the same solve on a multi-device plan (buildFastConvolution3D(..., devices)), the
+# slabs of the 2 l + 3 work vectors on their devices: x, b, r_shadow are the full host vectors, Pl is nothing or a host
+# preconditioner (ldiv!(Pl, v) on the WHOLE vector through the trampoline); a SparsifyingPreconditionerHIP there is refused by the
+# library ("a multi-device plan takes a host preconditioner callback").  bicgstabl_hip! and bicgstabl_batch_hip! refuse such a plan, as
+# before.  Memory: (2 l + 3 + 2) N / P complex per rank, checked by the library per device.  UNVERIFIED like the rest of this file:
+# written against include/lsfc.h.
 # ABI-LAYOUT lsfc_bicgstabl_opts size=88 l:0 max_mv_products:8 reltol:16 abstol:24 initially_zero:32 precond:40 precond_user:48 precond_on_device:56 r_shadow:64 reserved:72
 struct BicgstablOpts
     l::Cint; max_mv_products::Int64; reltol::Float64; abstol::Float64; initially_zero::Cint
     precond::Ptr{Cvoid}; precond_user::Ptr{Cvoid}; precond_on_device::Cint; r_shadow::Ptr{Cvoid}; reserved::NTuple{4, Cint}
 end
 function bicgstabl_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Complex{Float64}}, l::Int=2; Pl=nothing,
-                        max_mv_products=length(b), abstol=0.0, reltol=sqrt(eps(Float64)), log::Bool=true, initially_zero=false, r_shadow=nothing)
+                        max_mv_products=length(b), abstol=0.0, reltol=sqrt(eps(Float64)), log::Bool=true, initially_zero=false, r_shadow=nothing,
+                        _multi::Bool=false)
     _own_on_m(Pl)
     box = Ref{Any}(Pl)
     if Pl isa SparsifyingPreconditionerHIP        # applied on the device by the library itself: no host code inside the BiCG part
@@ -406,13 +413,19 @@ function bicgstabl_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Comp
     GC.@preserve box shadow begin
         opts = Ref(BicgstablOpts(l, max_mv_products, reltol, abstol, initially_zero ? 1 : 0, cb, user, ondev,
                                  r_shadow === nothing ? C_NULL : Ptr{Cvoid}(pointer(shadow)), (Cint(0), Cint(0), Cint(0), Cint(0))))
-        rc = ccall((:lsfc_bicgstabl, liblsfc), Cint,
+        rc = _multi ?
+             ccall((:lsfc_bicgstabl_multi, liblsfc), Cint,
+                   (Ptr{Cvoid}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Ref{BicgstablOpts}, Ptr{Float64}, Int64, Ref{GmresResult}, Cint),
+                   M.plan, x, b, opts, resnorm, cap, res, 0) :
+             ccall((:lsfc_bicgstabl, liblsfc), Cint,
                    (Ptr{Cvoid}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Ref{BicgstablOpts}, Ptr{Float64}, Int64, Ref{GmresResult}, Cint),
                    M.plan, x, b, opts, resnorm, cap, res, 0)
         (rc == 0 || rc == -5) || check(rc)
     end
     log ? (x, resnorm[1:min(res[].iters, cap)]) : x
 end
+bicgstabl_multi_hip!(x::Vector{Complex{Float64}}, M::FastMHIP, b::Vector{Complex{Float64}}, l::Int=2; kw...) =
+    bicgstabl_hip!(x, M, b, l; _multi=true, kw...)
 
 # bicgstabl_hip! for several right-hand sides in lock step, lsfc_bicgstabl_batch: columns of B, solutions in the columns of
 # X, r_shadow (optional) one shadow residual per column.  Every step of a cycle is one launch over the columns still

@@ -17,7 +17,13 @@
   kernels N L [L ...] three cycles of bicgstabl_ at each l on the cube of N, nothing recorded: the target of
                      `rocprofv3 --kernel-trace --stats -- python3 tools/bench_bicgstabl.py kernels 512 4 8`
                      (profiles/bicgstabl_kernel_stats.csv; the template argument in a kernel's name is its vector count)
-usage: python tools/bench_bicgstabl.py solve 256 512 | largest | batch 48 1 2 4 8 | kernels 512 4 8"""
+  multi N DEVICES [L] the same problem on a single-process multi-device plan (MultiDeviceFastM3D, bicgstabl_multi_, host vectors) at l = L (default 2),
+                     DEVICES a comma-separated list such as 0,1,2,3: one solve to reltol 1e-6, then the time of a cycle (capped
+                     solves of 2 and 10 cycles, best of three, the difference over 8) beside 2 l times the plan's measured apply
+                     (MultiDeviceFastM3D.bench) plus the vector-kernel time of a cycle on one device (its cycle minus 2 l of its
+                     applies).  Appended to profiles/bicgstabl_multi.jsonl.  A device listed more than once makes logical ranks
+                     on one GPU: the record then says that it is a rehearsal, which measures enqueue order and copy overhead, not scaling
+usage: python tools/bench_bicgstabl.py solve 256 512 | largest | batch 48 1 2 4 8 | kernels 512 4 8 | multi 256 0,0"""
 import json
 import os
 import sys
@@ -34,6 +40,7 @@ from tools.bench_configs import bump  # noqa: E402
 
 OUT = os.path.join(ROOT, "profiles", "bicgstabl.jsonl")
 OUT_BATCH = os.path.join(ROOT, "profiles", "bicgstabl_batch.jsonl")
+OUT_MULTI = os.path.join(ROOT, "profiles", "bicgstabl_multi.jsonl")
 
 
 def emit(rec, out=OUT):
@@ -212,7 +219,75 @@ def kernels(n, ls):
     M.close()
 
 
+def _cycle_seconds(solve_capped, l, reset=lambda: None):
+    """time of one cycle: capped solves of 2 and 10 cycles (after a warm-up), best of three each, the difference over 8 -- what
+    both share (staging of host vectors, the initial residual) cancels; reset() runs outside the timed window"""
+    cap = lambda c: 1 + 2 * l * c                                                   # noqa: E731
+    reset()
+    solve_capped(cap(2))
+    t, done = {}, {}
+    for c in (2, 10) * 3:
+        reset()
+        (_, h), sec, _pm = timed(lambda: solve_capped(cap(c)))
+        t[c], done[c] = min(t.get(c, sec), sec), h.iters
+    if done[10] <= done[2]:
+        sys.exit(f"the solve stops after {done[10]} cycles: too few to time one")
+    return (t[10] - t[2]) / (done[10] - done[2])
+
+
+def multi(n, devices, l=2, reltol=1e-6):
+    from fast_solver_lippmann_schwinger_amd.distributed import MultiDeviceFastM3D
+    N, P = n ** 3, len(devices)
+    h = 1.0 / n
+    x = -0.5 + h * np.arange(n)
+    k = 1.0 / h
+    nu = (bump(x)[None, None, :] / 0.3 * bump(x)[None, :, None] / 0.3 * bump(x)[:, None, None]).ravel()
+    M = MultiDeviceFastM3D(n, h, k, nu, devices=devices)
+    u_inc = np.tile(np.exp(1j * k * x), n * n)
+    rhs = -(M * u_inc - u_inc)
+    del u_inc
+    rehearsal = len(set(devices)) < P
+    on_one = max(devices.count(d) for d in set(devices))
+    rec = {"mode": "multi", "n": n, "N": N, "l": l, "reltol": reltol, "devices": devices, "ranks": P, "transport": M.transport,
+           "rehearsal_on_one_gpu": rehearsal, "vector_GB": N * 16 / 1e9,
+           "work_GB_per_device_by_the_rule": on_one * (2 * l + 3 + 2) * (N // P) * 16 / 1e9}
+    if rehearsal:
+        rec["note"] = ("rehearsal: a device is listed more than once, so logical ranks share one GPU -- this measures enqueue order and "
+                       "copy overhead, not scaling")
+    (u, hist), sec, pm = timed(lambda: lsfc.bicgstabl_multi_(np.zeros(N, complex), M, rhs, l=l, reltol=reltol, log=True))
+    rec["solve"] = {"mvps": hist.mvps, "cycles": hist.iters, "converged": hist.isconverged, "seconds": sec, "peak_used_GB": pm.peak_used_GB,
+                    "true_relres": float(np.linalg.norm(M * u - rhs) / np.linalg.norm(rhs))}
+    del u
+    x0 = np.zeros(N, complex)                              # (one buffer, zeroed outside the timed window: no page faults inside it)
+    rec["cycle_s"] = _cycle_seconds(lambda mv: lsfc.bicgstabl_multi_(x0, M, rhs, l=l, reltol=1e-14, max_mv_products=mv, log=True), l,
+                                    reset=lambda: x0.fill(0))
+    del x0
+    steps = 10
+    rec["apply_s"] = M.bench(steps, 2)["elapsed_s"] / steps
+    M.close()
+    del M, rhs
+    torch.cuda.empty_cache()
+    # one device: the vector kernels of a cycle = its cycle minus 2 l of its applies
+    M1, rhs1 = problem(n)
+    cyc1 = _cycle_seconds(lambda mv: lsfc.bicgstabl_(torch.zeros_like(rhs1), M1, rhs1, l=l, reltol=1e-14, max_mv_products=mv, log=True), l)
+    y = M1 * rhs1
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        y = M1 * rhs1
+    torch.cuda.synchronize()
+    app1 = (time.perf_counter() - t0) / steps
+    M1.close()
+    rec.update(single_device_cycle_s=cyc1, single_device_apply_s=app1, single_device_vector_kernels_s=cyc1 - 2 * l * app1,
+               expected_cycle_s=2 * l * rec["apply_s"] + (cyc1 - 2 * l * app1))
+    rec["cycle_over_expected"] = rec["cycle_s"] / rec["expected_cycle_s"]
+    emit(rec, OUT_MULTI)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 3 and sys.argv[1] == "multi":
+        multi(int(sys.argv[2]), [int(d) for d in sys.argv[3].split(",")], *[int(v) for v in sys.argv[4:5]])
+        sys.exit(0)
     mode, sizes = (sys.argv[1] if len(sys.argv) > 1 else "solve"), [int(v) for v in sys.argv[2:]]
     if mode == "solve":
         for n in sizes or [256, 512]:
