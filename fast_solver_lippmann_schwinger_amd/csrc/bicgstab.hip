@@ -27,6 +27,7 @@
 #include "plan.hpp"
 #include "krylov_blas.hpp"
 #include "reduce.hpp"
+#include "team.hpp"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -339,17 +340,15 @@ struct Solve {
     int64_t cycles = 0, mvps = 0;
 };
 
-// One slab of every vector on its own device, with what the kernels of that device work on: the plan itself with all nrhs
-// members (n = N, off = 0), or rank `rank` of a multi-device plan with its z slab of the one member.
-struct Rank {
-    lsfc_plan* p = nullptr; int device = 0, rank = 0;
-    int64_t n = 0, off = 0;                 // entries of the slab and its place in the whole vector
+// What the solve keeps per slab of the team (team.hpp: the plan itself with all nrhs members, n = N, or rank `rank` of a
+// multi-device plan with its z slab of the one member): what the kernels of that device work on.
+struct Rank : RankSlab {
     cplx* x = nullptr; const cplx* b = nullptr;
     DevBuf<cplx> work, scal, partial, table;
     DevBuf<double> tol2;
     Event ready, consumed;                  // TEAM: my rank sums have reached every table / my kernels so far have read my table
     Members B{};                            // of this rank's launches; B.m: the member list of the round
-    hipStream_t st() const { return p->stream; }
+    Rank(const RankSlab& s, cplx* x_, const cplx* b_) : RankSlab(s), x(x_), b(b_) {}
 };
 using Ranks = std::vector<std::unique_ptr<Rank>>;
 
@@ -362,15 +361,17 @@ using Ranks = std::vector<std::unique_ptr<Rank>>;
 // round (Precond::apply; TEAM: a host callback on the whole vector, gathered from the slabs and scattered back).
 // code[2 j], code[2 j + 1]: LSFC_BICG_* of member j and its cycle (of the breakdown, else the last one).
 template <bool TEAM>
-static void bicgstabl_run_as(lsfc_plan* root, Ranks& ranks, int nrhs, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
+static void bicgstabl_run_as(const SlabTeam& T, Ranks& ranks, int nrhs, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
                           const lsfc_bicgstabl_opts& o, int l, int64_t maxmv, double reltol, double abstol, double* resnorm, int64_t cap,
                           lsfc_gmres_result* res, int64_t* code) {
     const int P = (int)ranks.size(), nv = l + 1;
     Rank& k0 = *ranks[0];
+    lsfc_plan* root = T.root;
     const int64_t N = root->N, n = k0.n;                // (the slabs of a multi-device plan are equal)
     const int nb = blas_red_blocks(n);
     const int64_t wstride = (int64_t)(2 * l + 3) * n, uoff = (int64_t)nv * n, toff = 2 * (int64_t)nv * n;
-    auto each = [&](auto&& f) { for (auto& k : ranks) { if constexpr (TEAM) LSFC_HIP(hipSetDevice(k->device)); f(*k); } };
+    // (TEAM = false: one slab, whose device is current -- no call of the runtime around f)
+    auto each = [&](auto&& f) { if constexpr (TEAM) T.each([&](const RankSlab& s) { f(*ranks[(size_t)s.rank]); }); else f(k0); };
     each([&](Rank& k) {
         k.work.alloc((size_t)nrhs * (size_t)wstride);
         k.scal.alloc((size_t)nrhs * S_COUNT);
@@ -403,7 +404,7 @@ static void bicgstabl_run_as(lsfc_plan* root, Ranks& ranks, int nrhs, const cplx
         av.clear(); pv.clear();
         if constexpr (TEAM) {
             for (auto& k : ranks) { av.push_back(in(*k, 0)); pv.push_back(out(*k, 0)); }
-            multi_convolve_dev(root, av.data(), pv.data(), plan_operator(root));
+            T.apply(av.data(), pv.data());
         } else {
             for (int m : list) { av.push_back(in(k0, m)); pv.push_back(out(k0, m)); }
             plan_apply_batch_dev(root, av.data(), pv.data(), list.size());
@@ -411,13 +412,7 @@ static void bicgstabl_run_as(lsfc_plan* root, Ranks& ranks, int nrhs, const cplx
     };
     auto precondition = [&](const std::vector<int>& list, auto&& v) {
         if constexpr (TEAM) {
-            // host callback, in place on the whole vector (the two-argument ldiv!): gather the slabs, call, scatter
-            if (!pc.fn) return;
-            each([&](Rank& k) { LSFC_HIP(hipMemcpyAsync(vpin.p + k.off, v(k, 0), (size_t)n * sizeof(cplx), hipMemcpyDeviceToHost, k.st())); });
-            each([&](Rank& k) { LSFC_HIP(hipStreamSynchronize(k.st())); });
-            const int rc = pc.fn(pc.user, (double*)vpin.p, N);
-            if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-            each([&](Rank& k) { LSFC_HIP(hipMemcpyAsync(v(k, 0), vpin.p + k.off, (size_t)n * sizeof(cplx), hipMemcpyHostToDevice, k.st())); });
+            if (pc.fn) T.host_precond(pc, vpin.p, [&](const RankSlab& s) { return v(*ranks[(size_t)s.rank], 0); });
         } else {
             pv.clear();
             for (int m : list) pv.push_back(v(k0, m));
@@ -579,57 +574,31 @@ static void bicgstabl_run_as(lsfc_plan* root, Ranks& ranks, int nrhs, const cplx
 }
 
 // the form of the solve follows the plan: the team form on a multi-device plan (whatever its number of ranks)
-static void bicgstabl_run(lsfc_plan* root, Ranks& ranks, int nrhs, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
+static void bicgstabl_run(const SlabTeam& T, Ranks& ranks, int nrhs, const cplx* r_shadow, bool shadow_on_host, const Precond& pc,
                           const lsfc_bicgstabl_opts& o, int l, int64_t maxmv, double reltol, double abstol, double* resnorm, int64_t cap,
                           lsfc_gmres_result* res, int64_t* code) {
-    if (root->multi) bicgstabl_run_as<true>(root, ranks, nrhs, r_shadow, shadow_on_host, pc, o, l, maxmv, reltol, abstol, resnorm, cap, res, code);
-    else bicgstabl_run_as<false>(root, ranks, nrhs, r_shadow, shadow_on_host, pc, o, l, maxmv, reltol, abstol, resnorm, cap, res, code);
+    if (T.multi) bicgstabl_run_as<true>(T, ranks, nrhs, r_shadow, shadow_on_host, pc, o, l, maxmv, reltol, abstol, resnorm, cap, res, code);
+    else bicgstabl_run_as<false>(T, ranks, nrhs, r_shadow, shadow_on_host, pc, o, l, maxmv, reltol, abstol, resnorm, cap, res, code);
 }
 
-// The ranks of a multi-device plan, each with its z slab of the host vectors x and b staged on its device.  First the memory rule,
-// per DEVICE: every rank on it needs 2 l + 3 work vectors of N / P complex, and its staged x and b where its staging buffers do not
-// hold them yet.
-static void team_stage(lsfc_plan* plan, const cplx* x, const cplx* b, int l, Ranks& ranks) {
-    MultiState* ms = plan->multi.get();
-    std::vector<bool> stage((size_t)ms->P);
-    for (int r = 0; r < ms->P; ++r) stage[(size_t)r] = ms->sub[(size_t)r]->xs.n < (size_t)ms->sub[(size_t)r]->N;
-    for (int r = 0; r < ms->P; ++r) {
-        const int dev = ms->devices[(size_t)r];
-        int first = r, on = 0; double need = 0.0;
-        for (int q = 0; q < ms->P; ++q) if (ms->devices[(size_t)q] == dev) {
-            first = std::min(first, q); ++on;
-            need += ((double)(2 * l + 3) + (stage[(size_t)q] ? 2.0 : 0.0)) * (double)ms->sub[(size_t)q]->N * sizeof(cplx);
+// The memory rule of a solve on a multi-device plan, per DEVICE, before its host vectors are staged: every rank on it needs 2 l + 3
+// work vectors of N / P complex, and its staged x and b where its staging buffers do not hold them yet.
+static void team_stage(const SlabTeam& T, int l) {
+    for (const RankSlab& s : T.slabs) {
+        int first = s.rank, on = 0; double need = 0.0;
+        for (const RankSlab& q : T.slabs) if (q.device == s.device) {
+            first = std::min(first, q.rank); ++on;
+            need += ((double)(2 * l + 3) + (q.p->xs.n < (size_t)q.n ? 2.0 : 0.0)) * (double)q.n * sizeof(cplx);
         }
-        if (first != r) continue;                       // (a device is checked once, at its first rank)
+        if (first != s.rank) continue;                  // (a device is checked once, at its first rank)
         size_t free_b = 0, total_b = 0;
-        LSFC_HIP(hipSetDevice(dev));
+        LSFC_HIP(hipSetDevice(s.device));
         LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
         if (need > (double)free_b)
             fail(LSFC_ENOMEM, "lsfc_bicgstabl_multi: device %d: %d rank%s x (2 l + 3 = %d work vectors, + staged x and b) of %lld complex need %.1f GB of "
-                 "device memory, %.1f GB are free there -- lower l or spread the plan over more devices", dev, on, on == 1 ? "" : "s", 2 * l + 3,
-                 (long long)ms->sub[(size_t)r]->N, need / 1e9, (double)free_b / 1e9);
+                 "device memory, %.1f GB are free there -- lower l or spread the plan over more devices", s.device, on, on == 1 ? "" : "s", 2 * l + 3,
+                 (long long)s.n, need / 1e9, (double)free_b / 1e9);
     }
-    int64_t off = 0;
-    for (int r = 0; r < ms->P; ++r) {
-        lsfc_plan* p = ms->sub[(size_t)r].get();
-        LSFC_HIP(hipSetDevice(ms->devices[(size_t)r]));
-        plan_ensure_staging(p, p->N);
-        LSFC_HIP(hipMemcpyAsync(p->xs.p, x + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
-        LSFC_HIP(hipMemcpyAsync(p->ys.p, b + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
-        ranks.emplace_back(new Rank());
-        Rank& k = *ranks.back();
-        k.p = p; k.device = ms->devices[(size_t)r]; k.rank = r; k.n = p->N; k.off = off; k.x = p->xs.p; k.b = p->ys.p;
-        off += p->N;
-    }
-}
-// ... and x gathered back from the slabs
-static void team_gather(lsfc_plan* plan, Ranks& ranks, cplx* x) {
-    for (auto& k : ranks) {
-        LSFC_HIP(hipSetDevice(k->device));
-        LSFC_HIP(hipMemcpyAsync(x + k->off, k->x, (size_t)k->n * sizeof(cplx), hipMemcpyDeviceToHost, k->st()));
-    }
-    for (auto& k : ranks) { LSFC_HIP(hipSetDevice(k->device)); LSFC_HIP(hipStreamSynchronize(k->st())); }
-    LSFC_HIP(hipSetDevice(plan->device));
 }
 
 // the argument checks of the entry points, before any device call.  team: lsfc_bicgstabl_multi, the entry point of multi-device plans --
@@ -717,11 +686,15 @@ static void bicgstabl_entry(const char* fn, bool batch, bool team, lsfc_plan* pl
     const int64_t cap = resnorm_cap > 0 ? resnorm_cap : 0;
     plan_check_precond_op(plan, opts->precond, opts->precond_user, fn);
     const Precond pc(opts->precond, opts->precond_user, opts->precond_on_device != 0, batch, N, fn);
+    const SlabTeam T(plan);
     Ranks ranks;
-    const bool multi = plan->multi != nullptr, host = memspace == LSFC_MEM_HOST;
+    const bool multi = T.multi, host = memspace == LSFC_MEM_HOST;
     const size_t bytes = (size_t)n * (size_t)N * sizeof(cplx);
-    if (multi) team_stage(plan, (const cplx*)x, (const cplx*)b, l, ranks);
-    else {
+    if (multi) {
+        team_stage(T, l);
+        T.scatter((const cplx*)x, (const cplx*)b);
+        for (const RankSlab& s : T.slabs) ranks.emplace_back(new Rank(s, s.p->xs.p, s.p->ys.p));
+    } else {
         LSFC_HIP(hipSetDevice(plan->device));
         const bool stage = host && plan->xs.n < (size_t)n * (size_t)N;
         size_t free_b = 0, total_b = 0;
@@ -742,11 +715,9 @@ static void bicgstabl_entry(const char* fn, bool batch, bool team, lsfc_plan* pl
             LSFC_HIP(hipMemcpy(plan->ys.p, b, bytes, hipMemcpyHostToDevice));
             xd = plan->xs.p; bd = plan->ys.p;
         }
-        ranks.emplace_back(new Rank());
-        Rank& k = *ranks.back();
-        k.p = plan; k.device = plan->device; k.n = N; k.x = (cplx*)xd; k.b = bd;
+        ranks.emplace_back(new Rank(T.slabs[0], (cplx*)xd, bd));
     }
-    bicgstabl_run(plan, ranks, n, (const cplx*)opts->r_shadow, host, pc, *opts, l, maxmv, reltol, abstol, resnorm, cap, results, code);
-    if (multi) team_gather(plan, ranks, (cplx*)x);
+    bicgstabl_run(T, ranks, n, (const cplx*)opts->r_shadow, host, pc, *opts, l, maxmv, reltol, abstol, resnorm, cap, results, code);
+    if (multi) { T.gather((cplx*)x); T.sync(); LSFC_HIP(hipSetDevice(plan->device)); }
     else if (host) LSFC_HIP(hipMemcpy(x, plan->xs.p, bytes, hipMemcpyDeviceToHost));
 }

@@ -14,6 +14,7 @@
 #include "apply.hpp"
 #include "pointwise.hpp"
 #include "dist_schedule.hpp"
+#include "team.hpp"
 #include <rccl/rccl.h>
 #include <cstring>
 #include <string>
@@ -71,101 +72,163 @@ static void phase3(lsfc_plan* p, const cplx* x, cplx* y, double alpha, double be
     pruned_xinv(p->tuning, slab_xpass(p, x, y, false, alpha, beta, part), st);
 }
 
-// Exchange of chunk c.  way in : S1 block (q*K + c)  -> rank q, lands in R1 chunk c at slot <source rank>
-//                       way back: R1 chunk c, slot q  -> rank q, lands in S1 block (<source rank>*K + c)
-// part = -1: whole blocks; 0 / 1: their lower / upper z halves (blocks are [z][m][Wc], z slowest: halves are contiguous)
-static void exchange(lsfc_plan* p, int c, bool back, hipStream_t st, int part = -1) {
-    DistState* d = p->dist.get();
-    const int P = d->nranks;
-    // (the message list -- peers, order, offsets -- is dist_schedule.hpp's, checked on the CPU for P = 2, 4, 8)
-    const std::vector<dsched::Msg> msgs = dsched::exchange_messages(d->rank, P, d->K, c, back, part, block_elems(p));
-    auto ptr = [&](const dsched::Msg& m) { return (m.in_s1 ? d->S1.p : d->R1.p) + m.off; };
-    ncclComm_t comm = (ncclComm_t)(back ? d->comm2 : d->comm);
-    if (d->force_comm && P == 1) {
+// The ranks this process drives: one rank of a multi-process plan (the plan itself, with the communicators of its DistState) or
+// all P sub-plans of a multi-device plan (MultiState's communicators, or the copy transport).  A stream of one device may wait
+// on an event of another, so one host thread enqueues the same schedule (dist_schedule.hpp) either way.
+namespace {
+using dsched::Lane; using dsched::Ev; using dsched::Op; using dsched::Step;
+struct Local {
+    std::vector<lsfc_plan*> plan;       // plan[i]->dist->rank is the rank; a multi-device plan drives them all, in rank order
+    int P, K;                           // ranks of the whole job, pipeline chunks
+    bool rccl;                          // blocks between different ranks: one RCCL group over the local ranks' message lists, or source-issued copies
+    bool force_comm = false;            // one rank, the self block sent through RCCL (LSFC_DIST_FORCE_COMM)
+    bool set_device = false;            // multi-device: the rank's device is made current before anything is enqueued for it
+    void* const* comm = nullptr; void* const* comm2 = nullptr;    // per local rank: way in / way back
+
+    explicit Local(lsfc_plan* p) {
+        if (p->multi) {
+            MultiState* ms = p->multi.get();
+            for (auto& sp : ms->sub) plan.push_back(sp.get());
+            rccl = ms->rccl; set_device = true; comm = ms->comm.data(); comm2 = ms->comm2.data();
+        } else {
+            plan.push_back(p);
+            rccl = true; force_comm = p->dist->force_comm; comm = &p->dist->comm; comm2 = &p->dist->comm2;
+        }
+        P = d(0)->nranks; K = d(0)->K;
+    }
+    int n() const { return (int)plan.size(); }
+    DistState* d(int i) const { return plan[(size_t)i]->dist.get(); }
+    void dev(int i) const { if (set_device) LSFC_HIP(hipSetDevice(plan[(size_t)i]->device)); }
+    template <class F> void each(F&& f) const { for (int i = 0; i < n(); ++i) { dev(i); f(i); } }
+    hipStream_t stream(int i, Lane on) const {
+        return on == Lane::COMPUTE ? plan[(size_t)i]->stream : on == Lane::COMPUTE2 ? d(i)->st2 : on == Lane::IN ? d(i)->cs1 : d(i)->cs2;
+    }
+    hipEvent_t event(int i, Ev ev, int c) const {
+        DistState* s = d(i);
+        switch (ev) {
+            case Ev::P1A: return s->ev_p1a; case Ev::P1: return s->ev_p1; case Ev::BACKA: return s->ev_backa;
+            case Ev::IN: return s->ev_in[(size_t)c]; case Ev::DONE: return s->ev_done[(size_t)c]; default: return s->ev_back[(size_t)c];
+        }
+    }
+};
+
+// Exchange of chunk c over the local ranks, on their streams `on`.
+//   way in  : S1 block (q, c)  -> rank q, lands in R1 slot (c, <source rank>)
+//   way back: R1 slot (c, q)   -> rank q, lands in S1 block (<source rank>, c)
+// part = -1: whole blocks; 0 / 1: their lower / upper z halves (blocks are [z][m][Wc], z slowest: halves are contiguous).
+// Every rank's message list -- peers, order, offsets -- is dist_schedule.hpp's, checked on the CPU for P = 2, 4, 8: the self
+// block first, a device copy; then the pairwise steps, as sends and receives of one RCCL group or, with all ranks local, as
+// copies issued by the source (copy engines instead of CUs; every source starts with a different peer).
+void exchange(const Local& L, int c, bool back, int part, Lane on) {
+    const int n = L.n(), P = L.P;
+    std::vector<std::vector<dsched::Msg>> msgs((size_t)n);
+    for (int i = 0; i < n; ++i) msgs[(size_t)i] = dsched::exchange_messages(L.d(i)->rank, P, L.K, c, back, part, block_elems(L.plan[0]));
+    auto ptr = [&](int i, const dsched::Msg& m) { return (m.in_s1 ? L.d(i)->S1.p : L.d(i)->R1.p) + m.off; };
+    auto comm = [&](int i) { return (ncclComm_t)(back ? L.comm2[i] : L.comm[i]); };
+    auto post = [&](int i, const dsched::Msg& m) {
+        if (m.send) LSFC_NCCL(ncclSend(ptr(i, m), (size_t)m.count * 2, ncclDouble, m.peer, comm(i), L.stream(i, on)));
+        else LSFC_NCCL(ncclRecv(ptr(i, m), (size_t)m.count * 2, ncclDouble, m.peer, comm(i), L.stream(i, on)));
+    };
+    if (L.force_comm && P == 1) {
         // single-rank exercise of the RCCL path: the self block travels through ncclSend/ncclRecv
         LSFC_NCCL(ncclGroupStart());
-        LSFC_NCCL(ncclSend(ptr(msgs[0]), (size_t)msgs[0].count * 2, ncclDouble, 0, comm, st));
-        LSFC_NCCL(ncclRecv(ptr(msgs[1]), (size_t)msgs[1].count * 2, ncclDouble, 0, comm, st));
+        post(0, msgs[0][0]); post(0, msgs[0][1]);
         LSFC_NCCL(ncclGroupEnd());
         return;
     }
-    LSFC_HIP(hipMemcpyAsync(ptr(msgs[1]), ptr(msgs[0]), (size_t)msgs[0].count * sizeof(cplx), hipMemcpyDeviceToDevice, st));
+    L.each([&](int i) {
+        LSFC_HIP(hipMemcpyAsync(ptr(i, msgs[(size_t)i][1]), ptr(i, msgs[(size_t)i][0]), (size_t)msgs[(size_t)i][0].count * sizeof(cplx), hipMemcpyDeviceToDevice, L.stream(i, on)));
+    });
     if (P == 1) return;
-    LSFC_NCCL(ncclGroupStart());
-    for (size_t i = 2; i < msgs.size(); ++i) {
-        const dsched::Msg& m = msgs[i];
-        if (m.send) LSFC_NCCL(ncclSend(ptr(m), (size_t)m.count * 2, ncclDouble, m.peer, comm, st));
-        else LSFC_NCCL(ncclRecv(ptr(m), (size_t)m.count * 2, ncclDouble, m.peer, comm, st));
+    if (L.rccl) {
+        LSFC_NCCL(ncclGroupStart());
+        for (int i = 0; i < n; ++i) for (size_t k = 2; k < msgs[(size_t)i].size(); ++k) post(i, msgs[(size_t)i][k]);
+        LSFC_NCCL(ncclGroupEnd());
+        return;
     }
-    LSFC_NCCL(ncclGroupEnd());
+    // (all ranks are local, i == rank: the send of step s to q = r + s lands where q's receive of step s, from r, points)
+    L.each([&](int r) {
+        for (int s = 1; s < P; ++s) {
+            const dsched::Msg& snd = msgs[(size_t)r][(size_t)(2 * s)];
+            const int q = snd.peer, dq = L.plan[(size_t)q]->device, dr = L.plan[(size_t)r]->device;
+            cplx* dst = ptr(q, msgs[(size_t)q][(size_t)(2 * s + 1)]);
+            const size_t bytes = (size_t)snd.count * sizeof(cplx);
+            if (dq == dr) LSFC_HIP(hipMemcpyAsync(dst, ptr(r, snd), bytes, hipMemcpyDeviceToDevice, L.stream(r, on)));
+            else LSFC_HIP(hipMemcpyPeerAsync(dst, dq, ptr(r, snd), dr, bytes, L.stream(r, on)));
+        }
+    });
 }
+
+// The overlapped apply: dist_schedule.hpp's steps (pipeline_steps, in the order of issue) on the streams and events of the local
+// ranks.  x[i], y[i]: the vectors of local rank i.  host_sync (the multi-device plan under LSFC_DIST_OVERLAP=0): the host waits
+// for the passes of a chunk on every rank before its way back is enqueued.
+struct Pipeline {
+    const Local& L; const cplx* const* x; cplx* const* y; bool use_nu; double alpha, beta; bool host_sync;
+    int current = -1;                   // the device this apply made current last (-1: not known), so that it is set once per change
+    void dev(int i) {
+        const int want = L.plan[(size_t)i]->device;
+        if (L.set_device && want != current) { LSFC_HIP(hipSetDevice(want)); current = want; }
+    }
+    void begin(const Step& s) {
+        if (!host_sync || s.op != Op::EXCH_BACK) return;
+        L.each([&](int i) { LSFC_HIP(hipStreamSynchronize(L.plan[(size_t)i]->stream)); if (L.d(i)->st2) LSFC_HIP(hipStreamSynchronize(L.d(i)->st2)); });
+        current = -1;
+    }
+    void wait(int i, Lane on, int q, Ev ev, int c) { dev(i); LSFC_HIP(hipStreamWaitEvent(L.stream(i, on), L.event(q, ev, c), 0)); }
+    void record(int i, Lane on, Ev ev, int c) { dev(i); LSFC_HIP(hipEventRecord(L.event(i, ev, c), L.stream(i, on))); }
+    void run(int i, const Step& s) {
+        dev(i);
+        lsfc_plan* p = L.plan[(size_t)i];
+        if (s.op == Op::XFWD) phase1(p, x[i], use_nu, L.stream(i, s.on), s.part);
+        else if (s.op == Op::PASSES) phase2(p, s.c, L.stream(i, s.on));
+        else phase3(p, x[i], y[i], alpha, beta, L.stream(i, s.on), s.part);
+    }
+    void exchange(const Step& s) { lsfc::exchange(L, s.c, s.op == Op::EXCH_BACK, s.part, s.on); current = -1; }
+};
+void pipelined_convolve(const Local& L, const cplx* const* x, cplx* const* y, const ConvOp& op, bool edges, bool host_sync) {
+    Pipeline sink{L, x, y, op.nu == NuSide::INPUT, op.alpha, op.beta, host_sync};
+    dsched::issue(dsched::pipeline_steps(L.K, edges, L.d(0)->st2 != nullptr), L.n(), sink);
+}
+
+// The seven stages of one apply, un-overlapped, each on the compute streams of all local ranks: name, bytes moved per rank
+// (N = local points, 16 B each) and what runs.  exchanges = false (simulated ranks, which have nobody to exchange with): the
+// compute stages only.
+struct Stage { const char* name; double bytes; std::function<void()> run; };
+std::vector<Stage> apply_stages(const Local& L, std::vector<const cplx*> x, std::vector<cplx*> y, bool exchanges) {
+    const double N = (double)L.plan[0]->N, C = 16.0, om2 = L.plan[0]->omega * L.plan[0]->omega;
+    const int K = L.K;
+    auto st = [L](int i) { return L.stream(i, Lane::COMPUTE); };
+    auto chunks = [L, K, st](void (*pass)(lsfc_plan*, int, hipStream_t)) { return [=] { L.each([&](int i) { for (int c = 0; c < K; ++c) pass(L.plan[(size_t)i], c, st(i)); }); }; };
+    auto alltoall = [L, K](bool back) { return [=] { for (int c = 0; c < K; ++c) exchange(L, c, back, -1, Lane::COMPUTE); }; };
+    std::vector<Stage> s;
+    s.push_back({"xfwd", N * (C + 8) + 2 * N * C, [=] { L.each([&](int i) { phase1(L.plan[(size_t)i], x[(size_t)i], true, st(i)); }); }});
+    if (exchanges) s.push_back({"alltoall_in", 2 * N * C, alltoall(false)});
+    s.push_back({"yfwd", 6 * N * C, chunks(phase2_yfwd)});
+    s.push_back({"zfused", 16 * N * C, chunks(phase2_zfused)});
+    s.push_back({"yinv", 6 * N * C, chunks(phase2_yinv)});
+    if (exchanges) s.push_back({"alltoall_back", 2 * N * C, alltoall(true)});
+    s.push_back({"xinv", 4 * N * C, [=] { L.each([&](int i) { phase3(L.plan[(size_t)i], x[(size_t)i], y[(size_t)i], 1.0, om2, st(i)); }); }});
+    return s;
+}
+} // namespace
 
 void dist_convolve_dev(lsfc_plan* p, const cplx* x, cplx* y, const ConvOp& op) {
     LSFC_REQUIRE(conv_forward_only(op), "the transposed and the adjoint operator are not available on a distributed plan");
-    const bool use_nu = op.nu == NuSide::INPUT; const double alpha = op.alpha, beta = op.beta;
     DistState* d = p->dist.get();
     LSFC_REQUIRE(!d->sim, "simulated ranks are driven through lsfc_dist_sim_apply");
     LSFC_REQUIRE(!d->member, "the ranks of a multi-device plan are driven through their parent plan");
-    hipStream_t st = p->stream;
+    const Local L(p);
     // LSFC_DIST_OVERLAP=0: no overlap -- every exchange on the compute stream, chunk after chunk (debugging aid)
     if ((d->nranks == 1 && !d->force_overlap) || d->no_overlap) {
-        phase1(p, x, use_nu, st);
-        for (int c = 0; c < d->K; ++c) { exchange(p, c, false, st); phase2(p, c, st); exchange(p, c, true, st); }
-        phase3(p, x, y, alpha, beta, st);
+        hipStream_t st = p->stream;
+        phase1(p, x, op.nu == NuSide::INPUT, st);
+        for (int c = 0; c < d->K; ++c) { exchange(L, c, false, -1, Lane::COMPUTE); phase2(p, c, st); exchange(L, c, true, -1, Lane::COMPUTE); }
+        phase3(p, x, y, op.alpha, op.beta, st);
         return;
     }
     // software pipeline over the K chunks of the owned x' range: the all-to-all of chunk c+1 (stream cs1) and the
-    // all-to-all back of chunk c-1 (stream cs2, second communicator) run while chunk c is transformed (stream st).
-    // The two ends of the pipeline are split once more over the z halves of the own slab, so that the first exchange
-    // starts after half of the x pass and the second half of the last exchange back hides half of the inverse x pass.
-    const bool edges = d->split_edges && d->lz % 2 == 0;
-    const int K = d->K;
-    if (edges) {
-        phase1(p, x, use_nu, st, 0);
-        LSFC_HIP(hipEventRecord(d->ev_p1a, st));
-        phase1(p, x, use_nu, st, 1);
-    } else {
-        phase1(p, x, use_nu, st);
-    }
-    LSFC_HIP(hipEventRecord(d->ev_p1, st));
-    if (edges) {
-        LSFC_HIP(hipStreamWaitEvent(d->cs1, d->ev_p1a, 0));
-        exchange(p, 0, false, d->cs1, 0);
-    }
-    LSFC_HIP(hipStreamWaitEvent(d->cs1, d->ev_p1, 0));
-    LSFC_HIP(hipStreamWaitEvent(d->cs2, d->ev_p1, 0));      // also orders cs2 after the previous apply's xinv reads of S1
-    for (int c = 0; c < K; ++c) {
-        if (edges && c == 0) exchange(p, 0, false, d->cs1, 1); else exchange(p, c, false, d->cs1);
-        LSFC_HIP(hipEventRecord(d->ev_in[c], d->cs1));
-    }
-    for (int c = 0; c < K; ++c) {
-        // (two compute streams: a chunk always runs on the stream of its parity, so its buffers -- A2 / R1 chunk c -- stay ordered
-        // from one apply to the next; everything the second stream does is behind ev_done -> cs2 -> ev_back -> the inverse x pass)
-        hipStream_t cst = ((c & 1) && d->st2) ? d->st2 : st;
-        LSFC_HIP(hipStreamWaitEvent(cst, d->ev_in[c], 0));
-        phase2(p, c, cst);
-        LSFC_HIP(hipEventRecord(d->ev_done[c], cst));
-        LSFC_HIP(hipStreamWaitEvent(d->cs2, d->ev_done[c], 0));
-        // (the S1 blocks this receive overwrites belong to chunk c, whose way-in sends finished before ev_in[c])
-        if (edges && c == K - 1) {
-            exchange(p, c, true, d->cs2, 0);
-            LSFC_HIP(hipEventRecord(d->ev_backa, d->cs2));
-            exchange(p, c, true, d->cs2, 1);
-        } else {
-            exchange(p, c, true, d->cs2);
-        }
-        LSFC_HIP(hipEventRecord(d->ev_back[c], d->cs2));
-    }
-    if (edges) {
-        // cs2 runs its exchanges in order: ev_backa implies every earlier chunk is back
-        LSFC_HIP(hipStreamWaitEvent(st, d->ev_backa, 0));
-        phase3(p, x, y, alpha, beta, st, 0);
-        LSFC_HIP(hipStreamWaitEvent(st, d->ev_back[K - 1], 0));
-        phase3(p, x, y, alpha, beta, st, 1);
-    } else {
-        for (int c = 0; c < K; ++c) LSFC_HIP(hipStreamWaitEvent(st, d->ev_back[c], 0));
-        phase3(p, x, y, alpha, beta, st);
-    }
+    // all-to-all back of chunk c-1 (stream cs2, second communicator) run while chunk c is transformed
+    pipelined_convolve(L, &x, &y, op, d->split_edges && d->lz % 2 == 0, false);
 }
 
 void dist_allreduce_sum(lsfc_plan* p, cplx* dev, int count) {
@@ -176,25 +239,16 @@ void dist_allreduce_sum(lsfc_plan* p, cplx* dev, int count) {
 
 void dist_profile_stages(lsfc_plan* p, const cplx* x, cplx* y, std::function<void(const char*, double, std::function<void()>)> add) {
     DistState* d = p->dist.get();
-    const double N = (double)p->N, C = 16.0, om2 = p->omega * p->omega;     // N = local points
-    hipStream_t st = p->stream;
-    const int K = d->K;
     // un-overlapped, stage by stage, all on the plan's stream (the production path overlaps the exchanges)
     const bool sim = d->sim || d->member;                       // simulated rank: compute stages only (per-rank kernel times at P ranks)
     if (sim) {
         // no exchange runs here, so the receive buffer would hold the zeros of plan creation and the y / z / y passes would
         // transform zeros -- on which this power-limited chip clocks ~9 % higher.  Prime it once with the x pass's own
         // output (same size: P * K blocks either way), i.e. with data of the statistics the real exchange delivers.
-        phase1(p, x, true, st);
-        LSFC_HIP(hipMemcpyAsync(d->R1.p, d->S1.p, std::min(d->R1.bytes(), d->S1.bytes()), hipMemcpyDeviceToDevice, st));
+        phase1(p, x, true, p->stream);
+        LSFC_HIP(hipMemcpyAsync(d->R1.p, d->S1.p, std::min(d->R1.bytes(), d->S1.bytes()), hipMemcpyDeviceToDevice, p->stream));
     }
-    add("xfwd", N * (C + 8) + 2 * N * C, [=] { phase1(p, x, true, st); });
-    if (!sim) add("alltoall_in", 2 * N * C, [=] { for (int c = 0; c < K; ++c) exchange(p, c, false, st); });
-    add("yfwd", 6 * N * C, [=] { for (int c = 0; c < K; ++c) phase2_yfwd(p, c, st); });
-    add("zfused", 16 * N * C, [=] { for (int c = 0; c < K; ++c) phase2_zfused(p, c, st); });
-    add("yinv", 6 * N * C, [=] { for (int c = 0; c < K; ++c) phase2_yinv(p, c, st); });
-    if (!sim) add("alltoall_back", 2 * N * C, [=] { for (int c = 0; c < K; ++c) exchange(p, c, true, st); });
-    add("xinv", 4 * N * C, [=] { phase3(p, x, y, 1.0, om2, st); });
+    for (Stage& s : apply_stages(Local(p), {x}, {y}, !sim)) add(s.name, s.bytes, std::move(s.run));
 }
 
 // ---------------------------------------------------------------------------
@@ -305,8 +359,8 @@ static void create_dist_plan(lsfc_plan** out, int64_t n, int64_t m, int64_t l, d
 
 // ---------------------------------------------------------------------------
 // Single-process multi-device plan: ONE host thread enqueues the work of all P ranks (one per device).  The schedule
-// is the three-stream pipeline of dist_convolve_dev, made explicit across devices with events (a stream of one device
-// may wait on an event of another).  Two transports for the slab exchanges:
+// is the one dist_convolve_dev runs (pipelined_convolve), with all P ranks local: a wait "of every rank" then covers them
+// all (a stream of one device may wait on an event of another).  Two transports for the slab exchanges:
 //   rccl  grouped ncclSend/ncclRecv over the communicators of ncclCommInitAll (distinct devices; the default)
 //   copy  hipMemcpyPeerAsync issued by the SOURCE rank on its communication stream (copy engines instead of CUs; also
 //         the only form that runs with a device listed twice, which is how the driver is tested on a one-GPU box)
@@ -317,162 +371,62 @@ MultiState::~MultiState() {
     if (red_pin) (void)hipHostFree(red_pin);
 }
 
-namespace {
-struct Multi {
-    lsfc_plan* root; MultiState* ms; int P, K;
-    explicit Multi(lsfc_plan* r) : root(r), ms(r->multi.get()), P(ms->P), K(ms->sub[0]->dist->K) {}
-    lsfc_plan* sub(int r) const { return ms->sub[(size_t)r].get(); }
-    DistState* d(int r) const { return sub(r)->dist.get(); }
-    void dev(int r) const { LSFC_HIP(hipSetDevice(ms->devices[(size_t)r])); }
-    hipStream_t st(int r) const { return sub(r)->stream; }
-    int64_t B() const { return block_elems(sub(0)); }
-
-    // Exchange of chunk c between all ranks.  `on`: 0 = the communication streams (cs1 way in, cs2 way back), 1 = the
-    // compute streams (per-stage profile).
-    void exchange(int c, bool back, int part, int on) const {
-        const int64_t Bfull = B(), Bp = part < 0 ? Bfull : Bfull / 2, off = part == 1 ? Bfull / 2 : 0;
-        auto s1 = [&](int r, int q) { return d(r)->S1.p + ((int64_t)q * K + c) * Bfull + off; };     // rank r's block for / from rank q
-        auto r1 = [&](int r, int q) { return d(r)->R1.p + ((int64_t)c * P + q) * Bfull + off; };     // rank r's slot of rank q
-        auto stream = [&](int r) { return on == 1 ? st(r) : (back ? d(r)->cs2 : d(r)->cs1); };
-        const size_t bytes = (size_t)Bp * sizeof(cplx);
-        if (!ms->rccl) {
-            for (int r = 0; r < P; ++r) {
-                dev(r);
-                for (int s = 0; s < P; ++s) {
-                    const int q = (r + s) % P;                  // every source starts with a different peer
-                    const cplx* src = back ? r1(r, q) : s1(r, q);
-                    cplx* dst = back ? s1(q, r) : r1(q, r);
-                    if (ms->devices[(size_t)q] == ms->devices[(size_t)r]) LSFC_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream(r)));
-                    else LSFC_HIP(hipMemcpyPeerAsync(dst, ms->devices[(size_t)q], src, ms->devices[(size_t)r], bytes, stream(r)));
-                }
-            }
-            return;
-        }
-        // every rank's message list is the one its own process would post (dist_schedule.hpp)
-        std::vector<std::vector<dsched::Msg>> msgs((size_t)P);
-        for (int r = 0; r < P; ++r) msgs[(size_t)r] = dsched::exchange_messages(r, P, K, c, back, part, Bfull);
-        auto ptr = [&](int r, const dsched::Msg& m) { return (m.in_s1 ? d(r)->S1.p : d(r)->R1.p) + m.off; };
-        for (int r = 0; r < P; ++r) {
-            dev(r);
-            LSFC_HIP(hipMemcpyAsync(ptr(r, msgs[(size_t)r][1]), ptr(r, msgs[(size_t)r][0]), bytes, hipMemcpyDeviceToDevice, stream(r)));
-        }
-        if (P == 1) return;
-        LSFC_NCCL(ncclGroupStart());
-        for (int r = 0; r < P; ++r) {
-            ncclComm_t comm = (ncclComm_t)(back ? ms->comm2[(size_t)r] : ms->comm[(size_t)r]);
-            for (size_t i = 2; i < msgs[(size_t)r].size(); ++i) {
-                const dsched::Msg& m = msgs[(size_t)r][i];
-                if (m.send) LSFC_NCCL(ncclSend(ptr(r, m), (size_t)m.count * 2, ncclDouble, m.peer, comm, stream(r)));
-                else LSFC_NCCL(ncclRecv(ptr(r, m), (size_t)m.count * 2, ncclDouble, m.peer, comm, stream(r)));
-            }
-        }
-        LSFC_NCCL(ncclGroupEnd());
-    }
-    void wait_all(hipStream_t s, hipEvent_t DistState::* ev) const { for (int q = 0; q < P; ++q) LSFC_HIP(hipStreamWaitEvent(s, d(q)->*ev, 0)); }
-    void wait_all(hipStream_t s, std::vector<hipEvent_t> DistState::* ev, int c) const {
-        for (int q = 0; q < P; ++q) LSFC_HIP(hipStreamWaitEvent(s, (d(q)->*ev)[(size_t)c], 0));
-    }
-};
-} // namespace
-
 void multi_synchronize(lsfc_plan* root) {
-    Multi M(root);
-    for (int r = 0; r < M.P; ++r) { M.dev(r); LSFC_HIP(hipDeviceSynchronize()); }
+    Local(root).each([](int) { LSFC_HIP(hipDeviceSynchronize()); });
 }
 
 void multi_convolve_dev(lsfc_plan* root, const cplx* const* x, cplx* const* y, const ConvOp& op) {
     LSFC_REQUIRE(conv_forward_only(op), "the transposed and the adjoint operator are not available on a multi-device plan");
-    const bool use_nu = op.nu == NuSide::INPUT; const double alpha = op.alpha, beta = op.beta;
-    Multi M(root);
-    const int P = M.P, K = M.K;
-    const bool overlap = !M.d(0)->no_overlap;
-    const bool edges = overlap && M.d(0)->split_edges && M.d(0)->lz % 2 == 0;
-    // phase 1 on every rank: k_xfwd, output packed per (destination rank, chunk)
-    for (int r = 0; r < P; ++r) {
-        M.dev(r);
-        if (edges) {
-            phase1(M.sub(r), x[r], use_nu, M.st(r), 0);
-            LSFC_HIP(hipEventRecord(M.d(r)->ev_p1a, M.st(r)));
-            phase1(M.sub(r), x[r], use_nu, M.st(r), 1);
-        } else phase1(M.sub(r), x[r], use_nu, M.st(r));
-        LSFC_HIP(hipEventRecord(M.d(r)->ev_p1, M.st(r)));
-    }
-    // way in.  A block may only land on rank q once q's previous apply has drained (its R1 / S1 are re-used): every
-    // communication stream waits for the x pass of EVERY rank, which on each rank follows the previous apply's last pass.
-    if (edges) {
-        for (int r = 0; r < P; ++r) { M.dev(r); M.wait_all(M.d(r)->cs1, &DistState::ev_p1a); }
-        M.exchange(0, false, 0, 0);
-    }
-    for (int r = 0; r < P; ++r) { M.dev(r); M.wait_all(M.d(r)->cs1, &DistState::ev_p1); M.wait_all(M.d(r)->cs2, &DistState::ev_p1); }
-    for (int c = 0; c < K; ++c) {
-        M.exchange(c, false, (edges && c == 0) ? 1 : -1, 0);
-        for (int r = 0; r < P; ++r) { M.dev(r); LSFC_HIP(hipEventRecord(M.d(r)->ev_in[(size_t)c], M.d(r)->cs1)); }
-    }
-    // y / z / y passes chunk by chunk; the way back of chunk c runs under the passes of chunk c + 1
-    for (int c = 0; c < K; ++c) {
-        for (int r = 0; r < P; ++r) {
-            M.dev(r);
-            hipStream_t cst = ((c & 1) && M.d(r)->st2) ? M.d(r)->st2 : M.st(r);   // odd chunks: the second compute stream (as dist_convolve_dev)
-            M.wait_all(cst, &DistState::ev_in, c);              // copy transport: every source signals its own blocks
-            phase2(M.sub(r), c, cst);
-            LSFC_HIP(hipEventRecord(M.d(r)->ev_done[(size_t)c], cst));
-            LSFC_HIP(hipStreamWaitEvent(M.d(r)->cs2, M.d(r)->ev_done[(size_t)c], 0));
-        }
-        if (!overlap) for (int r = 0; r < P; ++r) { M.dev(r); LSFC_HIP(hipStreamSynchronize(M.st(r))); if (M.d(r)->st2) LSFC_HIP(hipStreamSynchronize(M.d(r)->st2)); }
-        if (edges && c == K - 1) {
-            M.exchange(c, true, 0, 0);
-            for (int r = 0; r < P; ++r) { M.dev(r); LSFC_HIP(hipEventRecord(M.d(r)->ev_backa, M.d(r)->cs2)); }
-            M.exchange(c, true, 1, 0);
-        } else M.exchange(c, true, -1, 0);
-        for (int r = 0; r < P; ++r) { M.dev(r); LSFC_HIP(hipEventRecord(M.d(r)->ev_back[(size_t)c], M.d(r)->cs2)); }
-    }
-    // phase 3: k_xinv reads the packed blocks; rank r needs the blocks of every source (their cs2 streams run in order,
-    // so the event of the last chunk covers the earlier ones)
-    for (int r = 0; r < P; ++r) {
-        M.dev(r);
-        if (edges) {
-            M.wait_all(M.st(r), &DistState::ev_backa);
-            phase3(M.sub(r), x[r], y[r], alpha, beta, M.st(r), 0);
-            M.wait_all(M.st(r), &DistState::ev_back, K - 1);
-            phase3(M.sub(r), x[r], y[r], alpha, beta, M.st(r), 1);
-        } else {
-            M.wait_all(M.st(r), &DistState::ev_back, K - 1);
-            phase3(M.sub(r), x[r], y[r], alpha, beta, M.st(r));
-        }
-    }
+    const Local L(root);
+    // LSFC_DIST_OVERLAP=0: the same steps, no split of the pipeline ends, the host between the passes of a chunk and its way back
+    const bool overlap = !L.d(0)->no_overlap;
+    pipelined_convolve(L, x, y, op, overlap && L.d(0)->split_edges && L.d(0)->lz % 2 == 0, !overlap);
+}
+
+// ---------------------------------------------------------------------------
+// A team of slabs (team.hpp)
+SlabTeam::SlabTeam(lsfc_plan* r) : root(r), multi(r->multi != nullptr) {
+    if (!multi) { slabs.push_back({r, r->device, 0, r->N, 0}); return; }
+    int64_t off = 0;
+    for (auto& sp : r->multi->sub) { slabs.push_back({sp.get(), sp->device, (int)slabs.size(), sp->N, off}); off += sp->N; }
+}
+void SlabTeam::apply(const cplx* const* in, cplx* const* out) const {
+    if (multi) multi_convolve_dev(root, in, out, plan_operator(root));
+    else plan_apply_dev(root, in[0], out[0]);
+}
+void SlabTeam::scatter(const cplx* x, const cplx* b) const {
+    each([&](const RankSlab& s) {
+        plan_ensure_staging(s.p, s.n);
+        LSFC_HIP(hipMemcpyAsync(s.p->xs.p, x + s.off, (size_t)s.n * sizeof(cplx), hipMemcpyHostToDevice, s.st()));
+        if (b) LSFC_HIP(hipMemcpyAsync(s.p->ys.p, b + s.off, (size_t)s.n * sizeof(cplx), hipMemcpyHostToDevice, s.st()));
+    });
+}
+void SlabTeam::gather(cplx* x, bool from_ys) const {
+    each([&](const RankSlab& s) { LSFC_HIP(hipMemcpyAsync(x + s.off, from_ys ? s.p->ys.p : s.p->xs.p, (size_t)s.n * sizeof(cplx), hipMemcpyDeviceToHost, s.st())); });
 }
 
 void multi_convolve_host(lsfc_plan* root, const cplx* x, cplx* y, const ConvOp& op) {
     LSFC_REQUIRE(conv_forward_only(op), "the transposed and the adjoint operator are not available on a multi-device plan");
-    Multi M(root);
-    std::vector<const cplx*> xd((size_t)M.P); std::vector<cplx*> yd((size_t)M.P);
-    int64_t off = 0;
-    for (int r = 0; r < M.P; ++r) {
-        lsfc_plan* p = M.sub(r);
-        M.dev(r);
-        if (p->xs.n < (size_t)p->N) { p->xs.alloc((size_t)p->N); p->ys.alloc((size_t)p->N); }
-        LSFC_HIP(hipMemcpyAsync(p->xs.p, x + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
-        xd[(size_t)r] = p->xs.p; yd[(size_t)r] = p->ys.p; off += p->N;
-    }
+    const SlabTeam T(root);
+    T.scatter(x, nullptr);
+    std::vector<const cplx*> xd; std::vector<cplx*> yd;
+    for (const RankSlab& s : T.slabs) { xd.push_back(s.p->xs.p); yd.push_back(s.p->ys.p); }
     multi_convolve_dev(root, xd.data(), yd.data(), op);
-    off = 0;
-    for (int r = 0; r < M.P; ++r) {
-        lsfc_plan* p = M.sub(r);
-        M.dev(r);
-        LSFC_HIP(hipMemcpyAsync(y + off, p->ys.p, (size_t)p->N * sizeof(cplx), hipMemcpyDeviceToHost, p->stream));
-        off += p->N;
-    }
-    for (int r = 0; r < M.P; ++r) { M.dev(r); LSFC_HIP(hipStreamSynchronize(M.st(r))); }
+    T.gather(y, true);
+    T.sync();
 }
 
 // sum over the ranks of `count` complex scalars held at dev[r] on devices[r]; the result replaces every copy
 void multi_allreduce_sum(lsfc_plan* root, cplx* const* dev, int count) {
-    Multi M(root);
-    if (M.P == 1) return;
-    if (M.ms->rccl) {
+    const Local L(root);
+    MultiState* ms = root->multi.get();
+    const int P = L.P;
+    auto st = [&](int r) { return L.stream(r, Lane::COMPUTE); };
+    if (P == 1) return;
+    if (ms->rccl) {
         LSFC_NCCL(ncclGroupStart());
-        for (int r = 0; r < M.P; ++r)
-            LSFC_NCCL(ncclAllReduce(dev[r], dev[r], (size_t)count * 2, ncclDouble, ncclSum, (ncclComm_t)M.ms->comm[(size_t)r], M.st(r)));
+        for (int r = 0; r < P; ++r)
+            LSFC_NCCL(ncclAllReduce(dev[r], dev[r], (size_t)count * 2, ncclDouble, ncclSum, (ncclComm_t)ms->comm[(size_t)r], st(r)));
         LSFC_NCCL(ncclGroupEnd());
         return;
     }
@@ -480,21 +434,21 @@ void multi_allreduce_sum(lsfc_plan* root, cplx* const* dev, int count) {
     // holds 256 scalars per rank, longer reductions (classical Gram-Schmidt with restart > 256) go in pieces
     if (count > 256) {
         for (int c0 = 0; c0 < count; c0 += 256) {
-            std::vector<cplx*> piece((size_t)M.P);
-            for (int r = 0; r < M.P; ++r) piece[(size_t)r] = dev[r] + c0;
+            std::vector<cplx*> piece((size_t)P);
+            for (int r = 0; r < P; ++r) piece[(size_t)r] = dev[r] + c0;
             multi_allreduce_sum(root, piece.data(), std::min(256, count - c0));
         }
         return;
     }
-    cplx* pin = M.ms->red_pin;
-    for (int r = 0; r < M.P; ++r) { M.dev(r); LSFC_HIP(hipMemcpyAsync(pin + (size_t)(r + 1) * 256, dev[r], (size_t)count * sizeof(cplx), hipMemcpyDeviceToHost, M.st(r))); }
-    for (int r = 0; r < M.P; ++r) { M.dev(r); LSFC_HIP(hipStreamSynchronize(M.st(r))); }
+    cplx* pin = ms->red_pin;
+    L.each([&](int r) { LSFC_HIP(hipMemcpyAsync(pin + (size_t)(r + 1) * 256, dev[r], (size_t)count * sizeof(cplx), hipMemcpyDeviceToHost, st(r))); });
+    L.each([&](int r) { LSFC_HIP(hipStreamSynchronize(st(r))); });
     for (int i = 0; i < count; ++i) {
         cplx acc = make_double2(0.0, 0.0);
-        for (int r = 0; r < M.P; ++r) { acc.x += pin[(size_t)(r + 1) * 256 + i].x; acc.y += pin[(size_t)(r + 1) * 256 + i].y; }
+        for (int r = 0; r < P; ++r) { acc.x += pin[(size_t)(r + 1) * 256 + i].x; acc.y += pin[(size_t)(r + 1) * 256 + i].y; }
         pin[i] = acc;
     }
-    for (int r = 0; r < M.P; ++r) { M.dev(r); LSFC_HIP(hipMemcpyAsync(dev[r], pin, (size_t)count * sizeof(cplx), hipMemcpyHostToDevice, M.st(r))); }
+    L.each([&](int r) { LSFC_HIP(hipMemcpyAsync(dev[r], pin, (size_t)count * sizeof(cplx), hipMemcpyHostToDevice, st(r))); });
     // (the next reduction rewrites the pinned scratch: it starts with copies INTO it that are stream-ordered behind these, and the
     // host only touches it after synchronising every rank's stream above)
 }
@@ -502,35 +456,28 @@ void multi_allreduce_sum(lsfc_plan* root, cplx* const* dev, int count) {
 // per-stage timing of one apply on the ranks' staging vectors: every stage runs on all ranks, un-overlapped, with a
 // device-wide synchronisation in between; the time of a stage is the slowest rank's
 void multi_profile(lsfc_plan* root, int reps, int max_stages, const char** names, double* ms, double* bytes, int* nstages) {
-    Multi M(root);
-    const int P = M.P, K = M.K;
-    const double N = (double)M.sub(0)->N, C = 16.0, om2 = root->omega * root->omega;
-    for (int r = 0; r < P; ++r) {
-        lsfc_plan* p = M.sub(r);
-        M.dev(r);
-        if (p->xs.n < (size_t)p->N) { p->xs.alloc((size_t)p->N); p->ys.alloc((size_t)p->N); LSFC_HIP(hipMemset(p->xs.p, 0, p->xs.bytes())); }
-    }
-    struct Stage { const char* name; double bytes; std::function<void()> run; };
-    std::vector<Stage> stages;
-    auto each = [&M, P](std::function<void(int)> f) { return [&M, P, f] { for (int r = 0; r < P; ++r) { M.dev(r); f(r); } }; };
-    stages.push_back({"xfwd", N * (C + 8) + 2 * N * C, each([&M](int r) { phase1(M.sub(r), M.sub(r)->xs.p, true, M.st(r)); })});
-    stages.push_back({"alltoall_in", 2 * N * C, [&M, K] { for (int c = 0; c < K; ++c) M.exchange(c, false, -1, 1); }});
-    stages.push_back({"yfwd", 6 * N * C, each([&M, K](int r) { for (int c = 0; c < K; ++c) phase2_yfwd(M.sub(r), c, M.st(r)); })});
-    stages.push_back({"zfused", 16 * N * C, each([&M, K](int r) { for (int c = 0; c < K; ++c) phase2_zfused(M.sub(r), c, M.st(r)); })});
-    stages.push_back({"yinv", 6 * N * C, each([&M, K](int r) { for (int c = 0; c < K; ++c) phase2_yinv(M.sub(r), c, M.st(r)); })});
-    stages.push_back({"alltoall_back", 2 * N * C, [&M, K] { for (int c = 0; c < K; ++c) M.exchange(c, true, -1, 1); }});
-    stages.push_back({"xinv", 4 * N * C, each([&M, om2](int r) { phase3(M.sub(r), M.sub(r)->xs.p, M.sub(r)->ys.p, 1.0, om2, M.st(r)); })});
+    const Local L(root);
+    const int P = L.P;
+    std::vector<const cplx*> xd; std::vector<cplx*> yd;
+    L.each([&](int r) {
+        lsfc_plan* p = L.plan[(size_t)r];
+        const bool fresh = p->xs.n < (size_t)p->N;
+        plan_ensure_staging(p, p->N);
+        if (fresh) LSFC_HIP(hipMemset(p->xs.p, 0, p->xs.bytes()));
+        xd.push_back(p->xs.p); yd.push_back(p->ys.p);
+    });
+    const std::vector<Stage> stages = apply_stages(L, xd, yd, true);
     LSFC_REQUIRE((int)stages.size() <= max_stages, "max_stages too small (need %d)", (int)stages.size());
     *nstages = (int)stages.size();
     std::vector<hipEvent_t> e0((size_t)P), e1((size_t)P);
-    for (int r = 0; r < P; ++r) { M.dev(r); LSFC_HIP(hipEventCreate(&e0[(size_t)r])); LSFC_HIP(hipEventCreate(&e1[(size_t)r])); }
+    L.each([&](int r) { LSFC_HIP(hipEventCreate(&e0[(size_t)r])); LSFC_HIP(hipEventCreate(&e1[(size_t)r])); });
     for (size_t i = 0; i < stages.size(); ++i) { names[i] = stages[i].name; bytes[i] = stages[i].bytes; ms[i] = 0.0; }
     for (int rep = 0; rep < reps; ++rep)
         for (size_t i = 0; i < stages.size(); ++i) {
             multi_synchronize(root);
-            for (int r = 0; r < P; ++r) { M.dev(r); LSFC_HIP(hipEventRecord(e0[(size_t)r], M.st(r))); }
+            L.each([&](int r) { LSFC_HIP(hipEventRecord(e0[(size_t)r], L.stream(r, Lane::COMPUTE))); });
             stages[i].run();
-            for (int r = 0; r < P; ++r) { M.dev(r); LSFC_HIP(hipEventRecord(e1[(size_t)r], M.st(r))); }
+            L.each([&](int r) { LSFC_HIP(hipEventRecord(e1[(size_t)r], L.stream(r, Lane::COMPUTE))); });
             multi_synchronize(root);
             float worst = 0;
             for (int r = 0; r < P; ++r) { float t = 0; LSFC_HIP(hipEventElapsedTime(&t, e0[(size_t)r], e1[(size_t)r])); worst = std::max(worst, t); }
@@ -671,7 +618,7 @@ int lsfc_dist_sim_apply(lsfc_plan** plans, int nranks, const double* const* x, d
         std::vector<const cplx*> xd((size_t)nranks); std::vector<cplx*> yd((size_t)nranks);
         for (int r = 0; r < nranks; ++r) {
             lsfc_plan* p = plans[r];
-            if (p->xs.n < (size_t)p->N) { p->xs.alloc((size_t)p->N); p->ys.alloc((size_t)p->N); }
+            plan_ensure_staging(p, p->N);
             LSFC_HIP(hipMemcpy(p->xs.p, x[r], (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice));
             xd[r] = p->xs.p; yd[r] = p->ys.p;
         }
@@ -681,13 +628,13 @@ int lsfc_dist_sim_apply(lsfc_plan** plans, int nranks, const double* const* x, d
         for (int c = 0; c < K; ++c) {
             // way in: block (q*K + c) of rank r's S1 -> slot r of chunk c of rank q's R1
             for (int r = 0; r < nranks; ++r) for (int q = 0; q < nranks; ++q)
-                LSFC_HIP(hipMemcpy(plans[q]->dist->R1.p + ((int64_t)c * nranks + r) * B, plans[r]->dist->S1.p + ((int64_t)q * K + c) * B,
+                LSFC_HIP(hipMemcpy(plans[q]->dist->R1.p + dsched::r1_slot(c, nranks, r, B), plans[r]->dist->S1.p + dsched::s1_block(q, K, c, B),
                                    (size_t)B * sizeof(cplx), hipMemcpyDeviceToDevice));
             for (int r = 0; r < nranks; ++r) phase2(plans[r], c, plans[r]->stream);
             sync_all();
             // way back: slot q of chunk c of rank r's R1 -> block (r*K + c) of rank q's S1
             for (int r = 0; r < nranks; ++r) for (int q = 0; q < nranks; ++q)
-                LSFC_HIP(hipMemcpy(plans[q]->dist->S1.p + ((int64_t)r * K + c) * B, plans[r]->dist->R1.p + ((int64_t)c * nranks + q) * B,
+                LSFC_HIP(hipMemcpy(plans[q]->dist->S1.p + dsched::s1_block(r, K, c, B), plans[r]->dist->R1.p + dsched::r1_slot(c, nranks, q, B),
                                    (size_t)B * sizeof(cplx), hipMemcpyDeviceToDevice));
         }
         for (int r = 0; r < nranks; ++r) {

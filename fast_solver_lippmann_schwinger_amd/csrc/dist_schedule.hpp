@@ -53,4 +53,76 @@ inline std::vector<Msg> exchange_messages(int rank, int P, int K, int c, bool ba
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// The overlapped apply as data: the steps of one apply for one rank, in the order they are enqueued.  Streams of a rank:
+// its compute stream, a second compute stream for the odd chunks (two_streams), one communication stream per direction.
+// The x pass runs in two z halves where `edges` (part 0 / 1, else -1: whole), so that the first exchange starts after half of it;
+// the way in of all chunks goes on IN; the y / z / y passes of chunk c run on the compute stream of its parity while the way back
+// of chunk c - 1 goes on BACK; the last exchange back is split the same way and hides half of the inverse x pass.
+// An event belongs to a rank.  A wait with `all` waits for that event of EVERY rank the process drives (one rank of a
+// multi-process job, where RCCL orders the remote side; all P of a multi-device plan, where a block has landed once its
+// source's event has fired); the others wait for the rank's own event.  BACK runs in order, so the event of the last
+// exchange back covers the earlier chunks.
+enum class Op { XFWD, EXCH_IN, PASSES, EXCH_BACK, XINV };
+enum class Lane { COMPUTE, COMPUTE2, IN, BACK };
+enum class Ev { NONE, P1A, P1, IN, DONE, BACKA, BACK };     // IN, DONE, BACK: one per chunk
+struct Wait { Ev ev; int c; bool all; };
+struct Step {
+    Op op; int c, part;             // chunk (exchanges, passes) and z half (x passes, exchanges; -1: whole)
+    Lane on;
+    std::vector<Wait> waits;
+    Ev rec; int rec_c;              // recorded behind the step (NONE: nothing)
+};
+inline bool is_exchange(Op op) { return op == Op::EXCH_IN || op == Op::EXCH_BACK; }
+
+inline std::vector<Step> pipeline_steps(int K, bool edges, bool two_streams) {
+    std::vector<Step> s;
+    if (edges) s.push_back({Op::XFWD, 0, 0, Lane::COMPUTE, {}, Ev::P1A, 0});
+    s.push_back({Op::XFWD, 0, edges ? 1 : -1, Lane::COMPUTE, {}, Ev::P1, 0});
+    // way in.  A block may only land on a rank once that rank's previous apply has drained (its R1 / S1 are re-used): the x pass
+    // of EVERY rank, which on each rank follows the previous apply's last pass
+    if (edges) s.push_back({Op::EXCH_IN, 0, 0, Lane::IN, {{Ev::P1A, 0, true}}, Ev::NONE, 0});
+    for (int c = 0; c < K; ++c) {
+        std::vector<Wait> w;
+        if (c == 0) w.push_back({Ev::P1, 0, true});
+        s.push_back({Op::EXCH_IN, c, (edges && c == 0) ? 1 : -1, Lane::IN, w, Ev::IN, c});
+    }
+    for (int c = 0; c < K; ++c) {
+        // (a chunk always runs on the stream of its parity, so its buffers -- A2 / R1 chunk c -- stay ordered from one apply to the next)
+        s.push_back({Op::PASSES, c, -1, ((c & 1) && two_streams) ? Lane::COMPUTE2 : Lane::COMPUTE, {{Ev::IN, c, true}}, Ev::DONE, c});
+        // (the S1 blocks the way back overwrites belong to chunk c, whose way in finished before IN[c]; P1: behind the previous
+        // apply's inverse x pass, which read them)
+        std::vector<Wait> w;
+        if (c == 0) w.push_back({Ev::P1, 0, true});
+        w.push_back({Ev::DONE, c, false});
+        if (edges && c == K - 1) {
+            s.push_back({Op::EXCH_BACK, c, 0, Lane::BACK, w, Ev::BACKA, 0});
+            s.push_back({Op::EXCH_BACK, c, 1, Lane::BACK, {}, Ev::BACK, c});
+        } else s.push_back({Op::EXCH_BACK, c, -1, Lane::BACK, w, Ev::BACK, c});
+    }
+    if (edges) s.push_back({Op::XINV, 0, 0, Lane::COMPUTE, {{Ev::BACKA, 0, true}}, Ev::NONE, 0});
+    s.push_back({Op::XINV, 0, edges ? 1 : -1, Lane::COMPUTE, {{Ev::BACK, K - 1, true}}, Ev::NONE, 0});
+    return s;
+}
+
+// Enqueues the steps for the nlocal ranks a process drives, step by step: the waits of every rank, the step itself -- an
+// exchange once for all ranks (one RCCL group, or source-issued copies), anything else rank by rank -- and the records.
+// Every record of a step is enqueued before any wait of a later one, which is what lets a stream wait for another rank's event.
+// Sink: begin(step), wait(r, lane, q, ev, c), run(r, step), exchange(step), record(r, lane, ev, c).
+template <class Sink> void issue(const std::vector<Step>& steps, int nlocal, Sink& sink) {
+    for (const Step& s : steps) {
+        sink.begin(s);
+        for (int r = 0; r < nlocal; ++r) {
+            for (const Wait& w : s.waits)
+                for (int q = w.all ? 0 : r; q < (w.all ? nlocal : r + 1); ++q) sink.wait(r, s.on, q, w.ev, w.c);
+            if (is_exchange(s.op)) continue;
+            sink.run(r, s);
+            if (s.rec != Ev::NONE) sink.record(r, s.on, s.rec, s.rec_c);
+        }
+        if (!is_exchange(s.op)) continue;
+        sink.exchange(s);
+        if (s.rec != Ev::NONE) for (int r = 0; r < nlocal; ++r) sink.record(r, s.on, s.rec, s.rec_c);
+    }
+}
+
 }} // namespace lsfc::dsched

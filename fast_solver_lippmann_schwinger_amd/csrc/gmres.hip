@@ -6,6 +6,7 @@
 // only O(restart) scalars per step cross to the host.
 #include "plan.hpp"
 #include "krylov_blas.hpp"
+#include "team.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <complex>
@@ -85,24 +86,27 @@ static void solve_least_squares(const std::vector<zc>& H, int ldh, double beta, 
     }
 }
 
-// The solver is written once over a TEAM of members, each holding one slab of every vector on its own device:
+// The solver is written once over a team of slabs (team.hpp), each holding one slab of every vector on its own device:
 //   one member   ordinary plans, and one rank of a multi-PROCESS slab plan (inner products completed by ncclAllReduce)
 //   P members    the ranks of a single-process multi-DEVICE plan, all driven from the calling thread
 // Every vector operation is enqueued member by member; the O(restart) scalars of a step are identical on all members
-// after the reduction and are read back from member 0.
+// after the reduction and are read back from member 0.  What GMRES adds to a slab: its workspace, x and b.
 namespace {
 struct Member { lsfc_plan* p; GmresWorkspace* w; cplx* x; const cplx* b; };
 struct Request;
 
 struct Team {
+    SlabTeam slabs;
     lsfc_plan* root;
-    std::vector<Member> mem;
+    std::vector<Member> mem;            // mem[i] works on slabs.slabs[i]
     bool reduce = false;                // local inner products are partial sums
     GmresWorkspace* rootw = nullptr;    // pinned host vector of the preconditioner callback
+    explicit Team(lsfc_plan* r) : slabs(r), root(r) {}
 
     static void dev(const Member& m) { LSFC_HIP(hipSetDevice(m.p->device)); }
     static cplx* V(const Member& m, int j) { return m.w->V.p + (size_t)j * (size_t)m.p->N; }
-    template <class F> void each(F&& f) { for (auto& m : mem) { dev(m); f(m); } }
+    // (one member: its device is made current every time, as a host callback of the caller may have left another one current)
+    template <class F> void each(F&& f) { if (!slabs.multi) dev(mem[0]); slabs.each([&](const RankSlab& s) { f(mem[(size_t)s.rank]); }); }
 
     void apply(const Request& q);
     void allreduce(int off, int count) {
@@ -141,10 +145,10 @@ struct Request {
 };
 
 void Team::apply(const Request& q) {
-    if (!root->multi) { dev(mem[0]); plan_apply_dev(root, q.in(mem[0]), q.out(mem[0])); return; }
     std::vector<const cplx*> xi; std::vector<cplx*> yo;
     for (auto& m : mem) { xi.push_back(q.in(m)); yo.push_back(q.out(m)); }
-    multi_convolve_dev(root, xi.data(), yo.data(), plan_operator(root));
+    if (!slabs.multi) dev(mem[0]);
+    slabs.apply(xi.data(), yo.data());
 }
 
 struct Resolved { lsfc_gmres_opts o; int restart; int64_t maxiter; double reltol, abstol; };
@@ -398,15 +402,7 @@ void precondition(Team& T, const Precond& pc, int col) {
         pc.apply(&v, 1, T.rootw->vpin, m.p->stream);
         return;
     }
-    // host callback, in place on the whole vector (the two-argument ldiv!): gather the slabs, call, scatter
-    cplx* vpin = T.rootw->vpin;
-    int64_t off = 0;
-    T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(vpin + off, Team::V(m, col), (size_t)m.p->N * sizeof(cplx), hipMemcpyDeviceToHost, m.p->stream)); off += m.p->N; });
-    T.sync();
-    const int rc = pc.fn(pc.user, (double*)vpin, T.root->N);
-    if (rc != 0) fail(LSFC_EINVAL, "preconditioner callback returned %d", rc);
-    off = 0;
-    T.each([&](Member& m) { LSFC_HIP(hipMemcpyAsync(Team::V(m, col), vpin + off, (size_t)m.p->N * sizeof(cplx), hipMemcpyHostToDevice, m.p->stream)); off += m.p->N; });
+    T.slabs.host_precond(pc, T.rootw->vpin, [&](const RankSlab& s) { return Team::V(T.mem[(size_t)s.rank], col); });
 }
 
 // one solve over a team
@@ -430,7 +426,7 @@ void solve(Team& T, const Resolved& r, double* resnorm, int64_t cap, lsfc_gmres_
 
 void gmres_run(lsfc_plan* p, cplx* x, const cplx* b, const lsfc_gmres_opts* opts_in, double* resnorm, int64_t cap, lsfc_gmres_result* res) {
     const Resolved r = resolve(opts_in, p->N);
-    Team T; T.root = p;
+    Team T(p);
     GmresWorkspace* w = workspace(p, r.restart, r.o.precond != nullptr && !r.o.precond_on_device);
     T.mem.push_back({p, w, x, b});
     T.rootw = w;
@@ -462,13 +458,12 @@ void gmres_run_batch(lsfc_plan* p, cplx* x, const cplx* b, int nrhs, const lsfc_
     std::vector<std::unique_ptr<GmresWorkspace>> ws;
     for (int j = 0; j < nrhs; ++j) ws.push_back(new_workspace(p->N, r.restart, pc.fn && !pc.on_device && j == 0));      // (one pinned vector serves every member's callback)
     LSFC_HIP(hipStreamSynchronize(p->stream));
-    std::vector<Team> teams((size_t)nrhs);
+    std::vector<Team> teams((size_t)nrhs, Team(p));
     std::vector<Solve> S;
     S.reserve((size_t)nrhs);
     std::vector<Solve*> act;
     for (int j = 0; j < nrhs; ++j) {
         Team& T = teams[(size_t)j];
-        T.root = p;
         T.mem.push_back({p, ws[(size_t)j].get(), x + (int64_t)j * p->N, b + (int64_t)j * p->N});
         S.emplace_back(T, r, resnorm ? resnorm + (int64_t)j * cap : nullptr, cap, res + j, true);
         act.push_back(&S.back());
@@ -504,27 +499,13 @@ void gmres_run_multi(lsfc_plan* root, cplx* x_host, const cplx* b_host, const ls
     LSFC_REQUIRE(root->multi, "not a multi-device plan");
     const Resolved r = resolve(opts_in, root->N);
     LSFC_REQUIRE(!(r.o.precond && r.o.precond_on_device), "a multi-device plan takes a host preconditioner callback");
-    Team T; T.root = root;
+    Team T(root);
     T.rootw = workspace(root, r.restart, r.o.precond != nullptr, false);
     T.reduce = root->multi->P > 1;
-    int64_t off = 0;
-    for (auto& sp : root->multi->sub) {
-        lsfc_plan* p = sp.get();
-        LSFC_HIP(hipSetDevice(p->device));
-        GmresWorkspace* w = workspace(p, r.restart, false);
-        plan_ensure_staging(p, p->N);
-        LSFC_HIP(hipMemcpyAsync(p->xs.p, x_host + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
-        LSFC_HIP(hipMemcpyAsync(p->ys.p, b_host + off, (size_t)p->N * sizeof(cplx), hipMemcpyHostToDevice, p->stream));
-        T.mem.push_back({p, w, p->xs.p, p->ys.p});
-        off += p->N;
-    }
+    T.slabs.scatter(x_host, b_host);
+    T.slabs.each([&](const RankSlab& s) { T.mem.push_back({s.p, workspace(s.p, r.restart, false), s.p->xs.p, s.p->ys.p}); });
     solve(T, r, resnorm, cap, res);
-    off = 0;
-    for (auto& m : T.mem) {
-        Team::dev(m);
-        LSFC_HIP(hipMemcpyAsync(x_host + off, m.x, (size_t)m.p->N * sizeof(cplx), hipMemcpyDeviceToHost, m.p->stream));
-        off += m.p->N;
-    }
+    T.slabs.gather(x_host);
     T.sync();
     LSFC_HIP(hipSetDevice(root->device));
 }

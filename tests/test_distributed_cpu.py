@@ -167,6 +167,22 @@ def test_exchange_schedule_for_2_4_8_ranks(tmp_path):
     assert r.returncode == 0 and b"failures: 0" in r.stdout, r.stdout.decode()[-2000:]
 
 
+def test_pipeline_schedule_two_applies(tmp_path):
+    # the stream and event schedule dist.hip executes (pipeline_steps and issue of csrc/dist_schedule.hpp) for P = 1, 2, 4 local
+    # ranks, K = 1, 2, 4, split ends or not, one and two compute streams, two applies back to back, streams as in-order queues:
+    # no wait ahead of its record, no wait cycle, every read of an S1 block, an R1 slot or an A2 chunk behind the write that
+    # produced it, every overwrite behind the previous apply's reads -- and five broken schedules refused.  The header alone,
+    # with the host compiler, warnings as errors
+    import subprocess
+    exe = str(tmp_path / "dsched")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tests", "emu", "dist_schedule_test.cpp")],
+                       capture_output=True)
+    assert r.returncode == 0, r.stderr.decode()
+    r = subprocess.run([exe], capture_output=True, timeout=300)
+    out = r.stdout.decode()
+    assert r.returncode == 0 and "pipeline schedules checked: 36, failures: 0" in out, out[-2000:]
+
+
 def test_slab_range():
     assert slab_range(512, 3, 8) == (192, 256)
     with pytest.raises(ValueError):

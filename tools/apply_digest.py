@@ -16,6 +16,11 @@ The applies (seeded inputs; device vectors unless "host" is said):
                        x, y and z, 2D along y (the fused axis), 16 points along the other axes -- on random even symbols: M * b, the
                        bare convolution and describe_passes under the default tuning and under z_persist = 3, 5, 6; apply_batch of
                        three right-hand sides under the default tuning
+  slab plans           MultiDeviceFastM3D with a device listed several times -- 64 x 16 x 16 on [0]*4 (K = 4) under LSFC_DIST_OVERLAP
+                       1 / 0, LSFC_DIST_SPLIT_EDGES 1 / 0 and LSFC_DIST_COMPUTE_STREAMS 1 / 2, 16 x 16 x 12 on [0]*4 (three planes per
+                       rank: no split of the pipeline ends), 32 x 16 x 16 on [0]*8 --, SimulatedRanks with two ranks, and
+                       build_distributed_3d with one rank, sequential and under LSFC_DIST_FORCE_OVERLAP=1 LSFC_DIST_CHUNKS=4:
+                       M * b and the bare convolution, host vectors and device slabs
 
     python tools/apply_digest.py                                    one JSON line per apply, this tree's library
     python tools/apply_digest.py --libs parent=/path/to/liblsfc.so,this= [--out profiles/plan_split_refactor.jsonl]
@@ -34,7 +39,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-ENV = ("LSFC_2D_TILED", "LSFC_HOST_PIPELINE", "LSFC_BATCH_FUSE", "LSFC_HOST_COPY")
+ENV = ("LSFC_2D_TILED", "LSFC_HOST_PIPELINE", "LSFC_BATCH_FUSE", "LSFC_HOST_COPY", "LSFC_DIST_OVERLAP", "LSFC_DIST_SPLIT_EDGES",
+       "LSFC_DIST_COMPUTE_STREAMS", "LSFC_DIST_CHUNKS", "LSFC_DIST_FORCE_OVERLAP", "LSFC_DIST_FORCE_COMM", "LSFC_MULTI_TRANSPORT")
 
 
 def emit(label, a):
@@ -160,6 +166,58 @@ def child():
                 emit(f"{label} z_persist={zp} M*b", M * b)
                 emit(f"{label} z_persist={zp} convolution", conv(M, b))
             M.close()
+
+
+    # slab plans: the ranks of one process (a device listed several times), simulated ranks, one rank of a multi-process plan
+    from fast_solver_lippmann_schwinger_amd.distributed import MultiDeviceFastM3D, SimulatedRanks, build_distributed_3d
+
+    def slab_applies(label, dims, devices):
+        n, m, l = dims
+        N, P = n * m * l, len(devices)
+        M = MultiDeviceFastM3D(n, 1.0 / n, 9.0, rng.uniform(-0.3, 0.3, N), devices=devices, m=m, l=l)
+        b = vec(N)
+        emit(f"{label} host M*b", M * b)
+        emit(f"{label} host convolution", lsfc.FFTconvolution(M, b))
+        xs = [torch.from_numpy(np.ascontiguousarray(s)).cuda() for s in np.split(b, P)]
+        ys = [torch.empty_like(x) for x in xs]
+        for mode, what in ((0, "M*b"), (1, "convolution")):
+            for _ in range(2):                             # back to back: the buffers of the first apply are re-used
+                M.apply_dev(xs, ys, mode)
+            M.synchronize()
+            emit(f"{label} device slabs {what}", torch.cat(ys))
+        M.close()
+
+    for overlap in ("1", "0"):
+        for edges in ("1", "0"):
+            for streams in ("1", "2"):
+                os.environ.update(LSFC_DIST_OVERLAP=overlap, LSFC_DIST_SPLIT_EDGES=edges, LSFC_DIST_COMPUTE_STREAMS=streams)
+                slab_applies(f"multi 64x16x16 [0]*4 overlap={overlap} edges={edges} streams={streams}", (64, 16, 16), [0] * 4)
+    for k in ("LSFC_DIST_OVERLAP", "LSFC_DIST_SPLIT_EDGES", "LSFC_DIST_COMPUTE_STREAMS"):
+        os.environ.pop(k)
+    slab_applies("multi 16x16x12 [0]*4", (16, 16, 12), [0] * 4)
+    slab_applies("multi 32x16x16 [0]*8", (32, 16, 16), [0] * 8)
+
+    n, m, l = 32, 16, 16
+    nu, b = rng.uniform(-0.3, 0.3, n * m * l), vec(n * m * l)
+    S = SimulatedRanks(n, m, l, 1.0 / n, 9.0, nu, 2)
+    emit("SimulatedRanks 32x16x16 P=2 M*b", S.apply(b))
+    emit("SimulatedRanks 32x16x16 P=2 convolution", S.convolve(b))
+    S.close()
+    for label, env in (("sequential", {}), ("LSFC_DIST_FORCE_OVERLAP=1 LSFC_DIST_CHUNKS=4", {"LSFC_DIST_FORCE_OVERLAP": "1", "LSFC_DIST_CHUNKS": "4"})):
+        os.environ.update(env)
+        M = build_distributed_3d(n, 1.0 / n, 9.0, nu, 0, 1, 0, m=m, l=l)
+        emit(f"build_distributed_3d one rank {label} host M*b", M * b)
+        emit(f"build_distributed_3d one rank {label} host convolution", lsfc.FFTconvolution(M, b))
+        xb = torch.from_numpy(b).cuda()
+        yb = torch.empty_like(xb)
+        for _ in range(2):
+            M.mul_(yb, xb)
+        M.synchronize()
+        emit(f"build_distributed_3d one rank {label} device M*b", yb)
+        emit(f"build_distributed_3d one rank {label} device convolution", lsfc.FFTconvolution(M, xb))
+        M.close()
+        for k in env:
+            os.environ.pop(k)
 
 
 def main():

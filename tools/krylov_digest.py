@@ -8,6 +8,7 @@ identity plan and the preconditioner diag(lambda), so only the reductions see th
   gmres_            N = 1025, restart 5, 64, 65, 100: blocked MGS, CGS (block remainders, the 64-column boundary of the
                     fused CGS sweep, the chunked x += V y)
   gmres_            four ranks on one device (MultiDeviceFastM3D 16 x 22 x 36, restart 65): MGS, CGS, DGKS, unfused and all-reduced
+  bicgstabl_multi_  the same four ranks, l = 1, 2, with and without the host callback (the rank sums and the gather / scatter)
   gmres_batch_      the three right-hand sides of test_batch_equals_single_solves_bitwise: MGS, CGS, DGKS
   bicgstabl_        N = 4097, l = 1, 2, 4, 8;  bicgstabl_batch_ with three members at l = 2
   symmetry_defect   a 16^3 plan (blas_dot / blas_nrm2 called directly)
@@ -88,6 +89,10 @@ def child():
     for orth in ORTH:
         x, h = lsfc.gmres_(np.zeros(N, complex), M, b, Pl=scale, restart=65, maxiter=100, log=True, orth_meth=ORTH[orth])
         emit(f"gmres four ranks on one device restart=65 {orth}", x, [h])
+    for l_ in (1, 2):
+        for name, Pl in (("no callback", None), ("host callback", scale)):
+            x, h = lsfc.bicgstabl_multi_(np.zeros(N, complex), M, b, l=l_, Pl=Pl, max_mv_products=60, log=True)
+            emit(f"bicgstabl_multi four ranks on one device l={l_} {name}", x, [h])
     M.close()
 
     N = 4097
