@@ -40,6 +40,11 @@ def main(n=48):
     res = np.linalg.norm(fastconv * u - rhs) / np.linalg.norm(rhs)
     print(f"true relative residual {res:.3e}")
     U = (u + u_inc).reshape((n, n, n), order="F")   # :85, total field
+    # beyond the reference, which stops at the field on the grid: the far-field pattern -k^2 R_far (nu .* u_total) in six directions
+    theta = np.array([[1.0, 0, 0], [-1.0, 0, 0], [0, 1.0, 0], [0, -1.0, 0], [0, 0, 1.0], [0, 0, -1.0]])
+    pattern = ls.Receivers(x, y, z, k=k, directions=theta).scattered_field(fastconv, u + u_inc)
+    for t, a in zip(theta, pattern):
+        print(f"far field in direction {t}: {a.real:+.6e} {a.imag:+.6e}i  (|.| = {abs(a):.6e})")
     return U, info
 
 

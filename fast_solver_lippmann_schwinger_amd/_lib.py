@@ -19,6 +19,7 @@ LSFC_ORTH_MGS, LSFC_ORTH_CGS, LSFC_ORTH_DGKS = 0, 1, 2
 LSFC_EINVAL, LSFC_ENODEV, LSFC_ENOMEM, LSFC_ENOTCONV = -1, -2, -3, -5
 LSFC_UNIQUE_ID_BYTES = 128
 LSFC_OP_N, LSFC_OP_T, LSFC_OP_H = 0, 1, 2
+LSFC_RECV_POINTS, LSFC_RECV_FARFIELD = 0, 1
 # how a member of lsfc_bicgstabl_batch ended (status[2 j]); 2..7: the scalar of a breakdown
 (LSFC_BICG_CONVERGED, LSFC_BICG_MAX_MV, LSFC_BICG_RHO, LSFC_BICG_SIGMA, LSFC_BICG_BETA, LSFC_BICG_ALPHA, LSFC_BICG_GAMMA,
  LSFC_BICG_RESIDUAL) = range(8)
@@ -102,6 +103,11 @@ SIGNATURES = {
     "lsfc_precond_inverse_precision": (_I, [_P, C.POINTER(_I)]),
     "lsfc_precond_blocktri_info": (_I, [_P, C.POINTER(_L), C.POINTER(_D)]),
     "lsfc_precond_blocktri_get_block": (_I, [_P, _L, _P, _L]),
+    "lsfc_receivers_create": (_I, [_PP, _I, C.POINTER(_L), C.POINTER(_D), _D, _D, _I, _P, _L, _I]),
+    "lsfc_receivers_destroy": (_I, [_P]),
+    "lsfc_receivers_set_stream": (_I, [_P, _P]),
+    "lsfc_receivers_apply": (_I, [_P, _P, _P, _P, _L, _I, _I]),
+    "lsfc_receivers_info": (_I, [_P, C.POINTER(_L)]),
     "lsfc_sparsify_pattern": (_I, [_L, _L, _L, C.POINTER(_L), _P, _P, _P]),
     "lsfc_sparsify_build": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_plan_set_stream": (_I, [_P, _P]),

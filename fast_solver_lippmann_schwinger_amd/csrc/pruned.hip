@@ -8,7 +8,7 @@
 
 namespace lsfc {
 
-void warmup_pointwise(); void warmup_krylov_blas(); void warmup_symbol(); void warmup_precond(); void warmup_trisolve(); void warmup_blocktri();      // pointwise.hip, krylov_blas.hip, symbol.hip, precond.hip, trisolve.hip, blocktri.hip
+void warmup_pointwise(); void warmup_krylov_blas(); void warmup_symbol(); void warmup_precond(); void warmup_trisolve(); void warmup_blocktri(); void warmup_receivers();      // pointwise.hip, krylov_blas.hip, symbol.hip, precond.hip, trisolve.hip, blocktri.hip, receivers.hip
 extern const PrunedFamily pruned_family_f2, pruned_family_f3, pruned_family_f5;     // fft_kernels.hip, one per compilation
 
 // 2: L = 2^k (32..2048);  3: L = 3 * 2^k (48..1536);  5: L = 5 * 2^k (80..1280);  0: not supported
@@ -38,7 +38,7 @@ void pruned_warmup(int device) {
     // LSFC_EAGER_LOAD=0 (developer switch, diagnostics only): leave the code objects to HIP's lazy loading at first launch
     if (const char* e = getenv("LSFC_EAGER_LOAD")) if (e[0] == '0') return;
     pruned_family_f2.warmup(); pruned_family_f3.warmup(); pruned_family_f5.warmup();
-    warmup_pointwise(); warmup_krylov_blas(); warmup_symbol(); warmup_precond(); warmup_trisolve(); warmup_blocktri();
+    warmup_pointwise(); warmup_krylov_blas(); warmup_symbol(); warmup_precond(); warmup_trisolve(); warmup_blocktri(); warmup_receivers();
     LSFC_HIP(hipDeviceSynchronize());
     done.insert(device);
 }

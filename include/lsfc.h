@@ -542,6 +542,56 @@ int lsfc_sparsify_pattern(int64_t n, int64_t m, int64_t l, int64_t* nnz, int64_t
 int lsfc_sparsify_build(lsfc_plan* plan, int64_t* rowptr, int64_t* col, double* As_val, double* AG_val,
                         double* Msp_val, double* sigma, int memspace);
 
+/* ---- off-grid sources and receivers ------------------------------------------- */
+
+/* The reference's drivers build the incident field on the host and stop at the total field on the grid
+ * (examples/example3D.jl:46-50, :78-81; examples/example.jl:40-44, :85-99).  lsfc_receivers is what comes before and after:
+ * the dense nrecv x N sampling operator R between grid vectors and nrecv receivers off the grid, never stored, with its
+ * transpose and its adjoint.  Grid: dims = (n, m[, l]) points x_i = origin + h (ix, iy[, iz]), x fastest; k > 0 real.  The
+ * rows are the reference's free-space Green's function weighted by h^d (src/FastConvolution3D.jl:188,
+ * src/FastConvolution.jl:268), or its far-field limit:
+ *     LSFC_RECV_POINTS    3D   R[r,i] = h^3 e^{ik|p_r - x_i|} / (4 pi |p_r - x_i|)            coords: nrecv points p_r
+ *                         2D   R[r,i] = h^2 (i/4) (J0 + i Y0)(k |p_r - x_i|)
+ *     LSFC_RECV_FARFIELD  3D   R[r,i] = (h^3 / 4 pi) e^{-ik theta_r . x_i}                   coords: nrecv unit vectors theta_r
+ *                         2D   R[r,i] = h^2 e^{i pi/4} / sqrt(8 pi k)  e^{-ik theta_r . x_i}
+ * so that R_points(rho theta) q -> e^{ik rho} / rho^((d-1)/2) R_far(theta) q as rho -> infinity.
+ * lsfc_receivers_apply works on nrhs vectors stored back to back:
+ *     LSFC_OP_N   out_j[r] = sum_i R[r,i] in_j[i]             in: nrhs * N,      out: nrhs * nrecv
+ *     LSFC_OP_T   out_j[i] = sum_r R[r,i] in_j[r]             in: nrhs * nrecv,  out: nrhs * N      (the field of point sources)
+ *     LSFC_OP_H   out_j[i] = sum_r conj(R[r,i]) in_j[r]                                             (far field: plane waves)
+ * `out` must not alias `in`.  With a plan the medium is fused into the operation: N becomes -omega^2 R (nu .* u), the
+ * scattered field at the receivers for the total field u; T becomes -omega^2 nu .* (R^T w) and H becomes
+ * -omega^2 conj(nu) .* (R^H w) -- the conjugation is outermost, the rule of lsfc_plan_set_op.  nu and omega are the plan's
+ * (real or complex nu, read on the device at the time the kernels run); the plan's op is neither read nor changed.
+ * Sums: a receiver's sum over the grid is the two-stage fixed-order reduction the Krylov kernels use, a grid point's sum over
+ * the receivers runs r = 0 .. nrecv-1.  Two applies of the same input give the same bits, and the bits of one receiver's
+ * (grid point's) or one member's result do not depend on nrecv, on nrhs, on its place among the others or on what they hold.
+ * Members go through the kernels in groups of up to 8; the kernel function is evaluated once per (point, receiver) and group.
+ * Work buffers (block partials, staging of host vectors) belong to the object and grow on first use: do not apply one object
+ * from two streams or threads at once.  LSFC_MEM_DEVICE: stream-ordered on the object's stream (lsfc_receivers_set_stream,
+ * NULL = the legacy default stream), returns without synchronising.  LSFC_MEM_HOST: staged through device memory, synchronises.
+ * LSFC_EINVAL, before any device call, lsfc_last_error names the cause: a NULL argument; ndim not 2 or 3; a dimension < 1 (or
+ * 2^31 grid points and more); h <= 0 or k <= 0; nrecv < 1; nrhs < 1; an unknown kind, op or memspace; a far-field direction
+ * whose norm differs from 1 by more than 1e-12; a point receiver closer than 1e-8 h to a grid point (the nearest grid point
+ * is found by rounding; the message names the receiver's index); a plan whose lsfc_plan_size is not N or whose device differs;
+ * a distributed, simulated-rank or multi-device plan ("not available on ...").
+ * Out of scope: multi-device and multi-process plans; receivers on grid points (the kernel is singular there); quadrature
+ * corrections for receivers inside the support of nu -- the sum is the plain trapezoidal rule, spectrally accurate for
+ * receivers at a distance from a smooth, compactly supported nu; NUFFT-accelerated evaluation; gradient assembly. */
+typedef struct lsfc_receivers lsfc_receivers;
+#define LSFC_RECV_POINTS   0
+#define LSFC_RECV_FARFIELD 1
+/* coords: nrecv * ndim doubles on the host (copied) */
+int lsfc_receivers_create(lsfc_receivers** out, int ndim, const int64_t dims[3], const double origin[3], double h, double k,
+                          int kind, const double* coords, int64_t nrecv, int device);
+int lsfc_receivers_destroy(lsfc_receivers* rc);
+int lsfc_receivers_set_stream(lsfc_receivers* rc, void* hip_stream);
+/* op: LSFC_OP_N | LSFC_OP_T | LSFC_OP_H; plan may be NULL */
+int lsfc_receivers_apply(lsfc_receivers* rc, lsfc_plan* plan, const double* in, double* out, int64_t nrhs, int op, int memspace);
+/* out: N, nrecv, receivers per thread of the forward kernel, receivers per LDS chunk of the T / H kernel, members per group,
+ * bytes of the tables (receiver coordinates, or the nrecv (n + m + l) complex far-field factors) */
+int lsfc_receivers_info(const lsfc_receivers* rc, int64_t out[6]);
+
 /* ---- streams, timing, profiling ------------------------------------------ */
 
 /* Run the plan on a caller-owned hipStream_t (NULL = the legacy default stream). */

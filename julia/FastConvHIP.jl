@@ -552,4 +552,70 @@ function bicgstabl_batch_hip!(X::Matrix{Complex{Float64}}, V::FastMHIPView, B::M
     _solve_with_ops(P -> _with_op(M -> bicgstabl_batch_hip!(X, M, B, l; Pl=P, kw...), V), V, Pl)
 end
 
+# Off-grid sources and receivers -- lsfc_receivers_* (include/lsfc.h): the dense nrecv x N sampling operator R between grid
+# vectors and point receivers (points = ...) or far-field directions (directions = ...), never stored.  The reference's drivers
+# build u_inc on the host and stop at the total field on the grid (examples/example3D.jl:46-50, :78-81); R * q, transpose(R) * w
+# and R' * w are what comes after and before.  x, y[, z]: the axis vectors given to buildFastConvolution[3D]; coordinates: one
+# receiver per COLUMN (ndim x nrecv, which is nrecv * ndim doubles receiver after receiver, as the C ABI takes them).
+# scattered_field(R, M, u) = -omega^2 R (nu .* u) for the total field u, with the medium of M fused into the kernel.
+# NOTE: like the rest of this binding this section is written against include/lsfc.h and has not been executed (no Julia
+# toolchain where the library is built and tested).
+const RECV_POINTS = Cint(0); const RECV_FARFIELD = Cint(1)
+mutable struct ReceiversHIP
+    rc::Ptr{Cvoid}
+    N::Int64
+    nrecv::Int64
+    function ReceiversHIP(rc, N, nrecv)
+        R = new(rc, N, nrecv)
+        finalizer(R -> ccall((:lsfc_receivers_destroy, liblsfc), Cint, (Ptr{Cvoid},), R.rc), R)
+        return R
+    end
+end
+function Receivers(x, y, z=nothing; k, points=nothing, directions=nothing, device=0)
+    (points === nothing) != (directions === nothing) || throw(ArgumentError("give exactly one of points and directions"))
+    axes = z === nothing ? (x, y) : (x, y, z)
+    ndim = length(axes)
+    h = Float64(x[2] - x[1])
+    dims = Int64[length(a) for a in axes]; append!(dims, ones(Int64, 3 - ndim))
+    origin = Float64[a[1] for a in axes]; append!(origin, zeros(3 - ndim))
+    coords = Matrix{Float64}(points === nothing ? directions : points)
+    size(coords, 1) == ndim || throw(DimensionMismatch("coordinates: one receiver per column, $ndim rows"))
+    rc = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:lsfc_receivers_create, liblsfc), Cint,
+                (Ref{Ptr{Cvoid}}, Cint, Ptr{Int64}, Ptr{Float64}, Float64, Float64, Cint, Ptr{Float64}, Int64, Cint),
+                rc, ndim, dims, origin, h, Float64(k), points === nothing ? RECV_FARFIELD : RECV_POINTS, coords, size(coords, 2), device))
+    return ReceiversHIP(rc[], prod(dims), size(coords, 2))
+end
+struct TransposeReceiversHIP; parent::ReceiversHIP; end
+struct AdjointReceiversHIP; parent::ReceiversHIP; end
+_op(::TransposeReceiversHIP) = OP_T
+_op(::AdjointReceiversHIP) = OP_H
+LinearAlgebra.transpose(R::ReceiversHIP) = TransposeReceiversHIP(R)
+LinearAlgebra.adjoint(R::ReceiversHIP) = AdjointReceiversHIP(R)
+Base.size(R::ReceiversHIP) = (R.nrecv, R.N)
+Base.size(V::Union{TransposeReceiversHIP,AdjointReceiversHIP}) = (V.parent.N, V.parent.nrecv)
+Base.eltype(::Union{ReceiversHIP,TransposeReceiversHIP,AdjointReceiversHIP}) = Complex{Float64}
+function receivers_info(R::ReceiversHIP)       # N, nrecv, receivers per thread, receivers per LDS chunk, members per group, table bytes
+    out = zeros(Int64, 6)
+    check(ccall((:lsfc_receivers_info, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Int64}), R.rc, out))
+    return out
+end
+# columns of B through R (op N), transpose(R) or R'; plan: C_NULL, or the plan whose medium is fused in
+function _receivers_apply!(Y::VecOrMat{Complex{Float64}}, R::ReceiversHIP, plan::Ptr{Cvoid}, B::VecOrMat{Complex{Float64}}, op::Cint)
+    nin, nout = op == OP_N ? (R.N, R.nrecv) : (R.nrecv, R.N)
+    (size(B, 1) == nin && size(Y, 1) == nout && size(B, 2) == size(Y, 2)) || throw(DimensionMismatch("receivers apply"))
+    check(ccall((:lsfc_receivers_apply, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Complex{Float64}}, Ptr{Complex{Float64}}, Int64, Cint, Cint),
+                R.rc, plan, B, Y, size(B, 2), op, 0))
+    return Y
+end
+_out(R::ReceiversHIP, B, op) = zeros(Complex{Float64}, op == OP_N ? R.nrecv : R.N, size(B)[2:end]...)
+*(R::ReceiversHIP, q::VecOrMat{Complex{Float64}}) = _receivers_apply!(_out(R, q, OP_N), R, C_NULL, q, OP_N)
+*(V::Union{TransposeReceiversHIP,AdjointReceiversHIP}, w::VecOrMat{Complex{Float64}}) = _receivers_apply!(_out(V.parent, w, _op(V)), V.parent, C_NULL, w, _op(V))
+LinearAlgebra.mul!(Y::VecOrMat{Complex{Float64}}, R::ReceiversHIP, q::VecOrMat{Complex{Float64}}) = _receivers_apply!(Y, R, C_NULL, q, OP_N)
+LinearAlgebra.mul!(Y::VecOrMat{Complex{Float64}}, V::Union{TransposeReceiversHIP,AdjointReceiversHIP}, w::VecOrMat{Complex{Float64}}) =
+    _receivers_apply!(Y, V.parent, C_NULL, w, _op(V))
+scattered_field(R::ReceiversHIP, M::FastMHIP, u::VecOrMat{Complex{Float64}}) = _receivers_apply!(_out(R, u, OP_N), R, M.plan, u, OP_N)
+adjoint_source(R::ReceiversHIP, M::FastMHIP, w::VecOrMat{Complex{Float64}}) = _receivers_apply!(_out(R, w, OP_H), R, M.plan, w, OP_H)
+receivers_set_stream(R::ReceiversHIP, stream::Ptr{Cvoid}) = check(ccall((:lsfc_receivers_set_stream, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), R.rc, stream))
+
 end # module
