@@ -20,6 +20,8 @@ LSFC_EINVAL, LSFC_ENODEV, LSFC_ENOMEM, LSFC_ENOTCONV = -1, -2, -3, -5
 LSFC_UNIQUE_ID_BYTES = 128
 LSFC_OP_N, LSFC_OP_T, LSFC_OP_H = 0, 1, 2
 LSFC_RECV_POINTS, LSFC_RECV_FARFIELD = 0, 1
+LSFC_BORN_ACCUMULATE, LSFC_BORN_REAL = 1, 2
+LSFC_BORN_GMRES, LSFC_BORN_BICGSTABL = 0, 1
 # how a member of lsfc_bicgstabl_batch ended (status[2 j]); 2..7: the scalar of a breakdown
 (LSFC_BICG_CONVERGED, LSFC_BICG_MAX_MV, LSFC_BICG_RHO, LSFC_BICG_SIGMA, LSFC_BICG_BETA, LSFC_BICG_ALPHA, LSFC_BICG_GAMMA,
  LSFC_BICG_RESIDUAL) = range(8)
@@ -45,6 +47,11 @@ class BicgstablOpts(C.Structure):                  # lsfc_bicgstabl_opts
 
 class BlocktriOpts(C.Structure):                   # lsfc_blocktri_opts
     _fields_ = [("inverse_precision", C.c_int), ("pivoting", C.c_int), ("reserved", C.c_int * 6)]
+
+
+class BornOpts(C.Structure):                       # lsfc_born_opts
+    _fields_ = [("solver", C.c_int), ("restart", C.c_int), ("l", C.c_int), ("maxiter", C.c_int64), ("reltol", C.c_double),
+                ("abstol", C.c_double), ("precond", C.c_void_p), ("chunk", C.c_int64), ("reserved", C.c_int * 6)]
 
 
 class LsfcError(RuntimeError):
@@ -108,6 +115,15 @@ SIGNATURES = {
     "lsfc_receivers_set_stream": (_I, [_P, _P]),
     "lsfc_receivers_apply": (_I, [_P, _P, _P, _P, _L, _I, _I]),
     "lsfc_receivers_info": (_I, [_P, C.POINTER(_L)]),
+    "lsfc_born_scale": (_I, [_P, _P, _I, _P, _P, _L, _I]),
+    "lsfc_born_image": (_I, [_P, _P, _P, _L, _D, _D, _U, _P, _I]),
+    "lsfc_born_create": (_I, [_PP, _P, _P, C.POINTER(BornOpts)]),
+    "lsfc_born_destroy": (_I, [_P]),
+    "lsfc_born_set_background": (_I, [_P, _P, _L, _I]),
+    "lsfc_born_fields": (_I, [_P, _PP, C.POINTER(_L)]),
+    "lsfc_born_data": (_I, [_P, _P, _I]),
+    "lsfc_born_apply": (_I, [_P, _P, _I, _P, _I, _U, _I]),
+    "lsfc_born_info": (_I, [_P, C.POINTER(_L), C.POINTER(GmresResult)]),
     "lsfc_sparsify_pattern": (_I, [_L, _L, _L, C.POINTER(_L), _P, _P, _P]),
     "lsfc_sparsify_build": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_plan_set_stream": (_I, [_P, _P]),

@@ -315,6 +315,8 @@ void warmup_receivers() {
     LSFC_HIP(hipGetLastError());
 }
 
+int receivers_device(const lsfc_receivers* rc) { return rc->device; }
+
 } // namespace lsfc
 
 using namespace lsfc;

@@ -10,5 +10,7 @@ static constexpr int RECV_PASS = 256;    // receivers of one forward launch (bou
 
 // loads this translation unit's code object on the current device (pruned.hip: pruned_warmup)
 void warmup_receivers();
+// the device an object lives on (born.hip checks it against the plan's)
+int receivers_device(const lsfc_receivers* rc);
 
 } // namespace lsfc

@@ -41,6 +41,10 @@ __device__ __forceinline__ cplx csubmul(cplx a, cplx c, cplx b) {
 __device__ __forceinline__ cplx caddmul(cplx a, cplx c, cplx b) {
     return make_double2(a.x + fma(c.x, b.x, -c.y * b.y), a.y + fma(c.x, b.y, c.y * b.x));
 }
+// a * b (born.hip: the pointwise products of the linearised scattering kernels)
+__device__ __forceinline__ cplx cprod(cplx a, cplx b) {
+    return make_double2(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x));
+}
 // acc += c * q, the product rounded before it is added (the gemv loops)
 __device__ __forceinline__ void cmul_acc(cplx& acc, cplx c, cplx q) {
     acc.x += fma(c.x, q.x, -c.y * q.y);

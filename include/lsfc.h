@@ -577,7 +577,7 @@ int lsfc_sparsify_build(lsfc_plan* plan, int64_t* rowptr, int64_t* col, double* 
  * a distributed, simulated-rank or multi-device plan ("not available on ...").
  * Out of scope: multi-device and multi-process plans; receivers on grid points (the kernel is singular there); quadrature
  * corrections for receivers inside the support of nu -- the sum is the plain trapezoidal rule, spectrally accurate for
- * receivers at a distance from a smooth, compactly supported nu; NUFFT-accelerated evaluation; gradient assembly. */
+ * receivers at a distance from a smooth, compactly supported nu; NUFFT-accelerated evaluation. */
 typedef struct lsfc_receivers lsfc_receivers;
 #define LSFC_RECV_POINTS   0
 #define LSFC_RECV_FARFIELD 1
@@ -591,6 +591,83 @@ int lsfc_receivers_apply(lsfc_receivers* rc, lsfc_plan* plan, const double* in, 
 /* out: N, nrecv, receivers per thread of the forward kernel, receivers per LDS chunk of the T / H kernel, members per group,
  * bytes of the tables (receiver coordinates, or the nrecv (n + m + l) complex far-field factors) */
 int lsfc_receivers_info(const lsfc_receivers* rc, int64_t out[6]);
+
+/* ---- linearised scattering: the Born operator J, J^H and the misfit gradient ---- */
+
+/* With M = I + omega^2 G diag(nu), M u_s = u_inc_s and the data d_s = -omega^2 R (nu .* u_s) of lsfc_receivers_apply with a plan,
+ * the Frechet derivative of nu -> d and its adjoint are (G symmetric, so that G M^T = M G)
+ *     J_s dnu = -omega^2 R M^-T (u_s .* dnu)                                 one M^T solve per source, then the plain R
+ *     J^H r   = sum_s -omega^2 conj(u_s .* p_s),   M p_s = R^T conj(r_s)     one M solve per source (reciprocity)
+ * J is complex-linear in dnu and holds for a complex nu as it stands; for a real nu the gradient of
+ * phi = 1/2 sum_s ||d_s - d_obs_s||^2 is Re(J^H (d - d_obs)).  conj(M)^-1 is none of N / T / H: the conjugations of J^H sit in the
+ * two kernel-level entries below, which are usable on their own.  N, device and stream are the plan's; the plan's nu and op are
+ * neither read nor changed by them.  Vectors: nrhs members back to back, LSFC_MEM_HOST (staged, synchronises) or LSFC_MEM_DEVICE
+ * (stream-ordered on the plan's stream).
+ *   lsfc_born_scale   out_j[i] = dnu[i] u_j[i].  dnu: N doubles, or N (re, im) pairs with dnu_is_complex; read once per group of up
+ *                     to 8 members.  out may be u.
+ *   lsfc_born_image   g[i] = (LSFC_BORN_ACCUMULATE ? g[i] : 0) + sum_j scale conj(u_j[i] p_j[i]), serially in member order j: a
+ *                     point's bits depend on the order of the members and on nothing else -- one call of 17 members, calls of
+ *                     8 + 8 + 1 with LSFC_BORN_ACCUMULATE and 17 calls of one give the same bits.  LSFC_BORN_REAL: g is N doubles and
+ *                     receives the real part, bit for bit that of the complex result (the running real part never reads the
+ *                     imaginary one, so g itself carries it from launch to launch).
+ * LSFC_EINVAL, before any device call: NULL argument; nrhs < 1; an unknown flag, dnu_is_complex or memspace; a distributed,
+ * simulated-rank or multi-device plan ("not available on ..."). */
+#define LSFC_BORN_ACCUMULATE 1u
+#define LSFC_BORN_REAL       2u
+int lsfc_born_scale(lsfc_plan* plan, const double* dnu, int dnu_is_complex, const double* u, double* out, int64_t nrhs, int memspace);
+int lsfc_born_image(lsfc_plan* plan, const double* u, const double* p, int64_t nrhs, double scale_re, double scale_im,
+                    unsigned flags /* LSFC_BORN_ACCUMULATE | LSFC_BORN_REAL */, double* g, int memspace);
+
+/* The object: a plan, a receivers object and solver options; it owns the background fields U (nsrc x N, on the device), the data
+ * and its work vectors, and borrows plan, receivers and preconditioner (they must outlive it).
+ * Sequences, each over `chunk` sources at a time with x0 = 0, through lsfc_gmres_batch / lsfc_bicgstabl_batch with LSFC_MEM_DEVICE
+ * on the plan's stream (the receivers object and the preconditioner are moved onto that stream):
+ *     lsfc_born_set_background   batched solve on M -> U; then the plan-fused R on all of U -> data
+ *     lsfc_born_apply, OP_N      lsfc_born_scale (times -omega^2) -> batched solve on M^T -> plain R
+ *     lsfc_born_apply, OP_H      conj -> plain R^T -> batched solve on M -> lsfc_born_image with scale -omega^2
+ * State: the plan's op and the preconditioner's op are set for the solves (T for OP_N, N otherwise) and PUT BACK TO WHAT THEY WERE
+ * on every way out, errors included.
+ * Preconditioner: it must be able to follow.  A block-tridiagonal object serves both directions; an object of lsfc_precond_create
+ * (host LU, no transposed apply) is accepted for OP_H and the background, and OP_N with it is LSFC_EINVAL naming the reason.
+ * Symmetry: lsfc_born_create runs the symmetry check of lsfc_plan_set_op(T); a plan whose defect is above 1e-10 fails with that
+ * message.
+ * Memory rule, checked by lsfc_born_set_background before anything is allocated: nsrc N 16 B for U; per member of a chunk the
+ * solver's vectors (restart + 2, or 2 l + 3 for BiCGStab(l)) and two work vectors; one more work vector (staging of host dnu / g).
+ * LSFC_ENOMEM gives the figures and the largest chunk / nsrc that would fit.  chunk <= 0: the largest that fits, at most 64.
+ * Non-convergence: a source that does not converge does not stop the others; the outputs are written, the call returns
+ * LSFC_ENOTCONV, lsfc_last_error names the first such source and its stage, lsfc_born_info has every source's result.
+ * Repeatability: two calls with the same input give the same bits.
+ * LSFC_EINVAL, before any device call, lsfc_last_error names the cause: a NULL argument; a non-zero reserved word; an unknown
+ * solver, op or flag; l outside 1..8; chunk > 64; LSFC_OP_T; LSFC_BORN_REAL with OP_N; apply, fields or data before
+ * lsfc_born_set_background; receivers whose N or device differ from the plan's; a distributed, simulated-rank or multi-device plan.
+ * Out of scope: multi-device and multi-process plans; warm starts and recycled Krylov spaces across sources or calls;
+ * regularisation, line searches and an optimiser; the second-order adjoint; receivers inside the support of nu; per-source
+ * receiver sets. */
+typedef struct lsfc_born lsfc_born;
+#define LSFC_BORN_GMRES     0
+#define LSFC_BORN_BICGSTABL 1
+typedef struct lsfc_born_opts {
+    int solver;            /* LSFC_BORN_GMRES | LSFC_BORN_BICGSTABL */
+    int restart, l;        /* as lsfc_gmres_opts / lsfc_bicgstabl_opts */
+    int64_t maxiter;       /* GMRES iterations / BiCGStab(l) max_mv_products; <= 0: N */
+    double reltol, abstol; /* reltol < 0: sqrt(eps) */
+    lsfc_precond* precond; /* NULL or a library object, applied on the device in group sweeps */
+    int64_t chunk;         /* sources solved in lock step; <= 0: the largest that fits, at most 64 */
+    int reserved[6];       /* zero */
+} lsfc_born_opts;
+int lsfc_born_create(lsfc_born** out, lsfc_plan* plan, lsfc_receivers* rc, const lsfc_born_opts* opts);
+int lsfc_born_destroy(lsfc_born* b);
+/* solves M u_s = u_inc_s for s < nsrc (u_inc: nsrc * N complex), keeps U on the device, forms d_s = -omega^2 R (nu .* u_s); call
+ * again after lsfc_plan_set_nu* */
+int lsfc_born_set_background(lsfc_born* b, const double* u_inc, int64_t nsrc, int memspace);
+int lsfc_born_fields(const lsfc_born* b, const double** u_dev, int64_t* nsrc);       /* device pointer, nsrc * N complex */
+int lsfc_born_data(lsfc_born* b, double* d, int memspace);                           /* nsrc * nrecv complex */
+/* LSFC_OP_N: dnu (N doubles, or N complex with in_is_complex) -> dd (nsrc * nrecv).  LSFC_OP_H: r (nsrc * nrecv complex) -> g
+ * (N complex; N doubles = Re with LSFC_BORN_REAL).  LSFC_OP_T is refused. */
+int lsfc_born_apply(lsfc_born* b, const double* in, int in_is_complex, double* out, int op, unsigned flags, int memspace);
+/* out: N, nrecv, nsrc, chunk, solver, bytes of device memory held, batched solves of the last call, operator applications of the
+ * last call; last (may be NULL): nsrc results of the last call's solves */
+int lsfc_born_info(const lsfc_born* b, int64_t out[8], lsfc_gmres_result* last /* nsrc entries, may be NULL */);
 
 /* ---- streams, timing, profiling ------------------------------------------ */
 

@@ -618,4 +618,80 @@ scattered_field(R::ReceiversHIP, M::FastMHIP, u::VecOrMat{Complex{Float64}}) = _
 adjoint_source(R::ReceiversHIP, M::FastMHIP, w::VecOrMat{Complex{Float64}}) = _receivers_apply!(_out(R, w, OP_H), R, M.plan, w, OP_H)
 receivers_set_stream(R::ReceiversHIP, stream::Ptr{Cvoid}) = check(ccall((:lsfc_receivers_set_stream, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), R.rc, stream))
 
+# Linearised scattering -- lsfc_born_* (include/lsfc.h): J = d(data)/d(nu) for data d_s = -omega^2 R (nu .* u_s), M u_s = u_inc_s,
+# its adjoint and the misfit gradient, device-resident.  B = Born(M, R, U_inc) solves for the background fields of the columns of
+# U_inc; B * dnu is J dnu (nrecv x nsrc), B' * r is J^H r, misfit(B, d_obs) returns (phi, gradient), update!(B, nu) moves the
+# medium.  The plan's op and the preconditioner's op are set by the library for the solves and put back.
+const BORN_ACCUMULATE = Cuint(1); const BORN_REAL = Cuint(2)
+const BORN_GMRES = Cint(0); const BORN_BICGSTABL = Cint(1)
+struct BornOpts                    # lsfc_born_opts
+    solver::Cint; restart::Cint; l::Cint; maxiter::Int64; reltol::Float64; abstol::Float64
+    precond::Ptr{Cvoid}; chunk::Int64; reserved::NTuple{6,Cint}
+end
+mutable struct Born
+    b::Ptr{Cvoid}
+    M::FastMHIP; R::ReceiversHIP; Pl
+    U_inc::Matrix{Complex{Float64}}
+    converged::Bool
+    function Born(M::FastMHIP, R::ReceiversHIP, U_inc::Matrix{Complex{Float64}}; Pl=nothing, solver=:gmres, reltol=1e-8, restart=30, l=2,
+                  maxiter=0, chunk=0)
+        (Pl === nothing || Pl isa SparsifyingPreconditionerHIP) || throw(ArgumentError("Born: Pl must be a SparsifyingPreconditionerHIP (not a wrapper of one)"))
+        opts = Ref(BornOpts(solver == :gmres ? BORN_GMRES : BORN_BICGSTABL, restart, l, maxiter, reltol, 0.0,
+                            Pl === nothing ? C_NULL : Pl.pc, chunk, ntuple(_ -> Cint(0), 6)))
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:lsfc_born_create, liblsfc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{BornOpts}), out, M.plan, R.rc, opts))
+        B = new(out[], M, R, Pl, U_inc, true)
+        finalizer(B -> ccall((:lsfc_born_destroy, liblsfc), Cint, (Ptr{Cvoid},), B.b), B)
+        set_background!(B, U_inc)
+        return B
+    end
+end
+struct AdjointBorn; parent::Born; end
+LinearAlgebra.adjoint(B::Born) = AdjointBorn(B)
+LinearAlgebra.adjoint(V::AdjointBorn) = V.parent
+LinearAlgebra.transpose(::Born) = throw(ArgumentError("transpose(B) is not offered: J^T r = conj(J' conj(r))"))
+nsrc(B::Born) = size(B.U_inc, 2)
+Base.size(B::Born) = (B.R.nrecv * nsrc(B), B.R.N)
+Base.eltype(::Union{Born,AdjointBorn}) = Complex{Float64}
+# LSFC_ENOTCONV (-5) is a result: the outputs are written, B.converged says so and lasterror() names the first source
+_born_rc(B::Born, rc) = (rc == 0 || rc == -5) ? (B.converged = rc == 0; nothing) : check(rc)
+function set_background!(B::Born, U_inc::Matrix{Complex{Float64}})
+    size(U_inc, 1) == B.R.N || throw(DimensionMismatch("U_inc"))
+    B.U_inc = U_inc
+    _born_rc(B, ccall((:lsfc_born_set_background, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Complex{Float64}}, Int64, Cint), B.b, U_inc, size(U_inc, 2), 0))
+    return B
+end
+function data(B::Born)
+    d = zeros(Complex{Float64}, B.R.nrecv, nsrc(B))
+    check(ccall((:lsfc_born_data, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Complex{Float64}}, Cint), B.b, d, 0))
+    return d
+end
+function born_results(B::Born)     # per source: iterations, operator applications, converged, residual of the last call
+    out = zeros(Int64, 8); res = Vector{GmresResult}(undef, nsrc(B))
+    check(ccall((:lsfc_born_info, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{GmresResult}), B.b, out, res))
+    return res
+end
+function LinearAlgebra.mul!(dd::Matrix{Complex{Float64}}, B::Born, dnu::Union{Vector{Float64},Vector{Complex{Float64}}})
+    (length(dnu) == B.R.N && size(dd) == (B.R.nrecv, nsrc(B))) || throw(DimensionMismatch("Born apply"))
+    _born_rc(B, ccall((:lsfc_born_apply, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Complex{Float64}}, Cint, Cuint, Cint),
+                      B.b, dnu, eltype(dnu) <: Complex ? 1 : 0, dd, OP_N, 0, 0))
+    return dd
+end
+function LinearAlgebra.mul!(g::Union{Vector{Float64},Vector{Complex{Float64}}}, V::AdjointBorn, r::Matrix{Complex{Float64}})
+    B = V.parent
+    (length(g) == B.R.N && size(r) == (B.R.nrecv, nsrc(B))) || throw(DimensionMismatch("Born adjoint"))
+    _born_rc(B, ccall((:lsfc_born_apply, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Complex{Float64}}, Cint, Ptr{Cvoid}, Cint, Cuint, Cint),
+                      B.b, r, 1, g, OP_H, eltype(g) <: Complex ? Cuint(0) : BORN_REAL, 0))
+    return g
+end
+*(B::Born, dnu::Union{Vector{Float64},Vector{Complex{Float64}}}) = mul!(zeros(Complex{Float64}, B.R.nrecv, nsrc(B)), B, dnu)
+*(V::AdjointBorn, r::Matrix{Complex{Float64}}) = mul!(zeros(Complex{Float64}, V.parent.R.N), V, r)
+# (phi, grad): phi = 1/2 sum |d - d_obs|^2, grad = J^H (d - d_obs), its real part when nu is real
+function misfit(B::Born, d_obs::Matrix{Complex{Float64}})
+    res = data(B) .- d_obs
+    g = nu_is_complex(B.M) ? zeros(Complex{Float64}, B.R.N) : zeros(Float64, B.R.N)
+    return 0.5 * sum(abs2, res), mul!(g, B', res)
+end
+update!(B::Born, nu::NuVector) = (set_nu!(B.M, nu); set_background!(B, B.U_inc))
+
 end # module
