@@ -1,4 +1,16 @@
-// Host-side interface of the block-tridiagonal factorisation of Msp (blocktri.hip), used by precond.hip.
+// Host-side interface of the block-tridiagonal factorisation of Msp and the apply of Msp^{-1} from it, used by precond.hip.
+//
+// As, AG and Msp of the sparsifying preconditioner (src/preconditioner.jl:27-58; examples/example3D.jl:57-68) carry the
+// full 9-point / 27-point stencil of an n x m (x l) grid, x fastest.  With the slowest axis as block index Msp is
+// block tridiagonal: K blocks of b = N / K rows, diagonal blocks D_k, couplings L_k (block k to k-1), U_k (k to k+1).
+// Exact block elimination
+//     S_0 = D_0,   S_k = D_k - L_k S_{k-1}^{-1} U_{k-1}
+//     forward   z_k = S_k^{-1} (w_k - L_k z_{k-1})
+//     backward  x_{K-1} = z_{K-1},   x_k = z_k - S_k^{-1} (U_k x_{k+1})
+// with the explicit inverses S_k^{-1} stored dense (column-major, K b^2 16 B).  The reference has UMFPACK's lu(Msp) here.
+//
+// blocktri_factor.hip computes the inverses, once per object; blocktri_sweep.hip runs the two sweeps, 2 K - 1 steps per
+// apply; blocktri_object.hpp is the object the two share.
 #pragma once
 #include "common.hpp"
 

@@ -8,7 +8,7 @@ the same operator).  Its factors and As are uploaded once; `ldiv_` then runs ent
 CSR SpMV + the two level-scheduled sparse triangular solves of csrc/trisolve.hip, replayed from one hipGraph), so under `gmres_` the Krylov
 vector never crosses PCIe.  Msp / As are assembled on the device by sparsify.py (src/SparsifyingMatrix*.jl).
 
-A second route factorises on the device as well (csrc/blocktri.hip, lsfc_precond_create_blocktri): with the slowest grid
+A second route factorises on the device as well (csrc/blocktri_factor.hip, lsfc_precond_create_blocktri): with the slowest grid
 axis as block index Msp is block tridiagonal, and exact block elimination with dense explicit inverses of the Schur
 blocks replaces the sparse LU.  `SparsifyingPreconditioner(Msp, As, factor="blocktri", nblocks=...)` takes host
 matrices; `SparsifyingPreconditioner.from_operator(M)` assembles and factorises from the plan of a FastM / FastM3D

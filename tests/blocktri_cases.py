@@ -1,4 +1,4 @@
-"""Synthetic block-tridiagonal inputs for csrc/blocktri.hip and a long-double reference of its two sweeps (test
+"""Synthetic block-tridiagonal inputs for csrc/blocktri_factor.hip and a long-double reference of the two sweeps of csrc/blocktri_sweep.hip (test
 infrastructure, not product code; no GPU).
 
 The physical cases of tests/test_gpu_precond_blocktri.py have six block sizes and the 9- / 27-point stencil only.  The

@@ -1,4 +1,4 @@
-"""Host restatement of the partial row pivoting of csrc/blocktri.hip and the inputs that need it (test infrastructure,
+"""Host restatement of the partial row pivoting of csrc/blocktri_factor.hip and the inputs that need it (test infrastructure,
 not product code; no GPU).
 
 Pivot rule, as the device follows it: at elimination step p the candidates are rows p .. b-1 of column p (the rows that

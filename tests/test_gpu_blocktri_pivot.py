@@ -1,4 +1,4 @@
-"""GPU tests of partial row pivoting inside the Schur blocks of the block-tridiagonal preconditioner (csrc/blocktri.hip:
+"""GPU tests of partial row pivoting inside the Schur blocks of the block-tridiagonal preconditioner (csrc/blocktri_factor.hip:
 k_bt_pivot_panel, k_bt_swap_rows, k_bt_unscramble; lsfc_precond_create_blocktri_opts).
 
 Inputs (tests/blocktri_pivot_ref.py): the planted 2 x 2 of the shape suite, synthetic pairs with every block row permuted

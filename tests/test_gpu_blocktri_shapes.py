@@ -1,4 +1,4 @@
-"""GPU tests of the block-tridiagonal preconditioner (csrc/blocktri.hip) at every boundary of its kernel shapes: the
+"""GPU tests of the block-tridiagonal preconditioner (csrc/blocktri_factor.hip, csrc/blocktri_sweep.hip) at every boundary of its kernel shapes: the
 synthetic inputs of tests/blocktri_cases.py (`SHAPES`: block sizes on both sides of each tile constant, patterns that are
 no stencils), both storages of the inverses, every group size from 1 to 8.
 

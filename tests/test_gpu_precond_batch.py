@@ -1,4 +1,4 @@
-"""GPU tests of the device preconditioner applied to several right-hand sides at once (csrc/blocktri.hip:
+"""GPU tests of the device preconditioner applied to several right-hand sides at once (csrc/blocktri_sweep.hip:
 blocktri_enqueue_batch; csrc/precond.hip: lsfc_precond_apply_batch and the one apply sequence; csrc/gmres.hip: the second rendezvous of
 lsfc_gmres_batch): groups of up to 8 vectors go through one sweep that reads every S_k^{-1} once.
 

@@ -1,4 +1,4 @@
-"""GPU tests of the preconditioner factorised on the device (csrc/blocktri.hip: lsfc_precond_create_blocktri,
+"""GPU tests of the preconditioner factorised on the device (csrc/blocktri_factor.hip: lsfc_precond_create_blocktri,
 lsfc_precond_create_from_plan): block-tridiagonal elimination of Msp with dense explicit inverses of the Schur blocks.
 
 References: scipy's sparse LU of the same Msp, the numpy restatement of the elimination (tests/blocktri_ref.py) and

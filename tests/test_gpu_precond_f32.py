@@ -1,4 +1,4 @@
-"""GPU tests of the device preconditioner with its Schur inverses stored in single precision (csrc/blocktri.hip,
+"""GPU tests of the device preconditioner with its Schur inverses stored in single precision (csrc/blocktri_factor.hip, csrc/blocktri_sweep.hip,
 LSFC_PRECOND_INV_F32; `inverse_dtype="complex64"`): the factorisation is the fp64 one, every S_k^{-1} is rounded once to an
 interleaved float pair when it is stored, and the sweeps widen on load and sum in fp64.
 

@@ -1,5 +1,5 @@
 """GPU tests of the transposed and the adjoint device preconditioner (lsfc_precond_set_op, P.T, P.H): the transposed sweeps
-of csrc/blocktri.hip on the stored S_k^{-1}, single and in groups, at both storages of the inverses.
+of csrc/blocktri_sweep.hip on the stored S_k^{-1}, single and in groups, at both storages of the inverses.
 
 References and bounds are those of tests/test_gpu_blocktri_shapes.py for the N apply (the arithmetic is the same sums in
 another order): the transposed sweeps in long double on the blocks fetched from the object
@@ -25,7 +25,7 @@ STORAGES = gs.STORAGES
 # the subset of blocktri_cases.SHAPES that the issue names ...
 _NAMED = {(1, 5), (17, 3), (64, 3), (65, 3), (96, 3), (97, 3), (98, 3), (129, 2), (257, 2), (70, 2), (1025, 2), (2049, 2)}
 SUBSET = [s for s in bc.SHAPES if s[:2] in _NAMED]
-# ... and one shape on each side of every tile constant of the transposed kernels (csrc/blocktri.hip)
+# ... and one shape on each side of every tile constant of the transposed kernels (csrc/blocktri_sweep.hip)
 LOCAL = [
     (4, 3, "scattered"), (5, 3, "scattered"),              # WT_COLS = 4: columns in flight per wave of the walk kernel
     (32, 3, "scattered"), (33, 3, "scattered"),            # ST_WAVES * WT_COLS = 32: columns per pass of the walk kernel
@@ -165,7 +165,7 @@ def test_one_object_through_every_captured_sequence(lsfc, shape):
         P.close()
 
 
-def _bb_cols(b):                                           # columns per workgroup of the N group product (csrc/blocktri.hip)
+def _bb_cols(b):                                           # columns per workgroup of the N group product (csrc/blocktri_sweep.hip)
     return 32 if b < 1024 else (64 if b < 2048 else 128)
 
 

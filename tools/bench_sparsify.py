@@ -9,7 +9,7 @@ One JSON line per measurement on stdout and appended to --out.
     python tools/bench_sparsify.py --out profiles/sparsify_timing.jsonl
 
 --factor: the preconditioner factorised on the device instead (SparsifyingPreconditioner.from_operator: assembly plus
-block-tridiagonal factorisation, csrc/blocktri.hip) -- set-up time, time per apply beside its byte floor
+block-tridiagonal factorisation, csrc/blocktri_factor.hip) -- set-up time, time per apply beside its byte floor
 2 K b^2 16 B / 6.29 TB/s, and, where scipy's splu of the same Msp is affordable (2D, 3D up to 24^3), the host-LU route
 with its level-scheduled apply on the same pair.
 

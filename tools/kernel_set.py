@@ -14,7 +14,13 @@ is placed.
     python tools/kernel_set.py --compare A B [--out profiles/pruned_args_refactor.jsonl]
                                                        A, B: csrc directories of two builds.  One JSON line per family: kernels,
                                                        names only in A, names only in B, kernels whose code or descriptor
-                                                       differs; exit status 1 if any of the three counts is not zero"""
+                                                       differs; exit status 1 if any of the three counts is not zero
+    python tools/kernel_set.py --compare-objects A1.o[,A2.o...] B1.o[,B2.o...] [--out profiles/blocktri_split_refactor.jsonl]
+                                                       the same comparison between the union of the kernels of the objects A
+                                                       and the union of those of B (a source file split in two, say): one JSON
+                                                       line.  A name in two objects of one side is an error.  Names that
+                                                       contain k_warmup_ (one empty kernel per unit) are listed apart and are
+                                                       no difference."""
 import argparse
 import hashlib
 import json
@@ -39,6 +45,8 @@ def kernels(obj):
     with tempfile.TemporaryDirectory() as tmp:
         fatbin, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "gfx950.co")
         tool("llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fatbin)
+        if os.path.getsize(fatbin) == 0:            # no such section: a unit without device code
+            return {}
         tool("clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fatbin}", f"--output={co}")
         listing = tool("llvm-readelf", "-S", "-s", "-W", co)
         with open(co, "rb") as f:
@@ -76,12 +84,49 @@ def family_object(csrc, fam):
     return os.path.join(csrc, "build", f"fft_kernels_f{fam}.o")
 
 
+def union(objs):
+    """the kernels of several object files as one set, without the warm-up kernels: (kernels, sorted names of the warm-up kernels)"""
+    out, warmup = {}, []
+    for obj in objs:
+        for name, h in kernels(obj).items():
+            if name in out or name in warmup:
+                sys.exit(f"{obj}: kernel {name} is in another object of the same side as well")
+            if "k_warmup_" in name:
+                warmup.append(name)
+            else:
+                out[name] = h
+    return out, sorted(warmup)
+
+
+def compare(what, a, b, out, **more):
+    """One JSON line on the kernel sets a and b (printed, appended to `out`); the number of names on one side only or differing"""
+    only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+    differ = sorted(k for k in set(a) & set(b) if a[k] != b[k])
+    for tag, names in (("only in A", only_a), ("only in B", only_b), ("differs", differ)):
+        for k in names:
+            print(f"# {what}, {tag}: {k}", file=sys.stderr)
+    line = json.dumps({"check": "kernel_set", **more, "kernels_a": len(a), "kernels_b": len(b), "only_in_a": len(only_a),
+                       "only_in_b": len(only_b), "differ": len(differ)})
+    print(line, flush=True)
+    if out:
+        with open(out, "a") as f:
+            f.write(line + "\n")
+    return len(only_a) + len(only_b) + len(differ)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("csrc", nargs="?", default=CSRC, help="csrc directory of a build (default: this tree's)")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="csrc directories of two builds")
+    ap.add_argument("--compare-objects", nargs=2, metavar=("A", "B"), help="two comma-separated lists of object files")
     ap.add_argument("--out", default="", help="append the comparison lines to this file")
     args = ap.parse_args()
+    if args.compare_objects:
+        sides = [spec.split(",") for spec in args.compare_objects]
+        (a, warm_a), (b, warm_b) = (union(objs) for objs in sides)
+        names = [[os.path.basename(o) for o in objs] for objs in sides]
+        bad = compare(" ".join(names[0]), a, b, args.out, objects_a=names[0], objects_b=names[1], warmup_a=warm_a, warmup_b=warm_b)
+        return 1 if bad else 0
     if not args.compare:
         for fam in FAMILIES:
             for name, h in sorted(kernels(family_object(args.csrc, fam)).items()):
@@ -90,18 +135,7 @@ def main():
     bad = 0
     for fam in FAMILIES:
         a, b = (kernels(family_object(d, fam)) for d in args.compare)
-        only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
-        differ = sorted(k for k in set(a) & set(b) if a[k] != b[k])
-        for what, names in (("only in A", only_a), ("only in B", only_b), ("differs", differ)):
-            for k in names:
-                print(f"# family {fam}, {what}: {k}", file=sys.stderr)
-        bad += len(only_a) + len(only_b) + len(differ)
-        line = json.dumps({"check": "kernel_set", "family": fam, "kernels_a": len(a), "kernels_b": len(b), "only_in_a": len(only_a),
-                           "only_in_b": len(only_b), "differ": len(differ)})
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
+        bad += compare(f"family {fam}", a, b, args.out, family=fam)
     return 1 if bad else 0
 
 

@@ -1,13 +1,16 @@
 """SHA-256 of the result of a fixed list of device preconditioner applies: the bitwise fingerprint of csrc/precond.hip,
-csrc/trisolve.hip and of the sweeps of csrc/blocktri.hip as the preconditioner object drives them.  Two builds of the
-library that print the same lines sum in the same order and schedule the triangular solves alike.
+csrc/trisolve.hip and of the sweeps of csrc/blocktri_sweep.hip as the preconditioner object drives them, and SHA-256 of what
+csrc/blocktri_factor.hip stored.  Two builds of the library that print the same lines sum in the same order, schedule the
+triangular solves alike and factorise alike.
 
   LU route       every entry of RECIPES in tests/test_gpu_precond.py (through its _Precond, _synthetic and _rhs) and the real
                  pairs ("2d", 33) and ("gv3", 16); each line also holds the twenty schedule counts (lsfc_precond_schedule, L then U)
   block-tridiagonal route
                  b = 17, 97, 98, 129, 257, 1025, 2049 of tests/blocktri_cases.SHAPES at both storages of the inverses:
                  solve, and solve_batch with 1, 3 and 8 right-hand sides, under op N, T and H; one 16^3 object made from a
-                 plan with pivoting="partial"
+                 plan with pivoting="partial"; the planted-pivot pair of tests/blocktri_pivot_ref.py (b = 70, K = 3, eps = 1e-9)
+                 with pivoting="auto", whose pass without pivoting breaks down.  Every object also gives a line on its
+                 factorisation: SHA-256 of every stored block and of every block's pivots, min_pivot_ratio as float.hex
 
     python tools/precond_digest.py                                  one JSON line per case, this tree's library
     python tools/precond_digest.py --libs parent=/path/to/liblsfc.so,this= [--out profiles/precond_split_refactor.jsonl]
@@ -34,8 +37,8 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-def emit(label, x, schedule=None):
-    rec = {"case": label, "x": sha(x)}
+def emit(label, x, schedule=None, **more):
+    rec = {"case": label, "x": sha(x), **more}
     if schedule is not None:
         rec["schedule"] = [int(v) for v in schedule]
     print("DIGEST " + json.dumps(rec), flush=True)
@@ -45,6 +48,7 @@ def child():
     import scipy.sparse.linalg as spla
     import fast_solver_lippmann_schwinger_amd as lsfc
     import blocktri_cases as bc
+    import blocktri_pivot_ref as pv
     import test_gpu_precond as gp
     from test_gpu_sparsify import case
 
@@ -60,6 +64,10 @@ def child():
         P.close()
 
     def every_op(label, P):
+        K = P.blocktri_info()["blocks"]                    # the factorisation: x is the digest of all stored blocks together
+        blocks = [sha(P.blocktri_block(k)) for k in range(K)]
+        emit(f"{label} factorisation", "".join(blocks).encode(), blocks=blocks, pivots=[sha(P.blocktri_pivots(k)) for k in range(K)],
+             min_pivot_ratio=float(P.blocktri_info()["min_pivot_ratio"]).hex())
         B = bc.right_hand_sides(P.N, max(GROUPS))
         for op, view in (("N", P), ("T", P.T), ("H", P.H)):
             emit(f"{label} {op} solve", view.solve(B[0]))
@@ -77,6 +85,11 @@ def child():
     every_op("blocktri from a 16^3 plan, partial pivoting", P)
     P.close()
     M.close()
+    Msp, As = pv.planted(1e-9)
+    P = lsfc.SparsifyingPreconditioner(Msp, As, factor="blocktri", nblocks=pv.PLANT_K, pivoting="auto")
+    assert P.blocktri_info()["pivoting"] == 1              # the pass without pivoting broke down
+    every_op("blocktri planted pivot b=70 K=3, auto pivoting", P)
+    P.close()
 
 
 def main():
@@ -105,8 +118,9 @@ def main():
         equal = da == db
         bad += not equal
         rec = {"check": "digest", "case": da["case"], f"x_sha256_{na}": da["x"], f"x_sha256_{nb}": db["x"], "equal": equal}
-        if "schedule" in da:
-            rec.update({f"schedule_{na}": da["schedule"], f"schedule_{nb}": db.get("schedule")})
+        for key in ("schedule", "blocks", "pivots", "min_pivot_ratio"):
+            if key in da:
+                rec.update({f"{key}_{na}": da[key], f"{key}_{nb}": db.get(key)})
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:
