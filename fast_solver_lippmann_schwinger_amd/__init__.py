@@ -6,7 +6,7 @@ from .operators import (FastM, FastM3D, OperatorView, ConvergenceHistory, FFTcon
                         referenceValsTrapRule, sampleG3D, sampleGConv, size, time_apply)
 from .preconditioner import SparsifyingPreconditioner
 from .receivers import Receivers
-from .born import BornOperator
+from .born import BornOperator, born_contract
 from .sparsify import (buildSparseA, buildSparseAG, buildSparseAConv, buildSparseAGConv, buildSparseA3DConv,
                        buildSparseAG3DConv, sparsifying_pair, sparsify_arrays, sparsify_pattern)
 from ._lib import LsfcError, device_count, load, host_register, host_unregister, host_empty
@@ -14,6 +14,6 @@ from ._lib import LsfcError, device_count, load, host_register, host_unregister,
 __all__ = ["FastM", "FastM3D", "OperatorView", "ConvergenceHistory", "FFTconvolution", "buildFastConvolution",
            "buildFastConvolution3D", "eltype", "fastconvolution", "gmres_", "gmres_batch_", "bicgstabl_", "bicgstabl_multi_", "bicgstabl_batch_", "apply_batch", "mul_", "profile_apply",
            "referenceValsTrapRule", "sampleG3D", "sampleGConv", "size", "time_apply", "LsfcError",
-           "device_count", "load", "SparsifyingPreconditioner", "Receivers", "BornOperator", "host_register", "host_unregister", "host_empty",
+           "device_count", "load", "SparsifyingPreconditioner", "Receivers", "BornOperator", "born_contract", "host_register", "host_unregister", "host_empty",
            "buildSparseA", "buildSparseAG", "buildSparseAConv", "buildSparseAGConv", "buildSparseA3DConv",
            "buildSparseAG3DConv", "sparsifying_pair", "sparsify_arrays", "sparsify_pattern"]

@@ -22,6 +22,7 @@ LSFC_OP_N, LSFC_OP_T, LSFC_OP_H = 0, 1, 2
 LSFC_RECV_POINTS, LSFC_RECV_FARFIELD = 0, 1
 LSFC_BORN_ACCUMULATE, LSFC_BORN_REAL = 1, 2
 LSFC_BORN_GMRES, LSFC_BORN_BICGSTABL = 0, 1
+LSFC_BORN_ADJOINT_STATE, LSFC_BORN_RECIPROCAL = 0, 1
 # how a member of lsfc_bicgstabl_batch ended (status[2 j]); 2..7: the scalar of a breakdown
 (LSFC_BICG_CONVERGED, LSFC_BICG_MAX_MV, LSFC_BICG_RHO, LSFC_BICG_SIGMA, LSFC_BICG_BETA, LSFC_BICG_ALPHA, LSFC_BICG_GAMMA,
  LSFC_BICG_RESIDUAL) = range(8)
@@ -124,6 +125,11 @@ SIGNATURES = {
     "lsfc_born_data": (_I, [_P, _P, _I]),
     "lsfc_born_apply": (_I, [_P, _P, _I, _P, _I, _U, _I]),
     "lsfc_born_info": (_I, [_P, C.POINTER(_L), C.POINTER(GmresResult)]),
+    "lsfc_born_contract": (_I, [_P, _P, _L, _P, _L, _P, _I, _P, _I, _U, _D, _D, _I]),
+    "lsfc_born_set_mode": (_I, [_P, _I]),
+    "lsfc_born_get_mode": (_I, [_P, C.POINTER(_I), C.POINTER(_L)]),
+    "lsfc_born_receiver_fields": (_I, [_P, _PP, C.POINTER(_L)]),
+    "lsfc_born_receiver_info": (_I, [_P, C.POINTER(_L), C.POINTER(GmresResult)]),
     "lsfc_sparsify_pattern": (_I, [_L, _L, _L, C.POINTER(_L), _P, _P, _P]),
     "lsfc_sparsify_build": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "lsfc_plan_set_stream": (_I, [_P, _P]),

@@ -10,8 +10,11 @@
 //     k_conj_small   the conjugated residuals in front of R^T
 // One 16-B access per complex, grid-stride loops over grid_for blocks, no atomics, no LDS, no host work inside a call.  conj(M)^-1
 // is none of N / T / H, which is why the conjugations of J^H sit in these kernels and not in an op.
+// Reciprocal mode (lsfc_born_set_mode): one solve per receiver and medium for V = M^-1 R^T, and since R M^-T = V^T both applies are
+// contractions of the stored U and V without a solve (born_contract.hip); k_identity_rows makes the right-hand sides' e_r.
 #include "plan.hpp"
 #include "receivers.hpp"
+#include "born_contract.hpp"
 #include "reduce.hpp"
 #include <algorithm>
 #include <memory>
@@ -30,6 +33,13 @@ struct lsfc_born {
     std::vector<lsfc_gmres_result> last;               // per source, of the last call
     int64_t last_solves = 0, last_mvps = 0, first_bad = -1;
     const char* bad_stage = "";
+    // reciprocal mode (lsfc_born_set_mode): the receiver fields V = M^-1 R^T, nrecv x N, and the block partials of the contraction
+    int mode = LSFC_BORN_ADJOINT_STATE;
+    lsfc::DevBuf<lsfc::cplx> V;
+    lsfc::DevBuf<double> cwork;
+    bool have_v = false;
+    std::vector<lsfc_gmres_result> recv_last;          // per receiver, of the last receiver-field solve
+    int64_t recv_solves = 0, recv_mvps = 0, recv_bad = -1;
 };
 
 namespace lsfc {
@@ -73,6 +83,13 @@ void k_born_image(const cplx* __restrict__ u, const cplx* __restrict__ p, cplx s
         }
         if constexpr (REAL) g[i] = acc.x; else reinterpret_cast<cplx*>(g)[i] = acc;
     }
+}
+
+// rows r0 .. r0 + cnt - 1 of the nrecv x nrecv identity, in front of R^T
+__global__ __launch_bounds__(BORN_THREADS) void k_identity_rows(cplx* __restrict__ out, int64_t r0, int64_t cnt, int64_t nrecv) {
+    const int64_t step = (int64_t)gridDim.x * BORN_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * BORN_THREADS + threadIdx.x; i < cnt * nrecv; i += step)
+        out[i] = make_double2(i % nrecv == r0 + i / nrecv ? 1.0 : 0.0, 0.0);
 }
 
 __global__ __launch_bounds__(BORN_THREADS) void k_conj_small(const cplx* __restrict__ in, cplx* __restrict__ out, int64_t n) {
@@ -143,11 +160,12 @@ int restart_of(const lsfc_born* b) { return b->o.restart > 0 ? b->o.restart : (i
 // work vectors of the solver per member: the rules of lsfc_gmres_batch and lsfc_bicgstabl_batch
 int solver_vectors(const lsfc_born* b) { return b->o.solver == LSFC_BORN_GMRES ? restart_of(b) + 2 : 2 * b->o.l + 3; }
 
-// cnt <= chunk solves in lock step, x0 = 0, under the op the plan has now; the results of sources s0 .. s0 + cnt - 1
-void solve_chunk(lsfc_born* b, const cplx* rhs, cplx* x, int64_t s0, int cnt, const char* stage) {
+// cnt <= chunk solves in lock step, x0 = 0, under the op the plan has now; res: the results of members s0 .. s0 + cnt - 1, counted
+// into solves / mvps / first_bad
+void solve_members(lsfc_born* b, const cplx* rhs, cplx* x, int64_t s0, int cnt, const char* stage, lsfc_gmres_result* res,
+                   int64_t& solves, int64_t& mvps, int64_t& first_bad) {
     lsfc_plan* p = b->plan;
     LSFC_HIP(hipMemsetAsync(x, 0, (size_t)cnt * (size_t)b->N * sizeof(cplx), p->stream));
-    lsfc_gmres_result* res = b->last.data() + s0;
     lsfc_precond_fn fn = b->o.precond ? &lsfc_precond_callback : nullptr;
     int rc;
     if (b->o.solver == LSFC_BORN_GMRES) {
@@ -163,27 +181,80 @@ void solve_chunk(lsfc_born* b, const cplx* rhs, cplx* x, int64_t s0, int cnt, co
         rc = lsfc_bicgstabl_batch(p, (double*)x, (const double*)rhs, cnt, &s, nullptr, 0, res, nullptr, LSFC_MEM_DEVICE);
     }
     nested(rc, stage);
-    ++b->last_solves;
+    ++solves;
     for (int j = 0; j < cnt; ++j) {
-        b->last_mvps += res[j].mvps;
-        if (!res[j].converged && b->first_bad < 0) { b->first_bad = s0 + j; b->bad_stage = stage; }
+        mvps += res[j].mvps;
+        if (!res[j].converged && first_bad < 0) first_bad = s0 + j;
     }
 }
 
-void begin_call(lsfc_born* b) {
-    b->last_solves = b->last_mvps = 0; b->first_bad = -1; b->bad_stage = "";
-    for (auto& r : b->last) r = lsfc_gmres_result{};
+// the solves of the sources s0 .. s0 + cnt - 1
+void solve_chunk(lsfc_born* b, const cplx* rhs, cplx* x, int64_t s0, int cnt, const char* stage) {
+    const int64_t bad = b->first_bad;
+    solve_members(b, rhs, x, s0, cnt, stage, b->last.data() + s0, b->last_solves, b->last_mvps, b->first_bad);
+    if (bad < 0 && b->first_bad >= 0) b->bad_stage = stage;
+}
+
+// preconditioner and receivers run on the plan's stream
+void bind_streams(lsfc_born* b) {
     LSFC_HIP(hipSetDevice(b->plan->device));
     if (b->o.precond) nested(lsfc_precond_set_stream(b->o.precond, b->plan->stream), "lsfc_born");
     nested(lsfc_receivers_set_stream(b->rc, b->plan->stream), "lsfc_born");
 }
 
-// LSFC_ENOTCONV after a call whose outputs are written: the first source that did not converge, and where
-int not_converged(const lsfc_born* b, int rc, const char* who) {
+void begin_call(lsfc_born* b) {
+    b->last_solves = b->last_mvps = 0; b->first_bad = -1; b->bad_stage = "";
+    for (auto& r : b->last) r = lsfc_gmres_result{};
+    bind_streams(b);
+}
+
+constexpr const char* RECEIVER_STAGE = "receiver-field solve on M";
+
+// bytes that reciprocal mode holds beside the rest: V and the block partials of the contraction
+double reciprocal_bytes(const lsfc_born* b, int64_t nsrc) {
+    return (double)b->nrecv * (double)b->N * sizeof(cplx) + (double)contract_n_work(b->N, nsrc, b->nrecv) * sizeof(double);
+}
+
+// V = M^-1 R^T, `chunk` receivers at a time: rows of the identity through R^T, then the object's solver on M with x0 = 0.  U, W and
+// small are allocated; V and cwork are allocated here.  A receiver that does not converge does not stop the others.
+void solve_receiver_fields(lsfc_born* b, const char* who) {
+    lsfc_plan* p = b->plan;
+    const int64_t N = b->N, nrecv = b->nrecv;
+    b->have_v = false;
+    b->recv_solves = b->recv_mvps = 0; b->recv_bad = -1;
+    b->recv_last.assign((size_t)nrecv, lsfc_gmres_result{});
+    if (!b->V.p) b->V.alloc((size_t)(nrecv * N));
+    b->cwork.alloc(contract_n_work(N, b->nsrc, nrecv));
+    const OpGuard guard(b, LSFC_OP_N, who);
+    cplx *rhs = b->W.p, *eye = b->small.p;
+    for (int64_t r0 = 0; r0 < nrecv; r0 += b->chunk) {
+        const int cnt = (int)std::min<int64_t>(b->chunk, nrecv - r0);
+        hipLaunchKernelGGL(k_identity_rows, dim3(grid_for(cnt * nrecv, BORN_THREADS)), dim3(BORN_THREADS), 0, p->stream, eye, r0, (int64_t)cnt, nrecv);
+        LSFC_HIP(hipGetLastError());
+        nested(lsfc_receivers_apply(b->rc, nullptr, (const double*)eye, (double*)rhs, cnt, LSFC_OP_T, LSFC_MEM_DEVICE), who);
+        solve_members(b, rhs, b->V.p + r0 * N, r0, cnt, RECEIVER_STAGE, b->recv_last.data() + r0, b->recv_solves, b->recv_mvps, b->recv_bad);
+    }
+    LSFC_HIP(hipStreamSynchronize(p->stream));
+    b->have_v = true;
+}
+
+// LSFC_ENOTCONV after a call whose outputs are written: the first source that did not converge, and where; with `receivers`, after
+// the sources, the first receiver of the receiver-field solve
+int not_converged(const lsfc_born* b, int rc, const char* who, bool receivers = false) {
+    if (rc == LSFC_OK && b->first_bad < 0 && receivers && b->recv_bad >= 0) {
+        const lsfc_gmres_result& r = b->recv_last[(size_t)b->recv_bad];
+        set_last_error("%s: receiver %lld did not converge in the %s (%lld iterations, %lld operator applications, residual %.3e); the receiver "
+                       "fields are kept, lsfc_born_receiver_info has every receiver's result", who, (long long)b->recv_bad, RECEIVER_STAGE,
+                       (long long)r.iters, (long long)r.mvps, r.final_resnorm);
+        return LSFC_ENOTCONV;
+    }
     if (rc != LSFC_OK || b->first_bad < 0) return rc;
     const lsfc_gmres_result& r = b->last[(size_t)b->first_bad];
+    char also[160] = "";
+    if (receivers && b->recv_bad >= 0)
+        snprintf(also, sizeof also, "; receiver %lld did not converge in the %s (lsfc_born_receiver_info)", (long long)b->recv_bad, RECEIVER_STAGE);
     set_last_error("%s: source %lld did not converge in the %s (%lld iterations, %lld operator applications, residual %.3e); the outputs are written, "
-                   "lsfc_born_info has every source's result", who, (long long)b->first_bad, b->bad_stage, (long long)r.iters, (long long)r.mvps, r.final_resnorm);
+                   "lsfc_born_info has every source's result%s", who, (long long)b->first_bad, b->bad_stage, (long long)r.iters, (long long)r.mvps, r.final_resnorm, also);
     return LSFC_ENOTCONV;
 }
 
@@ -277,12 +348,15 @@ int lsfc_born_set_background(lsfc_born* b, const double* u_inc, int64_t nsrc, in
         LSFC_HIP(hipSetDevice(p->device));
         LSFC_HIP(hipStreamSynchronize(p->stream));
         b->nsrc = 0;
-        b->U.release(); b->W.release(); b->data.release(); b->small.release();
+        b->U.release(); b->W.release(); b->data.release(); b->small.release(); b->V.release(); b->cwork.release();
+        b->have_v = false;
+        const bool recip = b->mode == LSFC_BORN_RECIPROCAL;
         // the memory rule, before anything is allocated: U, per member of a chunk the solver's vectors and two work vectors, one more
         {
             size_t free_b = 0, total_b = 0;
             LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
-            const double vec = (double)N * sizeof(cplx), per = ((double)solver_vectors(b) + 2.0) * vec, fixed = ((double)nsrc + 1.0) * vec;
+            const double vec = (double)N * sizeof(cplx), per = ((double)solver_vectors(b) + 2.0) * vec;
+            const double fixed = ((double)nsrc + 1.0) * vec + (recip ? reciprocal_bytes(b, nsrc) : 0.0);
             const int64_t cap = std::min<int64_t>(nsrc, KRYLOV_NRHS_MAX);
             const int64_t fit = (double)free_b > fixed ? (int64_t)(((double)free_b - fixed) / per) : 0;
             const int64_t chunk = b->o.chunk > 0 ? std::min<int64_t>(b->o.chunk, nsrc) : std::min(cap, fit);
@@ -290,6 +364,12 @@ int lsfc_born_set_background(lsfc_born* b, const double* u_inc, int64_t nsrc, in
             if (chunk < 1 || need > (double)free_b) {
                 const int64_t c1 = std::max<int64_t>(chunk, 1);
                 const double left = (double)free_b - (double)c1 * per - vec;
+                if (recip)
+                    fail(LSFC_ENOMEM, "lsfc_born_set_background: %lld sources x %lld complex (U), %lld receiver fields (V, reciprocal mode) with the contraction's "
+                         "work space, chunk %lld x (%d solver + 2 work) vectors and one more need %.2f GB of device memory, %.2f GB are free -- the largest "
+                         "nrecv that fits with %lld sources at chunk %lld is about %lld",
+                         (long long)nsrc, (long long)N, (long long)b->nrecv, (long long)c1, solver_vectors(b), need / 1e9, (double)free_b / 1e9, (long long)nsrc,
+                         (long long)c1, (long long)std::max(0.0, (left - (double)nsrc * vec) / (vec * 1.01)));
                 fail(LSFC_ENOMEM, "lsfc_born_set_background: %lld sources x %lld complex (U), chunk %lld x (%d solver + 2 work) vectors and one more need %.2f GB of device "
                      "memory, %.2f GB are free -- the largest chunk that fits with %lld sources is %lld, the largest nsrc at chunk %lld is %lld",
                      (long long)nsrc, (long long)N, (long long)c1, solver_vectors(b), need / 1e9, (double)free_b / 1e9, (long long)nsrc, (long long)std::min(cap, fit),
@@ -316,8 +396,9 @@ int lsfc_born_set_background(lsfc_born* b, const double* u_inc, int64_t nsrc, in
         nested(lsfc_receivers_apply(b->rc, p, (const double*)b->U.p, (double*)b->data.p, nsrc, LSFC_OP_N, LSFC_MEM_DEVICE), "lsfc_born_set_background");
         LSFC_HIP(hipStreamSynchronize(p->stream));
         b->nsrc = nsrc;
+        if (recip) solve_receiver_fields(b, "lsfc_born_set_background");
     });
-    return b ? not_converged(b, rc, "lsfc_born_set_background") : rc;
+    return b ? not_converged(b, rc, "lsfc_born_set_background", true) : rc;
 }
 
 int lsfc_born_fields(const lsfc_born* b, const double** u_dev, int64_t* nsrc) {
@@ -357,6 +438,33 @@ int lsfc_born_apply(lsfc_born* b, const double* in, int in_is_complex, double* o
         const int64_t N = b->N, nsrc = b->nsrc, nd = nsrc * b->nrecv;
         const bool host = memspace == LSFC_MEM_HOST, real = (flags & LSFC_BORN_REAL) != 0;
         const double w2 = p->omega * p->omega;
+        if (b->mode == LSFC_BORN_RECIPROCAL) {
+            // no solves, no OpGuard: two contractions of the stored U and V
+            LSFC_REQUIRE(b->have_v, "lsfc_born_apply: reciprocal mode without receiver fields (the receiver-field solve failed: lsfc_born_set_mode or lsfc_born_set_background again)");
+            b->last_solves = b->last_mvps = 0; b->first_bad = -1; b->bad_stage = "";
+            for (auto& r : b->last) { r = lsfc_gmres_result{}; r.converged = 1; }
+            LSFC_HIP(hipSetDevice(p->device));
+            cplx* stage = b->W.p + 2 * b->chunk * N;
+            const cplx scale = make_double2(-w2, 0.0);
+            if (op == LSFC_OP_N) {
+                const double* dnu = in;
+                if (host) {
+                    LSFC_HIP(hipMemcpyAsync(stage, in, (size_t)N * (in_is_complex ? 16 : 8), hipMemcpyHostToDevice, p->stream));
+                    dnu = (const double*)stage;
+                }
+                cplx* dd = host ? b->small.p : (cplx*)out;
+                contract_n_dev(p->stream, b->U.p, nsrc, b->V.p, b->nrecv, dnu, in_is_complex != 0, dd, scale, N, b->cwork.p);
+                if (host) LSFC_HIP(hipMemcpyAsync(out, dd, (size_t)nd * sizeof(cplx), hipMemcpyDeviceToHost, p->stream));
+            } else {
+                const cplx* r = (const cplx*)in;
+                if (host) { LSFC_HIP(hipMemcpyAsync(b->small.p, in, (size_t)nd * sizeof(cplx), hipMemcpyHostToDevice, p->stream)); r = b->small.p; }
+                double* g = host ? (double*)stage : out;
+                contract_h_dev(p->stream, b->U.p, nsrc, b->V.p, b->nrecv, r, g, scale, false, real, N);
+                if (host) LSFC_HIP(hipMemcpyAsync(out, g, (size_t)N * (real ? 8 : 16), hipMemcpyDeviceToHost, p->stream));
+            }
+            if (host) LSFC_HIP(hipStreamSynchronize(p->stream));
+            return;
+        }
         cplx *B = b->W.p, *X = b->W.p + b->chunk * N, *stage = b->W.p + 2 * b->chunk * N, *s0buf = b->small.p, *s1buf = b->small.p + nd;
         begin_call(b);
         const OpGuard guard(b, op == LSFC_OP_N ? LSFC_OP_T : LSFC_OP_N, "lsfc_born_apply");
@@ -397,9 +505,74 @@ int lsfc_born_info(const lsfc_born* b, int64_t out[8], lsfc_gmres_result* last) 
     return guarded([&] {
         LSFC_REQUIRE(b && out, "lsfc_born_info: NULL argument");
         out[0] = b->N; out[1] = b->nrecv; out[2] = b->nsrc; out[3] = b->chunk; out[4] = b->o.solver;
-        out[5] = (int64_t)(b->U.bytes() + b->W.bytes() + b->data.bytes() + b->small.bytes());
+        out[5] = (int64_t)(b->U.bytes() + b->W.bytes() + b->data.bytes() + b->small.bytes() + b->V.bytes() + b->cwork.bytes());
         out[6] = b->last_solves; out[7] = b->last_mvps;
         if (last) for (int64_t s = 0; s < b->nsrc; ++s) last[s] = b->last[(size_t)s];
+    });
+}
+
+int lsfc_born_set_mode(lsfc_born* b, int mode) {
+    bool solved = false;
+    const int rc = guarded([&] {
+        LSFC_REQUIRE(mode == LSFC_BORN_ADJOINT_STATE || mode == LSFC_BORN_RECIPROCAL,
+                     "lsfc_born_set_mode: unknown mode %d (LSFC_BORN_ADJOINT_STATE or LSFC_BORN_RECIPROCAL)", mode);
+        LSFC_REQUIRE(b, "lsfc_born_set_mode: NULL argument");
+        if (mode == b->mode && (mode == LSFC_BORN_ADJOINT_STATE || b->have_v || b->nsrc == 0)) return;
+        LSFC_HIP(hipSetDevice(b->plan->device));
+        LSFC_HIP(hipStreamSynchronize(b->plan->stream));
+        if (mode == LSFC_BORN_ADJOINT_STATE) {
+            b->V.release(); b->cwork.release(); b->have_v = false;
+            b->recv_last.clear(); b->recv_solves = b->recv_mvps = 0; b->recv_bad = -1;
+            b->mode = mode;
+            return;
+        }
+        if (b->nsrc > 0) {
+            // the memory rule of lsfc_born_set_background for what this adds, before anything is allocated
+            size_t free_b = 0, total_b = 0;
+            LSFC_HIP(hipMemGetInfo(&free_b, &total_b));
+            const double need = reciprocal_bytes(b, b->nsrc) - (double)b->V.bytes(), vec = (double)b->N * sizeof(cplx);
+            if (need > (double)free_b)
+                fail(LSFC_ENOMEM, "lsfc_born_set_mode: %lld receiver fields x %lld complex (V) with the contraction's work space need %.2f GB of device memory, "
+                     "%.2f GB are free -- the largest nrecv that fits is about %lld", (long long)b->nrecv, (long long)b->N, need / 1e9, (double)free_b / 1e9,
+                     (long long)((double)free_b / (vec * 1.01)));
+            b->mode = mode;
+            bind_streams(b);
+            solve_receiver_fields(b, "lsfc_born_set_mode");
+            solved = true;
+        }
+        b->mode = mode;
+    });
+    if (rc == LSFC_OK && solved && b->recv_bad >= 0) {
+        const int64_t keep = b->first_bad;
+        b->first_bad = -1;
+        const int out = not_converged(b, rc, "lsfc_born_set_mode", true);
+        b->first_bad = keep;
+        return out;
+    }
+    return rc;
+}
+
+int lsfc_born_get_mode(const lsfc_born* b, int* mode, int64_t* receiver_field_bytes) {
+    return guarded([&] {
+        LSFC_REQUIRE(b && mode && receiver_field_bytes, "lsfc_born_get_mode: NULL argument");
+        *mode = b->mode; *receiver_field_bytes = (int64_t)b->V.bytes();
+    });
+}
+
+int lsfc_born_receiver_fields(const lsfc_born* b, const double** v_dev, int64_t* nrecv) {
+    return guarded([&] {
+        LSFC_REQUIRE(b && v_dev && nrecv, "lsfc_born_receiver_fields: NULL argument");
+        LSFC_REQUIRE(b->mode == LSFC_BORN_RECIPROCAL, "lsfc_born_receiver_fields outside reciprocal mode (lsfc_born_set_mode(LSFC_BORN_RECIPROCAL))");
+        LSFC_REQUIRE(b->nsrc > 0 && b->have_v, "lsfc_born_receiver_fields before lsfc_born_set_background");
+        *v_dev = (const double*)b->V.p; *nrecv = b->nrecv;
+    });
+}
+
+int lsfc_born_receiver_info(const lsfc_born* b, int64_t out[4], lsfc_gmres_result* per_receiver) {
+    return guarded([&] {
+        LSFC_REQUIRE(b && out, "lsfc_born_receiver_info: NULL argument");
+        out[0] = b->nrecv; out[1] = b->recv_solves; out[2] = b->recv_mvps; out[3] = b->recv_bad;
+        if (per_receiver) for (size_t r = 0; r < b->recv_last.size(); ++r) per_receiver[r] = b->recv_last[r];
     });
 }
 

@@ -110,6 +110,7 @@ struct lsfc_plan {
     lsfc::DevBuf<double> nu;             // Re nu
     lsfc::DevBuf<double> nu_im;          // Im nu: allocated only while the plan's nu is complex (lsfc_plan_set_nu_complex)
     lsfc::DevBuf<lsfc::cplx> sym;        // pruned: storage-order tiled layout incl. 1/|pads|; rocFFT: FFT order incl. 1/|pads|
+    lsfc::DevBuf<double> contract_work;  // block partials of lsfc_born_contract (OP_N), grown on demand and kept: used on `stream` only
 
     // pruned pipeline
     lsfc::PrunedTuning tuning;

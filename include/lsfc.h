@@ -669,6 +669,62 @@ int lsfc_born_apply(lsfc_born* b, const double* in, int in_is_complex, double* o
  * last call; last (may be NULL): nsrc results of the last call's solves */
 int lsfc_born_info(const lsfc_born* b, int64_t out[8], lsfc_gmres_result* last /* nsrc entries, may be NULL */);
 
+/* Reciprocal mode: J and J^H without solves.  Every right-hand side of the solves above lies in a small fixed space: the adjoint
+ * sources R^T conj(r_s) span at most nrecv dimensions, and the M^T solves of J are only ever seen through R.  With the receiver
+ * fields
+ *     V = M^-1 R^T        (N x nrecv; column r is the field of receiver r used as a source: nrecv ordinary solves on M)
+ * and R M^-T = V^T the formulas above become contractions of the stored U and V:
+ *     (J dnu)[s, r] = -omega^2 sum_i dnu[i] u_s[i] v_r[i]
+ *     (J^H r)[i]    = -omega^2 sum_s conj(u_s[i]) sum_r conj(v_r[i]) r[s, r]
+ * Only transposes are used; nu may be complex.  Both sides contract the same U and V, so J and J^H are adjoint to rounding whatever
+ * the solver tolerance.
+ * Cost: nrecv solves per medium (every lsfc_born_set_background) against nsrc solves per apply in the adjoint-state mode above;
+ * an apply is then nsrc nrecv complex multiply-adds per grid point over nsrc + nrecv streamed vectors.  Reciprocal mode pays when
+ * (applies per medium) x nsrc > nrecv; the adjoint-state mode stays the right one for a single gradient with many receivers.
+ *
+ * lsfc_born_contract is the kernel-level entry, usable without the object (conventions of lsfc_born_image; u: nsrc x N, v: nrecv x N,
+ * members back to back; N, device and stream are the plan's):
+ *   LSFC_OP_N   in: N doubles, or N (re, im) pairs with in_is_complex; out[s nrecv + r] = scale sum_i (in[i] u_s[i]) v_r[i].
+ *               The sum over the points has two levels: blocks of points (their number and bounds depend on N alone), then the
+ *               blocks in order.  out[s, r] is its own chain of multiply-adds: its bits depend on u_s, v_r, in, scale and N, not on
+ *               the other members, on nsrc, nrecv or the pair's place.  flags must be 0.  The block partials (8 KB per block and
+ *               16 x 16 pairs) are device memory kept with the plan from the first call on.
+ *   LSFC_OP_H   in: nsrc x nrecv complex; out[i] = (LSFC_BORN_ACCUMULATE ? out[i] : 0) + conj(scale) sum_s conj(u_s[i]) q_s[i],
+ *               q_s[i] = sum_r conj(v_r[i]) in[s, r].  Order: q_s over the receivers in fours, in order; then per group of 16 sources,
+ *               in order, t_g = sum of conj(u_s) q_s over s = g, g + 4, g + 8, g + 12 in that order (g = 0..3), the group's value
+ *               (t_0 + t_1) + (t_2 + t_3), and conj(scale) times it added to the running out[i].  So one call and two calls cut at a
+ *               multiple of 16 sources, the second with LSFC_BORN_ACCUMULATE, give the same bits; other cuts agree to rounding.
+ *               LSFC_BORN_REAL: out is N doubles, bit for bit the real part of the complex result.
+ *   With conj(scale) in OP_H the two ops are adjoint for any scale.  Two calls give the same bits.  No atomics.
+ *   LSFC_EINVAL, before any device call: NULL argument; nsrc or nrecv < 1; an unknown op, flag, in_is_complex or memspace; LSFC_OP_T;
+ *   a flag with LSFC_OP_N; a real input with LSFC_OP_H; a distributed, simulated-rank or multi-device plan.
+ *
+ * The object: lsfc_born_set_mode may be called at any time after lsfc_born_create.  To LSFC_BORN_RECIPROCAL with a background
+ * present it solves for V at once, without one the next lsfc_born_set_background does; back to LSFC_BORN_ADJOINT_STATE (the default)
+ * releases V.  In reciprocal mode
+ *     lsfc_born_set_background   as above, then V: `chunk` receivers at a time, right-hand sides R^T e_r from lsfc_receivers_apply
+ *                                (LSFC_OP_T) on rows of the identity, the object's solver, tolerances and preconditioner on M, x0 = 0
+ *     lsfc_born_apply, OP_N / H  lsfc_born_contract with scale = -omega^2: no solve, the plan's and the preconditioner's state are not
+ *                                touched, LSFC_OK; lsfc_born_info reports 0 solves and 0 operator applications, every source
+ *                                converged in 0 iterations.  A host-LU preconditioner (lsfc_precond_create) therefore serves OP_N.
+ * Memory rule: reciprocal mode adds nrecv N 16 B for V (and the contraction's block partials, 8 KB x min(1024, N / 4096) per 16 x 16
+ * sources x receivers); checked in the same place, before anything is allocated; LSFC_ENOMEM also gives the largest nrecv that fits.
+ * Non-convergence: a receiver that does not converge does not stop the others; V is kept, the call returns LSFC_ENOTCONV and
+ * lsfc_last_error names the first such receiver and the stage "receiver-field solve on M" (a source that did not converge in the
+ * same call is named first); lsfc_born_receiver_info has every receiver's result.
+ * LSFC_EINVAL, before any device call, lsfc_last_error names the cause: an unknown mode; a NULL argument; lsfc_born_receiver_fields
+ * outside reciprocal mode or before lsfc_born_set_background. */
+#define LSFC_BORN_ADJOINT_STATE 0
+#define LSFC_BORN_RECIPROCAL    1
+int lsfc_born_contract(lsfc_plan* plan, const double* u, int64_t nsrc, const double* v, int64_t nrecv, const double* in, int in_is_complex,
+                       double* out, int op, unsigned flags, double scale_re, double scale_im, int memspace);
+int lsfc_born_set_mode(lsfc_born* b, int mode);
+int lsfc_born_get_mode(const lsfc_born* b, int* mode, int64_t* receiver_field_bytes);
+int lsfc_born_receiver_fields(const lsfc_born* b, const double** v_dev, int64_t* nrecv);   /* device pointer, nrecv * N complex */
+/* out: nrecv, batched solves, operator applications, first receiver not converged or -1 -- of the last receiver-field solve;
+ * per_receiver (may be NULL): nrecv results */
+int lsfc_born_receiver_info(const lsfc_born* b, int64_t out[4], lsfc_gmres_result* per_receiver);
+
 /* ---- streams, timing, profiling ------------------------------------------ */
 
 /* Run the plan on a caller-owned hipStream_t (NULL = the legacy default stream). */

@@ -622,8 +622,15 @@ receivers_set_stream(R::ReceiversHIP, stream::Ptr{Cvoid}) = check(ccall((:lsfc_r
 # its adjoint and the misfit gradient, device-resident.  B = Born(M, R, U_inc) solves for the background fields of the columns of
 # U_inc; B * dnu is J dnu (nrecv x nsrc), B' * r is J^H r, misfit(B, d_obs) returns (phi, gradient), update!(B, nu) moves the
 # medium.  The plan's op and the preconditioner's op are set by the library for the solves and put back.
+# Born(...; mode=:reciprocal) or set_mode!(B, :reciprocal): one solve per receiver and medium for the receiver fields V = M^-1 R^T
+# (receiver_fields(B)), after which B * dnu and B' * r are contractions of the stored U and V without any solve; it pays when
+# (applies per medium) x nsrc > nrecv.  born_contract is the kernel-level entry.  (This part of the binding is written against
+# include/lsfc.h and has not been executed: there is no Julia toolchain where the library is built and tested.)
 const BORN_ACCUMULATE = Cuint(1); const BORN_REAL = Cuint(2)
 const BORN_GMRES = Cint(0); const BORN_BICGSTABL = Cint(1)
+const BORN_ADJOINT_STATE = Cint(0); const BORN_RECIPROCAL = Cint(1)
+_born_mode(mode::Symbol) = mode == :adjoint_state ? BORN_ADJOINT_STATE : mode == :reciprocal ? BORN_RECIPROCAL :
+    throw(ArgumentError("Born: mode must be :adjoint_state or :reciprocal, not $(repr(mode))"))
 struct BornOpts                    # lsfc_born_opts
     solver::Cint; restart::Cint; l::Cint; maxiter::Int64; reltol::Float64; abstol::Float64
     precond::Ptr{Cvoid}; chunk::Int64; reserved::NTuple{6,Cint}
@@ -634,7 +641,8 @@ mutable struct Born
     U_inc::Matrix{Complex{Float64}}
     converged::Bool
     function Born(M::FastMHIP, R::ReceiversHIP, U_inc::Matrix{Complex{Float64}}; Pl=nothing, solver=:gmres, reltol=1e-8, restart=30, l=2,
-                  maxiter=0, chunk=0)
+                  maxiter=0, chunk=0, mode=:adjoint_state)
+        mode_code = _born_mode(mode)
         (Pl === nothing || Pl isa SparsifyingPreconditionerHIP) || throw(ArgumentError("Born: Pl must be a SparsifyingPreconditionerHIP (not a wrapper of one)"))
         opts = Ref(BornOpts(solver == :gmres ? BORN_GMRES : BORN_BICGSTABL, restart, l, maxiter, reltol, 0.0,
                             Pl === nothing ? C_NULL : Pl.pc, chunk, ntuple(_ -> Cint(0), 6)))
@@ -642,6 +650,7 @@ mutable struct Born
         check(ccall((:lsfc_born_create, liblsfc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{BornOpts}), out, M.plan, R.rc, opts))
         B = new(out[], M, R, Pl, U_inc, true)
         finalizer(B -> ccall((:lsfc_born_destroy, liblsfc), Cint, (Ptr{Cvoid},), B.b), B)
+        mode_code == BORN_ADJOINT_STATE || check(ccall((:lsfc_born_set_mode, liblsfc), Cint, (Ptr{Cvoid}, Cint), B.b, mode_code))
         set_background!(B, U_inc)
         return B
     end
@@ -693,5 +702,36 @@ function misfit(B::Born, d_obs::Matrix{Complex{Float64}})
     return 0.5 * sum(abs2, res), mul!(g, B', res)
 end
 update!(B::Born, nu::NuVector) = (set_nu!(B.M, nu); set_background!(B, B.U_inc))
+# :reciprocal with a background present solves for the receiver fields now; :adjoint_state releases them
+set_mode!(B::Born, mode::Symbol) = (_born_rc(B, ccall((:lsfc_born_set_mode, liblsfc), Cint, (Ptr{Cvoid}, Cint), B.b, _born_mode(mode))); B)
+function mode(B::Born)
+    m = Ref{Cint}(0); bytes = Ref{Int64}(0)
+    check(ccall((:lsfc_born_get_mode, liblsfc), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}), B.b, m, bytes))
+    return m[] == BORN_RECIPROCAL ? :reciprocal : :adjoint_state
+end
+# the device pointer of V (N x nrecv, column r the field of receiver r) and nrecv; valid until the next set_background! / update! / set_mode!
+function receiver_fields(B::Born)
+    p = Ref{Ptr{Complex{Float64}}}(C_NULL); n = Ref{Int64}(0)
+    check(ccall((:lsfc_born_receiver_fields, liblsfc), Cint, (Ptr{Cvoid}, Ref{Ptr{Complex{Float64}}}, Ref{Int64}), B.b, p, n))
+    return p[], n[]
+end
+function receiver_results(B::Born)  # (nrecv, batched solves, operator applications, first receiver not converged or -1), per receiver results
+    out = zeros(Int64, 4); res = Vector{GmresResult}(undef, B.R.nrecv)
+    check(ccall((:lsfc_born_receiver_info, liblsfc), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{GmresResult}), B.b, out, res))
+    return out, res
+end
+# lsfc_born_contract on host arrays: U (N x nsrc), V (N x nrecv); op = OP_N: x of length N -> nrecv x nsrc, out[r, s] = scale sum_i x[i] U[i, s] V[i, r];
+# op = OP_H: x (nrecv x nsrc) -> out (length N, real: its real part) = [out +] conj(scale) sum_s conj(U[i, s]) sum_r conj(V[i, r]) x[r, s]
+function born_contract(M::FastMHIP, U::Matrix{Complex{Float64}}, V::Matrix{Complex{Float64}}, x::Union{Array{Float64},Array{Complex{Float64}}};
+                       op=OP_N, scale=1.0 + 0.0im, real=false, accumulate=nothing)
+    N, ns, nr = size(U, 1), size(U, 2), size(V, 2)
+    (size(V, 1) == N && length(x) == (op == OP_N ? N : ns * nr)) || throw(DimensionMismatch("born_contract"))
+    out = op == OP_N ? zeros(Complex{Float64}, nr, ns) : accumulate !== nothing ? copy(accumulate) : real ? zeros(Float64, N) : zeros(Complex{Float64}, N)
+    flags = (real ? BORN_REAL : Cuint(0)) | (accumulate !== nothing ? BORN_ACCUMULATE : Cuint(0))
+    check(ccall((:lsfc_born_contract, liblsfc), Cint,
+                (Ptr{Cvoid}, Ptr{Complex{Float64}}, Int64, Ptr{Complex{Float64}}, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cuint, Float64, Float64, Cint),
+                M.plan, U, ns, V, nr, x, eltype(x) <: Complex ? 1 : 0, out, op, flags, Float64(Base.real(scale)), Float64(imag(scale)), 0))
+    return out
+end
 
 end # module
